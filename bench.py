@@ -10,6 +10,12 @@ A "step" is one whole log-density inference (u0 assembly + adaptive Tsit5 solve 
 post-processing + loss sums) over one synthetic Gaussian batch that is already resident in
 HBM.  metric = RHS evaluations per second (the integrator's `nf` counter / wall time).
 
+A plain run sets up, warms up, times the `--steps` steps and prints the JSON line (`ms_per_step` = wall time of one
+timed step).  `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (the inputs are seeded:
+the same arguments give the same inputs).  `--full` adds everything else after the timed region: the one-at-a-time
+figure, the roofline of the dominant kernel (rocprofv3 and fp32-MFMA child runs), the all-reduce alone (N > 1), the CPU
+baselines, the reference's benchmark suite and the gradient block.
+
 N GPUs: one process per GPU, the batch axis sharded (8192 columns per rank, weak scaling).
 Every rank solves its own shard; the only collective is the 5-float all-reduce behind the mean
 log-likelihood (RCCL over xGMI, through the C ABI's cnf_loss_allreduce), and `value` sums the
@@ -47,16 +53,43 @@ def parse_args():
     ap.add_argument("--kernel", default="auto", choices=["auto", "generic", "mfma"])
     ap.add_argument("--batch", type=int, default=8192, help="columns per GPU")
     ap.add_argument("--fixed-dt", type=float, default=0.0, help="use fixed steps instead of adaptive")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-reference-suite", action="store_true", help="skip the reference's own benchmark suite (a second of small calls after the timed region)")
-    ap.add_argument("--no-pmc", action="store_true", help="do not start the rocprofv3 child passes that measure roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline: the one-at-a-time figure, the "
+                         "roofline (with its rocprofv3 and fp32-MFMA child runs), the all-reduce alone, the CPU baselines, "
+                         "the reference's benchmark suite and the gradient block")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (logpx, regs, sums, loss) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-reference-suite", action="store_true", help="with --full: skip the reference's own benchmark suite (a second of small calls after the timed region)")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: do not start the rocprofv3 child passes that measure roofline.traffic")
     ap.add_argument("--prewarm", type=float, default=0.4,
                     help="seconds of untimed solves before the W counted warm-up steps: holds the clocks (DVFS) so that a short "
                          "timed region does not sit on the ramp")
     ap.add_argument("--fp32-child", action="store_true", help=argparse.SUPPRESS)   # internal: the CNF_STEP_FP32=1 leg
     ap.add_argument("--depth", type=int, default=2, choices=[1, 2, 3],
                     help="steps in flight: 2 = each step is submitted while the one before it runs (default); 1 = one at a time")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_MAX_COLS = 1 << 20     # 16 B per column (logpx + three regulariser rows): at most 16 MiB of outputs
+
+
+def dump_outputs(out_dir, logpx, regs, sums, loss, suffix=""):
+    """What a caller of the timed path receives from its last step: logpx (B), the regulariser rows (3 x B), the 5 loss sums
+    (all-reduced across ranks) and the loss formed from them.  Above DUMP_MAX_COLS columns a fixed seeded sample of them."""
+    os.makedirs(out_dir, exist_ok=True)
+    logpx = logpx.float().cpu().numpy()
+    regs = np.stack([r.float().cpu().numpy() for r in regs])
+    B = logpx.shape[0]
+    if B > DUMP_MAX_COLS:
+        cols = np.sort(np.random.default_rng(0).choice(B, DUMP_MAX_COLS, replace=False))
+        logpx, regs = logpx[cols], regs[:, cols]
+    arrays = {"logpx": logpx, "regs": regs, "sums": sums.float().cpu().numpy(), "loss": np.array([loss], np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
 
 
 def spawn_ranks(args):
@@ -395,8 +428,8 @@ def run_rank(args):
 
     def step():
         # one rank's share of `loss`: solve + post-processing + the 5 local sums in one C call, then the all-reduce
-        _, _, local = cnf.inference(icnf, mode, xs, ps, {}, eps=eps, with_sums=True)
-        return icnf.last_stats, reduce_sums(local)
+        logpx, regs, local = cnf.inference(icnf, mode, xs, ps, {}, eps=eps, with_sums=True)
+        return icnf.last_stats, reduce_sums(local), (logpx, regs)
 
     def sync():
         torch.cuda.synchronize(dev)
@@ -419,7 +452,7 @@ def run_rank(args):
         # the CNF_STEP_FP32=1 leg of the parent's JSON line: the same steps on the fp32-MFMA kernels (k_step3), timed alone
         t0 = time.perf_counter(); nf = 0
         for _ in range(args.steps):
-            st, _ = step(); nf += st["nf"]
+            st, _, _ = step(); nf += st["nf"]
         sync()
         el = time.perf_counter() - t0
         print("FP32CHILD " + json.dumps({"value": nf / el, "ms_per_step": el / args.steps * 1e3, "nf_per_solve": st["nf"],
@@ -441,7 +474,7 @@ def run_rank(args):
         # has its sums only then; the next step is already running behind it, so the GPU still goes from solve to solve)
         pend = []
         for _ in range(args.steps):
-            _, _, local = cnf.inference_submit(icnf, mode, xs, ps, {}, eps=eps, with_sums=True)
+            logpx, regs, local = cnf.inference_submit(icnf, mode, xs, ps, {}, eps=eps, with_sums=True)
             pend.append(local)
             if len(pend) >= args.depth:
                 nf_total += cnf.inference_collect(icnf)["nf"]
@@ -452,25 +485,27 @@ def run_rank(args):
         st = icnf.last_stats
     else:
         for _ in range(args.steps):
-            st, sums = step()
+            st, sums, (logpx, regs) = step()
             nf_total += st["nf"]
     sync()
     elapsed = time.perf_counter() - t0
     local_elapsed = elapsed
     k_mean_us, k_launches = C.c_float(), C.c_int()
     _lib.check(_lib.lib().cnf_solve_kernel_time(icnf.handle(), 0, C.byref(k_mean_us), C.byref(k_launches)), icnf.handle())
+    loss = cnf.loss_from_sums(icnf, mode, sums)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, logpx, regs, sums, loss, suffix=f"_rank{rank}" if world > 1 else "")
     # beside it, outside the timed region: the same K steps one at a time (each call returns when its solve has finished)
     one_at_a_time = None
-    if args.depth > 1 and world == 1:
+    if args.full and args.depth > 1 and world == 1:
         t1 = time.perf_counter()
         nf1 = 0
         for _ in range(args.steps):
-            st1, _ = step()
+            st1, _, _ = step()
             nf1 += st1["nf"]
         sync()
         e1 = time.perf_counter() - t1
         one_at_a_time = {"value": nf1 / e1, "ms_per_step": e1 / args.steps * 1e3}
-    loss = cnf.loss_from_sums(icnf, mode, sums)
 
     ranks_seen, per_rank_ms, allreduce_us = 1, [elapsed / args.steps * 1e3], None
     per_rank_loss = [loss]
@@ -484,6 +519,9 @@ def run_rank(args):
         dist.all_gather(gathered, torch.tensor([local_elapsed / args.steps * 1e3, loss], dtype=torch.float64, device=tdev))
         per_rank_ms = [float(g[0]) for g in gathered]
         per_rank_loss = [float(g[1]) for g in gathered]             # (every rank forms the loss from the all-reduced sums)
+    else:
+        nf_all = float(nf_total)
+    if world > 1 and args.full:
         # the collective by itself: 5 floats, latency-bound
         probe = torch.ones(5, dtype=torch.float32, device=dev)
         for _ in range(5):
@@ -495,12 +533,10 @@ def run_rank(args):
             probe = reduce_sums(probe * (1.0 / world))
         torch.cuda.synchronize(dev)
         allreduce_us = (time.perf_counter() - ta) / n_ar * 1e6
-    else:
-        nf_all = float(nf_total)
 
     # ---- roofline of the dominant kernel, measured live with HIP events on the launch stream
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         import ctypes as C
         l, h = _lib.lib(), icnf.handle()
         fl, by = C.c_double(), C.c_double()
@@ -621,14 +657,14 @@ def run_rank(args):
             # beside the split-bf16 number, outside the timed region: the SAME steps on the exact-fp32 MFMA kernels
             # (v_mfma_f32_16x16x4_f32; CNF_STEP_FP32 is read once per process, hence a child; this process idles meanwhile)
             roof["fp32_mfma"] = fp32_child_leg(args)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             kwb = dict(dt=args.fixed_dt, adaptive=False) if args.fixed_dt > 0 else kw
             out["cpu_baseline"], out["cpu_other"] = cpu_baseline(B, flat, xs_h, eps_h, kwb)
             out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
             out["nf_gpu_vs_cpu"] = {"gpu": st["nf"], "cpu": out["cpu_baseline"].get("nf_per_solve"),
                                     "note": "same workload and tolerances; the error estimate is at round-off level here, so the "
                                             "step count differs by an attempt between arithmetics (profiles/round3_step_trace.md)"}
-        if world == 1 and not args.no_reference_suite:
+        if args.full and world == 1 and not args.no_reference_suite:
             out["reference_suite"] = reference_suite()
             out["gradient"] = gradient_leg()
         print(json.dumps(out), flush=True)

@@ -60,7 +60,7 @@ def _unsharded_loss(B_per_rank, world, dt):
 def test_bench_two_ranks_on_one_card_over_gloo():
     B, dt = 1024, 0.125
     line, err = _run_bench({"CNF_BENCH_TRY_RCCL": "1"},
-                           ["--gpus", "2", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-pmc", "--no-reference-suite",
+                           ["--gpus", "2", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-pmc", "--no-reference-suite",
                             "--batch", str(B), "--fixed-dt", str(dt), "--prewarm", "0.05"])
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     with open(os.path.join(ROOT, "gpurun_out", "bench_2ranks_gloo.json"), "w") as f:
@@ -92,7 +92,7 @@ def test_bench_two_ranks_on_one_card_over_gloo():
 def test_bench_two_ranks_adaptive_submitted_solves():
     """The driver's form of the run (adaptive solve, submitted steps, README tolerances) with two ranks: finishes, counts both
     ranks' evaluations, and the per-rank adaptive solves land within the solver tolerance of each other's mean log-density."""
-    line, _ = _run_bench({}, ["--gpus", "2", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-pmc", "--no-reference-suite",
+    line, _ = _run_bench({}, ["--gpus", "2", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-pmc", "--no-reference-suite",
                               "--batch", "2048", "--prewarm", "0.05"])
     assert line["ranks_seen"] == 2 and line["steps_in_flight"] == 2
     assert np.isfinite(line["loss"]) and line["per_rank_loss"][0] == line["per_rank_loss"][1]

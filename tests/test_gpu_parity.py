@@ -355,7 +355,7 @@ def test_bench_line_on_this_gpu():
     metric, the roofline and CPU-baseline objects, the submitted steps and the one-at-a-time figure beside them."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline"],
                        cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-2000:])
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -375,6 +375,30 @@ def test_bench_line_on_this_gpu():
         assert rf["traffic_source"] and ("measured in this run" in rf["traffic_source"] or "not measured" in rf["traffic_source"])
         assert d["launches_per_solve"] == 1 and d["steps_in_flight"] == 2
         assert d["one_at_a_time"]["value"] > 1e4 and d["one_at_a_time"]["ms_per_step"] >= 0.9 * d["ms_per_step"]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """bench.py without --full: the headline line alone (nothing measured beside it), and --dump-outputs writes what the last
+    timed step returned -- logpx, the regulariser rows, the loss sums and the loss -- consistent with each other and the line."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-2000:])
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "RHS-evals/s" and d["higher_is_better"] is True
+    assert d["value"] > 1e4 and abs(d["value"] - d["nf_per_solve"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["roofline"] is None and d["one_at_a_time"] is None
+    assert not {"cpu_baseline", "reference_suite", "gradient"} & set(d)
+    out = {n: np.load(tmp_path / f"{n}.npy") for n in ("logpx", "regs", "sums", "loss")}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    B = 8192
+    assert out["logpx"].shape == (B,) and out["regs"].shape == (3, B) and out["sums"].shape == (5,) and out["loss"].shape == (1,)
+    assert np.all(np.isfinite(out["logpx"])) and np.all(np.isfinite(out["regs"]))
+    s = out["sums"].astype(np.float64)
+    assert s[4] == B and out["loss"][0] == d["loss"]
+    got = np.concatenate([[out["logpx"].sum(dtype=np.float64)], out["regs"].sum(axis=1, dtype=np.float64)])
+    assert np.allclose(got, s[:4], rtol=1e-4, atol=1e-4 * B), (got, s)
 
 
 def test_rhs_work_model():
