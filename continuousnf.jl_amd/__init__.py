@@ -49,6 +49,7 @@ from .base_icnf import (ICNF, ODEProblem, base_sol, construct, generate, generat
 from .dist import CondICNFDist, ICNFDist, ICNFDistribution, logpdf, pdf, rand, rand_
 from .icnf import augmented_f
 from .layers import Chain, CondLayer, Dense, PlanarLayer, setup
+from .rng import HIPRNG
 from .types import (FFJORD, RNODE, CondFFJORD, CondPlanar, CondRNODE, HIPJacVecMatrixMode,
                     HIPMatrixMode, HIPVecJacMatrixMode, Planar, TestMode, TrainMode)
 from . import mlj, parallel

@@ -109,6 +109,8 @@ _SIGNATURES = {
     "cnf_set_grad_split": (C.c_int, [C.c_int]),
     "cnf_selftest_hold_cus": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
     "cnf_selftest_split_product": (C.c_int, [_fp, _fp, _fp, C.c_int]),
+    "cnf_draw_normal": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, _fp, C.c_size_t, C.c_void_p]),
+    "cnf_draw_uint32": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, _fp, C.c_size_t, C.c_void_p]),
 }
 COMM_ID_BYTES = 128
 EXPORTS = tuple(_SIGNATURES)

@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _lib
 from .layers import Chain
+from .rng import HIPRNG
 from .types import (AbstractICNF, CondFFJORD, CondPlanar, CondRNODE, FFJORD, RNODE, HIPMatrixMode, HIPVecJacMatrixMode,
                     Mode, TestMode, TrainMode, _OutOfScope)
 
@@ -398,6 +399,7 @@ def construct(aicnf, nn: Chain, nvars: int, naugmented: int = 0, *, data_type=np
     rn = issubclass(aicnf, (RNODE, CondRNODE))
     if lambda1 is None: lambda1 = 1e-2 if rn else 0.0
     if lambda2 is None: lambda2 = 1e-2 if rn else 0.0
+    # rng: None (fresh host generator), an int seed, a numpy Generator, or a HIPRNG (eps and z0 drawn on the device)
     if rng is None:
         rng = np.random.default_rng()
     elif isinstance(rng, (int, np.integer)):
@@ -434,8 +436,14 @@ class ODEProblem:
 
 
 def draw_eps(icnf: ICNF, like: _Buf, B: int):
-    """``rand!(icnf.rng, icnf.epsdist, eps)`` (src/base_icnf.jl:277-278): N(0, I) probes."""
+    """``rand!(icnf.rng, icnf.epsdist, eps)`` (src/base_icnf.jl:277-278): N(0, I) probes.  With a ``HIPRNG`` they are drawn
+    on the device (cnf_draw_normal) where ``like`` lives -- on ``icnf.device`` and copied back for host arrays, so that one
+    seed gives one eps wherever the data are."""
     n_in = icnf.nvars + n_augment_input(icnf)
+    if isinstance(icnf.rng, HIPRNG):
+        if like.torch is not None:
+            return _Buf(icnf.rng.normal(n_in * B, like.arr.device, _stream(like)), n_in, B, like.torch)
+        return _Buf(icnf.rng.normal(n_in * B, icnf.device).cpu().numpy(), n_in, B, None)
     e = icnf.rng.standard_normal((B, n_in)).astype(np.float32).reshape(-1)
     if like.torch is not None:
         # through a small ring of PINNED staging buffers: the copy is enqueued (a pageable source makes the host wait for the
@@ -579,15 +587,20 @@ def generate_prob(icnf: ICNF, mode, ps, st, n: int, *, ys=None, z0=None, eps=Non
     """src/base_icnf.jl:358-380 (first row of SURVEY.md 8f): the sampling problem -- the same
     right-hand side integrated over ``reverse(tspan)`` from a draw of the base distribution.
     ``z0`` ((nvars+naugs) x n) and ``eps`` may be supplied to make the call deterministic;
-    by default both are drawn from icnf.rng (basedist / epsdist are N(0, I), base_icnf.jl:16-25)."""
+    by default both are drawn from icnf.rng (basedist / epsdist are N(0, I), base_icnf.jl:16-25); with a ``HIPRNG`` on the
+    device, z0 first and eps from the elements after it, and the sample comes back as a device tensor."""
     m = _mode_id(mode)
     n_in = icnf.nvars + n_augment_input(icnf)
     D = n_in + 1 + n_augment(icnf, mode)
     icnf.set_params(ps)
     icnf.set_cond(ys, n)
-    if z0 is None:
-        z0 = icnf.rng.standard_normal((n, n_in)).astype(np.float32).T
-    zb = _as_colmajor(z0, n_in, "z0")
+    if z0 is None and isinstance(icnf.rng, HIPRNG):
+        import torch                                    # drawn on the device, before eps: the sample is a device tensor
+        zb = _Buf(icnf.rng.normal(n_in * n, icnf.device), n_in, n, torch)
+    else:
+        if z0 is None:
+            z0 = icnf.rng.standard_normal((n, n_in)).astype(np.float32).T
+        zb = _as_colmajor(z0, n_in, "z0")
     if zb.B != n:
         raise ValueError("z0 must have n columns")
     if eps is None:

@@ -16,7 +16,8 @@
  *      0..nvars-1 data | nvars..n_in-1 augmented dims | n_in: dlogp | n_in+1: E | n_in+2: n
  *    (the last two rows exist in TrainMode only; n_in = nvars + naugs);
  *  - eps (the Hutchinson probe, `n_in x B`) is always an INPUT: the reference draws it
- *    once per inference call outside the RHS (src/base_icnf.jl:277-278);
+ *    once per inference call outside the RHS (src/base_icnf.jl:277-278); a caller that
+ *    wants it drawn on the device fills it with cnf_draw_normal (the generator below);
  *  - `stream` is a hipStream_t passed as void* (NULL = default stream); calls are
  *    asynchronous on it unless stated otherwise; a handle may be used from one stream
  *    at a time; there is no global state.
@@ -300,6 +301,25 @@ int cnf_grad_steps(cnf_handle h, float* hs, int cap);
  * stream-ordered.  It is the adjoint state at t0 restricted to the data rows (u0 = vcat(xs, zeros), src/base_icnf.jl:
  * 275-276): left behind by the backward sweep, nothing is recomputed.  B must be that call's batch size. */
 cnf_status cnf_grad_x(cnf_handle h, float* gx, int B, void* stream);
+
+/* ---- device random numbers ------------------------------------------
+ *
+ * The library's own counter-based generator, the counterpart of the device RNG the reference draws eps and
+ * the base sample z0 with on a GPU resource (rng_AT(::CUDALibs) = CURAND, ext/ContinuousNormalizingFlowsCUDAExt/
+ * ContinuousNormalizingFlowsCUDAExt.jl:5-7; draws at src/base_icnf.jl:277-278 and :367-370).  Philox4x32-10
+ * (Salmon et al., SC'11): element e = offset + i of stream (seed, subsequence) is word e & 3 of the block
+ * Philox4x32-10(counter = (q_lo, q_hi, sub_lo, sub_hi), key = (seed_lo, seed_hi)), q = e >> 2.  Normals: Box-Muller
+ * on the pairs (w0, w1) -> lanes 0, 1 and (w2, w3) -> lanes 2, 3 of a block, u1 = (w_even + 1) 2^-32,
+ * u2 = w_odd 2^-32, r = sqrt(-2 ln u1), even lane r cos(2 pi u2), odd lane r sin(2 pi u2), in double, rounded
+ * once to float.  out[i] is element offset + i, so a draw of [o, o+n) equals any split of it into consecutive
+ * pieces; eps[i + j n_in] (column-major n_in x B) = element offset + i + j n_in.  DEVICE `out` on `device`,
+ * enqueued on `stream` (of that device); no handle and no state: the caller advances `offset` by n per draw and
+ * gives each rank its own subsequence.  n = 0: CNF_OK, nothing launched; out NULL (n > 0), out not 4-byte aligned
+ * or offset + n past 2^64 - 1: CNF_ERR_BAD_ARG; no device: CNF_ERR_NO_DEVICE; a failed HIP call: CNF_ERR_HIP. */
+cnf_status cnf_draw_normal(int device, uint64_t seed, uint64_t subsequence, uint64_t offset,
+                           float* out, size_t n, void* stream);
+cnf_status cnf_draw_uint32(int device, uint64_t seed, uint64_t subsequence, uint64_t offset,
+                           uint32_t* out, size_t n, void* stream);
 
 /* ---- introspection --------------------------------------------------------------- */
 const char* cnf_status_string(cnf_status s);
