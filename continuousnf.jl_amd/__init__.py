@@ -46,9 +46,13 @@ from .base_icnf import (ICNF, ODEProblem, base_sol, construct, generate, generat
                         inference, inference_collect, inference_prob, inference_submit,
                         inference_sol, loss, loss_and_grad, loss_and_grad_collect, loss_and_grad_submit, loss_from_sums, loss_sums, n_augment,
                         n_augment_input, steer_tspan)
+from .base_icnf import base_sample
 from .dist import CondICNFDist, ICNFDist, ICNFDistribution, logpdf, pdf, rand, rand_
+from . import distributions
+from .distributions import DiagNormal, MvNormal, Rademacher, StdNormal
 from .icnf import augmented_f
 from .layers import Chain, CondLayer, Dense, PlanarLayer, setup
+from . import rng
 from .rng import HIPRNG
 from .types import (FFJORD, RNODE, CondFFJORD, CondPlanar, CondRNODE, HIPJacVecMatrixMode,
                     HIPMatrixMode, HIPVecJacMatrixMode, Planar, TestMode, TrainMode)

@@ -111,6 +111,9 @@ _SIGNATURES = {
     "cnf_selftest_split_product": (C.c_int, [_fp, _fp, _fp, C.c_int]),
     "cnf_draw_normal": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, _fp, C.c_size_t, C.c_void_p]),
     "cnf_draw_uint32": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, _fp, C.c_size_t, C.c_void_p]),
+    "cnf_draw_rademacher": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, _fp, C.c_size_t, C.c_void_p]),
+    "cnf_set_basedist": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, _fp, C.c_float]),
+    "cnf_base_sample": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_void_p]),
 }
 COMM_ID_BYTES = 128
 EXPORTS = tuple(_SIGNATURES)

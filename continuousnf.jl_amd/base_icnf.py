@@ -15,6 +15,7 @@ from typing import Any
 import numpy as np
 
 from . import _lib
+from .distributions import Rademacher, check_basedist, check_epsdist
 from .layers import Chain
 from .rng import HIPRNG
 from .types import (AbstractICNF, CondFFJORD, CondPlanar, CondRNODE, FFJORD, RNODE, HIPMatrixMode, HIPVecJacMatrixMode,
@@ -157,6 +158,8 @@ class ICNF:
     device: int = 0
     cond: bool = False          # COND type parameter (src/base_icnf.jl:44)
     n_cond: int = 0             # rows of ys = nn input size - (nvars + naugmented)
+    basedist: Any = None        # src/base_icnf.jl:16-21; None: MvNormal(Zeros, Eye), else a distributions.MvNormal
+    epsdist: Any = None         # src/base_icnf.jl:22-25; None: N(0, I) probes, else distributions.Rademacher()
     _handle: Any = field(default=None, repr=False)
     _cond_id: Any = field(default=None, repr=False)
     _params_id: Any = field(default=None, repr=False)
@@ -185,6 +188,10 @@ class ICNF:
             _lib.check(l.cnf_create(C.byref(h), C.byref(cfg)))
             self._handle = h
             _OPEN[id(self)] = weakref.ref(self)
+            if self.basedist is not None:        # (the default never calls it: that handle launches what it always did)
+                d = self.basedist
+                _lib.check(l.cnf_set_basedist(h, d.kind, d.mean.ctypes.data, d.whiten.ctypes.data, d.chol.ctypes.data,
+                                              d.logconst), h)
         return self._handle
 
     def __call__(self, xs, ps, st, *, eps=None):
@@ -376,10 +383,10 @@ def construct(aicnf, nn: Chain, nvars: int, naugmented: int = 0, *, data_type=np
             else: lambda3 = v
     if kw:
         raise TypeError(f"unknown keyword(s) {sorted(kw)}")
-    if basedist is not None or epsdist is not None:
-        # src/base_icnf.jl:16-25: both default to MvNormal(0, I) over the nvars + naugmented rows -- the log-density of the
-        # final state (inference_sol) and the draws of eps / z are built for that default only
-        raise NotImplementedError("basedist / epsdist other than the default MvNormal(Zeros, Eye) are not built")
+    # src/base_icnf.jl:16-25: both default to MvNormal(0, I) over the nvars + naugmented rows; a Gaussian base
+    # (distributions.MvNormal / DiagNormal) and Rademacher probes are built, anything else is refused
+    basedist = check_basedist(basedist, int(nvars) + int(naugmented))
+    epsdist = check_epsdist(epsdist)
     if not (isinstance(aicnf, type) and issubclass(aicnf, AbstractICNF)):
         raise TypeError("first argument must be a model tag such as RNODE or FFJORD")
     if issubclass(aicnf, _OutOfScope):
@@ -407,7 +414,7 @@ def construct(aicnf, nn: Chain, nvars: int, naugmented: int = 0, *, data_type=np
     return ICNF(aicnf, nn, int(nvars), int(naugmented), compute_mode, bool(inplace),
                 (float(tspan[0]), float(tspan[1])), float(steer_rate), dict(sol_kwargs or {}), rng,
                 float(np.float32(lambda1)), float(np.float32(lambda2)), float(np.float32(lambda3)),
-                int(device), bool(cond), int(n_cond))
+                int(device), bool(cond), int(n_cond), basedist, epsdist)
 
 
 def steer_tspan(icnf: ICNF, mode):
@@ -436,15 +443,20 @@ class ODEProblem:
 
 
 def draw_eps(icnf: ICNF, like: _Buf, B: int):
-    """``rand!(icnf.rng, icnf.epsdist, eps)`` (src/base_icnf.jl:277-278): N(0, I) probes.  With a ``HIPRNG`` they are drawn
-    on the device (cnf_draw_normal) where ``like`` lives -- on ``icnf.device`` and copied back for host arrays, so that one
-    seed gives one eps wherever the data are."""
+    """``rand!(icnf.rng, icnf.epsdist, eps)`` (src/base_icnf.jl:277-278): N(0, I) probes, or +-1 with
+    ``epsdist=Rademacher()``.  With a ``HIPRNG`` they are drawn on the device (cnf_draw_normal / cnf_draw_rademacher) where
+    ``like`` lives -- on ``icnf.device`` and copied back for host arrays, so that one seed gives one eps wherever the data are."""
     n_in = icnf.nvars + n_augment_input(icnf)
+    rad = isinstance(icnf.epsdist, Rademacher)
     if isinstance(icnf.rng, HIPRNG):
+        draw = icnf.rng.rademacher if rad else icnf.rng.normal
         if like.torch is not None:
-            return _Buf(icnf.rng.normal(n_in * B, like.arr.device, _stream(like)), n_in, B, like.torch)
-        return _Buf(icnf.rng.normal(n_in * B, icnf.device).cpu().numpy(), n_in, B, None)
-    e = icnf.rng.standard_normal((B, n_in)).astype(np.float32).reshape(-1)
+            return _Buf(draw(n_in * B, like.arr.device, _stream(like)), n_in, B, like.torch)
+        return _Buf(draw(n_in * B, icnf.device).cpu().numpy(), n_in, B, None)
+    if rad:
+        e = (1.0 - 2.0 * icnf.rng.integers(0, 2, size=(B, n_in))).astype(np.float32).reshape(-1)
+    else:
+        e = icnf.rng.standard_normal((B, n_in)).astype(np.float32).reshape(-1)
     if like.torch is not None:
         # through a small ring of PINNED staging buffers: the copy is enqueued (a pageable source makes the host wait for the
         # stream, which would put a bubble between two submitted gradients); a buffer is reused four draws later, long after
@@ -587,8 +599,10 @@ def generate_prob(icnf: ICNF, mode, ps, st, n: int, *, ys=None, z0=None, eps=Non
     """src/base_icnf.jl:358-380 (first row of SURVEY.md 8f): the sampling problem -- the same
     right-hand side integrated over ``reverse(tspan)`` from a draw of the base distribution.
     ``z0`` ((nvars+naugs) x n) and ``eps`` may be supplied to make the call deterministic;
-    by default both are drawn from icnf.rng (basedist / epsdist are N(0, I), base_icnf.jl:16-25); with a ``HIPRNG`` on the
-    device, z0 first and eps from the elements after it, and the sample comes back as a device tensor."""
+    by default both are drawn from icnf.rng (``rand!(rng, icnf.basedist, new_xs)``, ``rand!(rng, icnf.epsdist, eps)``); with a
+    ``HIPRNG`` on the device, z0 first and eps from the elements after it, and the sample comes back as a device tensor.  A
+    non-default ``basedist`` takes the standard normals the default would have drawn through ``mu + L n`` on the device
+    (cnf_base_sample), wherever they were drawn; a ``z0`` given by the caller is used as it is."""
     m = _mode_id(mode)
     n_in = icnf.nvars + n_augment_input(icnf)
     D = n_in + 1 + n_augment(icnf, mode)
@@ -597,10 +611,18 @@ def generate_prob(icnf: ICNF, mode, ps, st, n: int, *, ys=None, z0=None, eps=Non
     if z0 is None and isinstance(icnf.rng, HIPRNG):
         import torch                                    # drawn on the device, before eps: the sample is a device tensor
         zb = _Buf(icnf.rng.normal(n_in * n, icnf.device), n_in, n, torch)
+        if icnf.basedist is not None:
+            zb = _Buf(base_sample(icnf, zb.arr, n), n_in, n, torch)
     else:
-        if z0 is None:
+        drawn = z0 is None
+        if drawn:
             z0 = icnf.rng.standard_normal((n, n_in)).astype(np.float32).T
         zb = _as_colmajor(z0, n_in, "z0")
+        if drawn and icnf.basedist is not None:
+            import torch
+            raise_if_no_gpu()
+            nd = torch.from_numpy(zb.arr).to(torch.device("cuda", icnf.device))
+            zb = _Buf(base_sample(icnf, nd, n).cpu().numpy(), n_in, n, None)
     if zb.B != n:
         raise ValueError("z0 must have n columns")
     if eps is None:
@@ -614,6 +636,21 @@ def generate_prob(icnf: ICNF, mode, ps, st, n: int, *, ys=None, z0=None, eps=Non
     v[:, n_in:] = 0.0                                   # zrs = zeros(n_aug + 1, n)  (:367-368)
     t0, t1 = steer_tspan(icnf, mode)
     return ODEProblem(icnf, mode, u0, eb, (t1, t0), ps)  # reverse(tspan)  (:377)
+
+
+def base_sample(icnf: ICNF, normals, n: int):
+    """``mu + L n`` on the device (cnf_base_sample) for the ``n_in * n`` standard normals of a flat float32 CUDA tensor laid
+    out column by column; returns a new tensor of the same layout (a copy for the default base)."""
+    import torch
+    nrm = normals.contiguous().reshape(-1)
+    n_in = icnf.nvars + n_augment_input(icnf)
+    if nrm.numel() != n_in * n or nrm.dtype != torch.float32 or not nrm.is_cuda:
+        raise ValueError("normals must be n_in * n float32 values on the GPU")
+    out = torch.empty_like(nrm)
+    h = icnf.handle()
+    st = C.c_void_p(torch.cuda.current_stream(nrm.device).cuda_stream)
+    _lib.check(_lib.lib().cnf_base_sample(h, nrm.data_ptr(), out.data_ptr(), n, st), h)
+    return out
 
 
 def generate_sol(icnf: ICNF, mode, prob: ODEProblem):
@@ -811,10 +848,12 @@ def loss_and_grad_submit(icnf: ICNF, mode, xs, *args, eps=None):
     order -- an optimiser update enqueued next on the same stream consumes the gradient without the host ever waiting.
     ``loss_and_grad_collect(icnf)`` completes the oldest submission (at most three in flight).  ``ps`` must be a device tensor;
     it is uploaded with ``set_params_async``.  ``NotImplementedError`` where the gradient does not run in the launch of the
-    solve (use ``loss_and_grad``)."""
+    solve, or the model has a non-default ``basedist`` (use ``loss_and_grad``)."""
     import torch
     if not _is_torch(xs):
         raise ValueError("loss_and_grad_submit needs device tensors")
+    if icnf.basedist is not None:       # (refused before anything is drawn or uploaded, as cnf_loss_grad_submit itself would)
+        raise NotImplementedError("no in-launch gradient with a non-default basedist: use loss_and_grad")
     ys, ps, st = _split_cond_args(icnf, args)
     m = _mode_id(mode)
     xb = _xs_colmajor(icnf, xs)

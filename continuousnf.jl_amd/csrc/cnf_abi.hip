@@ -12,6 +12,7 @@
 #include "cnf_gradt.h"
 #include "cnf_adj3b.h"
 #include "cnf_step3.h"
+#include "cnf_dist.h"
 #include <immintrin.h>
 #include <sched.h>
 #include <vector>
@@ -133,6 +134,8 @@ struct cnf_ctx {
     float* stage = nullptr;       // device staging area of the *_host entry points, owned by the handle, grown on demand
     size_t stage_cap = 0;         //   (floats): no allocation per call, nothing to free on an error path
     float* d_sums = nullptr;      // 3 floats
+    BaseDist bd{};                // cnf_set_basedist: kind 0 = the default N(0, I), nothing of cnf_dist.hip is launched
+    float* d_bd = nullptr;        //   its arrays (mean | whiten | chol | prec), one allocation
     float* h_sums = nullptr;      // pinned, 3 floats
     std::string err;
 };
@@ -314,6 +317,7 @@ extern "C" cnf_status cnf_destroy(cnf_handle h) {
     if (h->h_mirror) (void)hipHostFree(h->h_mirror);
     if (h->stage) (void)hipFree(h->stage);
     if (h->d_sums) (void)hipFree(h->d_sums);
+    if (h->d_bd) (void)hipFree(h->d_bd);
     if (h->h_sums) (void)hipHostFree(h->h_sums);
     delete h;
     return CNF_OK;
@@ -405,6 +409,70 @@ static cnf_status check_call(cnf_handle h, int mode, int B) {
         const cnf_status s = collect_one(h, nullptr);
         if (s != CNF_OK) return s;
     }
+    return CNF_OK;
+}
+
+// basedist of construct (src/base_icnf.jl:16-21).  The arrays are checked and copied here; prec = W' W is formed in double from
+// the float W given (so it is the derivative of the log-density the device evaluates) and rounded once.
+extern "C" cnf_status cnf_set_basedist(cnf_handle h, int kind, const float* mean, const float* whiten, const float* chol,
+                                       float logconst) {
+    if (!h) return CNF_ERR_BAD_ARG;
+    if (kind < 0 || kind > 2) return fail(h, CNF_ERR_BAD_ARG, "basedist kind must be 0 (default), 1 (diagonal) or 2 (dense)");
+    if (hipSetDevice(h->device) != hipSuccess) { (void)hipGetLastError(); return fail(h, CNF_ERR_NO_DEVICE, "no device"); }
+    const size_t n = (size_t)h->nd.n_in, m = kind == 2 ? n * n : n;
+    std::vector<float> host;
+    if (kind != 0) {
+        if (!mean || !whiten || !chol) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+        if (!std::isfinite(logconst)) return fail(h, CNF_ERR_BAD_ARG, "logconst is not finite");
+        for (size_t i = 0; i < n; ++i)
+            if (!std::isfinite(mean[i])) return fail(h, CNF_ERR_BAD_ARG, "basedist: non-finite mean");
+        host.assign(n + 3 * m, 0.f);
+        float *hm = host.data(), *hw = hm + n, *hl = hw + m, *hp = hl + m;
+        for (size_t i = 0; i < n; ++i) hm[i] = mean[i];
+        for (size_t i = 0; i < n; ++i) {
+            const size_t d = kind == 2 ? i * n + i : i;
+            if (!std::isfinite(whiten[d]) || !(whiten[d] > 0.f) || !std::isfinite(chol[d]) || !(chol[d] > 0.f))
+                return fail(h, CNF_ERR_BAD_ARG, "basedist: the diagonals of whiten and chol must be finite and > 0");
+            for (size_t j = 0; kind == 2 && j < i; ++j)
+                if (!std::isfinite(whiten[i * n + j]) || !std::isfinite(chol[i * n + j]))
+                    return fail(h, CNF_ERR_BAD_ARG, "basedist: non-finite entry");
+        }
+        if (kind == 1) {
+            for (size_t i = 0; i < n; ++i) { hw[i] = whiten[i]; hl[i] = chol[i]; hp[i] = (float)((double)whiten[i] * whiten[i]); }
+        } else {
+            for (size_t i = 0; i < n; ++i)
+                for (size_t j = 0; j <= i; ++j) { hw[i * n + j] = whiten[i * n + j]; hl[i * n + j] = chol[i * n + j]; }
+            for (size_t i = 0; i < n; ++i)
+                for (size_t j = 0; j <= i; ++j) {
+                    double acc = 0.0;
+                    for (size_t k = i; k < n; ++k) acc += (double)hw[k * n + i] * hw[k * n + j];      // (W' W)_ij, k >= max(i, j)
+                    hp[i * n + j] = hp[j * n + i] = (float)acc;
+                }
+        }
+    }
+    // (a submitted inference, or its fallback, evaluates the base it was submitted with: none may be outstanding)
+    { const cnf_status ss = settle_submitted(h); if (ss != CNF_OK) return ss; }
+    HIPCHK(h, hipDeviceSynchronize());
+    if (h->d_bd) { (void)hipFree(h->d_bd); h->d_bd = nullptr; }
+    h->bd = BaseDist{};
+    if (kind == 0) return CNF_OK;
+    HIPCHK(h, hipMalloc(&h->d_bd, host.size() * sizeof(float)));
+    HIPCHK(h, hipMemcpy(h->d_bd, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    h->bd.kind = kind; h->bd.mean = h->d_bd; h->bd.whiten = h->d_bd + n; h->bd.chol = h->d_bd + n + m; h->bd.prec = h->d_bd + n + 2 * m;
+    h->bd.logconst = logconst;
+    return CNF_OK;
+}
+
+extern "C" cnf_status cnf_base_sample(cnf_handle h, const float* normals, float* z0, int B, void* stream) {
+    if (!h || !normals || !z0) return CNF_ERR_BAD_ARG;
+    if (B < 0) return fail(h, CNF_ERR_BAD_SHAPE, "negative batch");
+    if (normals == z0) return fail(h, CNF_ERR_BAD_ARG, "normals and z0 must be distinct buffers");
+    if (B == 0) return CNF_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t n = (size_t)h->nd.n_in * B;
+    if (h->bd.kind == 0) HIPCHK(h, hipMemcpyAsync(z0, normals, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    else launch_base_sample(h->nd.n_in, h->bd, normals, z0, B, (hipStream_t)stream);
+    HIPCHK(h, hipGetLastError());
     return CNF_OK;
 }
 
@@ -1422,6 +1490,9 @@ extern "C" cnf_status cnf_inference_post(cnf_handle h, int mode, const float* u_
     if (B == 0) return CNF_OK;
     HIPCHK(h, hipSetDevice(h->device));
     launch_post(h->nd, mode == CNF_MODE_TRAIN, u_final, logpx, regs, B, (hipStream_t)stream);
+    if (h->bd.kind)          // logpdf(icnf.basedist, z) - dlogp, afresh (the regulariser rows stay)
+        launch_base_post(h->nd.n_in, rows_of(h, mode), h->bd, nullptr, u_final, nullptr, logpx, regs, B, nullptr, nullptr, nullptr,
+                         (hipStream_t)stream);
     HIPCHK(h, hipGetLastError());
     return CNF_OK;
 }
@@ -1446,6 +1517,14 @@ static cnf_status inference_impl(cnf_handle h, int mode, const float* xs, const 
     if (s == CNF_OK && !ph.launched) {                      // (the one-attempt-at-a-time drivers leave it to the caller)
         enqueue_post(h, mode == CNF_MODE_TRAIN, h->last_state, ph, B, false, (hipStream_t)stream);   // stream-ordered
         HIPCHK(h, hipGetLastError());
+    }
+    if (s == CNF_OK && h->bd.kind) {
+        // a non-default base distribution: one more launch behind the solve (and its N(0, I) post-processing) overwrites logpx
+        // and the sums from the final state in the integrator's buffer -- also behind a submitted launch, in stream order
+        launch_base_post(h->nd.n_in, rows_of(h, mode), h->bd, h->last_state, h->U[0], h->U[1], logpx, regs, B, sums5, h->post_part,
+                         reinterpret_cast<unsigned*>(h->d_sums + 9), (hipStream_t)stream);
+        HIPCHK(h, hipGetLastError());
+        if (stats) stats->launches += 1;
     }
     return s;
 }
@@ -1758,7 +1837,7 @@ extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* 
         h->pt_valid = true;
     }
 
-    {   // small batches of a small two-layer tanh network: everything in one launch (wave_loss_grad above)
+    if (!h->bd.kind) {   // small batches of a small two-layer tanh network: everything in one launch (wave_loss_grad above)
         bool done = false;
         if ((s = wave_loss_grad(h, mode, xs, eps, B, opts, loss_out, grad, stats, stream, &done)) != CNF_OK || done) return s;
     }
@@ -1782,6 +1861,11 @@ extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* 
         enqueue_post(h, 1, h->last_state, ph, B, false, st);
         HIPCHK(h, hipGetLastError());
     }
+    if (h->bd.kind) {                                      // the loss of a non-default base distribution: logpx and the sums afresh
+        launch_base_post(n_in, D, h->bd, nullptr, fsol, nullptr, h->tmp_logpx, h->tmp_regs, B, h->d_sums, h->post_part,
+                         reinterpret_cast<unsigned*>(h->d_sums + 9), st);
+        HIPCHK(h, hipGetLastError());
+    }
     // (the five sums travel to the host behind the backward pass: the loss VALUE is not needed to start it)
     float* sums = reinterpret_cast<float*>(&h->h_state[2]);             // pinned; the initial-state slot is free by now
     HIPCHK(h, hipMemcpyAsync(sums, h->d_sums, 5 * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -1795,7 +1879,8 @@ extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* 
     if (fsteps_env > 0 && fsteps_env < fsteps) fsteps = fsteps_env;
     int ksplit = 1, filed = 0;
     HIPCHK(h, hipMemsetAsync(h->g_part, 0, (size_t)GRAD_MAX_KSPLIT * h->n_params * sizeof(float), st));
-    HIPCHK(h, launch_final_cotangent(nd, h->lam[2], fsol, h->g_lam, B, st));
+    if (h->bd.kind) { launch_base_cotangent(nd, D, h->bd, h->lam[2], fsol, h->g_lam, B, st); HIPCHK(h, hipGetLastError()); }
+    else HIPCHK(h, launch_final_cotangent(nd, h->lam[2], fsol, h->g_lam, B, st));
     const float invB = 1.0f / (float)B;
     const float lam_l = invB, lam_E = h->lam[0] * invB, lam_n = h->lam[1] * invB;   // constant scalar rows
     static const float A[6][5] = {
@@ -1951,7 +2036,7 @@ extern "C" cnf_status cnf_loss_grad_test(cnf_handle h, const float* xs, int B, c
     if ((s = ensure_capacity(h, B)) != CNF_OK) return s;
     if ((s = ensure_grad_capacity(h, B)) != CNF_OK) return s;
     bool done = false;
-    if ((s = wave_loss_grad(h, mode, xs, nullptr, B, opts, loss_out, grad, stats, stream, &done)) != CNF_OK) return s;
+    if (!h->bd.kind && (s = wave_loss_grad(h, mode, xs, nullptr, B, opts, loss_out, grad, stats, stream, &done)) != CNF_OK) return s;
     if (done) return CNF_OK;
     // ---- every other network: the recorded exact-trace solve, then k_adj_test (cnf_gradt.hip) over all of its steps in one launch ----
     hipStream_t st = (hipStream_t)stream;
@@ -1974,6 +2059,10 @@ extern "C" cnf_status cnf_loss_grad_test(cnf_handle h, const float* xs, int B, c
     }
     h->last_hs = rec.hs;
     launch_post(nd, 0, fsol, h->tmp_logpx, h->tmp_regs, B, st);
+    if (h->bd.kind) {          // a non-default base distribution: its log-density, and its d loss / d z(t1) for k_adj_test
+        launch_base_post(n_in, D, h->bd, nullptr, fsol, nullptr, h->tmp_logpx, h->tmp_regs, B, nullptr, nullptr, nullptr, st);
+        launch_base_cotangent(nd, D, h->bd, 0.f, fsol, h->g_W[0], B, st);
+    }
     launch_loss_sums(h->tmp_logpx, h->tmp_regs, B, h->d_sums, st);
     float* sums = reinterpret_cast<float*>(&h->h_state[2]);
     HIPCHK(h, hipMemcpyAsync(sums, h->d_sums, 5 * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -1993,6 +2082,7 @@ extern "C" cnf_status cnf_loss_grad_test(cnf_handle h, const float* xs, int B, c
     AdjTestArgs ta{};
     ta.P = h->d_params; ta.traj = first; ta.slot_stride = traj_slot_floats(h); ta.hs = h->traj_hs; ta.nsteps = rec.n;
     ta.ys = nd.n_cond > 0 ? h->d_ys : nullptr; ta.lam_l = 1.0f / (float)B; ta.lam_out = h->g_lam;
+    ta.lam_init = h->bd.kind ? h->g_W[0] : nullptr;
     ta.gpart = h->d_gt; ta.scratch = h->d_gt + (size_t)G * h->n_params; ta.scratch_per_wg = adj_test_scratch_floats(nd);
     ta.B = B; ta.n_params = (int)h->n_params;
     if (launch_adj_test(nd, ta, st) != hipSuccess) { (void)hipGetLastError(); return fail(h, CNF_ERR_UNSUPPORTED, "network too wide for the TestMode adjoint kernel"); }
@@ -2032,6 +2122,8 @@ extern "C" cnf_status cnf_loss_grad_submit(cnf_handle h, int mode, const float* 
                                            float* loss_dev, float* grad, void* stream) {
     if (!h) return CNF_ERR_BAD_ARG;
     if (h->submitted.size() >= 3) return fail(h, CNF_ERR_BAD_ARG, "three launches are submitted already: collect one first");
+    // (the gradient inside the solve's launch carries the N(0, I) cotangent: refused at once, nothing is enqueued)
+    if (h->bd.kind) return fail(h, CNF_ERR_UNSUPPORTED, "no in-launch gradient with a non-default base distribution: use cnf_loss_grad");
     h->collecting = true;
     cnf_status s = check_call(h, mode, B);
     if (s == CNF_OK && (!xs || !opts || !loss_dev || !grad || (mode == CNF_MODE_TRAIN && !eps))) s = fail(h, CNF_ERR_BAD_ARG, "null pointer");

@@ -1,0 +1,28 @@
+// The base distribution of a handle (cnf_set_basedist) and the launches that evaluate it (cnf_dist.hip): log-density
+// post-pass, terminal cotangent of the gradient, base sample.  Reference: icnf.basedist, src/base_icnf.jl:16-21, consumed by
+// logpdf(icnf.basedist, z) (:155, :177) and rand!(rng, icnf.basedist, new_xs) (:320-393).
+#pragma once
+#include "cnf_dev.h"
+
+// N(mean, Sigma), Sigma = L L', W = inv(L).  All pointers DEVICE memory.
+//   kind 1 (diagonal): whiten = 1 / sigma, chol = sigma, prec = 1 / sigma^2; n_in floats each
+//   kind 2 (dense):    whiten = W, chol = L (lower triangular), prec = W' W; n_in x n_in, ROW-major (entry (i, j) at i n_in + j)
+struct BaseDist {
+    int kind;                // 0: the default N(0, I) -- nothing of cnf_dist.hip is launched
+    const float* mean;
+    const float* whiten;
+    const float* chol;
+    const float* prec;
+    float logconst;          // c = sum_i log W_ii - n_in / 2 log(2 pi)
+};
+
+// logpx[b] = c - 1/2 |W (z_b - mean)|^2 - dlogp_b, afresh from the final state (st != null: U[st->cur], else U0); D floats per
+// sample.  regs (3 x B, written before by the N(0, I) post-processing) are read only; sums5 != null: also the five loss sums
+// (sum logpx, sum E, sum n, sum A, B), through `part` (4 floats per 64 samples) and `ticket` (zero between launches).
+void launch_base_post(int n_in, int D, const BaseDist& bd, const StepState* st, const float* U0, const float* U1, float* logpx,
+                      const float* regs, int B, float* sums5, float* part, unsigned* ticket, hipStream_t s);
+// lam[b] = (W' W (z_b - mean) + lambda3 unit(z_aug) on the augmented rows) / B   ([B][n_in]; fsol: D floats per sample)
+void launch_base_cotangent(const NetDesc& nd, int D, const BaseDist& bd, float lambda3, const float* fsol, float* lam, int B,
+                           hipStream_t s);
+// z0[b] = mean + L n_b   ([B][n_in] both; must not alias)
+void launch_base_sample(int n_in, const BaseDist& bd, const float* normals, float* z0, int B, hipStream_t s);

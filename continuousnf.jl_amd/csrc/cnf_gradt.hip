@@ -112,7 +112,8 @@ k_adj_test(NetDesc nd, AdjTestArgs a, const GtTab tab, int pq_lds) {
         for (int k = tid; k < nd.n_cond; k += GT_THREADS) x0[n_in + k] = a.ys[(size_t)b * nd.n_cond + k];
         {
             const float* uf = a.traj + (size_t)a.nsteps * a.slot_stride + (size_t)b * D;
-            for (int i = tid; i < n_in; i += GT_THREADS) lam[i] = uf[i] * a.lam_l;
+            const float* li = a.lam_init ? a.lam_init + (size_t)b * n_in : nullptr;
+            for (int i = tid; i < n_in; i += GT_THREADS) lam[i] = li ? li[i] : uf[i] * a.lam_l;
         }
         __syncthreads();
         for (int step = a.nsteps - 1; step >= 0; --step) {

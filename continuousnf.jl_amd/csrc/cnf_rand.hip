@@ -5,8 +5,8 @@
 //
 // Element e of stream (seed, sub) is word e & 3 of the block Philox4x32-10(ctr = (q_lo, q_hi, sub_lo, sub_hi),
 // key = (seed_lo, seed_hi)), q = e >> 2; its normal pairs lanes (0, 1) and (2, 3) of that block by Box-Muller, computed in
-// double and rounded once.  Every element is a function of (seed, sub, e) alone, so a draw of [o, o + n) equals any split of
-// it into consecutive pieces.
+// double and rounded once; its Rademacher value is +1.0f if bit 31 of its word is 0 and -1.0f if it is 1 (one word per element).
+// Every element is a function of (seed, sub, e) alone, so a draw of [o, o + n) equals any split of it into consecutive pieces.
 #include "../../include/cnfhip.h"
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -42,7 +42,8 @@ __device__ __forceinline__ void box_muller(uint32_t we, uint32_t wo, uint32_t& a
 
 // One counter block per thread and grid-stride step: elements 4q .. 4q+3 land at out[4q - offset ..] where they fall inside
 // [offset, last].  Full blocks take one 16-byte store when `vec` says the output is aligned for it (the same for every block).
-template <bool NORMAL>
+enum { DRAW_WORDS = 0, DRAW_NORMAL = 1, DRAW_RADEMACHER = 2 };
+template <int FORM>
 __global__ void __launch_bounds__(RAND_THREADS)
 k_draw(uint32_t* __restrict__ out, uint64_t offset, uint64_t last, uint64_t nblk, uint32_t k0, uint32_t k1, uint32_t s0,
        uint32_t s1, int vec) {
@@ -51,9 +52,13 @@ k_draw(uint32_t* __restrict__ out, uint64_t offset, uint64_t last, uint64_t nblk
     for (uint64_t b = (uint64_t)blockIdx.x * RAND_THREADS + threadIdx.x; b < nblk; b += stride) {
         const uint64_t q = q0 + b;
         uint4 w = philox4x32_10(make_uint4((uint32_t)q, (uint32_t)(q >> 32), s0, s1), k0, k1);
-        if constexpr (NORMAL) {
+        if constexpr (FORM == DRAW_NORMAL) {
             box_muller(w.x, w.y, w.x, w.y);
             box_muller(w.z, w.w, w.z, w.w);
+        }
+        if constexpr (FORM == DRAW_RADEMACHER) {          // the sign bit of the word under the bits of 1.0f
+            constexpr uint32_t one = 0x3F800000u, sign = 0x80000000u;
+            w = make_uint4((w.x & sign) | one, (w.y & sign) | one, (w.z & sign) | one, (w.w & sign) | one);
         }
         const uint64_t e0 = q << 2;                       // (e0 + 3 <= 2^64 - 1: no wrap)
         if (e0 >= offset && e0 + 3 <= last) {
@@ -74,7 +79,7 @@ k_draw(uint32_t* __restrict__ out, uint64_t offset, uint64_t last, uint64_t nblk
     }
 }
 
-cnf_status draw(int device, uint64_t seed, uint64_t sub, uint64_t offset, uint32_t* out, size_t n, void* stream, bool normal) {
+cnf_status draw(int device, uint64_t seed, uint64_t sub, uint64_t offset, uint32_t* out, size_t n, void* stream, int form) {
     if (n == 0) return CNF_OK;
     if (!out || ((uintptr_t)out & 3u) || (uint64_t)n > UINT64_MAX - offset) return CNF_ERR_BAD_ARG;
     int ndev = 0;
@@ -95,11 +100,14 @@ cnf_status draw(int device, uint64_t seed, uint64_t sub, uint64_t offset, uint32
     // full blocks start at out + 4q - offset: 16-byte aligned for all of them iff out - 4 (offset mod 4) floats is
     const int vec = (((uintptr_t)out - 4u * (uintptr_t)(offset & 3u)) & 15u) == 0;
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), s0 = (uint32_t)sub, s1 = (uint32_t)(sub >> 32);
-    if (normal)
-        hipLaunchKernelGGL(k_draw<true>, dim3(grid), dim3(RAND_THREADS), 0, (hipStream_t)stream, out, offset, last, nblk, k0, k1,
+    if (form == DRAW_NORMAL)
+        hipLaunchKernelGGL(k_draw<DRAW_NORMAL>, dim3(grid), dim3(RAND_THREADS), 0, (hipStream_t)stream, out, offset, last, nblk, k0, k1,
                            s0, s1, vec);
+    else if (form == DRAW_RADEMACHER)
+        hipLaunchKernelGGL(k_draw<DRAW_RADEMACHER>, dim3(grid), dim3(RAND_THREADS), 0, (hipStream_t)stream, out, offset, last, nblk,
+                           k0, k1, s0, s1, vec);
     else
-        hipLaunchKernelGGL(k_draw<false>, dim3(grid), dim3(RAND_THREADS), 0, (hipStream_t)stream, out, offset, last, nblk, k0, k1,
+        hipLaunchKernelGGL(k_draw<DRAW_WORDS>, dim3(grid), dim3(RAND_THREADS), 0, (hipStream_t)stream, out, offset, last, nblk, k0, k1,
                            s0, s1, vec);
     const hipError_t e = hipGetLastError();
     if (prev != device) (void)hipSetDevice(prev);
@@ -110,10 +118,16 @@ cnf_status draw(int device, uint64_t seed, uint64_t sub, uint64_t offset, uint32
 
 extern "C" cnf_status cnf_draw_normal(int device, uint64_t seed, uint64_t subsequence, uint64_t offset, float* out, size_t n,
                                       void* stream) {
-    return draw(device, seed, subsequence, offset, reinterpret_cast<uint32_t*>(out), n, stream, true);
+    return draw(device, seed, subsequence, offset, reinterpret_cast<uint32_t*>(out), n, stream, DRAW_NORMAL);
 }
 
 extern "C" cnf_status cnf_draw_uint32(int device, uint64_t seed, uint64_t subsequence, uint64_t offset, uint32_t* out, size_t n,
                                       void* stream) {
-    return draw(device, seed, subsequence, offset, out, n, stream, false);
+    return draw(device, seed, subsequence, offset, out, n, stream, DRAW_WORDS);
+}
+
+// rand!(rng, icnf.epsdist, eps) for Rademacher probes (epsdist, src/base_icnf.jl:22-25; draws at :233-397)
+extern "C" cnf_status cnf_draw_rademacher(int device, uint64_t seed, uint64_t subsequence, uint64_t offset, float* out, size_t n,
+                                          void* stream) {
+    return draw(device, seed, subsequence, offset, reinterpret_cast<uint32_t*>(out), n, stream, DRAW_RADEMACHER);
 }

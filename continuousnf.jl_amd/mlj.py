@@ -290,6 +290,8 @@ def fit_(mach: Machine, verbosity: int = 0) -> Machine:
 #   columns of the first weight = n_in + n_cond) | u32 acts[n_layers] (cnfhip.h codes) | u32 nvars |
 #   u32 naugs | u32 n_cond | u64 n_params | f32 ps[n_params] (Lux order: per layer weight out x in
 #   column-major, then bias).  Little endian throughout.
+# The file describes the network only: a non-default ``basedist`` / ``epsdist`` is not stored and has to be given to
+# ``construct`` again by whoever loads the parameters.
 # ---------------------------------------------------------------------------------------
 _MAGIC = b"CNFP"
 

@@ -27,7 +27,7 @@ def _launch(fn, device, seed, subsequence, offset, out, n, stream):
     import torch
     dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
     if out is None:
-        out = torch.empty(n, dtype=torch.float32 if fn == "cnf_draw_normal" else torch.uint32, device=dev)
+        out = torch.empty(n, dtype=torch.uint32 if fn == "cnf_draw_uint32" else torch.float32, device=dev)
     idx = out.device.index if out.device.index is not None else torch.cuda.current_device()
     if stream is None:
         stream = C.c_void_p(torch.cuda.current_stream(idx).cuda_stream)
@@ -40,6 +40,11 @@ def draw_normal(n, seed, subsequence=0, offset=0, device=0, stream=None):
     """Elements ``offset .. offset + n - 1`` of stream ``(seed, subsequence)`` as N(0, 1) float32: a new CUDA tensor of n
     entries on ``device``, filled on ``stream`` (default: torch's current stream there).  Stateless."""
     return _launch("cnf_draw_normal", device, seed, subsequence, offset, None, int(n), stream)
+
+
+def draw_rademacher(n, seed, subsequence=0, offset=0, device=0, stream=None):
+    """The same elements as Rademacher values (float32): +1 where bit 31 of the element's word is 0, -1 where it is 1."""
+    return _launch("cnf_draw_rademacher", device, seed, subsequence, offset, None, int(n), stream)
 
 
 def draw_uint32(n, seed, subsequence=0, offset=0, device=0, stream=None):
@@ -88,6 +93,11 @@ class HIPRNG:
         """The next n N(0, 1) float32 values as a CUDA tensor on ``device``, drawn on ``stream``."""
         o = self.take(n)
         return draw_normal(n, self.seed, self.subsequence, o, device, stream)
+
+    def rademacher(self, n, device, stream=None):
+        """The next n Rademacher (+-1) float32 values as a CUDA tensor on ``device``; ``offset`` advances by n as for ``normal``."""
+        o = self.take(n)
+        return draw_rademacher(n, self.seed, self.subsequence, o, device, stream)
 
     # host draws (not on the hot path)
     def uniform(self, *args, **kwargs):

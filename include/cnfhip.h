@@ -17,7 +17,7 @@
  *    (the last two rows exist in TrainMode only; n_in = nvars + naugs);
  *  - eps (the Hutchinson probe, `n_in x B`) is always an INPUT: the reference draws it
  *    once per inference call outside the RHS (src/base_icnf.jl:277-278); a caller that
- *    wants it drawn on the device fills it with cnf_draw_normal (the generator below);
+ *    wants it drawn on the device fills it with cnf_draw_normal or cnf_draw_rademacher (the generator below);
  *  - `stream` is a hipStream_t passed as void* (NULL = default stream); calls are
  *    asynchronous on it unless stated otherwise; a handle may be used from one stream
  *    at a time; there is no global state.
@@ -117,6 +117,28 @@ cnf_status cnf_set_params(cnf_handle h, const float* flat_dev, size_t n, void* s
  * the same B uses it.  Must be called again when ys, B or the parameters change. */
 cnf_status cnf_set_cond(cnf_handle h, const float* ys, int B, void* stream);
 cnf_status cnf_set_cond_host(cnf_handle h, const float* ys, int B);
+
+/* The base distribution, `basedist` of construct (src/base_icnf.jl:16-21): N(mean, Sigma) over the n_in = nvars + naugs rows of z,
+ * given as Sigma = L L' and W = inv(L).  It replaces MvNormal(0, I) wherever the reference consumes icnf.basedist:
+ * logpdf(icnf.basedist, z) in inference_sol (src/base_icnf.jl:155, :177) -- so in cnf_inference_post, cnf_inference*, the loss of
+ * cnf_loss_grad* and the terminal cotangent of their adjoint -- and rand!(rng, icnf.basedist, new_xs) in generate_prob
+ * (:320-393) through cnf_base_sample.  With c = logconst:  logpdf(z) = c - 1/2 |W (z - mean)|^2.
+ *   kind 0: back to the default (the other arguments are ignored); a handle on which this was never called with kind != 0
+ *           launches exactly what it launched before this entry point existed;
+ *   kind 1: diagonal -- whiten = 1 / sigma and chol = sigma, n_in floats each, every entry finite and > 0;
+ *   kind 2: dense -- whiten = W and chol = L, lower triangular n_in x n_in, ROW-major (entry (i, j) at [i n_in + j]; entries
+ *           above the diagonal are not read), diagonals finite and > 0.
+ * HOST pointers, copied at the call (synchronous; outstanding submissions are completed first).  logconst is what the caller
+ * computed in double, sum_i log W_ii - n_in / 2 log(2 pi), rounded once.  The base is not learnable: no gradient w.r.t. it.
+ * With a non-default base every solve keeps its N(0, I) post-processing and ONE small launch behind it on the same stream
+ * recomputes logpx (and the loss sums) afresh from the final state; gradients take the recorded solve (never the gradient
+ * inside the solve's launch), and cnf_loss_grad_submit returns CNF_ERR_UNSUPPORTED at once.
+ * CNF_ERR_BAD_ARG: unknown kind, a NULL pointer, a non-finite entry or a non-positive diagonal. */
+cnf_status cnf_set_basedist(cnf_handle h, int kind, const float* mean, const float* whiten, const float* chol,
+                            float logconst);
+/* rand!(rng, icnf.basedist, new_xs) (src/base_icnf.jl:320, :344, :368, :393) from standard normals already drawn
+ * (cnf_draw_normal): z0[:, b] = mean + L normals[:, b]; both n_in x B, DEVICE, distinct buffers.  Default base: a copy. */
+cnf_status cnf_base_sample(cnf_handle h, const float* normals, float* z0, int B, void* stream);
 
 /* Lock-step sharded solves.  The reference solves the whole D x B_total batch as
  * ONE ODE system (inference_prob src/base_icnf.jl:266-286), so the adaptive controller sees one
@@ -320,6 +342,12 @@ cnf_status cnf_draw_normal(int device, uint64_t seed, uint64_t subsequence, uint
                            float* out, size_t n, void* stream);
 cnf_status cnf_draw_uint32(int device, uint64_t seed, uint64_t subsequence, uint64_t offset,
                            uint32_t* out, size_t n, void* stream);
+/* Rademacher probes, rand!(rng, icnf.epsdist, eps) with epsdist = Rademacher (epsdist: src/base_icnf.jl:22-25; draws at
+ * :233-397): element e is +1.0f if bit 31 of word e of the same stream -- the word cnf_draw_uint32 returns for element e --
+ * is 0, and -1.0f if it is 1.  One word per element, so element e stays a function of (seed, subsequence, e) alone.
+ * Arguments, splitting and error codes as cnf_draw_normal. */
+cnf_status cnf_draw_rademacher(int device, uint64_t seed, uint64_t subsequence, uint64_t offset,
+                               float* out, size_t n, void* stream);
 
 /* ---- introspection --------------------------------------------------------------- */
 const char* cnf_status_string(cnf_status s);

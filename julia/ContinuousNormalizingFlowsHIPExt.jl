@@ -16,7 +16,7 @@ module ContinuousNormalizingFlowsHIPExt
 import ContinuousNormalizingFlows as CNF
 import ContinuousNormalizingFlows: ICNF, AbstractICNF, MatrixMode, TrainMode, TestMode, Mode, n_augment,
     n_augment_input, augmented_f, base_sol, rng_AT, base_AT
-import ComputationalResources, LuxCore, NNlib, Random, SciMLBase
+import ComputationalResources, Distributions, LinearAlgebra, LuxCore, NNlib, Random, SciMLBase
 
 const libcnfhip = get(ENV, "CNFHIP_LIB", "libcnfhip.so")
 
@@ -108,8 +108,38 @@ function handle(icnf::ICNF{T, <:HIPMatrixMode}) where {T}
                             first(layers).in_dims - icnf.nvars - n_augment_input(icnf))   # n_cond (0 unless Cond*)
             check(@ccall(libcnfhip.cnf_create(h::Ptr{Ptr{Cvoid}}, Ref(cfg)::Ptr{CnfConfig})::Cint), C_NULL)
         end
+        set_basedist!(h[], icnf.basedist, icnf.nvars + n_augment_input(icnf))
         h[]
     end
+end
+
+# icnf.basedist (src/base_icnf.jl:16-21) -> cnf_set_basedist: MvNormal(Zeros, Eye) is the library's default (nothing is called),
+# a diagonal or full covariance is handed over as (mean, W = inv(L), L, c) with Sigma = L L', computed in Float64 and rounded once;
+# anything else is an error.  Dense matrices go over ROW-major, i.e. as the transpose of Julia's column-major storage.
+# Untested, as the rest of this file: no Julia where this was written.
+function set_basedist!(h::Ptr{Cvoid}, d, n::Integer)
+    d isa Distributions.AbstractMvNormal ||
+        error("basedist $(typeof(d)) is not built: MvNormal with Zeros/Eye, a diagonal or a full covariance")
+    length(d) == n || error("basedist has length $(length(d)), the model has $n rows")
+    μ = Vector{Float64}(Distributions.mean(d))
+    Σ = Matrix{Float64}(Distributions.cov(d))
+    if all(iszero, μ) && Σ == LinearAlgebra.I
+        return nothing
+    end
+    if LinearAlgebra.isdiag(Σ)
+        σ = sqrt.(LinearAlgebra.diag(Σ))
+        w, l, kind = 1 ./ σ, σ, 1
+        c = sum(log, w) - n / 2 * log(2π)
+    else
+        L = Matrix(LinearAlgebra.cholesky(LinearAlgebra.Symmetric(Σ)).L)
+        W = Matrix(inv(LinearAlgebra.LowerTriangular(L)))
+        c = sum(log, LinearAlgebra.diag(W)) - n / 2 * log(2π)
+        w, l, kind = vec(permutedims(W)), vec(permutedims(L)), 2
+    end
+    m32, w32, l32 = Vector{Float32}(μ), Vector{Float32}(w), Vector{Float32}(l)
+    check(@ccall(libcnfhip.cnf_set_basedist(h::Ptr{Cvoid}, kind::Cint, m32::Ptr{Float32}, w32::Ptr{Float32}, l32::Ptr{Float32},
+                                            Float32(c)::Cfloat)::Cint), h)
+    nothing
 end
 
 # Upload `p` (ComponentArray -> flat vector: per layer weight, column-major, then bias) unless the handle already holds
