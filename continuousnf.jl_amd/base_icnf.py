@@ -196,8 +196,13 @@ class ICNF:
 
     def __call__(self, xs, ps, st, *, eps=None):
         """The Lux-layer form, src/base_icnf.jl:528-543: ``icnf(xs, ps, st)`` (conditional: ``icnf((xs, ys), ps, st)``)
-        = ``(first(inference(icnf, TrainMode(), xs[, ys], ps, st)), st)``."""
+        = ``(first(inference(icnf, TrainMode(), xs[, ys], ps, st)), st)``.  With a ``ps`` that requires grad the call goes
+        through ``vjp.differentiable_inference``: the result can be back-propagated to ``ps`` and ``xs``."""
         from .types import TrainMode
+        if _is_torch(ps) and ps.requires_grad:
+            from .vjp import differentiable_inference
+            args = (xs[0], xs[1], ps, st) if self.cond else (xs, ps, st)
+            return differentiable_inference(self, TrainMode(), *args, eps=eps)[0], st
         if self.cond:
             x, ys = xs
             return inference(self, TrainMode(), x, ys, ps, st, eps=eps)[0], st

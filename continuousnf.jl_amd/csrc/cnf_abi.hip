@@ -130,6 +130,13 @@ struct cnf_ctx {
     float* g_grad = nullptr;      // n_params (host-pointer variant)
     std::vector<float> last_hs;   // signed step sizes of the last cnf_loss_grad solve
     int grad_last_B = 0;          // batch of the last cnf_loss_grad call (g_lam holds its d loss / d u(t0))
+    // cnf_inference_record / cnf_inference_pullback: the record is the trajectory store, g_US[1], last_hs and these; any solve,
+    // parameter or conditioning upload or change of the base distribution on the handle ends it (rec_valid = false)
+    bool rec_valid = false;
+    int rec_mode = 0, rec_B = 0, rec_kernel = 0;
+    const float* rec_eps = nullptr;
+    float* d_cw = nullptr;        // [3][B] per-sample cotangents of the scalar rows, packed by k_vjp_cotangent
+    size_t cw_floats = 0;
     float* d_ys = nullptr;        // conditional models: copy of ys (n_cond x cond_B), kept for the weight gradient
     float* stage = nullptr;       // device staging area of the *_host entry points, owned by the handle, grown on demand
     size_t stage_cap = 0;         //   (floats): no allocation per call, nothing to free on an error path
@@ -318,6 +325,7 @@ extern "C" cnf_status cnf_destroy(cnf_handle h) {
     if (h->stage) (void)hipFree(h->stage);
     if (h->d_sums) (void)hipFree(h->d_sums);
     if (h->d_bd) (void)hipFree(h->d_bd);
+    if (h->d_cw) (void)hipFree(h->d_cw);
     if (h->h_sums) (void)hipHostFree(h->h_sums);
     delete h;
     return CNF_OK;
@@ -334,6 +342,7 @@ extern "C" cnf_status cnf_set_params(cnf_handle h, const float* flat_dev, size_t
     if (ms != CNF_OK) return fail(h, ms, "MFMA weight packing failed");
     HIPCHK(h, hipStreamSynchronize(s));
     h->have_params = true;
+    h->rec_valid = false;
     h->pt_valid = false;
     h->img_valid = false;
     h->bimg_valid = false;
@@ -351,6 +360,7 @@ extern "C" cnf_status cnf_set_params_host(cnf_handle h, const float* flat, size_
     if (ms != CNF_OK) return fail(h, ms, "MFMA weight packing failed");
     HIPCHK(h, hipDeviceSynchronize());
     h->have_params = true;
+    h->rec_valid = false;
     h->pt_valid = false;
     h->img_valid = false;
     h->bimg_valid = false;
@@ -455,6 +465,7 @@ extern "C" cnf_status cnf_set_basedist(cnf_handle h, int kind, const float* mean
     HIPCHK(h, hipDeviceSynchronize());
     if (h->d_bd) { (void)hipFree(h->d_bd); h->d_bd = nullptr; }
     h->bd = BaseDist{};
+    h->rec_valid = false;
     if (kind == 0) return CNF_OK;
     HIPCHK(h, hipMalloc(&h->d_bd, host.size() * sizeof(float)));
     HIPCHK(h, hipMemcpy(h->d_bd, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -484,6 +495,7 @@ extern "C" cnf_status cnf_set_cond(cnf_handle h, const float* ys, int B, void* s
     HIPCHK(h, hipSetDevice(h->device));
     // (a submitted inference reads d_cond until it ends, and its fallback would read it again: none may be outstanding)
     { const cnf_status ss = settle_submitted(h); if (ss != CNF_OK) return ss; }
+    h->rec_valid = false;
     const int cbs = (h->nd.dims[1] + 15) & ~15;
     if (h->cond_B != B || h->cbs != cbs) {
         HIPCHK(h, hipDeviceSynchronize());
@@ -922,6 +934,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
                              bool final_sync, PostHook* post) {
     cnf_status s = check_call(h, mode, B);
     if (s != CNF_OK) return s;
+    h->rec_valid = false;                                  // (every solve may overwrite what a record consists of)
     if (!u0 || !opts) return fail(h, CNF_ERR_BAD_ARG, "null pointer");      // u_out may be null: the state stays in U[cur]
     const int train = mode == CNF_MODE_TRAIN;
     if (train && !eps) return fail(h, CNF_ERR_BAD_ARG, "eps is required in TrainMode");
@@ -1812,42 +1825,18 @@ static cnf_status wave_loss_grad(cnf_handle h, int mode, const float* xs, const 
     return CNF_OK;
 }
 
-extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* eps, int B,
-                                    const cnf_solve_opts* opts, float* loss_out, float* grad,
-                                    cnf_solve_stats* stats, void* stream) {
+// The forward half of cnf_loss_grad (and cnf_inference_record in TrainMode): u0, the RECORDED solve -- stage states in the
+// trajectory store, the final state in g_US[1] --, logpx / regs in tmp_logpx / tmp_regs and the five loss sums in d_sums.
+static cnf_status train_forward(cnf_handle h, const float* xs, const float* eps, int B, const cnf_solve_opts* opts, Recorder& rec,
+                                cnf_solve_stats& sst, void* stream) {
     const int mode = CNF_MODE_TRAIN;
-    cnf_status s = check_call(h, mode, B);
-    if (s != CNF_OK) return s;
-    if (!xs || !eps || !opts || !loss_out || !grad) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
-    if (B < 1) return fail(h, CNF_ERR_BAD_SHAPE, "the loss is a mean over the batch: B must be >= 1");
-    const GradLayout gl = grad_layout(h->nd);
-    if (!grad_supported(h->nd, gl)) return fail(h, CNF_ERR_UNSUPPORTED, "network too wide for the gradient kernels");
-    if ((s = ensure_capacity(h, B)) != CNF_OK) return s;
-    if ((s = ensure_grad_capacity(h, B)) != CNF_OK) return s;
+    cnf_status s = CNF_OK;
     hipStream_t st = (hipStream_t)stream;
-    const NetDesc& nd = h->nd;
-    const int n_in = nd.n_in, D = n_in + 3;
-    const size_t n = (size_t)D * B;
-    const AdjMfmaLayout am = adj_mfma_layout(nd, gl);
-    // the pullback kernel follows the kernel choice of the solve: GENERIC -> VALU, otherwise MFMA when it fits
-    const bool adj_mfma = opts->kernel != CNF_KERNEL_GENERIC && adj_mfma_supported(nd, am);
-    if (!h->pt_valid) {
-        HIPCHK(h, launch_transpose_params(nd, h->d_params, h->d_PT, st));
-        HIPCHK(h, launch_pack_adj_images(nd, gl, am, h->d_params, h->d_adj_img, st));
-        h->pt_valid = true;
-    }
-
-    if (!h->bd.kind) {   // small batches of a small two-layer tanh network: everything in one launch (wave_loss_grad above)
-        bool done = false;
-        if ((s = wave_loss_grad(h, mode, xs, eps, B, opts, loss_out, grad, stats, stream, &done)) != CNF_OK || done) return s;
-    }
-
+    const int n_in = h->nd.n_in, D = n_in + 3;
     // ---- forward: u0, recorded solve, loss ------------------------------------------------------
     // (as an inference does: u0 is assembled from the data columns and the post-processing and the five loss sums are formed
     // inside the one-launch solves -- the recording forms included --, behind the solve otherwise; the final state goes
     // straight to fsol where the kernel can write it there)
-    Recorder rec;
-    cnf_solve_stats sst{};
     float* fsol = h->g_US[1];
     PostHook ph{h->tmp_logpx, h->tmp_regs, h->d_sums, xs};
     for (;;) {
@@ -1866,10 +1855,26 @@ extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* 
                          reinterpret_cast<unsigned*>(h->d_sums + 9), st);
         HIPCHK(h, hipGetLastError());
     }
-    // (the five sums travel to the host behind the backward pass: the loss VALUE is not needed to start it)
-    float* sums = reinterpret_cast<float*>(&h->h_state[2]);             // pinned; the initial-state slot is free by now
-    HIPCHK(h, hipMemcpyAsync(sums, h->d_sums, 5 * sizeof(float), hipMemcpyDeviceToHost, st));
+    return CNF_OK;
+}
 
+// The backward half of cnf_loss_grad (and cnf_inference_pullback in TrainMode): the discrete adjoint of the recorded steps `hs`
+// (sizes; their stage states lie in the trajectory store, the final state in g_US[1]) into grad, d / d u(t0) into g_lam.
+// cot == null: the cotangent of the loss -- three launch-wide scalars and k_final_cotangent / k_base_cotangent, the arithmetic
+// cnf_loss_grad has always had.  cot = [4][B] (rows logpx, E, n, A): k_vjp_cotangent forms the terminal cotangent and packs the
+// per-sample weights of the scalar rows into d_cw, which every pullback kernel then reads in place of the scalars.
+static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kernel, const std::vector<float>& rec_hs, const float* cot,
+                                 float* grad, hipStream_t st) {
+    cnf_status s = CNF_OK;
+    const NetDesc& nd = h->nd;
+    const int n_in = nd.n_in, D = n_in + 3;
+    const size_t n = (size_t)D * B;
+    const GradLayout gl = grad_layout(nd);
+    const AdjMfmaLayout am = adj_mfma_layout(nd, gl);
+    // the pullback kernel follows the kernel choice of the solve: GENERIC -> VALU, otherwise MFMA when it fits
+    const bool adj_mfma = kernel != CNF_KERNEL_GENERIC && adj_mfma_supported(nd, am);
+    const int rec_n = (int)rec_hs.size();
+    const float* cw = cot ? h->d_cw : nullptr;
     // ---- backward: discrete adjoint of the recorded steps ---------------------------------------
     // capacity is in samples of cap_B; with B <= cap_B at least grad_fsteps steps fit
     // (CNF_GRAD_FSTEPS=n: contract after every n steps instead -- measurements: fewer steps per contraction keep the factor rows
@@ -1879,10 +1884,13 @@ extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* 
     if (fsteps_env > 0 && fsteps_env < fsteps) fsteps = fsteps_env;
     int ksplit = 1, filed = 0;
     HIPCHK(h, hipMemsetAsync(h->g_part, 0, (size_t)GRAD_MAX_KSPLIT * h->n_params * sizeof(float), st));
-    if (h->bd.kind) { launch_base_cotangent(nd, D, h->bd, h->lam[2], fsol, h->g_lam, B, st); HIPCHK(h, hipGetLastError()); }
+    const float* fsol = h->g_US[1];
+    if (cot) { launch_vjp_cotangent(nd, D, h->bd, 1, fsol, cot, h->g_lam, h->d_cw, B, st); HIPCHK(h, hipGetLastError()); }
+    else if (h->bd.kind) { launch_base_cotangent(nd, D, h->bd, h->lam[2], fsol, h->g_lam, B, st); HIPCHK(h, hipGetLastError()); }
     else HIPCHK(h, launch_final_cotangent(nd, h->lam[2], fsol, h->g_lam, B, st));
     const float invB = 1.0f / (float)B;
-    const float lam_l = invB, lam_E = h->lam[0] * invB, lam_n = h->lam[1] * invB;   // constant scalar rows
+    // constant scalar rows; with per-sample weights the kernels multiply cw[r][b] in where these scalars stand, so they are 1
+    const float lam_l = cw ? 1.0f : invB, lam_E = cw ? 1.0f : h->lam[0] * invB, lam_n = cw ? 1.0f : h->lam[1] * invB;
     static const float A[6][5] = {
         {0, 0, 0, 0, 0},
         {TS_A21, 0, 0, 0, 0},
@@ -1895,17 +1903,18 @@ extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* 
         // The headline shape: the steps whose factor rows fit the arena in ONE launch on split-bf16 products (cnf_adj3b.hip;
         // the image is the forward kernels'), then one contraction over them -- 2 launches per run of steps instead of one
         // per step and one per run.
-        if ((s = traj_reserve(h, rec.n)) != CNF_OK) return s;
+        if ((s = traj_reserve(h, rec_n)) != CNF_OK) return s;
         const int run = std::min(fsteps, ADJ3B_MAX_STEPS);
-        for (int hi = rec.n - 1; hi >= 0; hi -= run) {
+        for (int hi = rec_n - 1; hi >= 0; hi -= run) {
             const int lo = std::max(0, hi - run + 1), cnt = hi - lo + 1;
             Adj3bSteps M{};
             M.traj = h->traj; M.slot_stride = traj_slot_floats(h); M.n = n;
             M.step_hi = hi; M.step_lo = lo;
-            for (int j = 0; j < cnt; ++j) M.hs[j] = rec.hs[hi - j];
+            for (int j = 0; j < cnt; ++j) M.hs[j] = rec_hs[hi - j];
             M.eps = eps; M.lam = h->g_lam; M.lam_out = h->g_lam;
             M.HS = h->g_HS; M.TS = h->g_TS; M.AB = h->g_AB; M.PB = h->g_PB;
             M.lam_l = lam_l; M.lam_E = lam_E; M.lam_n = lam_n;
+            M.cw = cw;
             for (int i = 0; i < 6; ++i) M.bw[i] = Bw[i];
             for (int m = 0; m < 6; ++m) for (int d = 0; d < 5; ++d) M.kc[m][d] = m - 1 - d >= 0 ? A[m][m - 1 - d] : 0.f;
             M.B = B;
@@ -1929,20 +1938,20 @@ extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* 
     // (MFMA pullback: the steps of a run are gathered and launched together -- as two launches over the whole run where the batch
     // leaves CUs idle, else one launch per step)
     int run0 = 0;                                          // first entry of the current run in h_steps
-    if (adj_mfma && rec.n > h->steps_cap) {
+    if (adj_mfma && rec_n > h->steps_cap) {
         HIPCHK(h, hipStreamSynchronize(st));
         if (h->d_steps) { (void)hipFree(h->d_steps); h->d_steps = nullptr; }
         if (h->h_steps) { (void)hipHostFree(h->h_steps); h->h_steps = nullptr; }
         h->steps_cap = 0;
-        const int cap = rec.n + 32;
+        const int cap = rec_n + 32;
         HIPCHK(h, hipMalloc(&h->d_steps, (size_t)cap * sizeof(AdjStepArgs)));
         HIPCHK(h, hipHostMalloc(&h->h_steps, (size_t)cap * sizeof(AdjStepArgs)));
         h->steps_cap = cap;
     }
-    for (int step = rec.n - 1; step >= 0; --step) {
+    for (int step = rec_n - 1; step >= 0; --step) {
         float* un;
         if ((s = traj_slot(h, step, &un)) != CNF_OK) return s;
-        const float hs = rec.hs[step];
+        const float hs = rec_hs[step];
         // stage states: U_1 = u_n, U_2..U_6 were filed behind it by the forward pass
         const float* US[6];
         for (int i = 0; i < 6; ++i) US[i] = un + (size_t)i * n;
@@ -1957,6 +1966,7 @@ extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* 
             for (int k = a.nw; k < 5; ++k) { a.w[k] = h->g_lam; a.wc[k] = 0.f; }     // unused slots: a readable array, weight 0
             a.cb = Bw[i]; a.hstep = hs;
             a.c_l = hs * Bw[i] * lam_l; a.c_E = hs * Bw[i] * lam_E; a.c_n = hs * Bw[i] * lam_n;
+            a.cw = cw;
             a.w_out = h->g_W[i];
             // every stage evaluation files its factors behind the earlier ones: rows [slot B, (slot + 1) B)
             const size_t slot = (size_t)filed * 6 + i;
@@ -1969,7 +1979,7 @@ extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* 
         if (adj_mfma) {        // the six stage pullbacks and the lambda update of this step in ONE launch
             S.first = 5; S.last = 0; S.B = B; S.lam_update = 1; S.lam_out = h->g_lam;
             for (int m = 0; m < 6; ++m) for (int d = 0; d < 5; ++d) S.kc[m][d] = m - 1 - d >= 0 ? A[m][m - 1 - d] : 0.f;
-            h->h_steps[rec.n - 1 - step] = S;
+            h->h_steps[rec_n - 1 - step] = S;
         } else {
             StageK ws{};
             ws.nk = 6;
@@ -2015,9 +2025,112 @@ extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* 
     }
     HIPCHK(h, launch_grad_reduce(h->g_part, grad, (int)h->n_params, ksplit, st));
     h->grad_last_B = B;                                    // (g_lam now holds d loss / d u(t0): cnf_grad_x)
+    return CNF_OK;
+}
+
+extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* eps, int B,
+                                    const cnf_solve_opts* opts, float* loss_out, float* grad,
+                                    cnf_solve_stats* stats, void* stream) {
+    const int mode = CNF_MODE_TRAIN;
+    cnf_status s = check_call(h, mode, B);
+    if (s != CNF_OK) return s;
+    if (!xs || !eps || !opts || !loss_out || !grad) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    if (B < 1) return fail(h, CNF_ERR_BAD_SHAPE, "the loss is a mean over the batch: B must be >= 1");
+    const GradLayout gl = grad_layout(h->nd);
+    if (!grad_supported(h->nd, gl)) return fail(h, CNF_ERR_UNSUPPORTED, "network too wide for the gradient kernels");
+    if ((s = ensure_capacity(h, B)) != CNF_OK) return s;
+    if ((s = ensure_grad_capacity(h, B)) != CNF_OK) return s;
+    hipStream_t st = (hipStream_t)stream;
+    const NetDesc& nd = h->nd;
+    const AdjMfmaLayout am = adj_mfma_layout(nd, gl);
+    if (!h->pt_valid) {
+        HIPCHK(h, launch_transpose_params(nd, h->d_params, h->d_PT, st));
+        HIPCHK(h, launch_pack_adj_images(nd, gl, am, h->d_params, h->d_adj_img, st));
+        h->pt_valid = true;
+    }
+
+    if (!h->bd.kind) {   // small batches of a small two-layer tanh network: everything in one launch (wave_loss_grad above)
+        bool done = false;
+        if ((s = wave_loss_grad(h, mode, xs, eps, B, opts, loss_out, grad, stats, stream, &done)) != CNF_OK || done) return s;
+    }
+
+    Recorder rec;
+    cnf_solve_stats sst{};
+    if ((s = train_forward(h, xs, eps, B, opts, rec, sst, stream)) != CNF_OK) return s;
+    // (the five sums travel to the host behind the backward pass: the loss VALUE is not needed to start it)
+    float* sums = reinterpret_cast<float*>(&h->h_state[2]);             // pinned; the initial-state slot is free by now
+    HIPCHK(h, hipMemcpyAsync(sums, h->d_sums, 5 * sizeof(float), hipMemcpyDeviceToHost, st));
+
+    if ((s = train_backward(h, eps, B, opts->kernel, rec.hs, nullptr, grad, st)) != CNF_OK) return s;
     HIPCHK(h, hipStreamSynchronize(st));
     if ((s = cnf_loss_from_sums(h, mode, sums, loss_out)) != CNF_OK) return s;
     if (stats) *stats = sst;
+    return CNF_OK;
+}
+
+// The forward half of cnf_loss_grad_test (and cnf_inference_record in TestMode): the recorded exact-trace solve -- u_n of every
+// accepted step in the trajectory store, the final state in g_US[1] --, logpx in tmp_logpx, the loss sums in d_sums.
+static cnf_status test_forward(cnf_handle h, const float* xs, int B, const cnf_solve_opts* opts, Recorder& rec, cnf_solve_stats& sst,
+                               void* stream) {
+    const int mode = CNF_MODE_TEST;
+    cnf_status s = CNF_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const NetDesc& nd = h->nd;
+    const int n_in = nd.n_in, D = n_in + 1;
+    float* u0 = h->g_US[0];
+    launch_build_u0(xs, u0, nd.nvars, D, B, st);
+    // the recorded forward pass files u_n after every accepted step (host-driven, one attempt at a time: solve_core's recording
+    // branch of the streamed driver).  Networks whose TestMode runs inside the fused step kernels (two layers, closed-form trace)
+    // take the generic right-hand side there: that branch is the one place where a TestMode solve records.
+    cnf_solve_opts ropts = *opts;
+    if (mfma_supported(h->mfma, nd, false, B)) ropts.kernel = CNF_KERNEL_GENERIC;
+    float* fsol = h->g_US[1];
+    for (;;) {
+        if ((s = solve_core(h, mode, u0, nullptr, fsol, B, &ropts, &sst, stream, &rec)) != CNF_OK) return s;
+        if (!rec.overflow) break;
+        if ((s = traj_reserve(h, rec.n + 8)) != CNF_OK) return s;
+    }
+    h->last_hs = rec.hs;
+    launch_post(nd, 0, fsol, h->tmp_logpx, h->tmp_regs, B, st);
+    if (h->bd.kind) {          // a non-default base distribution: its log-density, and its d loss / d z(t1) for k_adj_test
+        launch_base_post(n_in, D, h->bd, nullptr, fsol, nullptr, h->tmp_logpx, h->tmp_regs, B, nullptr, nullptr, nullptr, st);
+        launch_base_cotangent(nd, D, h->bd, 0.f, fsol, h->g_W[0], B, st);
+    }
+    launch_loss_sums(h->tmp_logpx, h->tmp_regs, B, h->d_sums, st);
+    return CNF_OK;
+}
+
+// The backward half: k_adj_test (cnf_gradt.hip) over all recorded steps in one launch, then the sum of its partials.  cot == null:
+// the cotangent of the loss (1 / B per sample); cot = [4][B]: k_vjp_cotangent leaves d / d z(t1) in g_W[0] and w_l = -cot_l in d_cw
+// (rows E, n, A do not exist in TestMode: their cotangents are not read).
+static cnf_status test_backward(cnf_handle h, int B, const std::vector<float>& rec_hs, const float* cot, float* grad, hipStream_t st) {
+    cnf_status s = CNF_OK;
+    const NetDesc& nd = h->nd;
+    const int rec_n = (int)rec_hs.size();
+    if (cot) { launch_vjp_cotangent(nd, nd.n_in + 1, h->bd, 0, h->g_US[1], cot, h->g_W[0], h->d_cw, B, st); HIPCHK(h, hipGetLastError()); }
+    // the step sizes to the device (behind the steps in the trajectory store's step-size array), scratch and partials of the kernel
+    if ((s = traj_reserve(h, rec_n + 1)) != CNF_OK) return s;
+    if (rec_n > 0) HIPCHK(h, hipMemcpyAsync(h->traj_hs, rec_hs.data(), (size_t)rec_n * sizeof(float), hipMemcpyHostToDevice, st));
+    const int G = adj_test_workgroups(B);
+    const size_t per_wg = adj_test_scratch_floats(nd) + h->n_params;
+    if ((size_t)G * per_wg > h->gt_floats) {
+        HIPCHK(h, hipStreamSynchronize(st));
+        if (h->d_gt) { (void)hipFree(h->d_gt); h->d_gt = nullptr; h->gt_floats = 0; }
+        HIPCHK(h, hipMalloc(&h->d_gt, (size_t)G * per_wg * sizeof(float)));
+        h->gt_floats = (size_t)G * per_wg;
+    }
+    float* first;
+    if ((s = traj_slot(h, 0, &first)) != CNF_OK) return s;
+    AdjTestArgs ta{};
+    ta.P = h->d_params; ta.traj = first; ta.slot_stride = traj_slot_floats(h); ta.hs = h->traj_hs; ta.nsteps = rec_n;
+    ta.ys = nd.n_cond > 0 ? h->d_ys : nullptr; ta.lam_l = 1.0f / (float)B; ta.lam_out = h->g_lam;
+    ta.lam_init = (cot || h->bd.kind) ? h->g_W[0] : nullptr;
+    ta.w_l = cot ? h->d_cw : nullptr;
+    ta.gpart = h->d_gt; ta.scratch = h->d_gt + (size_t)G * h->n_params; ta.scratch_per_wg = adj_test_scratch_floats(nd);
+    ta.B = B; ta.n_params = (int)h->n_params;
+    if (launch_adj_test(nd, ta, st) != hipSuccess) { (void)hipGetLastError(); return fail(h, CNF_ERR_UNSUPPORTED, "network too wide for the TestMode adjoint kernel"); }
+    HIPCHK(h, launch_grad_reduce(h->d_gt, grad, (int)h->n_params, G, st));
+    h->grad_last_B = B;                                    // (g_lam holds d loss / d z(t0): cnf_grad_x)
     return CNF_OK;
 }
 
@@ -2040,54 +2153,12 @@ extern "C" cnf_status cnf_loss_grad_test(cnf_handle h, const float* xs, int B, c
     if (done) return CNF_OK;
     // ---- every other network: the recorded exact-trace solve, then k_adj_test (cnf_gradt.hip) over all of its steps in one launch ----
     hipStream_t st = (hipStream_t)stream;
-    const NetDesc& nd = h->nd;
-    const int n_in = nd.n_in, D = n_in + 1;
-    float* u0 = h->g_US[0];
-    launch_build_u0(xs, u0, nd.nvars, D, B, st);
-    // the recorded forward pass files u_n after every accepted step (host-driven, one attempt at a time: solve_core's recording
-    // branch of the streamed driver).  Networks whose TestMode runs inside the fused step kernels (two layers, closed-form trace)
-    // take the generic right-hand side there: that branch is the one place where a TestMode solve records.
-    cnf_solve_opts ropts = *opts;
-    if (mfma_supported(h->mfma, nd, false, B)) ropts.kernel = CNF_KERNEL_GENERIC;
     Recorder rec;
     cnf_solve_stats sst{};
-    float* fsol = h->g_US[1];
-    for (;;) {
-        if ((s = solve_core(h, mode, u0, nullptr, fsol, B, &ropts, &sst, stream, &rec)) != CNF_OK) return s;
-        if (!rec.overflow) break;
-        if ((s = traj_reserve(h, rec.n + 8)) != CNF_OK) return s;
-    }
-    h->last_hs = rec.hs;
-    launch_post(nd, 0, fsol, h->tmp_logpx, h->tmp_regs, B, st);
-    if (h->bd.kind) {          // a non-default base distribution: its log-density, and its d loss / d z(t1) for k_adj_test
-        launch_base_post(n_in, D, h->bd, nullptr, fsol, nullptr, h->tmp_logpx, h->tmp_regs, B, nullptr, nullptr, nullptr, st);
-        launch_base_cotangent(nd, D, h->bd, 0.f, fsol, h->g_W[0], B, st);
-    }
-    launch_loss_sums(h->tmp_logpx, h->tmp_regs, B, h->d_sums, st);
+    if ((s = test_forward(h, xs, B, opts, rec, sst, stream)) != CNF_OK) return s;
     float* sums = reinterpret_cast<float*>(&h->h_state[2]);
     HIPCHK(h, hipMemcpyAsync(sums, h->d_sums, 5 * sizeof(float), hipMemcpyDeviceToHost, st));
-    // the step sizes to the device (behind the steps in the trajectory store's step-size array), scratch and partials of the kernel
-    if ((s = traj_reserve(h, rec.n + 1)) != CNF_OK) return s;
-    if (rec.n > 0) HIPCHK(h, hipMemcpyAsync(h->traj_hs, rec.hs.data(), (size_t)rec.n * sizeof(float), hipMemcpyHostToDevice, st));
-    const int G = adj_test_workgroups(B);
-    const size_t per_wg = adj_test_scratch_floats(nd) + h->n_params;
-    if ((size_t)G * per_wg > h->gt_floats) {
-        HIPCHK(h, hipStreamSynchronize(st));
-        if (h->d_gt) { (void)hipFree(h->d_gt); h->d_gt = nullptr; h->gt_floats = 0; }
-        HIPCHK(h, hipMalloc(&h->d_gt, (size_t)G * per_wg * sizeof(float)));
-        h->gt_floats = (size_t)G * per_wg;
-    }
-    float* first;
-    if ((s = traj_slot(h, 0, &first)) != CNF_OK) return s;
-    AdjTestArgs ta{};
-    ta.P = h->d_params; ta.traj = first; ta.slot_stride = traj_slot_floats(h); ta.hs = h->traj_hs; ta.nsteps = rec.n;
-    ta.ys = nd.n_cond > 0 ? h->d_ys : nullptr; ta.lam_l = 1.0f / (float)B; ta.lam_out = h->g_lam;
-    ta.lam_init = h->bd.kind ? h->g_W[0] : nullptr;
-    ta.gpart = h->d_gt; ta.scratch = h->d_gt + (size_t)G * h->n_params; ta.scratch_per_wg = adj_test_scratch_floats(nd);
-    ta.B = B; ta.n_params = (int)h->n_params;
-    if (launch_adj_test(nd, ta, st) != hipSuccess) { (void)hipGetLastError(); return fail(h, CNF_ERR_UNSUPPORTED, "network too wide for the TestMode adjoint kernel"); }
-    HIPCHK(h, launch_grad_reduce(h->d_gt, grad, (int)h->n_params, G, st));
-    h->grad_last_B = B;                                    // (g_lam holds d loss / d z(t0): cnf_grad_x)
+    if ((s = test_backward(h, B, rec.hs, nullptr, grad, st)) != CNF_OK) return s;
     HIPCHK(h, hipStreamSynchronize(st));
     if ((s = cnf_loss_from_sums(h, mode, sums, loss_out)) != CNF_OK) return s;
     if (stats) { *stats = sst; stats->launches += 2; }
@@ -2107,6 +2178,76 @@ extern "C" cnf_status cnf_loss_grad_test_host(cnf_handle h, const float* xs, int
     HIPCHK(h, hipMemcpy(h->stage, xs, nx * sizeof(float), hipMemcpyHostToDevice));
     if ((s = cnf_loss_grad_test(h, h->stage, B, opts, loss_out, h->g_grad, stats, nullptr)) != CNF_OK) return s;
     HIPCHK(h, hipMemcpy(grad, h->g_grad, h->n_params * sizeof(float), hipMemcpyDeviceToHost));
+    return CNF_OK;
+}
+
+// ---- differentiable inference: the two halves of cnf_loss_grad / cnf_loss_grad_test as entry points of their own -----------------
+// cnf_inference_record is the forward half (the recorded solve; outputs as cnf_inference), cnf_inference_pullback the backward
+// half for ANY cotangent of the four outputs: sum_b sum_r cot[r][b] d out_r[b] / d ps.  The samples are independent given the
+// accepted steps, so the generalisation of the loss's pullback is exact: the three launch-wide scalars of the scalar rows become
+// three floats per sample (k_vjp_cotangent packs them next to the general terminal cotangent; the pullback kernels read them
+// through AdjArgs::cw / Adj3bSteps::cw / AdjTestArgs::w_l, null on every other call).
+// k_solve_wave<GRAD>, the in-launch gradient of small networks, is NOT extended: it carries the cotangent of the loss only, so a
+// recorded call on such a network takes the recorded solve and the MFMA / generic pullback, as a non-default basedist already does.
+// Rows the handle does not integrate carry no cotangent: lambda1 = 0 -> E = 0 and cot_E is ignored, likewise lambda2 / n and
+// lambda3 / A, and rows 1-3 in TestMode.  A caller who wants d E builds the model with lambda1 != 0.
+extern "C" cnf_status cnf_inference_record(cnf_handle h, int mode, const float* xs, const float* eps, int B, const cnf_solve_opts* opts,
+                                           float* logpx, float* regs, cnf_solve_stats* stats, void* stream) {
+    cnf_status s = check_call(h, mode, B);
+    if (s != CNF_OK) return s;
+    const bool train = mode == CNF_MODE_TRAIN;
+    if (!xs || !opts || !logpx || !regs || (train && !eps)) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    if (B < 1) return fail(h, CNF_ERR_BAD_SHAPE, "a recorded inference needs B >= 1");
+    if (train) {
+        const GradLayout gl = grad_layout(h->nd);
+        if (!grad_supported(h->nd, gl)) return fail(h, CNF_ERR_UNSUPPORTED, "network too wide for the gradient kernels");
+    }
+    if ((s = ensure_capacity(h, B)) != CNF_OK) return s;
+    if ((s = ensure_grad_capacity(h, B)) != CNF_OK) return s;
+    hipStream_t st = (hipStream_t)stream;
+    if ((size_t)3 * B > h->cw_floats) {
+        HIPCHK(h, hipStreamSynchronize(st));
+        if (h->d_cw) { (void)hipFree(h->d_cw); h->d_cw = nullptr; h->cw_floats = 0; }
+        const size_t cap = ((size_t)3 * B + 1023) & ~(size_t)1023;
+        HIPCHK(h, hipMalloc(&h->d_cw, cap * sizeof(float)));
+        h->cw_floats = cap;
+    }
+    Recorder rec;
+    cnf_solve_stats sst{};
+    if (train) s = train_forward(h, xs, eps, B, opts, rec, sst, stream);
+    else s = test_forward(h, xs, B, opts, rec, sst, stream);
+    if (s != CNF_OK) return s;
+    HIPCHK(h, hipMemcpyAsync(logpx, h->tmp_logpx, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(regs, h->tmp_regs, (size_t)3 * B * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    h->rec_valid = true; h->rec_mode = mode; h->rec_B = B; h->rec_kernel = opts->kernel; h->rec_eps = train ? eps : nullptr;
+    if (stats) *stats = sst;
+    return CNF_OK;
+}
+
+extern "C" cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int B, float* grad, void* stream) {
+    if (!h) return CNF_ERR_BAD_ARG;
+    if (!cot || !grad) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    if (!h->rec_valid || B != h->rec_B || (size_t)h->last_hs.size() == 0 || !h->d_cw)
+        return fail(h, CNF_ERR_BAD_ARG, "no recorded solve of a batch of this size: call cnf_inference_record first");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    cnf_status s;
+    const std::vector<float> hs = h->last_hs;
+    if (h->rec_mode == CNF_MODE_TRAIN) {
+        if (!h->pt_valid) {
+            const GradLayout gl = grad_layout(h->nd);
+            const AdjMfmaLayout am = adj_mfma_layout(h->nd, gl);
+            HIPCHK(h, launch_transpose_params(h->nd, h->d_params, h->d_PT, st));
+            HIPCHK(h, launch_pack_adj_images(h->nd, gl, am, h->d_params, h->d_adj_img, st));
+            h->pt_valid = true;
+        }
+        s = train_backward(h, h->rec_eps, B, h->rec_kernel, hs, cot, grad, st);
+    } else {
+        s = test_backward(h, B, hs, cot, grad, st);
+    }
+    if (s != CNF_OK) { h->rec_valid = false; return s; }
+    HIPCHK(h, hipStreamSynchronize(st));
     return CNF_OK;
 }
 
@@ -2163,6 +2304,7 @@ extern "C" cnf_status cnf_set_params_async(cnf_handle h, const float* flat_dev, 
     cnf_status ms = mfma_plan_pack(h->mfma, h->nd, h->d_params, s);
     if (ms != CNF_OK) return fail(h, ms, "MFMA weight packing failed");
     h->have_params = true;
+    h->rec_valid = false;
     h->pt_valid = false; h->img_valid = false; h->bimg_valid = false;
     h->cond_B = 0;
     return CNF_OK;

@@ -20,6 +20,7 @@ struct Adj3bSteps {
     float* HS; float* TS;           // [6 steps][B][sum_in]
     float* AB; float* PB;           // [6 steps][B][sum_out]
     float lam_l, lam_E, lam_n;      // cotangents of the three scalar rows (constant along the solve)
+    const float* cw;                // null, or [3][B] per-sample cotangents (w_l, w_E, w_n) of those rows IN PLACE of the three scalars
     float bw[6];                    // b_i
     float kc[6][5];                 // kc[m][d] = a_{m, m-1-d} (0 past stage 0): what zbar_m adds to the sum of the d-th stage after it
     int B;

@@ -65,7 +65,10 @@ __device__ __forceinline__ f32x4 a3b_d2tanh4(const f32x4& h, const f32x4& d1) { 
 //            tbar_1 q_1, tbar_2 q_2 (lane order: coalesced both ways) and the owner rows s'_3, eps q_3, c_E zdot / |zdot|;
 //   PHASE 2, grid (tiles): per stage the parked state back, abar_3 = ahat s'_3 + eps q_3, the hbar chain (AB), zbar and the
 //            bookkeeping of lambda -- four barrier intervals instead of thirteen, and only the transposed weights resident.
-template <int PHASE>
+// CW: the cotangents of the three scalar rows are per sample (Adj3bSteps::cw) instead of the launch's three scalars.  A template
+// parameter, not a branch on the pointer: with the branch the one-launch form gained 4 bytes of scratch per lane at its 256
+// registers (profiles/vjp_kernel_resources.md), so the instantiations without weights stay exactly the code they were.
+template <int PHASE, bool CW = false>
 __global__ void __launch_bounds__(512, 2)
 k_adj3b(NetDesc nd, GradLayout gl, const char* __restrict__ imgb, Adj3bSteps M) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -296,6 +299,13 @@ k_adj3b(NetDesc nd, GradLayout gl, const char* __restrict__ imgb, Adj3bSteps M) 
         asm volatile("" : "+v"(zopq));
         const int orow = b0 + smp + zopq;
         const int ocnt = olive ? nv : 0;
+        // The cotangent of scalar row r of the owner lane's sample: the launch's scalar, or (CW) its entry of the [3][B] weights -- read
+        // where it is used (L2-resident, 12 B bytes per launch) instead of held over the stage: at this kernel's register budget
+        // a live float per lane is a spilled one.
+        auto own_cw = [&](int r, float c) __attribute__((always_inline)) -> float {
+            if (!CW) return c;
+            return olive ? M.cw[(size_t)r * M.B + orow] : 0.f;
+        };
       if (PHASE != 2) {
         // ---- sweep 1: forward.  I0: layer 1, tile `wave`, both halves (K = 32) ----
         {
@@ -370,7 +380,7 @@ k_adj3b(NetDesc nd, GradLayout gl, const char* __restrict__ imgb, Adj3bSteps M) 
             s3b_store4(ldsb + a3b::H2G + wb_wr + HBW, a3b::WP, pb);
             if (zown) {                                    // ahat = kbar_z + c_E zdot / |zdot|   (|zdot|^2: complete since the barrier)
                 const float nz = red8(0);
-                const float inv = (nd.norm_z && nz > 0.f) ? (a.hstep * a.cb * M.lam_E) * __builtin_amdgcn_rsqf(nz) : 0.f;
+                const float inv = (nd.norm_z && nz > 0.f) ? (a.hstep * a.cb * own_cw(1, M.lam_E)) * __builtin_amdgcn_rsqf(nz) : 0.f;
                 if (PHASE == 1) *ownp(a3b::AHAT) = ld4_mask(inv * zdv, ocnt);      // (parked; PHASE 2 adds kbar_z)
                 else *ownp(a3b::AHAT) = ld4_mask(*ownp(a3b::AHAT) + inv * zdv, ocnt);
             }
@@ -418,8 +428,8 @@ k_adj3b(NetDesc nd, GradLayout gl, const char* __restrict__ imgb, Adj3bSteps M) 
         // E1 (owner lanes): tau = -c_l eps + c_n eJ / |eJ| -> X0S as t_0, TS; the next stage's state is requested
         if (zown) {
             const float nj = red8(1);
-            const float inv = (nd.norm_j && nj > 0.f) ? (a.hstep * a.cb * M.lam_n) * __builtin_amdgcn_rsqf(nj) : 0.f;
-            const f32x4 tau = ld4_mask(inv * *ownp(a3b::EJ) - (a.hstep * a.cb * M.lam_l) * *ownp(a3b::EPSA), nv);
+            const float inv = (nd.norm_j && nj > 0.f) ? (a.hstep * a.cb * own_cw(2, M.lam_n)) * __builtin_amdgcn_rsqf(nj) : 0.f;
+            const f32x4 tau = ld4_mask(inv * *ownp(a3b::EJ) - (a.hstep * a.cb * own_cw(0, M.lam_l)) * *ownp(a3b::EPSA), nv);
             s3b_store4(x0w, a3b::NP, tau);
         }
         A3T(12);
@@ -607,11 +617,14 @@ hipError_t launch_adj3b(const NetDesc& nd, const GradLayout& g, const void* d_im
         M.step_hi - M.step_lo >= ADJ3B_MAX_STEPS || M.B < 1) return hipErrorInvalidValue;
     const int tiles = (M.B + 31) / 32, steps = M.step_hi - M.step_lo + 1;
     // (per launch: the attribute belongs to the current device, and a process may drive several)
+    // (the parked second launch reads no scalar-row cotangent: one instantiation)
     auto go = [&](auto phase_c, dim3 grid) -> hipError_t {
         constexpr int PH = decltype(phase_c)::value;
-        hipError_t e = hipFuncSetAttribute((const void*)k_adj3b<PH>, hipFuncAttributeMaxDynamicSharedMemorySize, a3b::TOTAL_BYTES);
+        const void* f = (M.cw && PH != 2) ? (const void*)k_adj3b<PH, PH != 2> : (const void*)k_adj3b<PH, false>;
+        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, a3b::TOTAL_BYTES);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_adj3b<PH>), grid, dim3(512), a3b::TOTAL_BYTES, s, nd, g, (const char*)d_img3b, M);
+        if (M.cw && PH != 2) hipLaunchKernelGGL((k_adj3b<PH, PH != 2>), grid, dim3(512), a3b::TOTAL_BYTES, s, nd, g, (const char*)d_img3b, M);
+        else hipLaunchKernelGGL((k_adj3b<PH, false>), grid, dim3(512), a3b::TOTAL_BYTES, s, nd, g, (const char*)d_img3b, M);
         return hipGetLastError();
     };
     if (!M.park || !adj3b_split(M.B, steps)) return go(std::integral_constant<int, 0>{}, dim3(tiles));

@@ -26,3 +26,10 @@ void launch_base_cotangent(const NetDesc& nd, int D, const BaseDist& bd, float l
                            hipStream_t s);
 // z0[b] = mean + L n_b   ([B][n_in] both; must not alias)
 void launch_base_sample(int n_in, const BaseDist& bd, const float* normals, float* z0, int B, hipStream_t s);
+// The terminal cotangent of cnf_inference_pullback for cot = [4][B] (rows logpx, E, n, A) and, in the same launch, the pack of
+// the per-sample weights of the three scalar rows for the pullback kernels (logpx = logpz - dlogp: the dlogp row carries -cot_l):
+//   lam[b] = cot_l[b] d logpdf(basedist, z_b) / d z + cot_A[b] unit(z_aug, b)     (N(0, I), kind 0: -cot_l[b] z_b)
+//   cw = [3][B]: w_l = -cot_l, w_E = cot_E, w_n = cot_n
+// with_A = 0 (TestMode, or a handle that does not integrate the A row): cot_A is not read.
+void launch_vjp_cotangent(const NetDesc& nd, int D, const BaseDist& bd, int with_A, const float* fsol, const float* cot, float* lam,
+                          float* cw, int B, hipStream_t s);

@@ -111,6 +111,47 @@ k_base_cotangent(NetDesc nd, int D, BaseDist bd, float lambda3, const float* __r
     }
 }
 
+// The general terminal cotangent (cnf_dist.h): k_base_cotangent with the sample's own (cot_l, cot_A) in place of (-1/B, lambda3/B),
+// kind 0 included (prec = I, mean = 0), and the [3][B] weights of the scalar rows written by the sample's first lane.
+__global__ void __launch_bounds__(256)
+k_vjp_cotangent(NetDesc nd, int D, BaseDist bd, int with_A, const float* __restrict__ fsol, const float* __restrict__ cot,
+                float* __restrict__ lam, float* __restrict__ cw, int B) {
+    const int tid = threadIdx.x, p = tid & 3;
+    const int b = blockIdx.x * 64 + (tid >> 2);
+    const int n_in = nd.n_in;
+    const float* c = fsol + (size_t)min(b, B - 1) * D;
+    const bool aug = with_A && nd.norm_z_aug && nd.naugs > 0;
+    float sa = 0.f;
+    if (aug) {
+        for (int i = nd.nvars + p; i < n_in; i += 4) sa = fmaf(c[i], c[i], sa);
+        sa += __shfl_xor(sa, 1, 64);
+        sa += __shfl_xor(sa, 2, 64);
+    }
+    if (b >= B) return;
+    const float gl = cot[b], gA = aug ? cot[3 * (size_t)B + b] : 0.f;
+    const float nrm = sqrtf(sa);
+    for (int i = p; i < n_in; i += 4) {
+        float v;                                     // -d logpdf / d z_i
+        if (bd.kind == 0) {
+            v = c[i];
+        } else if (bd.kind == 1) {
+            v = bd.prec[i] * (c[i] - bd.mean[i]);
+        } else {
+            const float* pr = bd.prec + (size_t)i * n_in;
+            v = 0.f;
+            for (int j = 0; j < n_in; ++j) v = fmaf(pr[j], c[j] - bd.mean[j], v);
+        }
+        v = -gl * v;
+        if (aug && i >= nd.nvars && nrm > 0.f) v = fmaf(gA, c[i] / nrm, v);
+        lam[(size_t)b * n_in + i] = v;
+    }
+    if (p == 0) {
+        cw[b] = -gl;
+        cw[(size_t)B + b] = cot[(size_t)B + b];
+        cw[2 * (size_t)B + b] = cot[2 * (size_t)B + b];
+    }
+}
+
 // z0[b][i] = mean_i + sum_{j <= i} L_ij n[b][j], one lane per entry; the sum runs over j upwards and the mean is added last
 __global__ void __launch_bounds__(256)
 k_base_sample(int n_in, BaseDist bd, const float* __restrict__ nrm, float* __restrict__ z0, size_t n) {
@@ -139,6 +180,11 @@ void launch_base_post(int n_in, int D, const BaseDist& bd, const StepState* st, 
 void launch_base_cotangent(const NetDesc& nd, int D, const BaseDist& bd, float lambda3, const float* fsol, float* lam, int B,
                            hipStream_t s) {
     hipLaunchKernelGGL(k_base_cotangent, dim3((B + 63) / 64), dim3(256), 0, s, nd, D, bd, lambda3, fsol, lam, B);
+}
+
+void launch_vjp_cotangent(const NetDesc& nd, int D, const BaseDist& bd, int with_A, const float* fsol, const float* cot, float* lam,
+                          float* cw, int B, hipStream_t s) {
+    hipLaunchKernelGGL(k_vjp_cotangent, dim3((B + 63) / 64), dim3(256), 0, s, nd, D, bd, with_A, fsol, cot, lam, cw, B);
 }
 
 void launch_base_sample(int n_in, const BaseDist& bd, const float* normals, float* z0, int B, hipStream_t s) {

@@ -27,11 +27,21 @@ struct AdjArgs {
     float cb;                       // b_i
     float hstep;                    // signed step size
     float c_l, c_E, c_n;            // h * b_i * (cotangents of the three scalar rows)
+    const float* cw;                // null (the loss: the three scalars above are all there is), or [3][B] per-sample cotangents
+                                    // (w_l, w_E, w_n) of the three scalar rows; then c_l = c_E = c_n = h * b_i  (adj_cw)
     float* w_out;                   // [B][n_in]
     float* HS; float* TS;           // [B][sum_in]
     float* AB; float* PB;           // [B][sum_out]
     int B;
 };
+
+// The cotangent of scalar row r (0: dlogp, 1: E, 2: n) of sample b, times h b_i.  Without per-sample weights it is the launch-wide
+// scalar c, untouched (a wave-uniform branch on the pointer: the loss's pullback keeps its arithmetic); with them c cw[r][b],
+// and 0 past the batch.
+__device__ __forceinline__ float adj_cw(const float* __restrict__ cw, int r, int b, int B, float c) {
+    if (!cw) return c;
+    return b < B ? c * cw[(size_t)r * B + b] : 0.f;
+}
 
 // the six stage pullbacks of one Runge-Kutta step in one launch (MFMA pullback): stages first .. last, then
 // lambda <- lambda + sum of their zbar

@@ -163,7 +163,7 @@ __global__ void k_adj(NetDesc nd, GradLayout gl, AdjArgs a) {
             float v = kb;
             if (nd.norm_z) {
                 const float nrm = sqrtf(nz[s]);
-                if (nrm > 0.f) v = fmaf(a.c_E, lds[(size_t)s * PS + L.H + hL + f] / nrm, v);
+                if (nrm > 0.f) v = fmaf(adj_cw(a.cw, 1, b, a.B, a.c_E), lds[(size_t)s * PS + L.H + hL + f] / nrm, v);
             }
             lds[(size_t)s * PS + L.HB0 + f] = v;
         }
@@ -252,10 +252,10 @@ __global__ void k_adj(NetDesc nd, GradLayout gl, AdjArgs a) {
                 float* S = lds + (size_t)s * PS;
                 float v = 0.f;
                 if (f < n_in) {
-                    v = -a.c_l * S[L.EPS + f];
+                    v = -adj_cw(a.cw, 0, b0 + s, a.B, a.c_l) * S[L.EPS + f];
                     if (nd.norm_j) {
                         const float nrm = sqrtf(nj[s]);
-                        if (nrm > 0.f) v = fmaf(a.c_n, S[L.T + f] / nrm, v);
+                        if (nrm > 0.f) v = fmaf(adj_cw(a.cw, 2, b0 + s, a.B, a.c_n), S[L.T + f] / nrm, v);
                     }
                 }
                 S[L.T + f] = v;
@@ -282,10 +282,10 @@ __global__ void k_adj(NetDesc nd, GradLayout gl, AdjArgs a) {
 #pragma unroll
             for (int s = 0; s < TS; ++s) {
                 float* S = lds + (size_t)s * PS;
-                float v = -a.c_l * S[L.EPS + f];
+                float v = -adj_cw(a.cw, 0, b0 + s, a.B, a.c_l) * S[L.EPS + f];
                 if (nd.norm_j) {
                     const float nrm = sqrtf(nj[s]);
-                    if (nrm > 0.f) v = fmaf(a.c_n, S[L.T + hL + f] / nrm, v);
+                    if (nrm > 0.f) v = fmaf(adj_cw(a.cw, 2, b0 + s, a.B, a.c_n), S[L.T + hL + f] / nrm, v);
                 }
                 S[L.TB + oL + f] = v;
             }
@@ -1196,7 +1196,10 @@ extern "C" int cnf_debug_adj_stamps(unsigned long long* out, int n) {
 // eps's place in E and sweep 3 is the tbar chain from it, layers L .. 2 (tbar_0 is nobody's); the hbar chain and the parked rows are
 // those of the VJP mode with tbar_L = omega where that has eps.  Factor rows: HS = h_{l-1}, TS = tau_{l-1}, AB = abar_l,
 // PB = s'_l .* tbar_l, so the contraction kernels do not know the difference.
-template <bool ALL_TANH, int PHASE, bool JM = false>
+// CW: per-sample cotangents of the scalar rows (AdjArgs::cw) -- a template parameter: as a branch on the pointer it cost the JVP
+// form 1.2 % at the headline shape (7.07 against 6.99 ms per gradient at B = 8192, profiles/vjp_timing.txt), so the instantiations
+// without weights are the code they were.
+template <bool ALL_TANH, int PHASE, bool JM = false, bool CW = false>
 __device__ __forceinline__ void adj_mfma_body(const NetDesc& nd, const GradLayout& gl, const AdjMfmaLayout& m, const float* __restrict__ img,
                                               const AdjStepArgs& S, float* __restrict__ SC, int ystage) {
     extern __shared__ float lds[];
@@ -1268,7 +1271,7 @@ __device__ __forceinline__ void adj_mfma_body(const NetDesc& nd, const GradLayou
             for (int r = ec; r < m.nin_p; r += AM_EC) if (ev) scrow[3 * m.sum_o + r] = lds[es * PS + zd + r];
             if (ev && ec == 0) scrow[3 * m.sum_o + m.nin_p] = nz;
         } else {
-            const float inv = (nd.norm_z && nz > 0.f) ? a.c_E * __builtin_amdgcn_rsqf(nz) : 0.f;
+            const float inv = (nd.norm_z && nz > 0.f) ? adj_cw(CW ? a.cw : nullptr, 1, eb, S.B, a.c_E) * __builtin_amdgcn_rsqf(nz) : 0.f;
             for (int rb = ec; rb < m.nin_p; rb += 4 * AM_EC) {
                 float kb[4];
                 am_kbar4(a, ev, eb, n_in, rb, kb);
@@ -1309,10 +1312,11 @@ __device__ __forceinline__ void adj_mfma_body(const NetDesc& nd, const GradLayou
     {   // J eps in S[cur]: omega = -c_l eps + c_n J eps / |J eps| -> E (over eps); pbar_L = s'_L .* omega -> S[nxt], PB
         float nj = 0.f;
         if (nd.norm_j) nj = am_colnorm2(lds + cur, PS, n_in, red);
-        const float inv = (nd.norm_j && nj > 0.f) ? a.c_n * __builtin_amdgcn_rsqf(nj) : 0.f;
+        const float inv = (nd.norm_j && nj > 0.f) ? adj_cw(CW ? a.cw : nullptr, 2, eb, S.B, a.c_n) * __builtin_amdgcn_rsqf(nj) : 0.f;
+        const float cl = adj_cw(CW ? a.cw : nullptr, 0, eb, S.B, a.c_l);
         for (int r = ec; r < m.dp[NL]; r += AM_EC) {
             float* Sr = lds + es * PS;
-            const float om = r < n_in ? fmaf(inv, Sr[cur + r], -a.c_l * Sr[m.E + r]) : 0.f;
+            const float om = r < n_in ? fmaf(inv, Sr[cur + r], -cl * Sr[m.E + r]) : 0.f;
             const float pb = om * Sr[m.D1 + oL + r];
             if (r < m.nin_p) Sr[m.E + r] = om;
             Sr[nxt + r] = pb;
@@ -1424,7 +1428,7 @@ __device__ __forceinline__ void adj_mfma_body(const NetDesc& nd, const GradLayou
             // free now that pbar_L (parked there by sweep 1) has been consumed by this GEMM.
             float nz = 0.f;
             if (nd.norm_z) nz = am_colnorm2(lds + zd, PS, n_in, red);
-            const float inv = (nd.norm_z && nz > 0.f) ? a.c_E * __builtin_amdgcn_rsqf(nz) : 0.f;
+            const float inv = (nd.norm_z && nz > 0.f) ? adj_cw(CW ? a.cw : nullptr, 1, eb, S.B, a.c_E) * __builtin_amdgcn_rsqf(nz) : 0.f;
             // (all five zbar slots are read -- the unused ones point at a readable array with weight 0 -- and four rows per thread
             // are requested before the first is used: one round trip to memory per four rows instead of up to six per row)
             for (int rb = ec; rb < m.nin_p; rb += 4 * AM_EC) {
@@ -1444,10 +1448,11 @@ __device__ __forceinline__ void adj_mfma_body(const NetDesc& nd, const GradLayou
     {
         float nj = 0.f;
         if (nd.norm_j) nj = am_colnorm2(lds + cur, PS, n_in, red);
-        const float inv = (nd.norm_j && nj > 0.f) ? a.c_n * __builtin_amdgcn_rsqf(nj) : 0.f;
+        const float inv = (nd.norm_j && nj > 0.f) ? adj_cw(CW ? a.cw : nullptr, 2, eb, S.B, a.c_n) * __builtin_amdgcn_rsqf(nj) : 0.f;
+        const float cl = adj_cw(CW ? a.cw : nullptr, 0, eb, S.B, a.c_l);
         for (int r = ec; r < m.dp[0]; r += AM_EC) {
             float v = 0.f;
-            if (r < n_in) v = fmaf(inv, lds[es * PS + cur + r], -a.c_l * lds[es * PS + m.E + r]);
+            if (r < n_in) v = fmaf(inv, lds[es * PS + cur + r], -cl * lds[es * PS + m.E + r]);
             lds[es * PS + nxt + r] = v;
             if (ev && r < in0) a.TS[(size_t)eb * gl.sum_in + r] = v;
         }
@@ -1511,7 +1516,7 @@ __device__ __forceinline__ void adj_mfma_body(const NetDesc& nd, const GradLayou
                                     : ((ev && r < n_in) ? a.eps[(size_t)eb * n_in + r] : 0.f);
     }
     am_barrier();
-    const float inv = (nd.norm_z && nz > 0.f) ? a.c_E * __builtin_amdgcn_rsqf(nz) : 0.f;
+    const float inv = (nd.norm_z && nz > 0.f) ? adj_cw(CW ? a.cw : nullptr, 1, eb, S.B, a.c_E) * __builtin_amdgcn_rsqf(nz) : 0.f;
     for (int rb = ec; rb < m.nin_p; rb += 4 * AM_EC) {
         float kb[4];
         if (rb == ec) { kb[0] = kb0[0]; kb[1] = kb0[1]; kb[2] = kb0[2]; kb[3] = kb0[3]; }
@@ -1576,29 +1581,29 @@ __device__ __forceinline__ void adj_mfma_body(const NetDesc& nd, const GradLayou
   }
 }
 
-template <bool ALL_TANH, bool JM>
+template <bool ALL_TANH, bool JM, bool CW = false>
 __global__ void __launch_bounds__(AM_THREADS)
 k_adj_mfma(NetDesc nd, GradLayout gl, AdjMfmaLayout m, const float* __restrict__ img, AdjStepArgs S) {
-    adj_mfma_body<ALL_TANH, 0, JM>(nd, gl, m, img, S, nullptr, 0);
+    adj_mfma_body<ALL_TANH, 0, JM, CW>(nd, gl, m, img, S, nullptr, 0);
 }
 
 // (one step in two launches with its arguments by value: 5 % faster than through the device array -- 128 + 124 against
 // 137 + 129 us per step at config 5, B = 2048 -- so a sub-run of ONE step takes this form)
-template <bool ALL_TANH, int PHASE, bool JM>
+template <bool ALL_TANH, int PHASE, bool JM, bool CW = false>
 __global__ void __launch_bounds__(AM_THREADS)
 k_adj_mfma_split(NetDesc nd, GradLayout gl, AdjMfmaLayout m, const float* __restrict__ img, AdjStepArgs S, float* __restrict__ SC) {
-    adj_mfma_body<ALL_TANH, PHASE, JM>(nd, gl, m, img, S, SC, blockIdx.y);
+    adj_mfma_body<ALL_TANH, PHASE, JM, CW>(nd, gl, m, img, S, SC, blockIdx.y);
 }
 
-template <bool ALL_TANH, int PHASE, bool JM>
+template <bool ALL_TANH, int PHASE, bool JM, bool CW = false>
 __global__ void __launch_bounds__(AM_THREADS)
 k_adj_mfma_run(NetDesc nd, GradLayout gl, AdjMfmaLayout m, const float* __restrict__ img, const AdjStepArgs* __restrict__ SA, int nsteps,
                float* __restrict__ SC) {
     if (PHASE == 1) {
         const int j = blockIdx.y / 6;
-        adj_mfma_body<ALL_TANH, 1, JM>(nd, gl, m, img, SA[j], SC + (size_t)6 * j * SA[j].B * m.SR, blockIdx.y % 6);
+        adj_mfma_body<ALL_TANH, 1, JM, CW>(nd, gl, m, img, SA[j], SC + (size_t)6 * j * SA[j].B * m.SR, blockIdx.y % 6);
     } else {
-        for (int j = 0; j < nsteps; ++j) adj_mfma_body<ALL_TANH, 2, JM>(nd, gl, m, img, SA[j], SC + (size_t)6 * j * SA[j].B * m.SR, 0);
+        for (int j = 0; j < nsteps; ++j) adj_mfma_body<ALL_TANH, 2, JM, CW>(nd, gl, m, img, SA[j], SC + (size_t)6 * j * SA[j].B * m.SR, 0);
     }
 }
 
@@ -1684,7 +1689,9 @@ __device__ __forceinline__ float adj3_fetch(const AdjArgs& a, const NetDesc& nd,
 
 static size_t adj3_lds_bytes(const AdjMfmaLayout& m) { return ((size_t)A3_NS * m.PS + (size_t)AM_EC * A3_NS) * sizeof(float); }
 
-template <bool ALL_TANH>
+// CW: per-sample cotangents of the scalar rows (AdjArgs::cw).  A template parameter here: the branch on the pointer cost
+// k_adj3<true> 36 bytes of scratch per lane at its 256 registers (profiles/vjp_kernel_resources.md).
+template <bool ALL_TANH, bool CW = false>
 __global__ void __launch_bounds__(AM_THREADS)
 k_adj3(NetDesc nd, GradLayout gl, AdjMfmaLayout m, const float* __restrict__ img, AdjStepArgs S) {
     extern __shared__ float lds[];
@@ -1872,7 +1879,7 @@ k_adj3(NetDesc nd, GradLayout gl, AdjMfmaLayout m, const float* __restrict__ img
 #pragma unroll
             for (int p8 = 0; p8 < 8; ++p8) nzs += red[e2 * 8 + p8];
             const float nz[2] = {nzs, nzs};
-            const float inv = (nd.norm_z && nz[hs] > 0.f) ? a.c_E * __builtin_amdgcn_rsqf(nz[hs]) : 0.f;
+            const float inv = (nd.norm_z && nz[hs] > 0.f) ? adj_cw(CW ? a.cw : nullptr, 1, eb, S.B, a.c_E) * __builtin_amdgcn_rsqf(nz[hs]) : 0.f;
             lds[e2 * PS + m.AH + ec] = (ev && ec < n_in) ? fmaf(inv, lds[e2 * PS + zd + ec], kbv[hs]) : 0.f;
         }
         am_barrier();                                   // zdot's buffer is the next epilogue's target
@@ -1896,10 +1903,11 @@ k_adj3(NetDesc nd, GradLayout gl, AdjMfmaLayout m, const float* __restrict__ img
 #pragma unroll
             for (int p8 = 0; p8 < 8; ++p8) njs += red[256 + e2 * 8 + p8];
             const float nj[2] = {njs, njs};
-            const float inv = (nd.norm_j && nj[hs] > 0.f) ? a.c_n * __builtin_amdgcn_rsqf(nj[hs]) : 0.f;
+            const float inv = (nd.norm_j && nj[hs] > 0.f) ? adj_cw(CW ? a.cw : nullptr, 2, eb, S.B, a.c_n) * __builtin_amdgcn_rsqf(nj[hs]) : 0.f;
+            const float cl = adj_cw(CW ? a.cw : nullptr, 0, eb, S.B, a.c_l);
             for (int r = ec; r < NI; r += AM_EC) {
                 float v = 0.f;
-                if (r < n_in) v = fmaf(inv, lds[e2 * PS + cur + r], -a.c_l * lds[e2 * PS + m.E + r]);
+                if (r < n_in) v = fmaf(inv, lds[e2 * PS + cur + r], -cl * lds[e2 * PS + m.E + r]);
                 lds[e2 * PS + nxt + r] = v;
                 if (ev && r < in0) __builtin_nontemporal_store(v, a.TS + (size_t)eb * gl.sum_in + r);
             }
@@ -2013,27 +2021,32 @@ hipError_t launch_adj_mfma_step(const NetDesc& nd, const GradLayout& g, const Ad
     for (int l = 0; l < nd.n_layers; ++l) all_tanh = all_tanh && nd.acts[l] == 1;
     static const bool generic_only = [] { const char* e = getenv("CNF_ADJ_GENERIC"); return e && e[0] == '1'; }();
     if (adj3_shape(nd, m) && !generic_only && S.first == 5 && S.last == 0 && S.lam_update && S.lam_out) {   // (whole steps: the zbar stay in the kernel)          // resident-fragment pullback (A/B switch: CNF_ADJ_GENERIC=1)
-        const void* f3 = all_tanh ? (const void*)k_adj3<true> : (const void*)k_adj3<false>;
+        const bool cw3 = S.st[0].cw != nullptr;
+        const void* f3 = all_tanh ? (cw3 ? (const void*)k_adj3<true, true> : (const void*)k_adj3<true>)
+                                  : (cw3 ? (const void*)k_adj3<false, true> : (const void*)k_adj3<false>);
         const size_t lds3 = adj3_lds_bytes(m);
         hipError_t e3 = hipFuncSetAttribute(f3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
         if (e3 != hipSuccess) return e3;
         const dim3 grid3((S.B + A3_NS - 1) / A3_NS);
-        if (all_tanh) hipLaunchKernelGGL(k_adj3<true>, grid3, dim3(AM_THREADS), lds3, s, nd, g, m, img, S);
+        if (all_tanh && cw3) hipLaunchKernelGGL((k_adj3<true, true>), grid3, dim3(AM_THREADS), lds3, s, nd, g, m, img, S);
+        else if (all_tanh) hipLaunchKernelGGL(k_adj3<true>, grid3, dim3(AM_THREADS), lds3, s, nd, g, m, img, S);
+        else if (cw3) hipLaunchKernelGGL((k_adj3<false, true>), grid3, dim3(AM_THREADS), lds3, s, nd, g, m, img, S);
         else hipLaunchKernelGGL(k_adj3<false>, grid3, dim3(AM_THREADS), lds3, s, nd, g, m, img, S);
         return hipGetLastError();
     }
     const int tiles = (S.B + AM_NS - 1) / AM_NS;
-    auto go = [&](auto tanh_c, auto jm_c) -> hipError_t {
-        constexpr bool T = decltype(tanh_c)::value, J = decltype(jm_c)::value;
-        hipError_t e = hipFuncSetAttribute((const void*)k_adj_mfma<T, J>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    auto go = [&](auto tanh_c, auto jm_c, auto cw_c) -> hipError_t {
+        constexpr bool T = decltype(tanh_c)::value, J = decltype(jm_c)::value, W = decltype(cw_c)::value;
+        hipError_t e = hipFuncSetAttribute((const void*)k_adj_mfma<T, J, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_adj_mfma<T, J>), dim3(tiles), dim3(AM_THREADS), lds, s, nd, g, m, img, S);
+        hipLaunchKernelGGL((k_adj_mfma<T, J, W>), dim3(tiles), dim3(AM_THREADS), lds, s, nd, g, m, img, S);
         return hipGetLastError();
     };
     using B1 = std::integral_constant<bool, true>;
     using B0 = std::integral_constant<bool, false>;
-    if (nd.jvp) return all_tanh ? go(B1{}, B1{}) : go(B0{}, B1{});
-    return all_tanh ? go(B1{}, B0{}) : go(B0{}, B0{});
+    auto go2 = [&](auto tanh_c, auto jm_c) -> hipError_t { return S.st[S.first].cw ? go(tanh_c, jm_c, B1{}) : go(tanh_c, jm_c, B0{}); };
+    if (nd.jvp) return all_tanh ? go2(B1{}, B1{}) : go2(B0{}, B1{});
+    return all_tanh ? go2(B1{}, B0{}) : go2(B0{}, B0{});
 }
 
 // Two launches for a run of whole steps when that is less sequential work: the stage-parallel launch costs ~0.7 of a stage per
@@ -2062,27 +2075,29 @@ hipError_t launch_adj_mfma_run(const NetDesc& nd, const GradLayout& g, const Adj
     bool all_tanh = true;
     for (int l = 0; l < nd.n_layers; ++l) all_tanh = all_tanh && nd.acts[l] == 1;
     const int tiles = (B + AM_NS - 1) / AM_NS;
-    auto pair = [&](auto tanh_c, auto jm_c) -> hipError_t {
-        constexpr bool T = decltype(tanh_c)::value, J = decltype(jm_c)::value;
+    auto pair = [&](auto tanh_c, auto jm_c, auto cw_c) -> hipError_t {
+        constexpr bool T = decltype(tanh_c)::value, J = decltype(jm_c)::value, W = decltype(cw_c)::value;
         if (nsteps == 1) {                                 // one step: its arguments by value
-            hipError_t e = hipFuncSetAttribute((const void*)k_adj_mfma_split<T, 1, J>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_adj_mfma_split<T, 2, J>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipError_t e = hipFuncSetAttribute((const void*)k_adj_mfma_split<T, 1, J, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_adj_mfma_split<T, 2, J, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_adj_mfma_split<T, 1, J>), dim3(tiles, 6), dim3(AM_THREADS), lds, s, nd, g, m, img, h_steps[0], scratch);
-            hipLaunchKernelGGL((k_adj_mfma_split<T, 2, J>), dim3(tiles), dim3(AM_THREADS), lds, s, nd, g, m, img, h_steps[0], scratch);
+            hipLaunchKernelGGL((k_adj_mfma_split<T, 1, J, W>), dim3(tiles, 6), dim3(AM_THREADS), lds, s, nd, g, m, img, h_steps[0], scratch);
+            hipLaunchKernelGGL((k_adj_mfma_split<T, 2, J, W>), dim3(tiles), dim3(AM_THREADS), lds, s, nd, g, m, img, h_steps[0], scratch);
             return hipGetLastError();
         }
-        hipError_t e = hipFuncSetAttribute((const void*)k_adj_mfma_run<T, 1, J>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_adj_mfma_run<T, 2, J>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void*)k_adj_mfma_run<T, 1, J, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_adj_mfma_run<T, 2, J, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_adj_mfma_run<T, 1, J>), dim3(tiles, 6 * nsteps), dim3(AM_THREADS), lds, s, nd, g, m, img, d_steps, nsteps, scratch);
-        hipLaunchKernelGGL((k_adj_mfma_run<T, 2, J>), dim3(tiles), dim3(AM_THREADS), lds, s, nd, g, m, img, d_steps, nsteps, scratch);
+        hipLaunchKernelGGL((k_adj_mfma_run<T, 1, J, W>), dim3(tiles, 6 * nsteps), dim3(AM_THREADS), lds, s, nd, g, m, img, d_steps, nsteps, scratch);
+        hipLaunchKernelGGL((k_adj_mfma_run<T, 2, J, W>), dim3(tiles), dim3(AM_THREADS), lds, s, nd, g, m, img, d_steps, nsteps, scratch);
         return hipGetLastError();
     };
     using B1 = std::integral_constant<bool, true>;
     using B0 = std::integral_constant<bool, false>;
-    if (nd.jvp) return all_tanh ? pair(B1{}, B1{}) : pair(B0{}, B1{});
-    return all_tanh ? pair(B1{}, B0{}) : pair(B0{}, B0{});
+    // (every stage of every step of a run carries the same weight pointer, or none)
+    auto pair2 = [&](auto tanh_c, auto jm_c) -> hipError_t { return h_steps[0].st[0].cw ? pair(tanh_c, jm_c, B1{}) : pair(tanh_c, jm_c, B0{}); };
+    if (nd.jvp) return all_tanh ? pair2(B1{}, B1{}) : pair2(B0{}, B1{});
+    return all_tanh ? pair2(B1{}, B0{}) : pair2(B0{}, B0{});
 }
 
 size_t adj_mfma_scratch_floats(const AdjMfmaLayout& m, size_t B, int nsteps) { return (size_t)6 * nsteps * B * (size_t)m.SR; }

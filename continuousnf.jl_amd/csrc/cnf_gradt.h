@@ -11,6 +11,7 @@ struct AdjTestArgs {
     int nsteps;
     const float* ys;           // [B][n_cond] or null
     float lam_l;               // cotangent of the dlogp row: 1 / B
+    const float* w_l;          // null, or [B]: per-sample cotangent of the dlogp row in place of lam_l (then lam_init is given too)
     const float* lam_init;     // [B][n_in]: d loss / d z(t1) of a non-default base distribution; null: z(t1) lam_l (N(0, I))
     float* lam_out;            // [B][n_in]: d loss / d z(t0)   (cnf_grad_x)
     float* gpart;              // [adj_test_workgroups(B)][n_params]: one partial of the flat gradient per workgroup

@@ -110,10 +110,11 @@ k_adj_test(NetDesc nd, AdjTestArgs a, const GtTab tab, int pq_lds) {
     for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
         // conditioning rows of x0 (constant over the solve) and d loss / d z(t1) = z(t1) / B
         for (int k = tid; k < nd.n_cond; k += GT_THREADS) x0[n_in + k] = a.ys[(size_t)b * nd.n_cond + k];
+        const float lam_l = a.w_l ? a.w_l[b] : a.lam_l;                     // (one sample per workgroup: uniform either way)
         {
             const float* uf = a.traj + (size_t)a.nsteps * a.slot_stride + (size_t)b * D;
             const float* li = a.lam_init ? a.lam_init + (size_t)b * n_in : nullptr;
-            for (int i = tid; i < n_in; i += GT_THREADS) lam[i] = li ? li[i] : uf[i] * a.lam_l;
+            for (int i = tid; i < n_in; i += GT_THREADS) lam[i] = li ? li[i] : uf[i] * lam_l;
         }
         __syncthreads();
         for (int step = a.nsteps - 1; step >= 0; --step) {
@@ -139,7 +140,7 @@ k_adj_test(NetDesc nd, AdjTestArgs a, const GtTab tab, int pq_lds) {
             }
             // ---- the six pullbacks, last stage first ----
             for (int st = 5; st >= 0; --st) {
-                const float c = hstep * tab.b[st] * a.lam_l;                 // cotangent of ldot = -tr J
+                const float c = hstep * tab.b[st] * lam_l;                   // cotangent of ldot = -tr J
                 for (int i = tid; i < n_in; i += GT_THREADS) {
                     float acc = tab.b[st] * lam[i];
                     for (int m = st + 1; m < 6; ++m) acc = fmaf(tab.a[m][st], Ws[m * n_in + i], acc);

@@ -99,7 +99,8 @@ class ICNFModel:
     """src/exts/mlj_ext/core_icnf.jl:1-29 (same field names and defaults; ``adtype`` has no meaning
     here -- the derivative is the device adjoint)."""
     m: ICNF
-    loss: Callable | None = None                            # the reference's second positional argument; None = `loss` (src/icnf.jl:481-490)
+    loss: Callable | None = None                            # the reference's second positional argument; None = `loss` (src/icnf.jl:481-490);
+                                                            # else loss(icnf, mode, xs, [ys,] ps, st) -> 0-dim tensor on vjp.differentiable_inference
     optimizers: tuple = field(default_factory=lambda: (Lion(),))
     n_epochs: int = 300
     adtype: Any = None                                      # accepted, unused: the derivative is the device adjoint
@@ -127,10 +128,11 @@ def fit(model: ICNFModel, verbosity: int, X, ys=None):
     a numpy array.  ``ys`` (n x n_cond) for the conditional models (core_cond_icnf.jl)."""
     import torch
     icnf = model.m
-    if model.loss is not None:
-        from .base_icnf import loss as _builtin_loss
-        if model.loss is not _builtin_loss:
-            raise NotImplementedError("ICNFModel.loss: the device adjoint differentiates the package's own loss (src/icnf.jl:481-490)")
+    # ICNFModel.loss (core_icnf.jl:1-29, :59-62): None or the package's own `loss` keep the device adjoint of that loss
+    # (loss_and_grad); any other callable loss(icnf, mode, xs, [ys,] ps, st) -> 0-dim tensor built on
+    # vjp.differentiable_inference is differentiated with torch.autograd in the synchronous loop.
+    from .base_icnf import loss as _builtin_loss
+    custom = model.loss if (model.loss is not None and model.loss is not _builtin_loss) else None
     x = _device_matrix(icnf, X)
     n = x.shape[1]
     y = None
@@ -149,7 +151,7 @@ def fit(model: ICNFModel, verbosity: int, X, ys=None):
     # update and the next parameter upload are enqueued behind them on the same stream, and the host only ever waits for the
     # launch before the previous one -- the GPU goes from one gradient straight into the next.  Where the gradient does not run
     # in the launch of the solve (larger networks), or a submitted launch gives up, the loop below is the synchronous one.
-    pipelined = model.callback is None and model.pipelined and x.is_cuda
+    pipelined = model.callback is None and model.pipelined and x.is_cuda and custom is None     # (a custom loss: synchronous)
     n_iter = len(model.optimizers) * model.n_epochs * ((n + bs - 1) // bs)
     losses_dev = torch.full((max(1, n_iter),), float("nan"), dtype=torch.float32, device=x.device)   # one scalar per iteration: no gradient buffer is kept
     pending = []                                                      # (loss index, batch indices) of the launches still in flight
@@ -166,7 +168,14 @@ def fit(model: ICNFModel, verbosity: int, X, ys=None):
     def sync_step(opt, state, idx, slot):
         xb = x[:, idx]
         args = (xb, y[:, idx], ps, st) if y is not None else (xb, ps, st)
-        val, g = loss_and_grad(icnf, TrainMode(), *args)
+        if custom is not None:
+            p = ps.detach().requires_grad_(True)               # (shares ps's storage: the optimiser updates ps in place below)
+            cargs = (xb, y[:, idx], p, st) if y is not None else (xb, p, st)
+            out = custom(icnf, TrainMode(), *cargs)
+            g, = torch.autograd.grad(out, p)
+            val = float(out.detach())
+        else:
+            val, g = loss_and_grad(icnf, TrainMode(), *args)
         opt.apply(state, ps, g)
         losses[slot] = val
         return val

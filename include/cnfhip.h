@@ -324,6 +324,25 @@ int cnf_grad_steps(cnf_handle h, float* hs, int cap);
  * 275-276): left behind by the backward sweep, nothing is recomputed.  B must be that call's batch size. */
 cnf_status cnf_grad_x(cnf_handle h, float* gx, int B, void* stream);
 
+/* ---- differentiable inference: the vector-Jacobian product of `inference` for ANY cotangent of its four outputs ----
+ * (what a custom loss -- ICNFModel(m, loss), src/exts/mlj_ext/core_icnf.jl:1-29 -- or a larger differentiable program around
+ * icnf(xs, ps, st), src/base_icnf.jl:528-543, needs; cnf_loss_grad is the special case cot = (-1/B, l1/B, l2/B, l3/B).)
+ *
+ * inference(icnf, mode, xs, ps, st) with the solve RECORDED on the handle: logpx[B], regs[3][B] as cnf_inference.
+ * eps NULL in TestMode.  The record (steps, stage states, final state, eps pointer) stays valid until the next call on
+ * this handle that solves, uploads parameters or conditioning, or changes the base distribution; the eps array must stay
+ * alive and unchanged as long as the record is used.  Always the recorded route: the in-launch gradient of small networks
+ * (k_solve_wave) carries the loss's cotangent only and is not used here. */
+cnf_status cnf_inference_record(cnf_handle h, int mode, const float* xs, const float* eps, int B,
+                                const cnf_solve_opts* opts, float* logpx, float* regs,
+                                cnf_solve_stats* stats, void* stream);
+/* grad[n_params] = sum_b sum_r cot[r][b] * d out_r[b] / d ps  through the recorded steps (step sizes are constants, as
+ * in cnf_loss_grad); cot = [4][B] DEVICE floats, rows (logpx, E, n, A).  cnf_grad_x / cnf_grad_steps apply afterwards.
+ * May be called several times on one record.  CNF_ERR_BAD_ARG ("no recorded solve") when the record is gone or B differs.
+ * Rows the handle does not integrate carry no cotangent: lambda1 = 0 means E = 0 and cot[1] is ignored, likewise lambda2 / n,
+ * lambda3 / A, and rows 1-3 in TestMode. */
+cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int B, float* grad, void* stream);
+
 /* ---- device random numbers ------------------------------------------
  *
  * The library's own counter-based generator, the counterpart of the device RNG the reference draws eps and

@@ -342,6 +342,38 @@ function loss_and_grad(icnf::ICNF{T, <:HIPMatrixMode}, ::TestMode, xs::AbstractM
     val[], grad
 end
 
+# ---- differentiable inference (cnf_inference_record / cnf_inference_pullback) -- UNTESTED like the rest of this file ----------
+# The vector-Jacobian product of `inference` for ANY cotangent of its four outputs: what a custom `ICNFModel.loss` or a larger
+# differentiable program around `icnf(xs, ps, st)` (src/base_icnf.jl:528-543) needs; `loss_and_grad` above is the special case
+# cot = (-1/B, λ₁/B, λ₂/B, λ₃/B).  Both entry points take DEVICE pointers: every array here is a device array (AMDGPU.jl
+# `ROCArray{Float32}`; `pointer` must give its device address).  `ϵ` must stay alive and unchanged while the record is used; the
+# record ends with the next call on the handle that solves, uploads parameters or conditioning, or changes the base distribution.
+function inference_record!(logp̂x, regs, icnf::ICNF{T, <:HIPMatrixMode}, mode, xs, ϵ, ps, st; stream = C_NULL) where {T}
+    h = handle(icnf)
+    set_params!(h, ps; force = true)
+    B = size(xs, 2)
+    t0, t1 = CNF.steer_tspan(icnf, mode)
+    kw = icnf.sol_kwargs
+    opts = CnfSolveOpts(t0, t1, get(kw, :abstol, 1.0f-6), get(kw, :reltol, 1.0f-3), get(kw, :dt, 0.0f0),
+                        get(kw, :adaptive, true) ? 1 : 0, min(get(kw, :maxiters, 100_000), typemax(Int32)), 0)
+    stats = CnfSolveStats()
+    m = mode_flag(mode)
+    ϵp = mode isa TrainMode ? pointer(ϵ) : Ptr{Float32}(C_NULL)
+    check(@ccall(libcnfhip.cnf_inference_record(h::Ptr{Cvoid}, m::Cint, pointer(xs)::Ptr{Float32}, ϵp::Ptr{Float32}, B::Cint,
+                                                Ref(opts)::Ptr{CnfSolveOpts}, pointer(logp̂x)::Ptr{Float32},
+                                                pointer(regs)::Ptr{Float32}, stats::Ref{CnfSolveStats}, stream::Ptr{Cvoid})::Cint), h)
+    logp̂x, regs
+end
+
+# grad[n_params] = Σ_b Σ_r cot[r, b] ∂out_r[b]/∂ps through the recorded steps; `cot` is 4 × B in memory order [4][B] (rows logp̂x,
+# Ė, ṅ, Ȧ: a B × 4 Julia matrix).  May be called several times on one record.
+function inference_pullback!(grad, icnf::ICNF{T, <:HIPMatrixMode}, cot, B::Integer; stream = C_NULL) where {T}
+    h = handle(icnf)
+    check(@ccall(libcnfhip.cnf_inference_pullback(h::Ptr{Cvoid}, pointer(cot)::Ptr{Float32}, B::Cint, pointer(grad)::Ptr{Float32},
+                                                  stream::Ptr{Cvoid})::Cint), h)
+    grad
+end
+
 # ---- parameter files (CNFP, written/read by continuousnf.jl_amd.mlj.save_params/load_params) ----
 function save_params(path, icnf::ICNF, nn_dims::Vector{Int}, acts::Vector{Int}, ps; n_cond = 0)
     open(path, "w") do io

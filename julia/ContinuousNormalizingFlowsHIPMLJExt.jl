@@ -49,6 +49,12 @@ end
 
 function fit_loop(model, x_and_y::Tuple, verbosity)
     icnf = model.m
+    # `hip_grad` is the gradient of the package's own loss (cnf_loss_grad).  A custom `model.loss` (core_icnf.jl:1-29) would be
+    # minimised along the WRONG gradient: refused.  Its gradient is the pullback of `inference` for the cotangent the loss
+    # defines (HIPExt.inference_record! / inference_pullback!, device arrays); the Python mirror's `fit` drives that loop.
+    model.loss === CNF.loss || throw(ArgumentError(
+        "ICNFModel.loss: the HIP backend's fit differentiates ContinuousNormalizingFlows.loss only; " *
+        "pull a custom loss back with inference_record! / inference_pullback!"))
     ps, st = LuxCore.setup(icnf.rng, icnf)                                   # core_icnf.jl:37
     ps = move(icnf.resource, ComponentArrays.ComponentArray(ps))             # :38, :40
     st = move(icnf.resource, st)
