@@ -957,7 +957,10 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
     int launches = 0;
 
     const bool use_mfma = k == CNF_KERNEL_MFMA && mfma_supported(h->mfma, h->nd, train, B);
-    h->trace_on = k == CNF_KERNEL_MFMA && !use_mfma;       // generic driver + an auxiliary MFMA kernel per stage
+    // generic driver + an auxiliary MFMA kernel per stage.  Not for the recorded TrainMode solve of the gradient path: k_jvp_mfma
+    // does not file the stage states the pullback starts from (k_mfma and the generic stage kernel do), so that solve runs the
+    // generic stage kernel
+    h->trace_on = k == CNF_KERNEL_MFMA && !use_mfma && !(rec && train);
     h->aux_train = train != 0; h->aux_eps = eps;
     if (h->trace_on && (s = ensure_adj_images(h, (hipStream_t)stream)) != CNF_OK) return s;
     // lock-step over shards only matters when the controller decides something
@@ -1328,7 +1331,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
             stats->nreject = snap->nreject;
             stats->t_final = snap->t;
             stats->dt_last = snap->dt;
-            stats->kernel_used = k;
+            stats->kernel_used = (k == CNF_KERNEL_MFMA && !use_mfma && !h->trace_on) ? CNF_KERNEL_GENERIC : k;
             stats->launches = launches;
         }
         if (snap->nonfinite) return fail(h, CNF_ERR_NONFINITE, "solver state became NaN/Inf");

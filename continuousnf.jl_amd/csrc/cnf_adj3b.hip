@@ -316,7 +316,7 @@ k_adj3b(NetDesc nd, GradLayout gl, const char* __restrict__ imgb, Adj3bSteps M) 
             S3_SB();
             f32x4 acc[2] = {zero4, zero4};
             s3b_mm<2>(acc, wF1, b);
-            const f32x4 ha = s3_tanh4(acc[0] + bv), hb = s3_tanh4(acc[1] + bv);
+            const f32x4 ha = s3_tanh4_grad(acc[0] + bv), hb = s3_tanh4_grad(acc[1] + bv);
             H1r[0] = ha; H1r[1] = hb;
             s3b_store4(ldsb + a3b::H1G + wb_wr, a3b::WP, ha);
             s3b_store4(ldsb + a3b::H1G + wb_wr + HBW, a3b::WP, hb);
@@ -337,7 +337,7 @@ k_adj3b(NetDesc nd, GradLayout gl, const char* __restrict__ imgb, Adj3bSteps M) 
                 s3b_mm<2>(acc, wF2[kb], b);
                 S3_SB();
             }
-            const f32x4 ha = s3_tanh4(acc[0] + bv), hb = s3_tanh4(acc[1] + bv);
+            const f32x4 ha = s3_tanh4_grad(acc[0] + bv), hb = s3_tanh4_grad(acc[1] + bv);
             H2r[0] = ha; H2r[1] = hb;
             s3b_store4(ldsb + a3b::H2G + wb_wr, a3b::WP, ha);
             s3b_store4(ldsb + a3b::H2G + wb_wr + HBW, a3b::WP, hb);
@@ -350,7 +350,7 @@ k_adj3b(NetDesc nd, GradLayout gl, const char* __restrict__ imgb, Adj3bSteps M) 
         if (zown) {
             const f32x4 bv3 = *(const f32x4*)(bias + 256 + r0);
             const f32x4 zsum = narrow();
-            zdv = s3_tanh4(zsum + bv3);                 // padded rows: zero weights and bias -> 0
+            zdv = s3_tanh4_grad(zsum + bv3);                 // padded rows: zero weights and bias -> 0
             const f32x4 d13 = s3_dtanh4(zdv);
             *ownp(a3b::D13) = d13;
             *ownp(a3b::D23) = a3b_d2tanh4(zdv, d13);

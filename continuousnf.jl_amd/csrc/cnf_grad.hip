@@ -1809,7 +1809,7 @@ k_adj3(NetDesc nd, GradLayout gl, AdjMfmaLayout m, const float* __restrict__ img
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float hh, dd1, dd2;
-            if (ALL_TANH) { hh = tanh_fast(x[j]); dd1 = fmaf(-hh, hh, 1.0f); dd2 = -2.0f * hh * dd1; }   // as the step kernels
+            if (ALL_TANH) { hh = tanh_grad(x[j]); dd1 = fmaf(-hh, hh, 1.0f); dd2 = -2.0f * hh * dd1; }   // (the step kernels' form above 0.25)
             else cnf_act2(act, x[j], hh, dd1, dd2);
             const bool live = r0 + j < out;            // padded rows stay exactly zero
             h[j] = live ? hh : 0.f; d1[j] = live ? dd1 : 0.f; d2[j] = live ? dd2 : 0.f;

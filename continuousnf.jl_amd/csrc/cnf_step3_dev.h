@@ -38,6 +38,9 @@ __device__ __forceinline__ f32x4 s3_tanh4(const f32x4& a) {
 #endif
     return f32x4{tanh_fast(a.x), tanh_fast(a.y), tanh_fast(a.z), tanh_fast(a.w)};
 }
+__device__ __forceinline__ f32x4 s3_tanh4_grad(const f32x4& a) {     // the pullbacks: relative accuracy near 0 (tanh_grad)
+    return f32x4{tanh_grad(a.x), tanh_grad(a.y), tanh_grad(a.z), tanh_grad(a.w)};
+}
 __device__ __forceinline__ f32x4 s3_dtanh4(const f32x4& h) {       // sigma' from h
     return f32x4{fmaf(-h.x, h.x, 1.f), fmaf(-h.y, h.y, 1.f), fmaf(-h.z, h.z, 1.f), fmaf(-h.w, h.w, 1.f)};
 }

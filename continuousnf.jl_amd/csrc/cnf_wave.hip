@@ -75,18 +75,6 @@ __device__ __forceinline__ float wv_wave_sum(float v) {            // every lane
     return (__int_as_float(__builtin_amdgcn_readlane(i, 0)) + __int_as_float(__builtin_amdgcn_readlane(i, 16))) +
            (__int_as_float(__builtin_amdgcn_readlane(i, 32)) + __int_as_float(__builtin_amdgcn_readlane(i, 48)));
 }
-// tanh for the gradient path: the exp2 / rcp form loses RELATIVE accuracy near 0 (1 - 2/(t + 1) with t ~ 1: an absolute
-// 6e-8), which a long span turns into 1e-4 of the gradient's scale on the 2-6-2 network; below 0.25 the odd Taylor polynomial
-// up to x^9 (truncation 2e-9 relative) takes over -- both forms on the signed argument, one select
-__device__ __forceinline__ float tanh_grad(float a) {
-    const float x2 = a * a;
-    float p = 0.021869488f;                       // 62/2835
-    p = fmaf(p, x2, -0.053968254f);               // -17/315
-    p = fmaf(p, x2, 0.13333333f);                 // 2/15
-    p = fmaf(p, x2, -0.33333334f);                // -1/3
-    const float small = fmaf(a * x2, p, a);
-    return fabsf(a) < 0.25f ? small : tanh_fast(a);
-}
 __device__ __forceinline__ float uni(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 
 // Tsit5 rows a_{s+1, 1..6} by value in the kernel arguments (scalar loads, indexed by the stage of a ROLLED stage loop)
