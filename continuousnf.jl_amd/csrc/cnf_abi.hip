@@ -7,6 +7,7 @@
 #include "cnf_grad.h"
 #include "cnf_trace.h"
 #include "cnf_mirror.h"
+#include "cnf_buf.h"
 #include "cnf_wave.h"
 #include "cnf_bcast.h"
 #include "cnf_gradt.h"
@@ -29,23 +30,39 @@
 
 #define CNF_ABI_VERSION 1
 
+// what the handle owns on the device and in pinned host memory (cnf_buf.h)
+struct DevAlloc {
+    static int alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+    static void free(void* p) { (void)hipFree(p); }
+};
+template <unsigned Flags>
+struct HostAlloc {
+    static int alloc(void** p, size_t bytes) { return (int)hipHostMalloc(p, bytes, Flags); }
+    static void free(void* p) { (void)hipHostFree(p); }
+};
+template <class T> using DevBuf = CnfBuf<T, DevAlloc>;
+template <class T> using PinnedBuf = CnfBuf<T, HostAlloc<hipHostMallocDefault>>;
+
+// the words of d_sums: 8 floats of sums, then the device tickets (zero between launches) and the kernel clock words
+enum { SUMS_NORM_TICKET = 8, SUMS_POST_TICKET = 9, SUMS_MEET_BASE = 10, SUMS_ABORT = 11, SUMS_CLOCK = 12 /* 3 x 64 bit */, SUMS_WORDS = 24 };
+
 struct cnf_ctx {
     NetDesc nd{};
     float lam[3]{};
     int device = 0;
     size_t n_params = 0;
-    float* d_params = nullptr;
+    DevBuf<float> d_params;
     bool have_params = false;
     MfmaPlan mfma{};              // packed weights etc. for the MFMA path (cnf_mfma.hip)
 
     // scratch, sized for cap_B samples
     size_t cap_B = 0;
-    float* arena = nullptr;       // one allocation carved into the buffers below
+    DevBuf<float> arena;          // one allocation carved into the buffers below (set by ensure_capacity, cleared with it)
     float* ws = nullptr;
     float* U[2] = {nullptr, nullptr};
     float* K1[2] = {nullptr, nullptr};
     float* Ks[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    float* d_cond = nullptr;      // conditional models: per-sample first-layer bias [cond_B][cbs]
+    DevBuf<float> d_cond;         // conditional models: per-sample first-layer bias [cond_B][cbs]
     int cond_B = 0, cbs = 0;
     float* tmp_logpx = nullptr;
     float* tmp_regs = nullptr;
@@ -77,14 +94,14 @@ struct cnf_ctx {
     int wait_us = 0, poll_limit = 0;   // cnf_set_solve_wait (0: the process defaults)
     float* step_trace = nullptr;  // cnf_set_step_trace: caller-owned device buffer, 4 floats per step attempt
     int step_trace_cap = 0;
-    float* partials = nullptr;    // 2 * MAX_PARTIALS floats
+    DevBuf<float> partials;       // 8 * MAX_PARTIALS floats
     StepState* last_state = nullptr; // device slot holding the state at the end of the last solve
-    StepState* d_state = nullptr;   // two slots: [0] canonical, [1] ping-pong partner of the fused MFMA path
-    StepState* h_state = nullptr; // pinned, two slots for pipelined polling + one init slot
+    DevBuf<StepState> d_state;      // two slots: [0] canonical, [1] ping-pong partner of the fused MFMA path
+    PinnedBuf<StepState> h_state; // pinned, two slots for pipelined polling + one init slot (init_state / loss_sums_host)
     // streamed solve: the step kernel mirrors the state into pinned, host-coherent memory after every
     // controller run as tagged granules (cnf_mirror.h); the host polls them
     typedef CnfMirrorT<StepState> HostMirror;
-    HostMirror* h_mirror = nullptr;        // host address
+    CnfBuf<HostMirror, HostAlloc<hipHostMallocCoherent | hipHostMallocMapped>> h_mirror;   // host address
     HostMirror* d_mirror = nullptr;        // the same memory as the device sees it
     unsigned mirror_base = 1;              // launch indices are monotonic over the handle's life: late launches of
                                            // an earlier solve can never look like news of the current one
@@ -93,40 +110,34 @@ struct cnf_ctx {
     void* shard_user = nullptr;
     cnf_comm shard_comm = nullptr;         // ... or an RCCL communicator: reduced on the stream, no host round trip
     // gradient path (cnf_loss_grad): transposed weights, per-step trajectory, adjoint scratch
-    float* d_PT = nullptr;
-    float* d_adj_img = nullptr;   // padded forward/reverse weight images of the MFMA pullback kernel
+    DevBuf<float> d_PT;
+    DevBuf<float> d_adj_img;      // padded forward/reverse weight images of the MFMA pullback kernel
     bool pt_valid = false;
     bool img_valid = false;       // d_adj_img holds the images of the current parameters
-    float* d_bimg = nullptr;      // k_solve_bcast's images (cnf_bcast.hip), packed on first use after a parameter change
-    float* d_gt = nullptr;        // k_adj_test: one partial of the flat gradient and a scratch per workgroup (cnf_gradt.hip)
-    size_t gt_floats = 0;
-    float* d_bstore = nullptr;    // ... and the store of its tiles' Runge-Kutta rows when a workgroup carries several (bcast_store_floats)
-    size_t bstore_floats = 0;
+    DevBuf<float> d_bimg;         // k_solve_bcast's images (cnf_bcast.hip), packed on first use after a parameter change
+    DevBuf<float> d_gt;           // k_adj_test: one partial of the flat gradient and a scratch per workgroup (cnf_gradt.hip)
+    DevBuf<float> d_bstore;       // ... and the store of its tiles' Runge-Kutta rows when a workgroup carries several (bcast_store_floats)
     bool bimg_valid = false;
     bool trace_on = false;        // this call evaluates through an auxiliary MFMA kernel (cnf_trace.hip) behind the generic driver
     bool aux_train = false;       //   false: TestMode exact trace; true: TrainMode JVP
     const float* aux_eps = nullptr;
-    float* traj = nullptr;             // trajectory store: traj_cap slots of 6 (n_in + 3) grad_cap_B floats (u_n, U_2..U_6)
-    float* traj_hs = nullptr;          // device: signed size of accepted step n (written by the step kernel)
+    DevBuf<float> traj;                // trajectory store: traj_cap slots of 6 (n_in + 3) grad_cap_B floats (u_n, U_2..U_6)
+    DevBuf<float> traj_hs;             // device: signed size of accepted step n (written by the step kernel)
     int traj_cap = 0;
     size_t grad_cap_B = 0;
     int grad_fsteps = 1;          // steps whose factor arrays are kept before one batch contraction
-    float* grad_arena = nullptr;
+    DevBuf<float> grad_arena;     // carved into the g_ pointers below (set by ensure_grad_capacity, cleared with it)
     float* g_US[5] = {};          // stage states 2..6
     float* g_W[6] = {};           // zbar per stage
     float* g_lam = nullptr;
     float *g_HS = nullptr, *g_TS = nullptr, *g_AB = nullptr, *g_PB = nullptr;
-    float* d_park = nullptr;      // parked state of the two-launch headline pullback (adj3b_park_floats)
-    size_t park_floats = 0;
-    float* d_sc = nullptr;        // scratch rows of the two-launch MFMA pullback (adj_mfma_scratch_floats)
-    size_t sc_floats = 0;
-    AdjStepArgs* d_steps = nullptr;      // ... and the arguments of the steps of its runs: device array and pinned staging
-    AdjStepArgs* h_steps = nullptr;
-    int steps_cap = 0;
+    DevBuf<float> d_park;         // parked state of the two-launch headline pullback (adj3b_park_floats)
+    DevBuf<float> d_sc;           // scratch rows of the two-launch MFMA pullback (adj_mfma_scratch_floats)
+    DevBuf<AdjStepArgs> d_steps;         // ... and the arguments of the steps of its runs: device array and pinned staging
+    PinnedBuf<AdjStepArgs> h_steps;
     float* g_part = nullptr;      // GRAD_MAX_KSPLIT x n_params
     NetDesc nd_wave{};            // what the wave kernels see: nd, or a one-layer tanh network with an identity layer appended
-    float* wg_traj = nullptr;     // k_solve_wave<GRAD>: z rows of u_n per accepted step, as the lanes hold them; + WV_GCAP step sizes
-    size_t wg_traj_floats = 0;
+    DevBuf<float> wg_traj;        // k_solve_wave<GRAD>: z rows of u_n per accepted step, as the lanes hold them; + WV_GCAP step sizes
     float* g_grad = nullptr;      // n_params (host-pointer variant)
     std::vector<float> last_hs;   // signed step sizes of the last cnf_loss_grad solve
     int grad_last_B = 0;          // batch of the last cnf_loss_grad call (g_lam holds its d loss / d u(t0))
@@ -135,15 +146,14 @@ struct cnf_ctx {
     bool rec_valid = false;
     int rec_mode = 0, rec_B = 0, rec_kernel = 0;
     const float* rec_eps = nullptr;
-    float* d_cw = nullptr;        // [3][B] per-sample cotangents of the scalar rows, packed by k_vjp_cotangent
-    size_t cw_floats = 0;
-    float* d_ys = nullptr;        // conditional models: copy of ys (n_cond x cond_B), kept for the weight gradient
-    float* stage = nullptr;       // device staging area of the *_host entry points, owned by the handle, grown on demand
-    size_t stage_cap = 0;         //   (floats): no allocation per call, nothing to free on an error path
-    float* d_sums = nullptr;      // 3 floats
+    DevBuf<float> d_cw;           // [3][B] per-sample cotangents of the scalar rows, packed by k_vjp_cotangent
+    DevBuf<float> d_ys;           // conditional models: copy of ys (n_cond x cond_B), kept for the weight gradient
+    DevBuf<float> stage;          // device staging area of the *_host entry points, owned by the handle, grown on demand:
+                                  //   no allocation per call, nothing to free on an error path
+    DevBuf<float> d_sums;         // SUMS_WORDS floats
     BaseDist bd{};                // cnf_set_basedist: kind 0 = the default N(0, I), nothing of cnf_dist.hip is launched
-    float* d_bd = nullptr;        //   its arrays (mean | whiten | chol | prec), one allocation
-    float* h_sums = nullptr;      // pinned, 3 floats
+    DevBuf<float> d_bd;           //   its arrays (mean | whiten | chol | prec), one allocation
+    PinnedBuf<float> h_sums;      // pinned, 4 floats
     std::string err;
 };
 
@@ -164,6 +174,22 @@ static const int MAX_PARTIALS = 1024;
 static cnf_status fail(cnf_handle h, cnf_status s, const char* msg) {
     if (h) h->err = msg;
     return s;
+}
+
+// grow-only reserve of one of the handle's buffers (n elements); an allocator's refusal is the call's HIP error
+#define RESERVE(h, buf, n) HIPCHK(h, (hipError_t)(buf).reserve(n))
+
+template <class T>
+static T* sums_word(cnf_handle h, int word) { return reinterpret_cast<T*>(h->d_sums.data() + word); }
+// h_state[2] serves twice: the initial state of a solve, and -- free again once the solve is enqueued -- the pinned landing
+// place of the five loss sums
+static StepState* init_state(cnf_handle h) { return &h->h_state[2]; }
+static float* loss_sums_host(cnf_handle h) { return reinterpret_cast<float*>(&h->h_state[2]); }
+// the integrator's buffers into the argument struct of a kernel that works on them (RhsArgs, NormArgs, TraceArgs)
+template <class Args>
+static void set_rk_buffers(cnf_handle h, Args& a) {
+    for (int i = 0; i < 2; ++i) { a.U[i] = h->U[i]; a.K1[i] = h->K1[i]; }
+    for (int i = 0; i < 5; ++i) a.Ks[i] = h->Ks[i];
 }
 
 static inline int rows_of(const cnf_ctx* h, int mode) {
@@ -253,26 +279,26 @@ extern "C" cnf_status cnf_create(cnf_handle* out, const cnf_config* cfg) {
         id_tail = (size_t)n_in * n_in + n_in;
     }
     hipError_t e = hipSetDevice(h->device);
-    if (e == hipSuccess) e = hipMalloc(&h->d_params, (h->n_params + id_tail) * sizeof(float));
+    if (e == hipSuccess) e = (hipError_t)h->d_params.reserve(h->n_params + id_tail);
     if (e == hipSuccess && id_tail) {
         std::vector<float> idm(id_tail, 0.f);
         for (int i = 0; i < n_in; ++i) idm[(size_t)i * n_in + i] = 1.f;
         e = hipMemcpy(h->d_params + h->n_params, idm.data(), id_tail * sizeof(float), hipMemcpyHostToDevice);
     }
-    if (e == hipSuccess) e = hipMalloc(&h->d_state, 2 * sizeof(StepState));
+    if (e == hipSuccess) e = (hipError_t)h->d_state.reserve(2);
     // (the one-launch solve uses it as 8-byte words: 2 x 1024 of the meetings, 2048 of the loss-sum partials)
-    if (e == hipSuccess) e = hipMalloc(&h->partials, 8 * MAX_PARTIALS * sizeof(float));
+    if (e == hipSuccess) e = (hipError_t)h->partials.reserve(8 * MAX_PARTIALS);
     if (e == hipSuccess) e = hipMemset(h->partials, 0, 8 * MAX_PARTIALS * sizeof(float));
-    if (e == hipSuccess) e = hipHostMalloc(&h->h_state, 3 * sizeof(StepState), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc(&h->d_sums, 24 * sizeof(float));      // 8 floats of sums, tickets, the kernel clock words
-    if (e == hipSuccess) e = hipMemset(h->d_sums, 0, 24 * sizeof(float));      // words 8.. are device tickets: zero between launches
-    if (e == hipSuccess) e = hipHostMalloc(&h->h_sums, 4 * sizeof(float), hipHostMallocDefault);
+    if (e == hipSuccess) e = (hipError_t)h->h_state.reserve(3);
+    if (e == hipSuccess) e = (hipError_t)h->d_sums.reserve(SUMS_WORDS);
+    if (e == hipSuccess) e = hipMemset(h->d_sums, 0, SUMS_WORDS * sizeof(float));
+    if (e == hipSuccess) e = (hipError_t)h->h_sums.reserve(4);
     // (four slots: the streamed solves use slot 0; the one-launch solves take slots 1, 2, 3 in turn, so that up to three
     // submitted launches can be in flight -- and one of them be run again on the streamed driver -- without overwriting
     // each other's final state)
-    if (e == hipSuccess) e = hipHostMalloc(&h->h_mirror, 4 * sizeof(*h->h_mirror), hipHostMallocCoherent | hipHostMallocMapped);
+    if (e == hipSuccess) e = (hipError_t)h->h_mirror.reserve(4);
     if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&h->d_mirror, h->h_mirror, 0);
-    if (e == hipSuccess) memset(h->h_mirror, 0, 4 * sizeof(*h->h_mirror));     // tag 0 is never a launch index (mirror_base starts at 1)
+    if (e == hipSuccess) memset(h->h_mirror, 0, 4 * sizeof(cnf_ctx::HostMirror));     // tag 0 is never a launch index (mirror_base starts at 1)
     if (e != hipSuccess) {
         cnf_destroy(h);
         return CNF_ERR_HIP;
@@ -296,51 +322,30 @@ static cnf_status settle_submitted(cnf_handle h);
 
 extern "C" cnf_status cnf_destroy(cnf_handle h) {
     if (!h) return CNF_ERR_BAD_ARG;
-    // called from a finaliser after the HIP runtime has shut down (process exit): nothing left to free on the device
-    if (hipSetDevice(h->device) != hipSuccess) { (void)hipGetLastError(); delete h; return CNF_OK; }
+    // Called from a finaliser after the HIP runtime has shut down (process exit): nothing may call into HIP to free memory any
+    // more, and the buffers free themselves when the handle is destroyed -- so on this path it is NOT destroyed.  The few
+    // hundred bytes of host memory go with the process.
+    if (hipSetDevice(h->device) != hipSuccess) { (void)hipGetLastError(); return CNF_OK; }
     sync_submitted(h);
     release_submitted(h);
     mfma_plan_free(h->mfma);
-    if (h->d_params) (void)hipFree(h->d_params);
-    if (h->d_cond) (void)hipFree(h->d_cond);
-    if (h->d_ys) (void)hipFree(h->d_ys);
-    if (h->d_PT) (void)hipFree(h->d_PT);
-    if (h->d_adj_img) (void)hipFree(h->d_adj_img);
-    if (h->d_park) (void)hipFree(h->d_park);
-    if (h->d_sc) (void)hipFree(h->d_sc);
-    if (h->d_steps) (void)hipFree(h->d_steps);
-    if (h->h_steps) (void)hipHostFree(h->h_steps);
-    if (h->d_bimg) (void)hipFree(h->d_bimg);
-    if (h->d_bstore) (void)hipFree(h->d_bstore);
-    if (h->d_gt) (void)hipFree(h->d_gt);
-    if (h->grad_arena) (void)hipFree(h->grad_arena);
-    if (h->traj) (void)hipFree(h->traj);
-    if (h->traj_hs) (void)hipFree(h->traj_hs);
-    if (h->wg_traj) (void)hipFree(h->wg_traj);
-    if (h->arena) (void)hipFree(h->arena);
-    if (h->d_state) (void)hipFree(h->d_state);
-    if (h->partials) (void)hipFree(h->partials);
-    if (h->h_state) (void)hipHostFree(h->h_state);
-    if (h->h_mirror) (void)hipHostFree(h->h_mirror);
-    if (h->stage) (void)hipFree(h->stage);
-    if (h->d_sums) (void)hipFree(h->d_sums);
-    if (h->d_bd) (void)hipFree(h->d_bd);
-    if (h->d_cw) (void)hipFree(h->d_cw);
-    if (h->h_sums) (void)hipHostFree(h->h_sums);
     delete h;
     return CNF_OK;
 }
 
-extern "C" cnf_status cnf_set_params(cnf_handle h, const float* flat_dev, size_t n, void* stream) {
-    if (!h || !flat_dev) return CNF_ERR_BAD_ARG;
+// what every parameter upload begins and ends with, around its own copy into d_params
+static cnf_status params_check(cnf_handle h, const float* flat, size_t n) {
+    if (!h || !flat) return CNF_ERR_BAD_ARG;
     if (n != h->n_params) return fail(h, CNF_ERR_BAD_SHAPE, "parameter count does not match the layer sizes");
-    hipStream_t s = (hipStream_t)stream;
     HIPCHK(h, hipSetDevice(h->device));
-    { const cnf_status ss = settle_submitted(h); if (ss != CNF_OK) return ss; }
-    HIPCHK(h, hipMemcpyAsync(h->d_params, flat_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return CNF_OK;
+}
+enum ParamsWait { PARAMS_NO_WAIT, PARAMS_WAIT_STREAM, PARAMS_WAIT_DEVICE };
+static cnf_status params_uploaded(cnf_handle h, hipStream_t s, ParamsWait wait) {
     cnf_status ms = mfma_plan_pack(h->mfma, h->nd, h->d_params, s);
     if (ms != CNF_OK) return fail(h, ms, "MFMA weight packing failed");
-    HIPCHK(h, hipStreamSynchronize(s));
+    if (wait == PARAMS_WAIT_STREAM) HIPCHK(h, hipStreamSynchronize(s));
+    if (wait == PARAMS_WAIT_DEVICE) HIPCHK(h, hipDeviceSynchronize());
     h->have_params = true;
     h->rec_valid = false;
     h->pt_valid = false;
@@ -350,22 +355,19 @@ extern "C" cnf_status cnf_set_params(cnf_handle h, const float* flat_dev, size_t
     return CNF_OK;
 }
 
+extern "C" cnf_status cnf_set_params(cnf_handle h, const float* flat_dev, size_t n, void* stream) {
+    cnf_status ss = params_check(h, flat_dev, n);
+    if (ss != CNF_OK || (ss = settle_submitted(h)) != CNF_OK) return ss;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(h, hipMemcpyAsync(h->d_params, flat_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return params_uploaded(h, s, PARAMS_WAIT_STREAM);
+}
+
 extern "C" cnf_status cnf_set_params_host(cnf_handle h, const float* flat, size_t n) {
-    if (!h || !flat) return CNF_ERR_BAD_ARG;
-    if (n != h->n_params) return fail(h, CNF_ERR_BAD_SHAPE, "parameter count does not match the layer sizes");
-    HIPCHK(h, hipSetDevice(h->device));
-    { const cnf_status ss = settle_submitted(h); if (ss != CNF_OK) return ss; }
+    cnf_status ss = params_check(h, flat, n);
+    if (ss != CNF_OK || (ss = settle_submitted(h)) != CNF_OK) return ss;
     HIPCHK(h, hipMemcpy(h->d_params, flat, n * sizeof(float), hipMemcpyHostToDevice));
-    cnf_status ms = mfma_plan_pack(h->mfma, h->nd, h->d_params, nullptr);
-    if (ms != CNF_OK) return fail(h, ms, "MFMA weight packing failed");
-    HIPCHK(h, hipDeviceSynchronize());
-    h->have_params = true;
-    h->rec_valid = false;
-    h->pt_valid = false;
-    h->img_valid = false;
-    h->bimg_valid = false;
-    h->cond_B = 0;
-    return CNF_OK;
+    return params_uploaded(h, nullptr, PARAMS_WAIT_DEVICE);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -373,15 +375,16 @@ static cnf_status ensure_capacity(cnf_handle h, int B) {
     if ((size_t)B <= h->cap_B) return CNF_OK;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());
-    if (h->arena) { (void)hipFree(h->arena); h->arena = nullptr; h->cap_B = 0; }
-    size_t cap = ((size_t)B + 255) & ~(size_t)255;
+    const size_t want = ((size_t)B + 255) & ~(size_t)255;
     const size_t Dmax = (size_t)h->nd.n_in + 3;
-    const size_t ws_f = ((size_t)2 * h->nd.sum_dims + (size_t)2 * h->nd.max_dim) * cap;
+    const size_t ws_1 = (size_t)2 * h->nd.sum_dims + (size_t)2 * h->nd.max_dim;       // floats per sample
+    const hipError_t arena_alloc = (hipError_t)h->arena.reserve((ws_1 + 9 * Dmax + 4) * want + want / 16);
+    // The pointers below exist only while the arena does: a failed reserve has left it empty, and they are all carved from
+    // null with no capacity (every offset is 0) before the error is returned.
+    const size_t cap = arena_alloc == hipSuccess ? want : 0;
     const size_t st_f = Dmax * cap;
-    const size_t total = ws_f + 9 * st_f + 4 * cap + cap / 16;
-    HIPCHK(h, hipMalloc(&h->arena, total * sizeof(float)));
     float* p = h->arena;
-    h->ws = p; p += ws_f;
+    h->ws = p; p += ws_1 * cap;
     for (int i = 0; i < 2; ++i) { h->U[i] = p; p += st_f; }
     for (int i = 0; i < 2; ++i) { h->K1[i] = p; p += st_f; }
     for (int i = 0; i < 5; ++i) { h->Ks[i] = p; p += st_f; }
@@ -389,17 +392,15 @@ static cnf_status ensure_capacity(cnf_handle h, int B) {
     h->tmp_regs = p; p += 3 * cap;
     h->post_part = p; p += cap / 16;
     h->cap_B = cap;
+    HIPCHK(h, arena_alloc);
     return CNF_OK;
 }
 
 // staging area for host-pointer calls: at least `nfloats` floats of device memory owned by the handle
 static cnf_status ensure_stage(cnf_handle h, size_t nfloats) {
-    if (nfloats <= h->stage_cap) return CNF_OK;
+    if (nfloats <= h->stage.capacity()) return CNF_OK;
     HIPCHK(h, hipDeviceSynchronize());
-    if (h->stage) { (void)hipFree(h->stage); h->stage = nullptr; h->stage_cap = 0; }
-    const size_t cap = (nfloats + 4095) & ~(size_t)4095;
-    HIPCHK(h, hipMalloc(&h->stage, cap * sizeof(float)));
-    h->stage_cap = cap;
+    RESERVE(h, h->stage, (nfloats + 4095) & ~(size_t)4095);
     return CNF_OK;
 }
 
@@ -463,11 +464,11 @@ extern "C" cnf_status cnf_set_basedist(cnf_handle h, int kind, const float* mean
     // (a submitted inference, or its fallback, evaluates the base it was submitted with: none may be outstanding)
     { const cnf_status ss = settle_submitted(h); if (ss != CNF_OK) return ss; }
     HIPCHK(h, hipDeviceSynchronize());
-    if (h->d_bd) { (void)hipFree(h->d_bd); h->d_bd = nullptr; }
+    h->d_bd.release();
     h->bd = BaseDist{};
     h->rec_valid = false;
     if (kind == 0) return CNF_OK;
-    HIPCHK(h, hipMalloc(&h->d_bd, host.size() * sizeof(float)));
+    RESERVE(h, h->d_bd, host.size());
     HIPCHK(h, hipMemcpy(h->d_bd, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
     h->bd.kind = kind; h->bd.mean = h->d_bd; h->bd.whiten = h->d_bd + n; h->bd.chol = h->d_bd + n + m; h->bd.prec = h->d_bd + n + 2 * m;
     h->bd.logconst = logconst;
@@ -499,11 +500,11 @@ extern "C" cnf_status cnf_set_cond(cnf_handle h, const float* ys, int B, void* s
     const int cbs = (h->nd.dims[1] + 15) & ~15;
     if (h->cond_B != B || h->cbs != cbs) {
         HIPCHK(h, hipDeviceSynchronize());
-        if (h->d_cond) { (void)hipFree(h->d_cond); h->d_cond = nullptr; }
-        if (h->d_ys) { (void)hipFree(h->d_ys); h->d_ys = nullptr; }
+        h->d_cond.release();             // (sized for this batch exactly, a smaller one too)
+        h->d_ys.release();
         h->cond_B = 0;
-        HIPCHK(h, hipMalloc(&h->d_cond, (size_t)B * cbs * sizeof(float)));
-        HIPCHK(h, hipMalloc(&h->d_ys, (size_t)B * h->nd.n_cond * sizeof(float)));
+        RESERVE(h, h->d_cond, (size_t)B * cbs);
+        RESERVE(h, h->d_ys, (size_t)B * h->nd.n_cond);
         h->cbs = cbs;
     }
     // the gradient path needs ys itself (d loss / d W1[:, n_in:] = sum_b abar_1 ys')
@@ -538,11 +539,16 @@ extern "C" int cnf_kernel_for(cnf_handle h, int mode, int B) {
     return trace_ok(h) ? CNF_KERNEL_MFMA : CNF_KERNEL_GENERIC;
 }
 
-// padded forward/reverse weight images shared by the pullback and the exact-trace kernels
+// padded forward/reverse weight images shared by the pullback and the exact-trace kernels: allocated on first use ...
+static cnf_status reserve_adj_images(cnf_handle h) {
+    RESERVE(h, h->d_adj_img, (size_t)adj_mfma_layout(h->nd, grad_layout(h->nd)).img_floats);
+    return CNF_OK;
+}
+// ... and packed on first use after a parameter change
 static cnf_status ensure_adj_images(cnf_handle h, hipStream_t st) {
     const GradLayout g = grad_layout(h->nd);
     const AdjMfmaLayout m = adj_mfma_layout(h->nd, g);
-    if (!h->d_adj_img) HIPCHK(h, hipMalloc(&h->d_adj_img, (size_t)m.img_floats * sizeof(float)));
+    { const cnf_status rs = reserve_adj_images(h); if (rs != CNF_OK) return rs; }
     if (!h->img_valid) {
         HIPCHK(h, launch_pack_adj_images(h->nd, g, m, h->d_params, h->d_adj_img, st));
         h->img_valid = true;
@@ -579,19 +585,17 @@ static cnf_status launch_trace(cnf_handle h, const float* u, float* du, bool in_
     const AdjMfmaLayout m = adj_mfma_layout(h->nd, g);
     TraceArgs a{};
     a.u = u; a.du = du; a.ys = h->nd.n_cond > 0 ? h->d_ys : nullptr;
-    a.st = in_solve ? h->d_state : nullptr;
-    a.K1[0] = h->K1[0]; a.K1[1] = h->K1[1];
+    a.st = in_solve ? h->d_state.data() : nullptr;
+    set_rk_buffers(h, a);
     a.du_is_k7 = du_is_k7 ? 1 : 0;
     a.B = B;
     a.nk = in_solve ? nk : 0;
-    for (int i = 0; i < 2; ++i) a.U[i] = h->U[i];
-    for (int i = 0; i < 5; ++i) a.Ks[i] = h->Ks[i];
     for (int i = 0; i < a.nk && i < 6; ++i) a.coef[i] = coef[i];
     a.also_unew = also_unew ? 1 : 0;
     a.norm_kind = -1;
     if (fuse) {
         a.norm_kind = fuse->norm_kind; a.fused_step = fuse->step ? 1 : 0;
-        a.partials = h->partials; a.ticket = reinterpret_cast<unsigned*>(h->d_sums + 8); a.st_mut = h->d_state;
+        a.partials = h->partials; a.ticket = sums_word<unsigned>(h, SUMS_NORM_TICKET); a.st_mut = h->d_state;
         a.n_total = (float)((size_t)rows_of(h, CNF_MODE_TEST) * B);
         a.mirror = fuse->mirror; a.seq = fuse->seq;
     }
@@ -618,10 +622,10 @@ extern "C" cnf_status cnf_solve_kernel_time(cnf_handle h, int enable, float* mea
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());
     unsigned long long w[3] = {0, 0, 0};
-    HIPCHK(h, hipMemcpy(w, h->d_sums + 12, sizeof w, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(w, sums_word<void>(h, SUMS_CLOCK), sizeof w, hipMemcpyDeviceToHost));
     if (mean_us) *mean_us = w[2] ? (float)((double)w[1] * 0.01 / (double)w[2]) : 0.f;       // s_memrealtime: 100 MHz
     if (launches) *launches = (int)w[2];
-    HIPCHK(h, hipMemset(h->d_sums + 12, 0, sizeof w));
+    HIPCHK(h, hipMemset(sums_word<void>(h, SUMS_CLOCK), 0, sizeof w));
     h->time_kernel = enable != 0;
     return CNF_OK;
 }
@@ -765,8 +769,7 @@ static int enqueue_attempt_generic(cnf_handle h, int train, const float* eps, in
     RhsArgs a{};
     a.st = h->d_state; a.B = B; a.S = h->cap_B; a.train = train; a.ws = h->ws; a.eps = eps;
     a.cond = h->mfma.cond; a.cbs = h->cbs;
-    for (int i = 0; i < 2; ++i) { a.U[i] = h->U[i]; a.K1[i] = h->K1[i]; }
-    for (int i = 0; i < 5; ++i) a.Ks[i] = h->Ks[i];
+    set_rk_buffers(h, a);
     if (h->trace_on && with_controller && !dump && trace_fused_ok(h, B)) {
         // TestMode on the 32-128-128-32 shape: the six stage evaluations, the error norm and the controller in ONE launch
         TraceFuse f; f.norm_kind = 2; f.step = true; f.mirror = mirror; f.seq = seq;
@@ -789,11 +792,10 @@ static int enqueue_attempt_generic(cnf_handle h, int train, const float* eps, in
     }
     NormArgs n{};
     n.st = h->d_state; n.kind = 2; n.n = (size_t)rows_of(h, train) * B;
-    for (int i = 0; i < 2; ++i) { n.U[i] = h->U[i]; n.K1[i] = h->K1[i]; }
-    for (int i = 0; i < 5; ++i) n.Ks[i] = h->Ks[i];
+    set_rk_buffers(h, n);
     n.partials = h->partials;
     if (with_controller) {      // error norm + controller in one launch
-        n.ticket = reinterpret_cast<unsigned*>(h->d_sums + 8); n.st_mut = h->d_state; n.ctrl_phase = 2; n.n_total = (float)n.n;
+        n.ticket = sums_word<unsigned>(h, SUMS_NORM_TICKET); n.st_mut = h->d_state; n.ctrl_phase = 2; n.n_total = (float)n.n;
         n.mirror = mirror; n.seq = seq;
     }
     launch_norm_partials(n, nblk, s);
@@ -843,23 +845,16 @@ static cnf_status traj_reserve(cnf_handle h, int steps) {
     int cap = h->traj_cap ? h->traj_cap : 32;
     while (cap < steps) cap *= 2;
     const size_t slot = traj_slot_floats(h);
-    float *nt = nullptr, *nh = nullptr;
+    // grown with its contents kept: new buffers, copy, swap -- the old ones (or, on an error, the new ones) go with nt / nh
+    DevBuf<float> nt, nh;
     HIPCHK(h, hipDeviceSynchronize());
-    HIPCHK(h, hipMalloc(&nt, slot * cap * sizeof(float)));
-    if (hipMalloc(&nh, (size_t)cap * sizeof(float)) != hipSuccess) {
-        (void)hipFree(nt);
-        return fail(h, CNF_ERR_HIP, "hipMalloc of the trajectory step-size array failed");
-    }
+    RESERVE(h, nt, slot * cap);
+    if (nh.reserve((size_t)cap) != 0) return fail(h, CNF_ERR_HIP, "hipMalloc of the trajectory step-size array failed");
     if (h->traj) {
-        hipError_t ce = hipMemcpy(nt, h->traj, slot * h->traj_cap * sizeof(float), hipMemcpyDeviceToDevice);
-        if (ce == hipSuccess) ce = hipMemcpy(nh, h->traj_hs, (size_t)h->traj_cap * sizeof(float), hipMemcpyDeviceToDevice);
-        if (ce != hipSuccess) {
-            (void)hipFree(nt); (void)hipFree(nh);
-            return fail(h, CNF_ERR_HIP, hipGetErrorString(ce));
-        }
-        (void)hipFree(h->traj); (void)hipFree(h->traj_hs);
+        HIPCHK(h, hipMemcpy(nt, h->traj, slot * h->traj_cap * sizeof(float), hipMemcpyDeviceToDevice));
+        HIPCHK(h, hipMemcpy(nh, h->traj_hs, (size_t)h->traj_cap * sizeof(float), hipMemcpyDeviceToDevice));
     }
-    h->traj = nt; h->traj_hs = nh; h->traj_cap = cap;
+    h->traj.swap(nt); h->traj_hs.swap(nh); h->traj_cap = cap;
     return CNF_OK;
 }
 static cnf_status traj_slot(cnf_handle h, int n, float** out) {
@@ -880,7 +875,7 @@ struct PostHook {
 static void enqueue_post(cnf_handle h, int train, const StepState* state, const PostHook& ph, int B, bool need_done,
                          hipStream_t st) {
     launch_post_state(h->nd, train, state, h->U[0], h->U[1], ph.logpx, ph.regs, B, st, need_done, ph.sums5, h->post_part,
-                      reinterpret_cast<unsigned*>(h->d_sums + 9));
+                      sums_word<unsigned>(h, SUMS_POST_TICKET));
 }
 static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const float* eps, float* u_out, int B,
                              const cnf_solve_opts* opts, cnf_solve_stats* stats, void* stream, Recorder* rec,
@@ -892,31 +887,53 @@ static std::mutex g_persist_mu;
 static int g_submitted_inflight = 0;               // (both under g_persist_mu)
 static hipStream_t g_submitted_stream = nullptr;
 
-// The outcome of the one-launch solve with launch index `seq`: its final state arrives in its slot of the host mirror.
-// *aborted: a wait inside the kernel ran out (the state says so itself: n_partials < 0) -- nothing of the launch is used,
-// the abort word is cleared (after the stream has drained: launches queued behind it read it too) and the caller runs
-// the solve again on the streamed driver.
-static cnf_status finish_one_launch(cnf_handle h, unsigned seq, int slot, hipStream_t st, StepState* fin, bool* aborted) {
-    const volatile cnf_ctx::HostMirror* hm = h->h_mirror + slot;
-    unsigned sq = 0;
+// Wait for a consistent snapshot of the mirror slot `hm` whose tag is news (`fresh(tag)`): *snap / *sq.  The spin backs off:
+// pause first, yield the core once the wait outlasts a few launches.  A faulted kernel would never publish: every 100000
+// spins the stream is asked -- an error is the call's, an idle stream without the snapshot is `unpublished`, an idle stream
+// with it ends the wait.
+template <class Fresh>
+static cnf_status mirror_wait(cnf_handle h, const volatile cnf_ctx::HostMirror* hm, hipStream_t st, StepState* snap, unsigned* sq,
+                              Fresh fresh, const char* unpublished) {
     for (long spins = 0;; ++spins) {
-        if (cnf_mirror_read(hm, fin, &sq) && sq == seq) break;
+        if (cnf_mirror_read(hm, snap, sq) && fresh(*sq)) return CNF_OK;
         if (spins < 4096) _mm_pause();
         else sched_yield();
         if (spins % 100000 == 99999) {
             hipError_t qe = hipStreamQuery(st);
             if (qe != hipSuccess && qe != hipErrorNotReady) HIPCHK(h, qe);
-            if (qe == hipSuccess && !(cnf_mirror_read(hm, fin, &sq) && sq == seq))
-                return fail(h, CNF_ERR_HIP, "the solve kernel finished without publishing a state");
+            if (qe == hipSuccess) return cnf_mirror_read(hm, snap, sq) && fresh(*sq) ? CNF_OK : fail(h, CNF_ERR_HIP, unpublished);
         }
     }
+}
+
+// the statistics of a solve that ended in the state `fin`
+static void fill_stats(cnf_solve_stats* stats, const StepState& fin, int nf, int kernel_used, int launches) {
+    if (!stats) return;
+    stats->nf = nf;
+    stats->naccept = fin.naccept;
+    stats->nreject = fin.nreject;
+    stats->t_final = fin.t;
+    stats->dt_last = fin.dt;
+    stats->kernel_used = kernel_used;
+    stats->launches = launches;
+}
+
+// The outcome of the one-launch solve with launch index `seq`: its final state arrives in its slot of the host mirror.
+// *aborted: a wait inside the kernel ran out (the state says so itself: n_partials < 0) -- nothing of the launch is used,
+// the abort word is cleared (after the stream has drained: launches queued behind it read it too) and the caller runs
+// the solve again on the streamed driver.
+static cnf_status finish_one_launch(cnf_handle h, unsigned seq, int slot, hipStream_t st, StepState* fin, bool* aborted) {
+    unsigned sq = 0;
+    const cnf_status ws = mirror_wait(h, h->h_mirror + slot, st, fin, &sq, [seq](unsigned tag) { return tag == seq; },
+                                      "the solve kernel finished without publishing a state");
+    if (ws != CNF_OK) return ws;
     *aborted = fin->n_partials < 0;
     if (*aborted) {
         // A workgroup dispatched late may have run after workgroup 0 advanced the index base and left words tagged with
         // the NEXT launch's first meeting: with the stream drained, the meeting words are cleared along with the abort word.
         HIPCHK(h, hipStreamSynchronize(st));
         HIPCHK(h, hipMemset(h->partials, 0, 8 * MAX_PARTIALS * sizeof(float)));
-        HIPCHK(h, hipMemset(h->d_sums + 11, 0, sizeof(float)));
+        HIPCHK(h, hipMemset(sums_word<int>(h, SUMS_ABORT), 0, sizeof(int)));
     } else if (!fin->done && !fin->nonfinite) return fail(h, CNF_ERR_MAXITERS, "maxiters reached before t1");
     return CNF_OK;
 }
@@ -974,7 +991,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
     if (trace_fused) nblk = trace_fused_grid(B);
 
     // initial state
-    StepState* init = &h->h_state[2];
+    StepState* init = init_state(h);
     memset(init, 0, sizeof *init);
     init->t = init->t0 = opts->t0;
     init->t1 = opts->t1;
@@ -1004,14 +1021,12 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
     const bool bcast_rec = rec && !rec->wg && train && bcast_store_floats(B, h->device) == 0;
     const bool bcast_ok = k == CNF_KERNEL_MFMA && (!rec || bcast_rec) && !wave_ok && bcast_solve_supported(h->nd, train != 0, B, h->device);
     if (bcast_ok && !lockstep && !h->no_persist) {
-        if (!h->d_bimg) HIPCHK(h, hipMalloc(&h->d_bimg, bcast_img_floats() * sizeof(float)));
+        RESERVE(h, h->d_bimg, bcast_img_floats());          // (allocated on first use)
         if (!h->bimg_valid) { bcast_pack(h->nd, h->d_params, h->d_bimg, st); HIPCHK(h, hipGetLastError()); h->bimg_valid = true; }
         const size_t need = bcast_store_floats(B, h->device);        // several tiles per workgroup: their rows live in global memory
-        if (need > h->bstore_floats) {
+        if (need > h->d_bstore.capacity()) {
             HIPCHK(h, hipStreamSynchronize(st));
-            if (h->d_bstore) { (void)hipFree(h->d_bstore); h->d_bstore = nullptr; h->bstore_floats = 0; }
-            HIPCHK(h, hipMalloc(&h->d_bstore, need * sizeof(float)));
-            h->bstore_floats = need;
+            RESERVE(h, h->d_bstore, need);
         }
     }
     // ... or of the 32-128-128-32 network in TestMode (exact trace: k_trace3s<SOLVE>, cnf_trace.hip)
@@ -1026,8 +1041,8 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
         const unsigned base = h->mirror_base;
         const int mslot = 1 + (int)(h->one_launch_count % 3);
         Solve3Args sv{};
-        sv.part = h->partials; sv.base_dev = reinterpret_cast<unsigned*>(h->d_sums + 10); sv.abort_flag = reinterpret_cast<int*>(h->d_sums + 11);
-        sv.t_out = h->time_kernel ? reinterpret_cast<unsigned long long*>(h->d_sums + 12) : nullptr;
+        sv.part = h->partials; sv.base_dev = sums_word<unsigned>(h, SUMS_MEET_BASE); sv.abort_flag = sums_word<int>(h, SUMS_ABORT);
+        sv.t_out = h->time_kernel ? sums_word<unsigned long long>(h, SUMS_CLOCK) : nullptr;
         sv.maxiters = (int)opts->maxiters; sv.hairer = hairer ? 1 : 0; sv.init = *init;
         // How long a wait inside the kernel lasts before it gives up: bounded in TIME (the kernel's 100 MHz clock) -- 2 ms per
         // tile a workgroup carries (a meeting's arrivals are microseconds apart when every workgroup is placed; a workgroup
@@ -1068,8 +1083,8 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
             const GradLayout g = grad_layout(h->nd);
             const AdjMfmaLayout m = adj_mfma_layout(h->nd, g);
             TraceArgs ta{};
-            ta.B = B; ta.U[0] = h->U[0]; ta.U[1] = h->U[1]; ta.K1[0] = h->K1[0]; ta.K1[1] = h->K1[1];
-            for (int i = 0; i < 5; ++i) ta.Ks[i] = h->Ks[i];
+            ta.B = B;
+            set_rk_buffers(h, ta);
             ta.norm_kind = -1; ta.st_mut = h->d_state; ta.n_total = (float)n;
             ta.mirror = h->d_mirror + mslot; ta.seq = base;
             s = launch_trace_solve(h->nd, g, m, h->d_adj_img, ta, sv, st) == hipSuccess ? CNF_OK : CNF_ERR_UNSUPPORTED;
@@ -1136,15 +1151,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
                     else final_sync = true;
                 }
                 if (final_sync) HIPCHK(h, hipStreamSynchronize(st));
-                if (stats) {
-                    stats->nf = (hairer ? 2 : 1) + 6 * attempts;
-                    stats->naccept = fin.naccept;
-                    stats->nreject = fin.nreject;
-                    stats->t_final = fin.t;
-                    stats->dt_last = fin.dt;
-                    stats->kernel_used = wave_ok ? CNF_KERNEL_MFMA : k;
-                    stats->launches = launches;
-                }
+                fill_stats(stats, fin, (hairer ? 2 : 1) + 6 * attempts, wave_ok ? CNF_KERNEL_MFMA : k, launches);
                 if (fin.nonfinite) {
                     // (the step sizes above may still be on their way into rec->hs, which the caller drops on this return)
                     if (rec && rec->wg) HIPCHK(h, hipStreamSynchronize(st));
@@ -1170,7 +1177,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
 
     // k1 = f(u0).  With the automatic initial dt on the fused path, the two norms and their controller phases
     // ride in the RHS launches themselves (the last workgroup to finish runs the phase): 2 launches, not 4.
-    unsigned* ticket = reinterpret_cast<unsigned*>(h->d_sums + 8);
+    unsigned* ticket = sums_word<unsigned>(h, SUMS_NORM_TICKET);
     bool fused_init = false;
     if (use_mfma && hairer && !lockstep) {
         s = mfma_rhs_init0(h->mfma, h->nd, train, h->d_state, h->U[0], eps, h->K1[0], h->partials, ticket, B, st);
@@ -1199,8 +1206,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
 
     NormArgs na{};
     na.st = h->d_state; na.n = n; na.partials = h->partials;
-    for (int i = 0; i < 2; ++i) { na.U[i] = h->U[i]; na.K1[i] = h->K1[i]; }
-    for (int i = 0; i < 5; ++i) na.Ks[i] = h->Ks[i];
+    set_rk_buffers(h, na);
 
     if (hairer && fused_init && h->trace_on) {
         // f1 = f(u0 + h*f0) -> Ks[0] with the second norm and the controller phase that sets dt, in the trace launch
@@ -1223,7 +1229,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
             launch_norm_partials(na, nblk, st);
             if ((s = lockstep_controller(h, h->d_state, h->partials, 0, (float)n, st)) != CNF_OK) return s;
         } else {        // norm + controller in one launch (the last block to finish runs the controller)
-            na.ticket = reinterpret_cast<unsigned*>(h->d_sums + 8); na.st_mut = h->d_state; na.ctrl_phase = 0; na.n_total = (float)n;
+            na.ticket = ticket; na.st_mut = h->d_state; na.ctrl_phase = 0; na.n_total = (float)n;
             launch_norm_partials(na, nblk, st);
             na.ticket = nullptr;
         }
@@ -1238,8 +1244,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
             RhsArgs a{};
             a.st = h->d_state; a.B = B; a.S = h->cap_B; a.train = train; a.ws = h->ws; a.eps = eps;
             a.cond = h->mfma.cond; a.cbs = h->cbs;
-            for (int i = 0; i < 2; ++i) { a.U[i] = h->U[i]; a.K1[i] = h->K1[i]; }
-            for (int i = 0; i < 5; ++i) a.Ks[i] = h->Ks[i];
+            set_rk_buffers(h, a);
             a.nk = 1; a.coef[0] = 1.f; a.du = h->Ks[0];
             launch_rhs_generic(h->nd, h->d_params, a, st);
         }
@@ -1248,7 +1253,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
             launch_norm_partials(na, nblk, st);
             if ((s = lockstep_controller(h, h->d_state, h->partials, 1, (float)n, st)) != CNF_OK) return s;
         } else {
-            na.ticket = reinterpret_cast<unsigned*>(h->d_sums + 8); na.st_mut = h->d_state; na.ctrl_phase = 1; na.n_total = (float)n;
+            na.ticket = ticket; na.st_mut = h->d_state; na.ctrl_phase = 1; na.n_total = (float)n;
             launch_norm_partials(na, nblk, st);
             na.ticket = nullptr;
         }
@@ -1325,15 +1330,8 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
         }
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipStreamSynchronize(st));
-        if (stats) {
-            stats->nf = nf + 6 * (snap->naccept + snap->nreject);
-            stats->naccept = snap->naccept;
-            stats->nreject = snap->nreject;
-            stats->t_final = snap->t;
-            stats->dt_last = snap->dt;
-            stats->kernel_used = (k == CNF_KERNEL_MFMA && !use_mfma && !h->trace_on) ? CNF_KERNEL_GENERIC : k;
-            stats->launches = launches;
-        }
+        fill_stats(stats, *snap, nf + 6 * (snap->naccept + snap->nreject),
+                   (k == CNF_KERNEL_MFMA && !use_mfma && !h->trace_on) ? CNF_KERNEL_GENERIC : k, launches);
         if (snap->nonfinite) return fail(h, CNF_ERR_NONFINITE, "solver state became NaN/Inf");
         return CNF_OK;
     }
@@ -1396,22 +1394,11 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
                 HIPCHK(h, hipStreamSynchronize(st));
                 return fail(h, CNF_ERR_MAXITERS, "maxiters reached before t1");
             }
-            // wait for a consistent snapshot newer than the last one read.  The spin backs off: pause first, yield the
-            // core once the wait outlasts a few launches.
+            // wait for a consistent snapshot newer than the last one read
             unsigned sq = 0;
             StepState snap;
-            for (long spins = 0;; ++spins) {
-                if (cnf_mirror_read(hm, &snap, &sq) && (int)(sq - base) > (int)seen) break;
-                if (spins < 4096) _mm_pause();
-                else sched_yield();
-                if (spins % 100000 == 99999) {                     // a faulted kernel would never publish
-                    hipError_t qe = hipStreamQuery(st);
-                    if (qe != hipSuccess && qe != hipErrorNotReady) HIPCHK(h, qe);
-                    if (qe == hipSuccess && !(cnf_mirror_read(hm, &snap, &sq) && (int)(sq - base) > (int)seen))
-                        return fail(h, CNF_ERR_HIP, "step kernels finished without publishing a state");
-                    if (qe == hipSuccess) break;
-                }
-            }
+            if ((s = mirror_wait(h, hm, st, &snap, &sq, [base, seen](unsigned tag) { return (int)(tag - base) > (int)seen; },
+                                 "step kernels finished without publishing a state")) != CNF_OK) return s;
             seen = (long)(sq - base);
             if (snap.done) { fin = snap; done = true; seen_done = seen; }
             need = 1;
@@ -1446,16 +1433,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
     // the step count is already known from the last mirror; the copy is stream-ordered work.  Callers that
     // hand u_out to the host wait here, cnf_inference goes straight on to the post-processing kernel.
     if (final_sync) HIPCHK(h, hipStreamSynchronize(st));
-    nf += 6 * (fin.naccept + fin.nreject);
-    if (stats) {
-        stats->nf = nf;
-        stats->naccept = fin.naccept;
-        stats->nreject = fin.nreject;
-        stats->t_final = fin.t;
-        stats->dt_last = fin.dt;
-        stats->kernel_used = k;
-        stats->launches = launches;
-    }
+    fill_stats(stats, fin, nf + 6 * (fin.naccept + fin.nreject), k, launches);
     if (fin.nonfinite) return fail(h, CNF_ERR_NONFINITE, "solver state became NaN/Inf");
     return CNF_OK;
 }
@@ -1538,7 +1516,7 @@ static cnf_status inference_impl(cnf_handle h, int mode, const float* xs, const 
         // a non-default base distribution: one more launch behind the solve (and its N(0, I) post-processing) overwrites logpx
         // and the sums from the final state in the integrator's buffer -- also behind a submitted launch, in stream order
         launch_base_post(h->nd.n_in, rows_of(h, mode), h->bd, h->last_state, h->U[0], h->U[1], logpx, regs, B, sums5, h->post_part,
-                         reinterpret_cast<unsigned*>(h->d_sums + 9), (hipStream_t)stream);
+                         sums_word<unsigned>(h, SUMS_POST_TICKET), (hipStream_t)stream);
         HIPCHK(h, hipGetLastError());
         if (stats) stats->launches += 1;
     }
@@ -1559,13 +1537,7 @@ static cnf_status finish_submission(cnf_handle h, const cnf_ctx::Submitted& sub,
     }
     if (s != CNF_OK) return s;
     if (!aborted) {
-        if (stats) {
-            const int attempts = fin.naccept + fin.nreject;
-            stats->nf = (sub.hairer ? 2 : 1) + 6 * attempts;
-            stats->naccept = fin.naccept; stats->nreject = fin.nreject;
-            stats->t_final = fin.t; stats->dt_last = fin.dt;
-            stats->kernel_used = sub.k; stats->launches = 1;
-        }
+        fill_stats(stats, fin, (sub.hairer ? 2 : 1) + 6 * (fin.naccept + fin.nreject), sub.k, 1);
         if (fin.nonfinite) return fail(h, CNF_ERR_NONFINITE, "solver state became NaN/Inf");
         return CNF_OK;
     }
@@ -1725,28 +1697,26 @@ extern "C" cnf_status cnf_loss_from_sums(cnf_handle h, int mode, const float* su
 static cnf_status ensure_grad_capacity(cnf_handle h, int B) {
     HIPCHK(h, hipSetDevice(h->device));
     const GradLayout g = grad_layout(h->nd);
-    if (!h->d_PT) HIPCHK(h, hipMalloc(&h->d_PT, h->n_params * sizeof(float)));
-    if (!h->d_adj_img) {
-        const AdjMfmaLayout m = adj_mfma_layout(h->nd, g);
-        HIPCHK(h, hipMalloc(&h->d_adj_img, (size_t)m.img_floats * sizeof(float)));
-    }
+    RESERVE(h, h->d_PT, h->n_params);                      // (allocated on first use, as the images are)
+    { const cnf_status rs = reserve_adj_images(h); if (rs != CNF_OK) return rs; }
     if ((size_t)B <= h->grad_cap_B) return CNF_OK;
     HIPCHK(h, hipDeviceSynchronize());
-    if (h->grad_arena) { (void)hipFree(h->grad_arena); h->grad_arena = nullptr; }
-    if (h->traj) { (void)hipFree(h->traj); (void)hipFree(h->traj_hs); h->traj = nullptr; h->traj_hs = nullptr; h->traj_cap = 0; }
-    h->grad_cap_B = 0;
-    const size_t cap = ((size_t)B + 63) & ~(size_t)63;
+    h->traj.release(); h->traj_hs.release();               // (its slots are sized by grad_cap_B)
+    const size_t want = ((size_t)B + 63) & ~(size_t)63;
     const size_t D = (size_t)h->nd.n_in + 3, n_in = h->nd.n_in;
     // the four factor arrays hold the 6 stages of `fsteps` steps: one batch contraction per fsteps steps
     // (K = 6 fsteps B); as many steps as fit a 1 GiB budget, at most 32
-    const size_t per_step = 12 * ((size_t)g.sum_in + g.sum_out) * cap;       // floats
-    size_t fsteps = ((size_t)1 << 28) / per_step;
+    const size_t per_step_1 = 12 * ((size_t)g.sum_in + g.sum_out);           // floats per sample
+    size_t fsteps = ((size_t)1 << 28) / (per_step_1 * want);
     if (fsteps < 1) fsteps = 1;
     if (fsteps > 32) fsteps = 32;
     h->grad_fsteps = (int)fsteps;
-    const size_t total = 5 * D * cap + 7 * n_in * cap + fsteps * per_step +
-                         ((size_t)GRAD_MAX_KSPLIT + 1) * h->n_params;
-    HIPCHK(h, hipMalloc(&h->grad_arena, total * sizeof(float)));
+    const size_t tail = ((size_t)GRAD_MAX_KSPLIT + 1) * h->n_params;
+    const hipError_t arena_alloc = (hipError_t)h->grad_arena.reserve((5 * D + 7 * n_in + fsteps * per_step_1) * want + tail);
+    // As in ensure_capacity: what is carved from the arena exists only while it does, and neither does what was computed into
+    // it -- the gradient cnf_grad_x hands out, a recorded solve, the trajectory.  A failed reserve leaves all of it cleared.
+    const size_t cap = arena_alloc == hipSuccess ? want : 0;
+    h->grad_last_B = 0; h->rec_valid = false; h->traj_cap = 0;
     float* p = h->grad_arena;
     for (int i = 0; i < 5; ++i) { h->g_US[i] = p; p += D * cap; }
     for (int i = 0; i < 6; ++i) { h->g_W[i] = p; p += n_in * cap; }
@@ -1755,9 +1725,10 @@ static cnf_status ensure_grad_capacity(cnf_handle h, int B) {
     h->g_TS = p; p += fsteps * 6 * (size_t)g.sum_in * cap;
     h->g_AB = p; p += fsteps * 6 * (size_t)g.sum_out * cap;
     h->g_PB = p; p += fsteps * 6 * (size_t)g.sum_out * cap;
-    h->g_part = p; p += (size_t)GRAD_MAX_KSPLIT * h->n_params;
+    h->g_part = p; p += cap ? (size_t)GRAD_MAX_KSPLIT * h->n_params : 0;
     h->g_grad = p;
     h->grad_cap_B = cap;
+    HIPCHK(h, arena_alloc);
     return CNF_OK;
 }
 
@@ -1787,11 +1758,9 @@ static cnf_status wave_loss_grad(cnf_handle h, int mode, const float* xs, const 
         if (rich_step * 256 > ((size_t)1 << 26)) rich_step = 0;
         if (rich_step) { while (rich_step * cap > ((size_t)1 << 26)) cap /= 2; }
         const size_t need = per_step * cap + WV_GCAP + part_f + rich_step * cap;
-        if (need > h->wg_traj_floats) {
+        if (need > h->wg_traj.capacity()) {
             HIPCHK(h, hipDeviceSynchronize());
-            if (h->wg_traj) { (void)hipFree(h->wg_traj); h->wg_traj = nullptr; h->wg_traj_floats = 0; }
-            HIPCHK(h, hipMalloc(&h->wg_traj, need * sizeof(float)));
-            h->wg_traj_floats = need;
+            RESERVE(h, h->wg_traj, need);
         }
         WaveGradArgs wg;
         wg.traj = h->wg_traj; wg.traj_cap = cap; wg.hs_out = h->wg_traj + per_step * cap;
@@ -1814,7 +1783,7 @@ static cnf_status wave_loss_grad(cnf_handle h, int mode, const float* xs, const 
         }
         if (rec.wg_done) {
             HIPCHK(h, launch_grad_reduce(wg.gpart, grad, (int)h->n_params, waves, st));
-            float* sums = reinterpret_cast<float*>(&h->h_state[2]);
+            float* sums = loss_sums_host(h);
             HIPCHK(h, hipMemcpyAsync(sums, h->d_sums, 5 * sizeof(float), hipMemcpyDeviceToHost, st));
             HIPCHK(h, hipStreamSynchronize(st));
             h->last_hs = rec.hs;
@@ -1855,7 +1824,7 @@ static cnf_status train_forward(cnf_handle h, const float* xs, const float* eps,
     }
     if (h->bd.kind) {                                      // the loss of a non-default base distribution: logpx and the sums afresh
         launch_base_post(n_in, D, h->bd, nullptr, fsol, nullptr, h->tmp_logpx, h->tmp_regs, B, h->d_sums, h->post_part,
-                         reinterpret_cast<unsigned*>(h->d_sums + 9), st);
+                         sums_word<unsigned>(h, SUMS_POST_TICKET), st);
         HIPCHK(h, hipGetLastError());
     }
     return CNF_OK;
@@ -1894,14 +1863,7 @@ static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kern
     const float invB = 1.0f / (float)B;
     // constant scalar rows; with per-sample weights the kernels multiply cw[r][b] in where these scalars stand, so they are 1
     const float lam_l = cw ? 1.0f : invB, lam_E = cw ? 1.0f : h->lam[0] * invB, lam_n = cw ? 1.0f : h->lam[1] * invB;
-    static const float A[6][5] = {
-        {0, 0, 0, 0, 0},
-        {TS_A21, 0, 0, 0, 0},
-        {TS_A31, TS_A32, 0, 0, 0},
-        {TS_A41, TS_A42, TS_A43, 0, 0},
-        {TS_A51, TS_A52, TS_A53, TS_A54, 0},
-        {TS_A61, TS_A62, TS_A63, TS_A64, TS_A65}};
-    static const float Bw[6] = {TS_A71, TS_A72, TS_A73, TS_A74, TS_A75, TS_A76};
+    static const AdjTableau T = adj_tableau(tsit5_row);
     if (adj_mfma && adj3b_supported(nd) && h->mfma.d_img3b) {
         // The headline shape: the steps whose factor rows fit the arena in ONE launch on split-bf16 products (cnf_adj3b.hip;
         // the image is the forward kernels'), then one contraction over them -- 2 launches per run of steps instead of one
@@ -1918,16 +1880,14 @@ static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kern
             M.HS = h->g_HS; M.TS = h->g_TS; M.AB = h->g_AB; M.PB = h->g_PB;
             M.lam_l = lam_l; M.lam_E = lam_E; M.lam_n = lam_n;
             M.cw = cw;
-            for (int i = 0; i < 6; ++i) M.bw[i] = Bw[i];
-            for (int m = 0; m < 6; ++m) for (int d = 0; d < 5; ++d) M.kc[m][d] = m - 1 - d >= 0 ? A[m][m - 1 - d] : 0.f;
+            memcpy(M.bw, T.b, sizeof M.bw);
+            memcpy(M.kc, T.kc, sizeof M.kc);
             M.B = B;
             if (adj3b_split(B, cnt)) {          // (batches that leave CUs idle: two launches, the parked state in between)
                 const size_t need = adj3b_park_floats(B, cnt);
-                if (need > h->park_floats) {
+                if (need > h->d_park.capacity()) {
                     HIPCHK(h, hipStreamSynchronize(st));
-                    if (h->d_park) { (void)hipFree(h->d_park); h->d_park = nullptr; h->park_floats = 0; }
-                    if (hipMalloc(&h->d_park, need * sizeof(float)) == hipSuccess) h->park_floats = need;
-                    else { (void)hipGetLastError(); h->d_park = nullptr; }      // (no room for the parked state: one launch per run)
+                    if (h->d_park.reserve(need) != 0) (void)hipGetLastError();  // (no room for the parked state: null, one launch per run)
                 }
                 M.park = h->d_park;
             }
@@ -1941,15 +1901,11 @@ static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kern
     // (MFMA pullback: the steps of a run are gathered and launched together -- as two launches over the whole run where the batch
     // leaves CUs idle, else one launch per step)
     int run0 = 0;                                          // first entry of the current run in h_steps
-    if (adj_mfma && rec_n > h->steps_cap) {
+    if (adj_mfma && (size_t)rec_n > h->h_steps.capacity()) {      // (the pair grows together; h_steps is reserved last)
         HIPCHK(h, hipStreamSynchronize(st));
-        if (h->d_steps) { (void)hipFree(h->d_steps); h->d_steps = nullptr; }
-        if (h->h_steps) { (void)hipHostFree(h->h_steps); h->h_steps = nullptr; }
-        h->steps_cap = 0;
-        const int cap = rec_n + 32;
-        HIPCHK(h, hipMalloc(&h->d_steps, (size_t)cap * sizeof(AdjStepArgs)));
-        HIPCHK(h, hipHostMalloc(&h->h_steps, (size_t)cap * sizeof(AdjStepArgs)));
-        h->steps_cap = cap;
+        h->d_steps.release(); h->h_steps.release();
+        RESERVE(h, h->d_steps, (size_t)rec_n + 32);
+        RESERVE(h, h->h_steps, (size_t)rec_n + 32);
     }
     for (int step = rec_n - 1; step >= 0; --step) {
         float* un;
@@ -1965,10 +1921,10 @@ static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kern
             a.ys = nd.n_cond > 0 ? h->d_ys : nullptr;
             a.lam = h->g_lam;
             a.nw = 0;
-            for (int m = i + 1; m < 6; ++m) { a.w[a.nw] = h->g_W[m]; a.wc[a.nw] = A[m][i]; ++a.nw; }
+            for (int m = i + 1; m < 6; ++m) { a.w[a.nw] = h->g_W[m]; a.wc[a.nw] = T.a[m][i]; ++a.nw; }
             for (int k = a.nw; k < 5; ++k) { a.w[k] = h->g_lam; a.wc[k] = 0.f; }     // unused slots: a readable array, weight 0
-            a.cb = Bw[i]; a.hstep = hs;
-            a.c_l = hs * Bw[i] * lam_l; a.c_E = hs * Bw[i] * lam_E; a.c_n = hs * Bw[i] * lam_n;
+            a.cb = T.b[i]; a.hstep = hs;
+            a.c_l = hs * T.b[i] * lam_l; a.c_E = hs * T.b[i] * lam_E; a.c_n = hs * T.b[i] * lam_n;
             a.cw = cw;
             a.w_out = h->g_W[i];
             // every stage evaluation files its factors behind the earlier ones: rows [slot B, (slot + 1) B)
@@ -1981,7 +1937,7 @@ static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kern
         }
         if (adj_mfma) {        // the six stage pullbacks and the lambda update of this step in ONE launch
             S.first = 5; S.last = 0; S.B = B; S.lam_update = 1; S.lam_out = h->g_lam;
-            for (int m = 0; m < 6; ++m) for (int d = 0; d < 5; ++d) S.kc[m][d] = m - 1 - d >= 0 ? A[m][m - 1 - d] : 0.f;
+            memcpy(S.kc, T.kc, sizeof S.kc);
             h->h_steps[rec_n - 1 - step] = S;
         } else {
             StageK ws{};
@@ -2000,11 +1956,9 @@ static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kern
                 bool two = adj_mfma_run_split(nd, am, B, nsub);
                 if (two) {
                     const size_t need = per_step * nsub;
-                    if (need > h->sc_floats) {
+                    if (need > h->d_sc.capacity()) {
                         HIPCHK(h, hipStreamSynchronize(st));
-                        if (h->d_sc) { (void)hipFree(h->d_sc); h->d_sc = nullptr; h->sc_floats = 0; }
-                        if (hipMalloc(&h->d_sc, need * sizeof(float)) == hipSuccess) h->sc_floats = need;
-                        else { (void)hipGetLastError(); two = false; }          // (no room for the parked rows: one launch per step)
+                        if (h->d_sc.reserve(need) != 0) { (void)hipGetLastError(); two = false; }   // (no room for the parked rows: one launch per step)
                     }
                 }
                 if (two) {
@@ -2031,6 +1985,17 @@ static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kern
     return CNF_OK;
 }
 
+// what the TrainMode pullback reads of the current parameters: their transpose and the padded weight images
+// (pt_valid and img_valid stay two flags: the exact-trace kernels pack the images alone, ensure_adj_images)
+static cnf_status ensure_pullback_params(cnf_handle h, hipStream_t st) {
+    if (h->pt_valid) return CNF_OK;
+    const GradLayout gl = grad_layout(h->nd);
+    HIPCHK(h, launch_transpose_params(h->nd, h->d_params, h->d_PT, st));
+    HIPCHK(h, launch_pack_adj_images(h->nd, gl, adj_mfma_layout(h->nd, gl), h->d_params, h->d_adj_img, st));
+    h->pt_valid = true;
+    return CNF_OK;
+}
+
 extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* eps, int B,
                                     const cnf_solve_opts* opts, float* loss_out, float* grad,
                                     cnf_solve_stats* stats, void* stream) {
@@ -2044,13 +2009,7 @@ extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* 
     if ((s = ensure_capacity(h, B)) != CNF_OK) return s;
     if ((s = ensure_grad_capacity(h, B)) != CNF_OK) return s;
     hipStream_t st = (hipStream_t)stream;
-    const NetDesc& nd = h->nd;
-    const AdjMfmaLayout am = adj_mfma_layout(nd, gl);
-    if (!h->pt_valid) {
-        HIPCHK(h, launch_transpose_params(nd, h->d_params, h->d_PT, st));
-        HIPCHK(h, launch_pack_adj_images(nd, gl, am, h->d_params, h->d_adj_img, st));
-        h->pt_valid = true;
-    }
+    if ((s = ensure_pullback_params(h, st)) != CNF_OK) return s;
 
     if (!h->bd.kind) {   // small batches of a small two-layer tanh network: everything in one launch (wave_loss_grad above)
         bool done = false;
@@ -2061,7 +2020,7 @@ extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* 
     cnf_solve_stats sst{};
     if ((s = train_forward(h, xs, eps, B, opts, rec, sst, stream)) != CNF_OK) return s;
     // (the five sums travel to the host behind the backward pass: the loss VALUE is not needed to start it)
-    float* sums = reinterpret_cast<float*>(&h->h_state[2]);             // pinned; the initial-state slot is free by now
+    float* sums = loss_sums_host(h);
     HIPCHK(h, hipMemcpyAsync(sums, h->d_sums, 5 * sizeof(float), hipMemcpyDeviceToHost, st));
 
     if ((s = train_backward(h, eps, B, opts->kernel, rec.hs, nullptr, grad, st)) != CNF_OK) return s;
@@ -2116,11 +2075,9 @@ static cnf_status test_backward(cnf_handle h, int B, const std::vector<float>& r
     if (rec_n > 0) HIPCHK(h, hipMemcpyAsync(h->traj_hs, rec_hs.data(), (size_t)rec_n * sizeof(float), hipMemcpyHostToDevice, st));
     const int G = adj_test_workgroups(B);
     const size_t per_wg = adj_test_scratch_floats(nd) + h->n_params;
-    if ((size_t)G * per_wg > h->gt_floats) {
+    if ((size_t)G * per_wg > h->d_gt.capacity()) {
         HIPCHK(h, hipStreamSynchronize(st));
-        if (h->d_gt) { (void)hipFree(h->d_gt); h->d_gt = nullptr; h->gt_floats = 0; }
-        HIPCHK(h, hipMalloc(&h->d_gt, (size_t)G * per_wg * sizeof(float)));
-        h->gt_floats = (size_t)G * per_wg;
+        RESERVE(h, h->d_gt, (size_t)G * per_wg);
     }
     float* first;
     if ((s = traj_slot(h, 0, &first)) != CNF_OK) return s;
@@ -2159,7 +2116,7 @@ extern "C" cnf_status cnf_loss_grad_test(cnf_handle h, const float* xs, int B, c
     Recorder rec;
     cnf_solve_stats sst{};
     if ((s = test_forward(h, xs, B, opts, rec, sst, stream)) != CNF_OK) return s;
-    float* sums = reinterpret_cast<float*>(&h->h_state[2]);
+    float* sums = loss_sums_host(h);
     HIPCHK(h, hipMemcpyAsync(sums, h->d_sums, 5 * sizeof(float), hipMemcpyDeviceToHost, st));
     if ((s = test_backward(h, B, rec.hs, nullptr, grad, st)) != CNF_OK) return s;
     HIPCHK(h, hipStreamSynchronize(st));
@@ -2208,12 +2165,9 @@ extern "C" cnf_status cnf_inference_record(cnf_handle h, int mode, const float* 
     if ((s = ensure_capacity(h, B)) != CNF_OK) return s;
     if ((s = ensure_grad_capacity(h, B)) != CNF_OK) return s;
     hipStream_t st = (hipStream_t)stream;
-    if ((size_t)3 * B > h->cw_floats) {
+    if ((size_t)3 * B > h->d_cw.capacity()) {
         HIPCHK(h, hipStreamSynchronize(st));
-        if (h->d_cw) { (void)hipFree(h->d_cw); h->d_cw = nullptr; h->cw_floats = 0; }
-        const size_t cap = ((size_t)3 * B + 1023) & ~(size_t)1023;
-        HIPCHK(h, hipMalloc(&h->d_cw, cap * sizeof(float)));
-        h->cw_floats = cap;
+        RESERVE(h, h->d_cw, ((size_t)3 * B + 1023) & ~(size_t)1023);
     }
     Recorder rec;
     cnf_solve_stats sst{};
@@ -2238,13 +2192,7 @@ extern "C" cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int
     cnf_status s;
     const std::vector<float> hs = h->last_hs;
     if (h->rec_mode == CNF_MODE_TRAIN) {
-        if (!h->pt_valid) {
-            const GradLayout gl = grad_layout(h->nd);
-            const AdjMfmaLayout am = adj_mfma_layout(h->nd, gl);
-            HIPCHK(h, launch_transpose_params(h->nd, h->d_params, h->d_PT, st));
-            HIPCHK(h, launch_pack_adj_images(h->nd, gl, am, h->d_params, h->d_adj_img, st));
-            h->pt_valid = true;
-        }
+        if ((s = ensure_pullback_params(h, st)) != CNF_OK) return s;
         s = train_backward(h, h->rec_eps, B, h->rec_kernel, hs, cot, grad, st);
     } else {
         s = test_backward(h, B, hs, cot, grad, st);
@@ -2292,25 +2240,18 @@ extern "C" cnf_status cnf_loss_grad_collect(cnf_handle h, cnf_solve_stats* stats
 // For a caller whose every launch on this handle goes to that one stream (then stream order is all the synchronisation there
 // is to do): the parameter update between two submitted gradients.
 extern "C" cnf_status cnf_set_params_async(cnf_handle h, const float* flat_dev, size_t n, void* stream) {
-    if (!h || !flat_dev) return CNF_ERR_BAD_ARG;
-    if (n != h->n_params) return fail(h, CNF_ERR_BAD_SHAPE, "parameter count does not match the layer sizes");
+    cnf_status ss = params_check(h, flat_dev, n);
+    if (ss != CNF_OK) return ss;
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(h, hipSetDevice(h->device));
     if (g_submitted_inflight > 0 && g_submitted_stream != s)
         return fail(h, CNF_ERR_BAD_ARG, "cnf_set_params_async: launches are in flight on another stream");
     // A submitted INFERENCE that gives up is run again by its collect call -- with the parameters (and conditioning) the handle
     // holds then.  Changing them under it would silently change its result: such submissions are settled first (host wait).
     // Submitted gradients are not re-run (a launch that gave up reports CNF_ERR_UNSUPPORTED), so they stay in flight.
     for (const auto& sub : h->submitted)
-        if (sub.launched && !sub.grad) { const cnf_status ss = settle_submitted(h); if (ss != CNF_OK) return ss; break; }
+        if (sub.launched && !sub.grad) { if ((ss = settle_submitted(h)) != CNF_OK) return ss; break; }
     HIPCHK(h, hipMemcpyAsync(h->d_params, flat_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    cnf_status ms = mfma_plan_pack(h->mfma, h->nd, h->d_params, s);
-    if (ms != CNF_OK) return fail(h, ms, "MFMA weight packing failed");
-    h->have_params = true;
-    h->rec_valid = false;
-    h->pt_valid = false; h->img_valid = false; h->bimg_valid = false;
-    h->cond_B = 0;
-    return CNF_OK;
+    return params_uploaded(h, s, PARAMS_NO_WAIT);
 }
 
 // d loss / d xs of the last cnf_loss_grad call: the adjoint state at t0 is d loss / d u(t0), and u0 = (xs; zeros) -- its first
