@@ -104,6 +104,8 @@ _SIGNATURES = {
     "cnf_set_shard_comm": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cnf_set_step_trace": (C.c_int, [C.c_void_p, _fp, C.c_int]),
     "cnf_grad_x": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_void_p]),
+    "cnf_set_grad_ys": (C.c_int, [C.c_void_p, C.c_int]),
+    "cnf_grad_ys": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_void_p]),
     "cnf_inference_record": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), _fp, _fp,
                                        C.POINTER(cnf_solve_stats), C.c_void_p]),
     "cnf_inference_pullback": (C.c_int, [C.c_void_p, _fp, C.c_int, _fp, C.c_void_p]),

@@ -196,10 +196,10 @@ class ICNF:
 
     def __call__(self, xs, ps, st, *, eps=None):
         """The Lux-layer form, src/base_icnf.jl:528-543: ``icnf(xs, ps, st)`` (conditional: ``icnf((xs, ys), ps, st)``)
-        = ``(first(inference(icnf, TrainMode(), xs[, ys], ps, st)), st)``.  With a ``ps`` that requires grad the call goes
-        through ``vjp.differentiable_inference``: the result can be back-propagated to ``ps`` and ``xs``."""
+        = ``(first(inference(icnf, TrainMode(), xs[, ys], ps, st)), st)``.  With a ``ps`` (or a ``ys``) that requires grad the
+        call goes through ``vjp.differentiable_inference``: the result can be back-propagated to ``ps``, ``xs`` and ``ys``."""
         from .types import TrainMode
-        if _is_torch(ps) and ps.requires_grad:
+        if (_is_torch(ps) and ps.requires_grad) or (self.cond and _is_torch(xs[1]) and xs[1].requires_grad):
             from .vjp import differentiable_inference
             args = (xs[0], xs[1], ps, st) if self.cond else (xs, ps, st)
             return differentiable_inference(self, TrainMode(), *args, eps=eps)[0], st
@@ -214,6 +214,7 @@ class ICNF:
             self._handle = None
             self._params_id = None
             self._cond_id = None
+            self._grad_ys_on = False
             _OPEN.pop(id(self), None)
 
     def __del__(self):
@@ -791,19 +792,47 @@ def loss(icnf: ICNF, mode, xs, *args, eps=None):
     return loss_from_sums(icnf, mode, sums)
 
 
-def loss_and_grad(icnf: ICNF, mode, xs, *args, eps=None, with_x=False):
+def set_grad_ys(icnf: ICNF, with_ys):
+    """The per-handle switch of the gradient w.r.t. ``ys`` (cnf_set_grad_ys), set from ``with_ys`` by every call that takes a
+    gradient.  ``ValueError`` when it is asked of an unconditional model (which has no switch to set)."""
+    if not icnf.cond:
+        if with_ys:
+            raise ValueError("with_ys: the model has no conditioning inputs")
+        return
+    on = bool(with_ys)
+    if on != getattr(icnf, "_grad_ys_on", False):      # (off on a fresh handle: calls that never ask make no call of it)
+        l, h = _lib.lib(), icnf.handle()
+        _lib.check(l.cnf_set_grad_ys(h, 1 if on else 0), h)
+        icnf._grad_ys_on = on
+
+
+def grad_ys(icnf: ICNF, B, dev, stream, host=False):
+    """d / d ys of the last gradient call (cnf_grad_ys): ``n_cond x B``, where ys lives -- a device tensor, or a numpy array
+    for host inputs."""
+    import torch
+    l, h = _lib.lib(), icnf.handle()
+    gy = torch.empty(B * icnf.n_cond, dtype=torch.float32, device=dev)
+    _lib.check(l.cnf_grad_ys(h, gy.data_ptr(), B, stream), h)
+    gy = gy.view(B, icnf.n_cond).t()
+    return gy.cpu().numpy() if host else gy
+
+
+def loss_and_grad(icnf: ICNF, mode, xs, *args, eps=None, with_x=False, with_ys=False):
     """``(loss, d loss / d ps)``: the pair ``MLJModelInterface.fit`` gets from Enzyme on
     ``loss(icnf, TrainMode(), xs, ps, st)`` (src/exts/mlj_ext/core_icnf.jl:59-73, src/icnf.jl:481-490),
     here from the discrete adjoint of the solve (cnf_loss_grad).  The gradient has the layout of
     ``ps`` and lives where ``xs`` lives (torch.cuda tensor or numpy array).  Conditional models:
-    ``(xs, ys, ps, st)`` as everywhere else.  Steering draws t1 exactly as ``loss`` does."""
+    ``(xs, ys, ps, st)`` as everywhere else.  Steering draws t1 exactly as ``loss`` does.  ``with_x`` / ``with_ys`` append
+    d loss / d xs (``nvars x B``) and, for a conditional model, d loss / d ys (``n_cond x B``) to the result; with
+    ``with_ys`` the gradient always takes the recorded solve."""
     if _mode_id(mode) != _lib.MODE_TRAIN:
-        return _loss_and_grad_test(icnf, mode, xs, *args, with_x=with_x)
+        return _loss_and_grad_test(icnf, mode, xs, *args, with_x=with_x, with_ys=with_ys)
     ys, ps, st = _split_cond_args(icnf, args)
     xb = _xs_colmajor(icnf, xs)
     B = xb.B
     icnf.set_params(ps)
     icnf.set_cond(ys, B)
+    set_grad_ys(icnf, with_ys)
     if eps is not None:
         eb = _as_colmajor(eps, icnf.nvars + n_augment_input(icnf), "eps")
         if eb.B != B:
@@ -843,8 +872,15 @@ def loss_and_grad(icnf: ICNF, mode, xs, *args, eps=None, with_x=False):
             gd = torch.empty(B * icnf.nvars, dtype=torch.float32, device=dev)
             _lib.check(l.cnf_grad_x(h, gd.data_ptr(), B, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), h)
             gx = gd.cpu().numpy().reshape(B, icnf.nvars).T
-        return float(val.value), grad, gx
-    return float(val.value), grad
+    out = (float(val.value), grad) + ((gx,) if with_x else ())
+    if with_ys:
+        if xb.torch is not None:
+            out += (grad_ys(icnf, B, xb.arr.device, _stream(xb)),)
+        else:
+            import torch
+            dev = torch.device("cuda", icnf.device)
+            out += (grad_ys(icnf, B, dev, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), host=True),)
+    return out
 
 
 def loss_and_grad_submit(icnf: ICNF, mode, xs, *args, eps=None):
@@ -866,6 +902,7 @@ def loss_and_grad_submit(icnf: ICNF, mode, xs, *args, eps=None):
     _trim_submitted(icnf)
     icnf.set_params_async(ps)
     icnf.set_cond(ys, B)
+    set_grad_ys(icnf, False)            # (a submitted gradient carries no d / d ys: the switch would refuse it)
     if m != _lib.MODE_TRAIN:
         eb = None
     elif eps is not None:
@@ -892,7 +929,7 @@ def loss_and_grad_collect(icnf: ICNF):
     return inference_collect(icnf)
 
 
-def _loss_and_grad_test(icnf: ICNF, mode, xs, *args, with_x=False):
+def _loss_and_grad_test(icnf: ICNF, mode, xs, *args, with_x=False, with_ys=False):
     """``loss(icnf, TestMode(), xs, ps, st)`` and its gradient through the exact-trace solve (cnf_loss_grad_test): what the
     reference's call tests and benchmark suite differentiate besides the TrainMode loss (test/call_tests.jl ``diff_loss``,
     benchmark/benchmarks.jl:60-99).  Small two-layer (or one-layer) tanh networks in the launch of the solve; every other Dense
@@ -904,6 +941,7 @@ def _loss_and_grad_test(icnf: ICNF, mode, xs, *args, with_x=False):
     B = xb.B
     icnf.set_params(ps)
     icnf.set_cond(ys, B)
+    set_grad_ys(icnf, with_ys)
     opts = _solve_opts(icnf, steer_tspan(icnf, mode))
     stats = _lib.cnf_solve_stats()
     val = C.c_float()
@@ -934,7 +972,10 @@ def _loss_and_grad_test(icnf: ICNF, mode, xs, *args, with_x=False):
     if xb.torch is None and gx is not None:
         gx = gx.cpu().numpy()
     grad = icnf.nn.grad_to_external(grad)
-    return (float(val.value), grad, gx) if with_x else (float(val.value), grad)
+    out = (float(val.value), grad) + ((gx,) if with_x else ())
+    if with_ys:
+        out += (grad_ys(icnf, B, dev, stream, host=xb.torch is None),)
+    return out
 
 
 def loss_sums(icnf: ICNF, logpx, regs):

@@ -11,6 +11,7 @@
 #include "cnf_wave.h"
 #include "cnf_bcast.h"
 #include "cnf_gradt.h"
+#include "cnf_condgrad.h"
 #include "cnf_adj3b.h"
 #include "cnf_step3.h"
 #include "cnf_dist.h"
@@ -147,6 +148,10 @@ struct cnf_ctx {
     int rec_mode = 0, rec_B = 0, rec_kernel = 0;
     const float* rec_eps = nullptr;
     DevBuf<float> d_cw;           // [3][B] per-sample cotangents of the scalar rows, packed by k_vjp_cotangent
+    // cnf_set_grad_ys / cnf_grad_ys: the gradient w.r.t. the conditioning inputs (cnf_condgrad.hip; k_adj_test's own in TestMode)
+    bool grad_ys = false;         // the switch: gradient calls also accumulate d / d ys
+    int gy_last_B = 0;            // batch of the last gradient call that did (0: none, or the switch was off during it)
+    DevBuf<float> d_gy;           // [B][dims[1]] row sums of abar_1, then [B][n_cond] the result
     DevBuf<float> d_ys;           // conditional models: copy of ys (n_cond x cond_B), kept for the weight gradient
     DevBuf<float> stage;          // device staging area of the *_host entry points, owned by the handle, grown on demand:
                                   //   no allocation per call, nothing to free on an error path
@@ -1716,7 +1721,7 @@ static cnf_status ensure_grad_capacity(cnf_handle h, int B) {
     // As in ensure_capacity: what is carved from the arena exists only while it does, and neither does what was computed into
     // it -- the gradient cnf_grad_x hands out, a recorded solve, the trajectory.  A failed reserve leaves all of it cleared.
     const size_t cap = arena_alloc == hipSuccess ? want : 0;
-    h->grad_last_B = 0; h->rec_valid = false; h->traj_cap = 0;
+    h->grad_last_B = 0; h->gy_last_B = 0; h->rec_valid = false; h->traj_cap = 0;
     float* p = h->grad_arena;
     for (int i = 0; i < 5; ++i) { h->g_US[i] = p; p += D * cap; }
     for (int i = 0; i < 6; ++i) { h->g_W[i] = p; p += n_in * cap; }
@@ -1740,6 +1745,7 @@ static cnf_status wave_loss_grad(cnf_handle h, int mode, const float* xs, const 
                                  float* loss_out, float* grad, cnf_solve_stats* stats, void* stream, bool* done,
                                  float* loss_dev = nullptr /* submit: the loss goes here (device), nothing is waited for */) {
     *done = false;
+    h->gy_last_B = 0;                                      // (the in-launch gradient carries no d / d ys)
     cnf_status s = CNF_OK;
     hipStream_t st = (hipStream_t)stream;
     const bool train = mode == CNF_MODE_TRAIN;
@@ -1830,6 +1836,18 @@ static cnf_status train_forward(cnf_handle h, const float* xs, const float* eps,
     return CNF_OK;
 }
 
+// d / d ys (cnf_set_grad_ys): room for the row sums S1 [B][dims[1]] and the result [B][n_cond] behind them.  Grow-only; like the
+// other on-demand buffers it grows behind a wait for the stream, so the steady state allocates nothing.
+static float* gy_result(cnf_handle h, int B) { return h->d_gy + (size_t)B * h->nd.dims[1]; }
+static cnf_status ensure_gy(cnf_handle h, int B, hipStream_t st) {
+    const size_t need = (size_t)B * ((size_t)h->nd.dims[1] + h->nd.n_cond);
+    if (need > h->d_gy.capacity()) {
+        HIPCHK(h, hipStreamSynchronize(st));
+        RESERVE(h, h->d_gy, (need + 4095) & ~(size_t)4095);
+    }
+    return CNF_OK;
+}
+
 // The backward half of cnf_loss_grad (and cnf_inference_pullback in TrainMode): the discrete adjoint of the recorded steps `hs`
 // (sizes; their stage states lie in the trajectory store, the final state in g_US[1]) into grad, d / d u(t0) into g_lam.
 // cot == null: the cotangent of the loss -- three launch-wide scalars and k_final_cotangent / k_base_cotangent, the arithmetic
@@ -1847,6 +1865,11 @@ static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kern
     const bool adj_mfma = kernel != CNF_KERNEL_GENERIC && adj_mfma_supported(nd, am);
     const int rec_n = (int)rec_hs.size();
     const float* cw = cot ? h->d_cw : nullptr;
+    // d / d ys: the layer-1 segment of the AB rows of every run, summed per sample beside the run's contraction (gy_runs counts them)
+    h->gy_last_B = 0;
+    const bool want_gy = h->grad_ys;
+    int gy_runs = 0;
+    if (want_gy && (s = ensure_gy(h, B, st)) != CNF_OK) return s;
     // ---- backward: discrete adjoint of the recorded steps ---------------------------------------
     // capacity is in samples of cap_B; with B <= cap_B at least grad_fsteps steps fit
     // (CNF_GRAD_FSTEPS=n: contract after every n steps instead -- measurements: fewer steps per contraction keep the factor rows
@@ -1976,12 +1999,18 @@ static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kern
             if (ks > ksplit) ksplit = ks;
             HIPCHK(h, launch_wgrad(nd, gl, h->g_AB, h->g_PB, h->g_HS, h->g_TS, h->g_part, (int)h->n_params,
                                    6 * filed * B, ks, ch, st));
+            if (want_gy) HIPCHK(h, launch_cond_rowsum(nd, gl, am, h->g_AB, h->d_gy, B, 6 * filed, gy_runs++ == 0, st));
             filed = 0;
         }
     }
     }
     HIPCHK(h, launch_grad_reduce(h->g_part, grad, (int)h->n_params, ksplit, st));
     h->grad_last_B = B;                                    // (g_lam now holds d loss / d u(t0): cnf_grad_x)
+    if (want_gy) {                                         // gy = W_1y' S1, once per pullback  (no run at all: no step, gy = 0)
+        if (!gy_runs) HIPCHK(h, hipMemsetAsync(h->d_gy, 0, (size_t)B * nd.dims[1] * sizeof(float), st));
+        HIPCHK(h, launch_cond_project(nd, h->d_params, h->d_gy, gy_result(h, B), B, st));
+        h->gy_last_B = B;                                  // (cnf_grad_ys)
+    }
     return CNF_OK;
 }
 
@@ -2011,7 +2040,7 @@ extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* 
     hipStream_t st = (hipStream_t)stream;
     if ((s = ensure_pullback_params(h, st)) != CNF_OK) return s;
 
-    if (!h->bd.kind) {   // small batches of a small two-layer tanh network: everything in one launch (wave_loss_grad above)
+    if (!h->bd.kind && !h->grad_ys) {   // small batches of a small two-layer tanh network: everything in one launch (wave_loss_grad above)
         bool done = false;
         if ((s = wave_loss_grad(h, mode, xs, eps, B, opts, loss_out, grad, stats, stream, &done)) != CNF_OK || done) return s;
     }
@@ -2069,6 +2098,8 @@ static cnf_status test_backward(cnf_handle h, int B, const std::vector<float>& r
     cnf_status s = CNF_OK;
     const NetDesc& nd = h->nd;
     const int rec_n = (int)rec_hs.size();
+    h->gy_last_B = 0;
+    if (h->grad_ys && (s = ensure_gy(h, B, st)) != CNF_OK) return s;
     if (cot) { launch_vjp_cotangent(nd, nd.n_in + 1, h->bd, 0, h->g_US[1], cot, h->g_W[0], h->d_cw, B, st); HIPCHK(h, hipGetLastError()); }
     // the step sizes to the device (behind the steps in the trajectory store's step-size array), scratch and partials of the kernel
     if ((s = traj_reserve(h, rec_n + 1)) != CNF_OK) return s;
@@ -2086,11 +2117,13 @@ static cnf_status test_backward(cnf_handle h, int B, const std::vector<float>& r
     ta.ys = nd.n_cond > 0 ? h->d_ys : nullptr; ta.lam_l = 1.0f / (float)B; ta.lam_out = h->g_lam;
     ta.lam_init = (cot || h->bd.kind) ? h->g_W[0] : nullptr;
     ta.w_l = cot ? h->d_cw : nullptr;
+    ta.gy = h->grad_ys ? gy_result(h, B) : nullptr;
     ta.gpart = h->d_gt; ta.scratch = h->d_gt + (size_t)G * h->n_params; ta.scratch_per_wg = adj_test_scratch_floats(nd);
     ta.B = B; ta.n_params = (int)h->n_params;
     if (launch_adj_test(nd, ta, st) != hipSuccess) { (void)hipGetLastError(); return fail(h, CNF_ERR_UNSUPPORTED, "network too wide for the TestMode adjoint kernel"); }
     HIPCHK(h, launch_grad_reduce(h->d_gt, grad, (int)h->n_params, G, st));
     h->grad_last_B = B;                                    // (g_lam holds d loss / d z(t0): cnf_grad_x)
+    if (h->grad_ys) h->gy_last_B = B;                      // (k_adj_test left d / d ys behind: cnf_grad_ys)
     return CNF_OK;
 }
 
@@ -2109,7 +2142,7 @@ extern "C" cnf_status cnf_loss_grad_test(cnf_handle h, const float* xs, int B, c
     if ((s = ensure_capacity(h, B)) != CNF_OK) return s;
     if ((s = ensure_grad_capacity(h, B)) != CNF_OK) return s;
     bool done = false;
-    if (!h->bd.kind && (s = wave_loss_grad(h, mode, xs, nullptr, B, opts, loss_out, grad, stats, stream, &done)) != CNF_OK) return s;
+    if (!h->bd.kind && !h->grad_ys && (s = wave_loss_grad(h, mode, xs, nullptr, B, opts, loss_out, grad, stats, stream, &done)) != CNF_OK) return s;
     if (done) return CNF_OK;
     // ---- every other network: the recorded exact-trace solve, then k_adj_test (cnf_gradt.hip) over all of its steps in one launch ----
     hipStream_t st = (hipStream_t)stream;
@@ -2216,6 +2249,7 @@ extern "C" cnf_status cnf_loss_grad_submit(cnf_handle h, int mode, const float* 
     if (h->submitted.size() >= 3) return fail(h, CNF_ERR_BAD_ARG, "three launches are submitted already: collect one first");
     // (the gradient inside the solve's launch carries the N(0, I) cotangent: refused at once, nothing is enqueued)
     if (h->bd.kind) return fail(h, CNF_ERR_UNSUPPORTED, "no in-launch gradient with a non-default base distribution: use cnf_loss_grad");
+    if (h->grad_ys) return fail(h, CNF_ERR_UNSUPPORTED, "no in-launch gradient w.r.t. ys (cnf_set_grad_ys is on): use cnf_loss_grad");
     h->collecting = true;
     cnf_status s = check_call(h, mode, B);
     if (s == CNF_OK && (!xs || !opts || !loss_dev || !grad || (mode == CNF_MODE_TRAIN && !eps))) s = fail(h, CNF_ERR_BAD_ARG, "null pointer");
@@ -2262,6 +2296,24 @@ extern "C" cnf_status cnf_grad_x(cnf_handle h, float* gx, int B, void* stream) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpy2DAsync(gx, (size_t)h->nd.nvars * sizeof(float), h->g_lam, (size_t)h->nd.n_in * sizeof(float),
                                (size_t)h->nd.nvars * sizeof(float), (size_t)B, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return CNF_OK;
+}
+
+// The switch of the gradient w.r.t. the conditioning inputs: plain host state, nothing is invalidated.
+extern "C" cnf_status cnf_set_grad_ys(cnf_handle h, int enable) {
+    if (!h) return CNF_ERR_BAD_ARG;
+    if (h->nd.n_cond <= 0) return fail(h, CNF_ERR_BAD_ARG, "cnf_set_grad_ys: the model has no conditioning inputs");
+    h->grad_ys = enable != 0;
+    return CNF_OK;
+}
+
+// d / d ys of the last gradient call, [B][n_cond] as cnf_set_cond takes ys (left behind by k_cond_project / k_adj_test).
+extern "C" cnf_status cnf_grad_ys(cnf_handle h, float* gy, int B, void* stream) {
+    if (!h || !gy) return CNF_ERR_BAD_ARG;
+    if (B < 1 || B != h->gy_last_B || !h->d_gy)
+        return fail(h, CNF_ERR_BAD_ARG, "cnf_grad_ys: no gradient of a batch of this size has been computed with cnf_set_grad_ys on");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(gy, gy_result(h, B), (size_t)B * h->nd.n_cond * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return CNF_OK;
 }
 

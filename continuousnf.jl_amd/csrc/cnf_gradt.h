@@ -14,6 +14,7 @@ struct AdjTestArgs {
     const float* w_l;          // null, or [B]: per-sample cotangent of the dlogp row in place of lam_l (then lam_init is given too)
     const float* lam_init;     // [B][n_in]: d loss / d z(t1) of a non-default base distribution; null: z(t1) lam_l (N(0, I))
     float* lam_out;            // [B][n_in]: d loss / d z(t0)   (cnf_grad_x)
+    float* gy;                 // null, or [B][n_cond]: d loss / d ys, the conditioning rows of hbar_0 summed over stages and steps (cnf_grad_ys)
     float* gpart;              // [adj_test_workgroups(B)][n_params]: one partial of the flat gradient per workgroup
     float* scratch;            // [adj_test_workgroups(B)][scratch_per_wg]
     size_t scratch_per_wg;     // adj_test_scratch_floats(nd)

@@ -109,7 +109,10 @@ k_adj_test(NetDesc nd, AdjTestArgs a, const GtTab tab, int pq_lds) {
 
     for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
         // conditioning rows of x0 (constant over the solve) and d loss / d z(t1) = z(t1) / B
-        for (int k = tid; k < nd.n_cond; k += GT_THREADS) x0[n_in + k] = a.ys[(size_t)b * nd.n_cond + k];
+        for (int k = tid; k < nd.n_cond; k += GT_THREADS) {
+            x0[n_in + k] = a.ys[(size_t)b * nd.n_cond + k];
+            if (a.gy) a.gy[(size_t)b * nd.n_cond + k] = 0.f;                 // (owned by the thread that adds to it below)
+        }
         const float lam_l = a.w_l ? a.w_l[b] : a.lam_l;                     // (one sample per workgroup: uniform either way)
         {
             const float* uf = a.traj + (size_t)a.nsteps * a.slot_stride + (size_t)b * D;
@@ -231,6 +234,8 @@ k_adj_test(NetDesc nd, AdjTestArgs a, const GtTab tab, int pq_lds) {
                         float acc = 0.f;
                         for (int j = 0; j < out; ++j) acc = fmaf(Wm(l, j, k), ab[j], acc);
                         hb[k] = acc;
+                        // the conditioning rows of hbar_0 are this stage's d / d ys  (each element by its own thread, as gp above)
+                        if (l == 0 && k >= n_in && a.gy) a.gy[(size_t)b * nd.n_cond + (k - n_in)] += acc;
                     }
                     __syncthreads();
                 }

@@ -8,8 +8,9 @@ src/base_icnf.jl:528-543) and test/call_tests.jl:193-252 differentiates a closur
 adjoint of the recorded solve with per-sample cotangents.
 
 Rows the model does not integrate carry no cotangent: with ``lambda1 = 0`` the E row is identically zero and its cotangent is
-ignored, likewise ``lambda2`` / n and ``lambda3`` / A, and all three in TestMode.  Gradients are taken w.r.t. ``ps`` and ``xs``;
-``ys``, ``eps`` and the time span are constants.
+ignored, likewise ``lambda2`` / n and ``lambda3`` / A, and all three in TestMode.  Gradients are taken w.r.t. ``ps``, ``xs`` and,
+for a conditional model, the conditioning inputs ``ys`` (cnf_set_grad_ys / cnf_grad_ys: ``ys = encoder(context)`` trains through
+the flow); ``eps`` and the time span are constants.
 """
 from __future__ import annotations
 
@@ -19,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from .base_icnf import (ICNF, _as_colmajor, _is_torch, _mode_id, _solve_opts, _split_cond_args, _stream, _xs_colmajor,
-                        draw_eps, n_augment_input, raise_if_no_gpu, steer_tspan)
+                        draw_eps, grad_ys, n_augment_input, raise_if_no_gpu, set_grad_ys, steer_tspan)
 
 
 def _to_device(icnf: ICNF, a):
@@ -105,10 +106,11 @@ def _cot_matrix(cot, B, device):
     return out
 
 
-def inference_pullback(icnf: ICNF, cot, with_x=False):
-    """``sum_b sum_r cot[r][b] d out_r[b] / d ps`` (and ``/ d xs`` with ``with_x``) through the steps ``inference_record``
-    recorded, in the caller's parameter layout.  ``cot``: ``(g_logpx, (g_E, g_n, g_A))`` or a ``4 x B`` array; ``None`` entries
-    are zeros.  May be called several times on one record.  ``CNFError`` (``ERR_BAD_ARG``) when the record is gone."""
+def inference_pullback(icnf: ICNF, cot, with_x=False, with_ys=False):
+    """``sum_b sum_r cot[r][b] d out_r[b] / d ps`` (and ``/ d xs`` with ``with_x``, ``/ d ys`` -- ``n_cond x B``, conditional
+    models only -- with ``with_ys``, appended in that order) through the steps ``inference_record`` recorded, in the caller's
+    parameter layout.  ``cot``: ``(g_logpx, (g_E, g_n, g_A))`` or a ``4 x B`` array; ``None`` entries are zeros.  May be called
+    several times on one record.  ``CNFError`` (``ERR_BAD_ARG``) when the record is gone."""
     import torch
     l, h = _lib.lib(), icnf.handle()
     rec = getattr(icnf, "_record", None)
@@ -128,6 +130,7 @@ def inference_pullback(icnf: ICNF, cot, with_x=False):
     cm = _cot_matrix(cot, B, dev)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     grad = torch.empty(icnf.nn.n_params_internal, dtype=torch.float32, device=dev)
+    set_grad_ys(icnf, with_ys)
     _lib.check(l.cnf_inference_pullback(h, cm.data_ptr(), B, grad.data_ptr(), stream), h)
     grad = icnf.nn.grad_to_external(grad)
     gx = None
@@ -135,10 +138,13 @@ def inference_pullback(icnf: ICNF, cot, with_x=False):
         gx = torch.empty(B * icnf.nvars, dtype=torch.float32, device=dev)
         _lib.check(l.cnf_grad_x(h, gx.data_ptr(), B, stream), h)
         gx = gx.view(B, icnf.nvars).t()
+    gy = grad_ys(icnf, B, dev, stream, host) if with_ys else None
     if host:
         grad = grad.cpu().numpy()
         gx = gx.cpu().numpy() if gx is not None else None
-    return (grad, gx) if with_x else grad
+    if not with_x and not with_ys:
+        return grad
+    return (grad,) + ((gx,) if with_x else ()) + ((gy,) if with_ys else ())
 
 
 def _autograd_function():
@@ -147,12 +153,15 @@ def _autograd_function():
     class _Inference(torch.autograd.Function):
         @staticmethod
         def forward(ctx, icnf, mode, xs, ys, ps, eps, tspan):
+            if _is_torch(ys) and ys.requires_grad:   # (a ys that asks for nothing stays the caller's object: set_cond knows it)
+                ys = ys.detach()
             args = (ys, ps, None) if icnf.cond else (ps, None)
             logpx, (E, n, A) = inference_record(icnf, mode, xs.detach(), *args, eps=eps, tspan=tspan)
             rec = icnf._record
             ctx.icnf, ctx.mode, ctx.token = icnf, mode, rec["token"]
             # what a second recording needs: the solve is deterministic, so the same inputs give the same record bit for bit
             ctx.xs, ctx.ys, ctx.ps, ctx.eb, ctx.tspan = xs.detach(), ys, ps.detach(), rec["eb"], rec["tspan"]
+            ctx.ys_shape = None if ys is None else ys.shape
             ctx.ps_shape = ps.shape
             ctx.set_materialize_grads(False)
             return logpx.clone(), E.clone(), n.clone(), A.clone()
@@ -171,15 +180,19 @@ def _autograd_function():
             rec = getattr(icnf, "_record", None)
             if rec is None or rec["token"] is not ctx.token:
                 record_again()
+            # d / d ys is asked of the library only when whatever produced ys wants it (also after record_again)
+            need_ys = bool(ctx.needs_input_grad[3])
             try:
-                grad, gx = inference_pullback(icnf, cot, with_x=True)
+                res = inference_pullback(icnf, cot, with_x=True, with_ys=need_ys)
             except _lib.CNFError as e:          # the record was displaced by another call on the handle: record again
                 if e.status != _lib.ERR_BAD_ARG:
                     raise
                 record_again()
-                grad, gx = inference_pullback(icnf, cot, with_x=True)
+                res = inference_pullback(icnf, cot, with_x=True, with_ys=need_ys)
+            grad, gx = res[0], res[1]
+            gy = res[2].reshape(ctx.ys_shape).contiguous() if need_ys else None
             need_x, need_ps = ctx.needs_input_grad[2], ctx.needs_input_grad[4]
-            return (None, None, gx.contiguous() if need_x else None, None,
+            return (None, None, gx.contiguous() if need_x else None, gy,
                     grad.reshape(ctx.ps_shape) if need_ps else None, None, None)
 
     return _Inference
@@ -189,8 +202,8 @@ _FUNCTION = None
 
 
 def differentiable_inference(icnf: ICNF, mode, xs, *args, eps=None):
-    """``inference`` as a differentiable function of ``ps`` and ``xs`` (device tensors): forward = ``inference_record``,
-    backward = ``inference_pullback``.  Returns ``(logpx, (E, n, A))`` attached to the autograd graph.  If another call on the
+    """``inference`` as a differentiable function of ``ps``, ``xs`` and (conditional models) ``ys`` (device tensors): forward
+    = ``inference_record``, backward = ``inference_pullback`` (which is asked for d / d ys only when ``ys`` requires grad).  Returns ``(logpx, (E, n, A))`` attached to the autograd graph.  If another call on the
     model displaced the record before ``backward``, the solve is recorded again from the saved inputs (same outputs bit for
     bit: the solve is deterministic) and then pulled back."""
     global _FUNCTION

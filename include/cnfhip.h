@@ -323,6 +323,18 @@ int cnf_grad_steps(cnf_handle h, float* hs, int cap);
  * stream-ordered.  It is the adjoint state at t0 restricted to the data rows (u0 = vcat(xs, zeros), src/base_icnf.jl:
  * 275-276): left behind by the backward sweep, nothing is recomputed.  B must be that call's batch size. */
 cnf_status cnf_grad_x(cnf_handle h, float* gx, int B, void* stream);
+/* The gradient w.r.t. the conditioning inputs ys of a conditional model (nn(vcat(z, ys)), src/layers/cond_layer.jl:7-9,
+ * src/base_icnf.jl:288-309: in the reference ys is an ordinary array argument that Enzyme / Zygote differentiate).
+ * cnf_set_grad_ys: a per-handle switch, off by default; CNF_ERR_BAD_ARG on a handle with n_cond = 0.  While it is on,
+ * cnf_loss_grad, cnf_loss_grad_test and cnf_inference_pullback (and their _host forms) also accumulate d / d ys -- per stage
+ * pullback the rows of W_1' abar_1 that belong to ys -- into a buffer the handle owns; the two loss gradients then always take
+ * the recorded solve (never the launch of the solve itself), and cnf_loss_grad_submit returns CNF_ERR_UNSUPPORTED at once.
+ * While it is off every call launches exactly what it launches without this feature.  Toggling invalidates nothing.
+ * cnf_grad_ys: d / d ys of the last gradient call on this handle: gy is n_cond x B, laid out as cnf_set_cond takes ys, DEVICE
+ * memory, written stream-ordered.  CNF_ERR_BAD_ARG when the switch was off during that call, B is not that call's batch size,
+ * or no gradient has run. */
+cnf_status cnf_set_grad_ys(cnf_handle h, int enable);
+cnf_status cnf_grad_ys(cnf_handle h, float* gy, int B, void* stream);
 
 /* ---- differentiable inference: the vector-Jacobian product of `inference` for ANY cotangent of its four outputs ----
  * (what a custom loss -- ICNFModel(m, loss), src/exts/mlj_ext/core_icnf.jl:1-29 -- or a larger differentiable program around

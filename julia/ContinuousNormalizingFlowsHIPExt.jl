@@ -374,6 +374,22 @@ function inference_pullback!(grad, icnf::ICNF{T, <:HIPMatrixMode}, cot, B::Integ
     grad
 end
 
+# d / d ys of a conditional model (src/layers/cond_layer.jl:7-9: ys is an array argument Enzyme / Zygote differentiate like any
+# other).  set_grad_ys!(icnf, true) before the gradient call (loss_and_grad!, inference_pullback!); grad_ys! then copies the
+# n_cond x B result of that call into a device array laid out as ys.  Off by default; with the switch on the loss gradients take
+# the recorded solve and submitted gradients are refused.
+function set_grad_ys!(icnf::ICNF{T, <:HIPMatrixMode}, enable::Bool) where {T}
+    h = handle(icnf)
+    check(@ccall(libcnfhip.cnf_set_grad_ys(h::Ptr{Cvoid}, Cint(enable)::Cint)::Cint), h)
+    icnf
+end
+
+function grad_ys!(gy, icnf::ICNF{T, <:HIPMatrixMode}, B::Integer; stream = C_NULL) where {T}
+    h = handle(icnf)
+    check(@ccall(libcnfhip.cnf_grad_ys(h::Ptr{Cvoid}, pointer(gy)::Ptr{Float32}, B::Cint, stream::Ptr{Cvoid})::Cint), h)
+    gy
+end
+
 # ---- parameter files (CNFP, written/read by continuousnf.jl_amd.mlj.save_params/load_params) ----
 function save_params(path, icnf::ICNF, nn_dims::Vector{Int}, acts::Vector{Int}, ps; n_cond = 0)
     open(path, "w") do io
