@@ -57,7 +57,8 @@ from .rng import HIPRNG
 from .types import (FFJORD, RNODE, CondFFJORD, CondPlanar, CondRNODE, HIPJacVecMatrixMode,
                     HIPMatrixMode, HIPVecJacMatrixMode, Planar, TestMode, TrainMode)
 from .vjp import differentiable_inference, inference_pullback, inference_record, tempered_loss, weighted_loss
-from . import mlj, parallel, vjp
+from .gen_vjp import differentiable_generate, generate_pullback, generate_record, reverse_kl
+from . import gen_vjp, mlj, parallel, vjp
 from .mlj import (Adam, CondICNFModel, ICNFModel, Lion, Machine, fit, fit_, fitted_params, load_params, machine, save_params,
                   transform)
 

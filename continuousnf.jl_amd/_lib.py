@@ -122,6 +122,13 @@ _SIGNATURES = {
 }
 COMM_ID_BYTES = 128
 EXPORTS = tuple(_SIGNATURES)
+# the sampling direction (include/cnfhip_generate.h): a table of its own -- EXPORTS is the list include/cnfhip.h itself declares
+_SAMPLING_SIGNATURES = {
+    "cnf_generate_record": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), _fp, _fp,
+                                      C.POINTER(cnf_solve_stats), C.c_void_p]),
+    "cnf_generate_pullback": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _fp, _fp, C.c_void_p]),
+}
+SAMPLING_EXPORTS = tuple(_SAMPLING_SIGNATURES)
 
 _lib = None
 
@@ -159,7 +166,7 @@ def lib():
         except ImportError:
             pass
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()):
             f = getattr(l, name)
             f.restype, f.argtypes = res, args
         _lib = l

@@ -609,9 +609,23 @@ def generate_prob(icnf: ICNF, mode, ps, st, n: int, *, ys=None, z0=None, eps=Non
     ``HIPRNG`` on the device, z0 first and eps from the elements after it, and the sample comes back as a device tensor.  A
     non-default ``basedist`` takes the standard normals the default would have drawn through ``mu + L n`` on the device
     (cnf_base_sample), wherever they were drawn; a ``z0`` given by the caller is used as it is."""
-    m = _mode_id(mode)
     n_in = icnf.nvars + n_augment_input(icnf)
     D = n_in + 1 + n_augment(icnf, mode)
+    zb, eb = _generate_inputs(icnf, mode, ps, n, ys, z0, eps)
+    u0 = _empty_like(zb, D, n)
+    v = u0.arr.view(n, D) if u0.torch is not None else u0.arr.reshape(n, D)
+    src = zb.flat2d() if zb.torch is not None else zb.arr.reshape(n, n_in)
+    v[:, :n_in] = src
+    v[:, n_in:] = 0.0                                   # zrs = zeros(n_aug + 1, n)  (:367-368)
+    t0, t1 = steer_tspan(icnf, mode)
+    return ODEProblem(icnf, mode, u0, eb, (t1, t0), ps)  # reverse(tspan)  (:377)
+
+
+def _generate_inputs(icnf: ICNF, mode, ps, n: int, ys=None, z0=None, eps=None):
+    """What ``generate_prob`` uploads and draws, in its order: parameters, conditioning, the base draw ``z0`` and the probes
+    ``eps`` (n_in x n each, as _Buf)."""
+    _mode_id(mode)
+    n_in = icnf.nvars + n_augment_input(icnf)
     icnf.set_params(ps)
     icnf.set_cond(ys, n)
     if z0 is None and isinstance(icnf.rng, HIPRNG):
@@ -635,13 +649,7 @@ def generate_prob(icnf: ICNF, mode, ps, st, n: int, *, ys=None, z0=None, eps=Non
         eb = draw_eps(icnf, zb, n)
     else:
         eb = _as_colmajor(eps, n_in, "eps")
-    u0 = _empty_like(zb, D, n)
-    v = u0.arr.view(n, D) if u0.torch is not None else u0.arr.reshape(n, D)
-    src = zb.flat2d() if zb.torch is not None else zb.arr.reshape(n, n_in)
-    v[:, :n_in] = src
-    v[:, n_in:] = 0.0                                   # zrs = zeros(n_aug + 1, n)  (:367-368)
-    t0, t1 = steer_tspan(icnf, mode)
-    return ODEProblem(icnf, mode, u0, eb, (t1, t0), ps)  # reverse(tspan)  (:377)
+    return zb, eb
 
 
 def base_sample(icnf: ICNF, normals, n: int):
@@ -665,8 +673,14 @@ def generate_sol(icnf: ICNF, mode, prob: ODEProblem):
     return fsol.view()[: icnf.nvars, :]
 
 
-def generate(icnf: ICNF, mode, ps, st=None, n: int = 1, *, ys=None, z0=None, eps=None):
-    """src/base_icnf.jl:447-455 (conditional: :457-466, ``ys`` as keyword here)."""
+def generate(icnf: ICNF, mode, ps, st=None, n: int = 1, *, ys=None, z0=None, eps=None, with_logp=False):
+    """src/base_icnf.jl:447-455 (conditional: :457-466, ``ys`` as keyword here).  ``with_logp``: return ``(xs, logq)``, the
+    samples and their log-density under the flow from the one solve (``gen_vjp.generate_record``: with ``naugmented > 0`` the
+    density of the whole n_in-dimensional final state; TestMode exact, TrainMode the Hutchinson estimate for the ``eps``
+    used).  Without it the call launches exactly what it always has."""
+    if with_logp:
+        from .gen_vjp import generate_record
+        return generate_record(icnf, mode, ps, st, n, ys=ys, z0=z0, eps=eps)
     return generate_sol(icnf, mode, generate_prob(icnf, mode, ps, st, n, ys=ys, z0=z0, eps=eps))
 
 

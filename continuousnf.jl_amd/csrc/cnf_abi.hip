@@ -147,6 +147,8 @@ struct cnf_ctx {
     bool rec_valid = false;
     int rec_mode = 0, rec_B = 0, rec_kernel = 0;
     const float* rec_eps = nullptr;
+    int rec_kind = 0;             // whose record it is: REC_INFERENCE (cnf_inference_record) or REC_GENERATE (cnf_generate_record)
+    DevBuf<float> d_gz0;          // cnf_generate_record: the handle's copy of the base draw z0 [B][n_in] (read again by the pullback)
     DevBuf<float> d_cw;           // [3][B] per-sample cotangents of the scalar rows, packed by k_vjp_cotangent
     // cnf_set_grad_ys / cnf_grad_ys: the gradient w.r.t. the conditioning inputs (cnf_condgrad.hip; k_adj_test's own in TestMode)
     bool grad_ys = false;         // the switch: gradient calls also accumulate d / d ys
@@ -163,6 +165,7 @@ struct cnf_ctx {
 };
 
 static const int MAX_PARTIALS = 1024;
+enum { REC_INFERENCE = 1, REC_GENERATE = 2 };
 
 #define HIPCHK(h, call)                                                                  \
     do {                                                                                 \
@@ -1853,8 +1856,10 @@ static cnf_status ensure_gy(cnf_handle h, int B, hipStream_t st) {
 // cot == null: the cotangent of the loss -- three launch-wide scalars and k_final_cotangent / k_base_cotangent, the arithmetic
 // cnf_loss_grad has always had.  cot = [4][B] (rows logpx, E, n, A): k_vjp_cotangent forms the terminal cotangent and packs the
 // per-sample weights of the scalar rows into d_cw, which every pullback kernel then reads in place of the scalars.
+// gen != null (cnf_generate_pullback; cot is null then): the same per-sample pullback seeded by k_generate_cotangent instead.
+struct GenCot { const float* cot_z; const float* cot_logq; };
 static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kernel, const std::vector<float>& rec_hs, const float* cot,
-                                 float* grad, hipStream_t st) {
+                                 float* grad, hipStream_t st, const GenCot* gen = nullptr) {
     cnf_status s = CNF_OK;
     const NetDesc& nd = h->nd;
     const int n_in = nd.n_in, D = n_in + 3;
@@ -1864,7 +1869,7 @@ static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kern
     // the pullback kernel follows the kernel choice of the solve: GENERIC -> VALU, otherwise MFMA when it fits
     const bool adj_mfma = kernel != CNF_KERNEL_GENERIC && adj_mfma_supported(nd, am);
     const int rec_n = (int)rec_hs.size();
-    const float* cw = cot ? h->d_cw : nullptr;
+    const float* cw = (cot || gen) ? h->d_cw : nullptr;
     // d / d ys: the layer-1 segment of the AB rows of every run, summed per sample beside the run's contraction (gy_runs counts them)
     h->gy_last_B = 0;
     const bool want_gy = h->grad_ys;
@@ -1880,7 +1885,8 @@ static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kern
     int ksplit = 1, filed = 0;
     HIPCHK(h, hipMemsetAsync(h->g_part, 0, (size_t)GRAD_MAX_KSPLIT * h->n_params * sizeof(float), st));
     const float* fsol = h->g_US[1];
-    if (cot) { launch_vjp_cotangent(nd, D, h->bd, 1, fsol, cot, h->g_lam, h->d_cw, B, st); HIPCHK(h, hipGetLastError()); }
+    if (gen) { launch_generate_cotangent(n_in, gen->cot_z, gen->cot_logq, h->g_lam, h->d_cw, B, st); HIPCHK(h, hipGetLastError()); }
+    else if (cot) { launch_vjp_cotangent(nd, D, h->bd, 1, fsol, cot, h->g_lam, h->d_cw, B, st); HIPCHK(h, hipGetLastError()); }
     else if (h->bd.kind) { launch_base_cotangent(nd, D, h->bd, h->lam[2], fsol, h->g_lam, B, st); HIPCHK(h, hipGetLastError()); }
     else HIPCHK(h, launch_final_cotangent(nd, h->lam[2], fsol, h->g_lam, B, st));
     const float invB = 1.0f / (float)B;
@@ -2093,14 +2099,16 @@ static cnf_status test_forward(cnf_handle h, const float* xs, int B, const cnf_s
 
 // The backward half: k_adj_test (cnf_gradt.hip) over all recorded steps in one launch, then the sum of its partials.  cot == null:
 // the cotangent of the loss (1 / B per sample); cot = [4][B]: k_vjp_cotangent leaves d / d z(t1) in g_W[0] and w_l = -cot_l in d_cw
-// (rows E, n, A do not exist in TestMode: their cotangents are not read).
-static cnf_status test_backward(cnf_handle h, int B, const std::vector<float>& rec_hs, const float* cot, float* grad, hipStream_t st) {
+// (rows E, n, A do not exist in TestMode: their cotangents are not read); gen != null: k_generate_cotangent leaves them instead.
+static cnf_status test_backward(cnf_handle h, int B, const std::vector<float>& rec_hs, const float* cot, float* grad, hipStream_t st,
+                                const GenCot* gen = nullptr) {
     cnf_status s = CNF_OK;
     const NetDesc& nd = h->nd;
     const int rec_n = (int)rec_hs.size();
     h->gy_last_B = 0;
     if (h->grad_ys && (s = ensure_gy(h, B, st)) != CNF_OK) return s;
-    if (cot) { launch_vjp_cotangent(nd, nd.n_in + 1, h->bd, 0, h->g_US[1], cot, h->g_W[0], h->d_cw, B, st); HIPCHK(h, hipGetLastError()); }
+    if (gen) { launch_generate_cotangent(nd.n_in, gen->cot_z, gen->cot_logq, h->g_W[0], h->d_cw, B, st); HIPCHK(h, hipGetLastError()); }
+    else if (cot) { launch_vjp_cotangent(nd, nd.n_in + 1, h->bd, 0, h->g_US[1], cot, h->g_W[0], h->d_cw, B, st); HIPCHK(h, hipGetLastError()); }
     // the step sizes to the device (behind the steps in the trajectory store's step-size array), scratch and partials of the kernel
     if ((s = traj_reserve(h, rec_n + 1)) != CNF_OK) return s;
     if (rec_n > 0) HIPCHK(h, hipMemcpyAsync(h->traj_hs, rec_hs.data(), (size_t)rec_n * sizeof(float), hipMemcpyHostToDevice, st));
@@ -2115,8 +2123,8 @@ static cnf_status test_backward(cnf_handle h, int B, const std::vector<float>& r
     AdjTestArgs ta{};
     ta.P = h->d_params; ta.traj = first; ta.slot_stride = traj_slot_floats(h); ta.hs = h->traj_hs; ta.nsteps = rec_n;
     ta.ys = nd.n_cond > 0 ? h->d_ys : nullptr; ta.lam_l = 1.0f / (float)B; ta.lam_out = h->g_lam;
-    ta.lam_init = (cot || h->bd.kind) ? h->g_W[0] : nullptr;
-    ta.w_l = cot ? h->d_cw : nullptr;
+    ta.lam_init = (cot || gen || h->bd.kind) ? h->g_W[0] : nullptr;
+    ta.w_l = (cot || gen) ? h->d_cw : nullptr;
     ta.gy = h->grad_ys ? gy_result(h, B) : nullptr;
     ta.gpart = h->d_gt; ta.scratch = h->d_gt + (size_t)G * h->n_params; ta.scratch_per_wg = adj_test_scratch_floats(nd);
     ta.B = B; ta.n_params = (int)h->n_params;
@@ -2211,6 +2219,7 @@ extern "C" cnf_status cnf_inference_record(cnf_handle h, int mode, const float* 
     HIPCHK(h, hipMemcpyAsync(regs, h->tmp_regs, (size_t)3 * B * sizeof(float), hipMemcpyDeviceToDevice, st));
     HIPCHK(h, hipStreamSynchronize(st));
     h->rec_valid = true; h->rec_mode = mode; h->rec_B = B; h->rec_kernel = opts->kernel; h->rec_eps = train ? eps : nullptr;
+    h->rec_kind = REC_INFERENCE;
     if (stats) *stats = sst;
     return CNF_OK;
 }
@@ -2218,8 +2227,8 @@ extern "C" cnf_status cnf_inference_record(cnf_handle h, int mode, const float* 
 extern "C" cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int B, float* grad, void* stream) {
     if (!h) return CNF_ERR_BAD_ARG;
     if (!cot || !grad) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
-    if (!h->rec_valid || B != h->rec_B || (size_t)h->last_hs.size() == 0 || !h->d_cw)
-        return fail(h, CNF_ERR_BAD_ARG, "no recorded solve of a batch of this size: call cnf_inference_record first");
+    if (!h->rec_valid || h->rec_kind != REC_INFERENCE || B != h->rec_B || (size_t)h->last_hs.size() == 0 || !h->d_cw)
+        return fail(h, CNF_ERR_BAD_ARG, "no recorded inference of a batch of this size: call cnf_inference_record first");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     cnf_status s;
@@ -2231,6 +2240,93 @@ extern "C" cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int
         s = test_backward(h, B, hs, cot, grad, st);
     }
     if (s != CNF_OK) { h->rec_valid = false; return s; }
+    HIPCHK(h, hipStreamSynchronize(st));
+    return CNF_OK;
+}
+
+// ---- differentiable sampling: generate with the log-density of the sample, and its pullback -----------------------------------
+// cnf_generate_record integrates u0 = [z0; 0] over the span the caller gives (reverse(tspan)) with the solve RECORDED, as
+// cnf_inference_record does, and reads both outputs off the one final state: z = its rows 1..n_in and
+// logq = logpdf(basedist, z0) + dlogp (sign +: the dlogp row integrates -tr J along the way the sample travels, `inference`
+// subtracts what it gains on the way back).  cnf_generate_pullback is the discrete adjoint of those steps for any cotangent of
+// (z, logq): the terminal cotangent is lam = cot_z on the state rows and +cot_logq on the dlogp row (k_generate_cotangent), zero
+// on the E and n rows, and the pullback kernels are those of cnf_inference_pullback, unchanged -- signed step sizes included.
+// d / d z0 is what they leave in g_lam plus cot_logq d logpdf(basedist, z0) / d z0 (k_generate_z0_grad).
+extern "C" cnf_status cnf_generate_record(cnf_handle h, int mode, const float* z0, const float* eps, int B, const cnf_solve_opts* opts,
+                                          float* z_out, float* logq, cnf_solve_stats* stats, void* stream) {
+    cnf_status s = check_call(h, mode, B);
+    if (s != CNF_OK) return s;
+    const bool train = mode == CNF_MODE_TRAIN;
+    if (!z0 || !opts || !z_out || !logq || (train && !eps)) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    if (B < 1) return fail(h, CNF_ERR_BAD_SHAPE, "a recorded sampling solve needs B >= 1");
+    if (train) {
+        const GradLayout gl = grad_layout(h->nd);
+        if (!grad_supported(h->nd, gl)) return fail(h, CNF_ERR_UNSUPPORTED, "network too wide for the gradient kernels");
+    }
+    if ((s = ensure_capacity(h, B)) != CNF_OK) return s;
+    if ((s = ensure_grad_capacity(h, B)) != CNF_OK) return s;
+    hipStream_t st = (hipStream_t)stream;
+    const NetDesc& nd = h->nd;
+    const int n_in = nd.n_in, D = rows_of(h, mode);
+    const size_t nz = (size_t)n_in * B;
+    if ((size_t)3 * B > h->d_cw.capacity() || nz > h->d_gz0.capacity()) {
+        HIPCHK(h, hipStreamSynchronize(st));
+        RESERVE(h, h->d_cw, ((size_t)3 * B + 1023) & ~(size_t)1023);
+        RESERVE(h, h->d_gz0, (nz + 1023) & ~(size_t)1023);
+    }
+    // u0 = [z0; 0] in g_US[0] (not in the integrator's own U[0]: a one-launch solve that gives up is run again from it), and the
+    // handle's copy of z0 for the pullback
+    float* u0 = h->g_US[0];
+    HIPCHK(h, hipMemsetAsync(u0, 0, (size_t)D * B * sizeof(float), st));
+    HIPCHK(h, hipMemcpy2DAsync(u0, (size_t)D * sizeof(float), z0, (size_t)n_in * sizeof(float), (size_t)n_in * sizeof(float), (size_t)B,
+                               hipMemcpyDeviceToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->d_gz0, z0, nz * sizeof(float), hipMemcpyDeviceToDevice, st));
+    // (TestMode records on the generic right-hand side where it otherwise runs inside the fused step kernels: test_forward)
+    cnf_solve_opts ropts = *opts;
+    if (!train && mfma_supported(h->mfma, nd, false, B)) ropts.kernel = CNF_KERNEL_GENERIC;
+    float* fsol = h->g_US[1];
+    Recorder rec;
+    cnf_solve_stats sst{};
+    for (;;) {
+        if ((s = solve_core(h, mode, u0, train ? eps : nullptr, fsol, B, &ropts, &sst, stream, &rec, true, nullptr)) != CNF_OK) return s;
+        if (!rec.overflow) break;
+        if ((s = traj_reserve(h, rec.n + 8)) != CNF_OK) return s;       // more steps than slots: grow, solve again
+    }
+    h->last_hs = rec.hs;
+    launch_generate_post(n_in, D, h->bd, fsol, h->d_gz0, z_out, logq, B, st);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(st));
+    h->grad_last_B = 0; h->gy_last_B = 0;
+    h->rec_valid = true; h->rec_mode = mode; h->rec_B = B; h->rec_kernel = opts->kernel; h->rec_eps = train ? eps : nullptr;
+    h->rec_kind = REC_GENERATE;
+    if (stats) { *stats = sst; stats->launches += 1; }
+    return CNF_OK;
+}
+
+extern "C" cnf_status cnf_generate_pullback(cnf_handle h, const float* cot_z, const float* cot_logq, int B, float* grad, float* grad_z0,
+                                            void* stream) {
+    if (!h) return CNF_ERR_BAD_ARG;
+    if (!grad) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    if (!cot_z && !cot_logq) return fail(h, CNF_ERR_BAD_ARG, "both cotangents are null");
+    if (!h->rec_valid || h->rec_kind != REC_GENERATE || B != h->rec_B || (size_t)h->last_hs.size() == 0 || !h->d_cw || !h->d_gz0)
+        return fail(h, CNF_ERR_BAD_ARG, "no recorded sampling solve of a batch of this size: call cnf_generate_record first");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    cnf_status s;
+    const std::vector<float> hs = h->last_hs;
+    const GenCot gen{cot_z, cot_logq};
+    if (h->rec_mode == CNF_MODE_TRAIN) {
+        if ((s = ensure_pullback_params(h, st)) != CNF_OK) return s;
+        s = train_backward(h, h->rec_eps, B, h->rec_kernel, hs, nullptr, grad, st, &gen);
+    } else {
+        s = test_backward(h, B, hs, nullptr, grad, st, &gen);
+    }
+    if (s != CNF_OK) { h->rec_valid = false; return s; }
+    h->grad_last_B = 0;                                    // (g_lam is d / d u(t_start) of a SAMPLING solve: cnf_grad_x is not defined for it)
+    if (grad_z0) {
+        launch_generate_z0_grad(h->nd.n_in, h->bd, h->g_lam, cot_logq, h->d_gz0, grad_z0, B, st);
+        HIPCHK(h, hipGetLastError());
+    }
     HIPCHK(h, hipStreamSynchronize(st));
     return CNF_OK;
 }

@@ -33,3 +33,13 @@ void launch_base_sample(int n_in, const BaseDist& bd, const float* normals, floa
 // with_A = 0 (TestMode, or a handle that does not integrate the A row): cot_A is not read.
 void launch_vjp_cotangent(const NetDesc& nd, int D, const BaseDist& bd, int with_A, const float* fsol, const float* cot, float* lam,
                           float* cw, int B, hipStream_t s);
+
+// ---- differentiable sampling (cnf_generate_record / cnf_generate_pullback); all arrays [B][rows], kind 0 included ----
+// z_out[b] = rows 1..n_in of fsol[b] (D floats per sample), logq[b] = logpdf(base, z0_b) + dlogp_b
+void launch_generate_post(int n_in, int D, const BaseDist& bd, const float* fsol, const float* z0, float* z_out, float* logq, int B,
+                          hipStream_t s);
+// The terminal cotangent: lam = cot_z, cw = [3][B]: w_l = +cot_logq, w_E = w_n = 0 (null cotangents: zeros).  n_in >= 1.
+void launch_generate_cotangent(int n_in, const float* cot_z, const float* cot_logq, float* lam, float* cw, int B, hipStream_t s);
+// gz0 = lam0 + cot_logq d logpdf(base, z0) / d z0   (cot_logq null: a copy; gz0 must not alias lam0)
+void launch_generate_z0_grad(int n_in, const BaseDist& bd, const float* lam0, const float* cot_logq, const float* z0, float* gz0,
+                             int B, hipStream_t s);

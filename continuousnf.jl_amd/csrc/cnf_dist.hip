@@ -169,6 +169,77 @@ k_base_sample(int n_in, BaseDist bd, const float* __restrict__ nrm, float* __res
     z0[e] = v + bd.mean[i];
 }
 
+// ---- differentiable sampling (cnf_generate_record / cnf_generate_pullback) ----
+// The sample and its log-density from the final state of the reverse solve and the base draw it started from:
+//   z_out[b] = rows 1..n_in of fsol[b],   logq[b] = logpdf(base, z0_b) + dlogp_b    (k_base_post's arithmetic at z0, sign +;
+//   kind 0: k_post_state's N(0, I)).  Four lanes per sample.
+__global__ void __launch_bounds__(256)
+k_generate_post(int n_in, int D, BaseDist bd, const float* __restrict__ fsol, const float* __restrict__ z0,
+                float* __restrict__ z_out, float* __restrict__ logq, int B) {
+    const int tid = threadIdx.x, p = tid & 3;
+    const int b = blockIdx.x * 64 + (tid >> 2);
+    const size_t bb = (size_t)min(b, B - 1);
+    const float* c = fsol + bb * D;
+    const float* z = z0 + bb * n_in;
+    float ss;
+    if (bd.kind == 0) {
+        ss = 0.f;
+        for (int i = p; i < n_in; i += 4) ss = fmaf(z[i], z[i], ss);
+        ss += __shfl_xor(ss, 1, 64);
+        ss += __shfl_xor(ss, 2, 64);
+    } else {
+        ss = whitened_sq(bd, z, n_in, p);
+    }
+    if (b >= B) return;
+    for (int i = p; i < n_in; i += 4) z_out[bb * n_in + i] = c[i];
+    if (p == 0) {
+        const float log2pi = 1.8378770664093453f;
+        const float logpz = bd.kind == 0 ? -0.5f * fmaf((float)n_in, log2pi, ss) : fmaf(-0.5f, ss, bd.logconst);
+        logq[b] = logpz + c[n_in];
+    }
+}
+
+// The terminal cotangent of sampling: lam = cot_z (null: zeros), and the [3][B] weights of the scalar rows -- +cot_logq (null:
+// zeros) on the dlogp row, zero on the E and n rows, which are integrated but are not outputs of sampling.
+__global__ void __launch_bounds__(256)
+k_generate_cotangent(int n_in, const float* __restrict__ cot_z, const float* __restrict__ cot_logq, float* __restrict__ lam,
+                     float* __restrict__ cw, int B) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < (size_t)n_in * B) lam[e] = cot_z ? cot_z[e] : 0.f;
+    if (e < (size_t)B) {
+        cw[e] = cot_logq ? cot_logq[e] : 0.f;
+        cw[(size_t)B + e] = 0.f;
+        cw[2 * (size_t)B + e] = 0.f;
+    }
+}
+
+// grad_z0[b] = lam0[b] + cot_logq[b] d logpdf(base, z0_b) / d z0 = lam0[b] - cot_logq[b] prec (z0_b - mean)   (kind 0: z0_b;
+// the expression of k_vjp_cotangent).  One lane per entry; must not alias lam0.
+__global__ void __launch_bounds__(256)
+k_generate_z0_grad(int n_in, BaseDist bd, const float* __restrict__ lam0, const float* __restrict__ cot_logq,
+                   const float* __restrict__ z0, float* __restrict__ gz0, int B) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)n_in * B) return;
+    const size_t b = e / (size_t)n_in;
+    const int i = (int)(e - b * (size_t)n_in);
+    float g = lam0[e];
+    if (cot_logq) {
+        const float* c = z0 + b * n_in;
+        float v;                                     // -d logpdf / d z_i
+        if (bd.kind == 0) {
+            v = c[i];
+        } else if (bd.kind == 1) {
+            v = bd.prec[i] * (c[i] - bd.mean[i]);
+        } else {
+            const float* pr = bd.prec + (size_t)i * n_in;
+            v = 0.f;
+            for (int j = 0; j < n_in; ++j) v = fmaf(pr[j], c[j] - bd.mean[j], v);
+        }
+        g = fmaf(-cot_logq[b], v, g);
+    }
+    gz0[e] = g;
+}
+
 }  // namespace
 
 void launch_base_post(int n_in, int D, const BaseDist& bd, const StepState* st, const float* U0, const float* U1, float* logpx,
@@ -190,4 +261,20 @@ void launch_vjp_cotangent(const NetDesc& nd, int D, const BaseDist& bd, int with
 void launch_base_sample(int n_in, const BaseDist& bd, const float* normals, float* z0, int B, hipStream_t s) {
     const size_t n = (size_t)n_in * B;
     hipLaunchKernelGGL(k_base_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_in, bd, normals, z0, n);
+}
+
+void launch_generate_post(int n_in, int D, const BaseDist& bd, const float* fsol, const float* z0, float* z_out, float* logq, int B,
+                          hipStream_t s) {
+    hipLaunchKernelGGL(k_generate_post, dim3((B + 63) / 64), dim3(256), 0, s, n_in, D, bd, fsol, z0, z_out, logq, B);
+}
+
+void launch_generate_cotangent(int n_in, const float* cot_z, const float* cot_logq, float* lam, float* cw, int B, hipStream_t s) {
+    const size_t n = (size_t)n_in * B;
+    hipLaunchKernelGGL(k_generate_cotangent, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_in, cot_z, cot_logq, lam, cw, B);
+}
+
+void launch_generate_z0_grad(int n_in, const BaseDist& bd, const float* lam0, const float* cot_logq, const float* z0, float* gz0,
+                             int B, hipStream_t s) {
+    const size_t n = (size_t)n_in * B;
+    hipLaunchKernelGGL(k_generate_z0_grad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_in, bd, lam0, cot_logq, z0, gz0, B);
 }

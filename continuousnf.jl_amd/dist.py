@@ -66,16 +66,17 @@ def pdf(d: ICNFDist, A, *, eps=None):
     return lp.exp() if _is_torch(lp) else np.exp(lp)
 
 
-def rand(d: ICNFDist, n: int = None, *, z0=None, eps=None):
+def rand(d: ICNFDist, n: int = None, *, z0=None, eps=None, with_logpdf=False):
     """``rand(d, n)`` (src/exts/dist_ext/core_icnf.jl:46-58): ``generate(d.m, d.mode, d.ps, d.st, n)``; ``rand(d)``: one
-    draw, as a vector of nvars entries."""
+    draw, as a vector of nvars entries.  ``with_logpdf``: ``(draws, logq)`` -- the log-density of each draw under the flow from
+    the solve that produced it (``generate(..., with_logp=True)``); for one draw a vector and a scalar."""
     if not isinstance(d.m, ICNF):
         raise NotImplementedError("Not Implemented")
     if n is None:
-        return rand(d, 1, z0=z0, eps=eps)[:, 0]
-    if isinstance(d, CondICNFDist):
-        return generate(d.m, d.mode, d.ps, d.st, n, ys=d.ys[:, :n], z0=z0, eps=eps)
-    return generate(d.m, d.mode, d.ps, d.st, n, z0=z0, eps=eps)
+        r = rand(d, 1, z0=z0, eps=eps, with_logpdf=with_logpdf)
+        return (r[0][:, 0], r[1][0]) if with_logpdf else r[:, 0]
+    kw = dict(ys=d.ys[:, :n]) if isinstance(d, CondICNFDist) else {}
+    return generate(d.m, d.mode, d.ps, d.st, n, z0=z0, eps=eps, with_logp=with_logpdf, **kw)
 
 
 def rand_(d: ICNFDist, A, *, z0=None, eps=None):

@@ -355,6 +355,9 @@ cnf_status cnf_inference_record(cnf_handle h, int mode, const float* xs, const f
  * lambda3 / A, and rows 1-3 in TestMode. */
 cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int B, float* grad, void* stream);
 
+/* ---- differentiable sampling: cnf_generate_record / cnf_generate_pullback (declared in cnfhip_generate.h, part of this header) ---- */
+#include "cnfhip_generate.h"
+
 /* ---- device random numbers ------------------------------------------
  *
  * The library's own counter-based generator, the counterpart of the device RNG the reference draws eps and

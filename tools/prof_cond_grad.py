@@ -70,9 +70,10 @@ def child(leg, window):
     if parent:                                       # (an earlier build does not export the entry points added since)
         import ctypes
         l = ctypes.CDLL(_lib.LIB_PATH)
-        for name in list(_lib._SIGNATURES):
-            if not hasattr(l, name):
-                _lib._SIGNATURES.pop(name)
+        for table in (_lib._SIGNATURES, _lib._SAMPLING_SIGNATURES):
+            for name in list(table):
+                if not hasattr(l, name):
+                    table.pop(name)
     import continuousnf.jl_amd as cnf
     from continuousnf.jl_amd import base_icnf, configs
     if parent:                                       # ... and has no switch to set
