@@ -46,10 +46,10 @@ from .base_icnf import (ICNF, ODEProblem, base_sol, construct, generate, generat
                         inference, inference_collect, inference_prob, inference_submit,
                         inference_sol, loss, loss_and_grad, loss_and_grad_collect, loss_and_grad_submit, loss_from_sums, loss_sums, n_augment,
                         n_augment_input, steer_tspan)
-from .base_icnf import base_sample
+from .base_icnf import base_logpdf_pullback, base_sample, base_sample_pullback
 from .dist import CondICNFDist, ICNFDist, ICNFDistribution, logpdf, pdf, rand, rand_
 from . import distributions
-from .distributions import DiagNormal, MvNormal, Rademacher, StdNormal
+from .distributions import DiagNormal, LearnableNormal, MvNormal, Rademacher, StdNormal
 from .icnf import augmented_f
 from .layers import Chain, CondLayer, Dense, PlanarLayer, setup
 from . import rng

@@ -129,6 +129,12 @@ _SAMPLING_SIGNATURES = {
     "cnf_generate_pullback": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _fp, _fp, C.c_void_p]),
 }
 SAMPLING_EXPORTS = tuple(_SAMPLING_SIGNATURES)
+# the gradient w.r.t. the base distribution (include/cnfhip_basegrad.h): likewise a table of its own
+_BASEGRAD_SIGNATURES = {
+    "cnf_base_logpdf_pullback": (C.c_int, [C.c_void_p, _fp, C.c_int, _fp, _fp, C.c_void_p]),
+    "cnf_base_sample_pullback": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _fp, _fp, C.c_void_p]),
+}
+BASEGRAD_EXPORTS = tuple(_BASEGRAD_SIGNATURES)
 
 _lib = None
 
@@ -166,7 +172,7 @@ def lib():
         except ImportError:
             pass
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()):
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) + list(_BASEGRAD_SIGNATURES.items()):
             f = getattr(l, name)
             f.restype, f.argtypes = res, args
         _lib = l

@@ -15,7 +15,7 @@ from typing import Any
 import numpy as np
 
 from . import _lib
-from .distributions import Rademacher, check_basedist, check_epsdist
+from .distributions import LearnableNormal, Rademacher, check_basedist, check_epsdist, learnable
 from .layers import Chain
 from .rng import HIPRNG
 from .types import (AbstractICNF, CondFFJORD, CondPlanar, CondRNODE, FFJORD, RNODE, HIPMatrixMode, HIPVecJacMatrixMode,
@@ -158,11 +158,13 @@ class ICNF:
     device: int = 0
     cond: bool = False          # COND type parameter (src/base_icnf.jl:44)
     n_cond: int = 0             # rows of ys = nn input size - (nvars + naugmented)
-    basedist: Any = None        # src/base_icnf.jl:16-21; None: MvNormal(Zeros, Eye), else a distributions.MvNormal
+    basedist: Any = None        # src/base_icnf.jl:16-21; None: MvNormal(Zeros, Eye), else a distributions.MvNormal (a
+                                # LearnableNormal is uploaded again whenever its tensors changed: set_basedist)
     epsdist: Any = None         # src/base_icnf.jl:22-25; None: N(0, I) probes, else distributions.Rademacher()
     _handle: Any = field(default=None, repr=False)
     _cond_id: Any = field(default=None, repr=False)
     _params_id: Any = field(default=None, repr=False)
+    _base_id: Any = field(default=None, repr=False)
 
     # type parameters of the reference struct (src/base_icnf.jl:42-51)
     @property
@@ -189,17 +191,39 @@ class ICNF:
             self._handle = h
             _OPEN[id(self)] = weakref.ref(self)
             if self.basedist is not None:        # (the default never calls it: that handle launches what it always did)
-                d = self.basedist
-                _lib.check(l.cnf_set_basedist(h, d.kind, d.mean.ctypes.data, d.whiten.ctypes.data, d.chol.ctypes.data,
-                                              d.logconst), h)
+                if isinstance(self.basedist, LearnableNormal):
+                    self.basedist.refresh()
+                self._upload_basedist()
         return self._handle
+
+    def _upload_basedist(self):
+        d = self.basedist
+        _lib.check(_lib.lib().cnf_set_basedist(self._handle, d.kind, d.mean.ctypes.data, d.whiten.ctypes.data, d.chol.ctypes.data,
+                                               d.logconst), self._handle)
+        self._base_id = (d, getattr(d, "generation", 0))
+
+    def set_basedist(self):
+        """A ``LearnableNormal`` base: reduce and upload its current values (cnf_set_basedist, synchronous) if a tensor's
+        identity or in-place version changed, or another ``LearnableNormal`` was assigned to ``basedist``, since the last
+        upload.  Called by every call that solves (through ``set_params``); any other base was uploaded with the handle."""
+        d = self.basedist
+        if not isinstance(d, LearnableNormal):
+            return
+        if len(d) != self.nvars + self.naugmented:
+            raise ValueError(f"basedist has length {len(d)}, the model has nvars + naugmented = {self.nvars + self.naugmented} rows")
+        self.handle()
+        d.refresh()
+        if self._base_id is None or self._base_id[0] is not d or self._base_id[1] != d.generation:
+            self._upload_basedist()
 
     def __call__(self, xs, ps, st, *, eps=None):
         """The Lux-layer form, src/base_icnf.jl:528-543: ``icnf(xs, ps, st)`` (conditional: ``icnf((xs, ys), ps, st)``)
         = ``(first(inference(icnf, TrainMode(), xs[, ys], ps, st)), st)``.  With a ``ps`` (or a ``ys``) that requires grad the
-        call goes through ``vjp.differentiable_inference``: the result can be back-propagated to ``ps``, ``xs`` and ``ys``."""
+        call goes through ``vjp.differentiable_inference``: the result can be back-propagated to ``ps``, ``xs`` and ``ys``, and to
+        the tensors of a ``LearnableNormal`` base (which triggers this route too when they require grad)."""
         from .types import TrainMode
-        if (_is_torch(ps) and ps.requires_grad) or (self.cond and _is_torch(xs[1]) and xs[1].requires_grad):
+        if (_is_torch(ps) and ps.requires_grad) or (self.cond and _is_torch(xs[1]) and xs[1].requires_grad) \
+                or (isinstance(self.basedist, LearnableNormal) and self.basedist.requires_grad):
             from .vjp import differentiable_inference
             args = (xs[0], xs[1], ps, st) if self.cond else (xs, ps, st)
             return differentiable_inference(self, TrainMode(), *args, eps=eps)[0], st
@@ -230,6 +254,7 @@ class ICNF:
         import torch
         if self.nn.planar is not None or not (_is_torch(ps) and ps.is_cuda):
             return self.set_params(ps)
+        self.set_basedist()
         p = ps.detach().to(torch.float32).contiguous().reshape(-1)
         h = self.handle()
         st = C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
@@ -242,6 +267,7 @@ class ICNF:
         """Upload ``ps`` (the ``p`` of augmented_f) unless it is the vector already resident."""
         h = self.handle()
         l = _lib.lib()
+        self.set_basedist()
         if self.nn.planar is not None:
             # (u, w, b) -> the MLP layout the kernels see (layers.Chain.to_internal); keyed on the caller's object below
             ps_ext = ps
@@ -621,9 +647,11 @@ def generate_prob(icnf: ICNF, mode, ps, st, n: int, *, ys=None, z0=None, eps=Non
     return ODEProblem(icnf, mode, u0, eb, (t1, t0), ps)  # reverse(tspan)  (:377)
 
 
-def _generate_inputs(icnf: ICNF, mode, ps, n: int, ys=None, z0=None, eps=None):
+def _generate_inputs(icnf: ICNF, mode, ps, n: int, ys=None, z0=None, eps=None, normals_out=None):
     """What ``generate_prob`` uploads and draws, in its order: parameters, conditioning, the base draw ``z0`` and the probes
-    ``eps`` (n_in x n each, as _Buf)."""
+    ``eps`` (n_in x n each, as _Buf).  ``normals_out``: a list that receives the standard normals a non-default base turned
+    into ``z0`` here (a flat device tensor, column by column) -- what ``differentiable_generate`` keeps for the pullback of the
+    draw; nothing is appended when the caller gave ``z0``."""
     _mode_id(mode)
     n_in = icnf.nvars + n_augment_input(icnf)
     icnf.set_params(ps)
@@ -632,6 +660,8 @@ def _generate_inputs(icnf: ICNF, mode, ps, n: int, ys=None, z0=None, eps=None):
         import torch                                    # drawn on the device, before eps: the sample is a device tensor
         zb = _Buf(icnf.rng.normal(n_in * n, icnf.device), n_in, n, torch)
         if icnf.basedist is not None:
+            if normals_out is not None:
+                normals_out.append(zb.arr)
             zb = _Buf(base_sample(icnf, zb.arr, n), n_in, n, torch)
     else:
         drawn = z0 is None
@@ -642,6 +672,8 @@ def _generate_inputs(icnf: ICNF, mode, ps, n: int, ys=None, z0=None, eps=None):
             import torch
             raise_if_no_gpu()
             nd = torch.from_numpy(zb.arr).to(torch.device("cuda", icnf.device))
+            if normals_out is not None:
+                normals_out.append(nd.reshape(-1))
             zb = _Buf(base_sample(icnf, nd, n).cpu().numpy(), n_in, n, None)
     if zb.B != n:
         raise ValueError("z0 must have n columns")
@@ -665,6 +697,43 @@ def base_sample(icnf: ICNF, normals, n: int):
     st = C.c_void_p(torch.cuda.current_stream(nrm.device).cuda_stream)
     _lib.check(_lib.lib().cnf_base_sample(h, nrm.data_ptr(), out.data_ptr(), n, st), h)
     return out
+
+
+def base_logpdf_pullback(icnf: ICNF, w):
+    """``sum_b w[b] d logpdf(basedist; s_b) / d (mean, scale)`` (cnf_base_logpdf_pullback) for a ``LearnableNormal`` base, where
+    ``s_b`` is the final state of the current inference record (or of the last ``loss_and_grad``), or the base draw ``z0`` of
+    the current sampling record.  ``w``: ``B`` float32 values on the GPU.  Returns device tensors ``(g_mean [n_in], g_scale)``,
+    ``g_scale`` shaped like the distribution's scale (``n_in``, or ``n_in x n_in`` with zeros above the diagonal)."""
+    import torch
+    d = learnable(icnf.basedist)
+    n_in = icnf.nvars + n_augment_input(icnf)
+    w = w.detach().to(torch.float32).contiguous().reshape(-1)
+    if not w.is_cuda:
+        raise ValueError("w must live on the GPU")
+    out = torch.empty(n_in + (n_in if d.kind == 1 else n_in * n_in), dtype=torch.float32, device=w.device)
+    h = icnf.handle()
+    st = C.c_void_p(torch.cuda.current_stream(w.device).cuda_stream)
+    _lib.check(_lib.lib().cnf_base_logpdf_pullback(h, w.data_ptr(), w.numel(), out.data_ptr(), out[n_in:].data_ptr(), st), h)
+    return out[:n_in], (out[n_in:] if d.kind == 1 else out[n_in:].view(n_in, n_in))
+
+
+def base_sample_pullback(icnf: ICNF, normals, g_z0):
+    """The vector-Jacobian product of ``base_sample`` (cnf_base_sample_pullback) for a ``LearnableNormal`` base: ``normals`` and
+    ``g_z0`` are ``n_in x n`` on the GPU (any strides); returns ``(sum_b g_z0[:, b], tril(sum_b g_z0[:, b] normals[:, b]'))``
+    -- the diagonal of the latter for a ``std`` base -- as device tensors."""
+    import torch
+    d = learnable(icnf.basedist)
+    n_in = icnf.nvars + n_augment_input(icnf)
+    if normals.dim() != 2 or normals.shape[0] != n_in or tuple(g_z0.shape) != tuple(normals.shape) or not normals.is_cuda:
+        raise ValueError("normals and g_z0 must be n_in x n on the GPU")
+    n = int(normals.shape[1])
+    nb = normals.detach().to(torch.float32).t().contiguous()          # [n][n_in]: sample b contiguous
+    gb = g_z0.detach().to(device=nb.device, dtype=torch.float32).t().contiguous()
+    out = torch.empty(n_in + (n_in if d.kind == 1 else n_in * n_in), dtype=torch.float32, device=nb.device)
+    h = icnf.handle()
+    st = C.c_void_p(torch.cuda.current_stream(nb.device).cuda_stream)
+    _lib.check(_lib.lib().cnf_base_sample_pullback(h, nb.data_ptr(), gb.data_ptr(), n, out.data_ptr(), out[n_in:].data_ptr(), st), h)
+    return out[:n_in], (out[n_in:] if d.kind == 1 else out[n_in:].view(n_in, n_in))
 
 
 def generate_sol(icnf: ICNF, mode, prob: ODEProblem):
@@ -831,16 +900,23 @@ def grad_ys(icnf: ICNF, B, dev, stream, host=False):
     return gy.cpu().numpy() if host else gy
 
 
-def loss_and_grad(icnf: ICNF, mode, xs, *args, eps=None, with_x=False, with_ys=False):
+def loss_and_grad(icnf: ICNF, mode, xs, *args, eps=None, with_x=False, with_ys=False, with_base=False):
     """``(loss, d loss / d ps)``: the pair ``MLJModelInterface.fit`` gets from Enzyme on
     ``loss(icnf, TrainMode(), xs, ps, st)`` (src/exts/mlj_ext/core_icnf.jl:59-73, src/icnf.jl:481-490),
     here from the discrete adjoint of the solve (cnf_loss_grad).  The gradient has the layout of
     ``ps`` and lives where ``xs`` lives (torch.cuda tensor or numpy array).  Conditional models:
     ``(xs, ys, ps, st)`` as everywhere else.  Steering draws t1 exactly as ``loss`` does.  ``with_x`` / ``with_ys`` append
     d loss / d xs (``nvars x B``) and, for a conditional model, d loss / d ys (``n_cond x B``) to the result; with
-    ``with_ys`` the gradient always takes the recorded solve."""
+    ``with_ys`` the gradient always takes the recorded solve.  ``with_base`` (a ``LearnableNormal`` base, device tensors)
+    appends ``(d loss / d mean, d loss / d scale)`` last: the log-density of the final state pulled back with the loss's
+    cotangent ``-1/B`` (cnf_base_logpdf_pullback); ``ValueError`` with any other base."""
+    if with_base:
+        learnable(icnf.basedist)
+        if not _is_torch(xs):
+            raise ValueError("with_base needs device tensors")
     if _mode_id(mode) != _lib.MODE_TRAIN:
-        return _loss_and_grad_test(icnf, mode, xs, *args, with_x=with_x, with_ys=with_ys)
+        out = _loss_and_grad_test(icnf, mode, xs, *args, with_x=with_x, with_ys=with_ys)
+        return out + (_loss_base_grad(icnf, xs),) if with_base else out
     ys, ps, st = _split_cond_args(icnf, args)
     xb = _xs_colmajor(icnf, xs)
     B = xb.B
@@ -894,7 +970,17 @@ def loss_and_grad(icnf: ICNF, mode, xs, *args, eps=None, with_x=False, with_ys=F
             import torch
             dev = torch.device("cuda", icnf.device)
             out += (grad_ys(icnf, B, dev, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), host=True),)
+    if with_base:
+        out += (_loss_base_grad(icnf, xs),)
     return out
+
+
+def _loss_base_grad(icnf: ICNF, xs):
+    """(d loss / d mean, d loss / d scale) of the ``loss_and_grad`` call that has just returned: the loss is ``-mean(logpx)``
+    plus terms that do not depend on the base, so every sample carries ``-1/B``."""
+    import torch
+    B = xs.shape[1]
+    return base_logpdf_pullback(icnf, torch.full((B,), -1.0 / B, dtype=torch.float32, device=xs.device))
 
 
 def loss_and_grad_submit(icnf: ICNF, mode, xs, *args, eps=None):

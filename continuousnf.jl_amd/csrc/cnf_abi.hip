@@ -15,6 +15,7 @@
 #include "cnf_adj3b.h"
 #include "cnf_step3.h"
 #include "cnf_dist.h"
+#include "cnf_basegrad.h"
 #include <immintrin.h>
 #include <sched.h>
 #include <vector>
@@ -160,11 +161,19 @@ struct cnf_ctx {
     DevBuf<float> d_sums;         // SUMS_WORDS floats
     BaseDist bd{};                // cnf_set_basedist: kind 0 = the default N(0, I), nothing of cnf_dist.hip is launched
     DevBuf<float> d_bd;           //   its arrays (mean | whiten | chol | prec), one allocation
+    // cnf_base_logpdf_pullback / cnf_base_sample_pullback (cnf_basegrad.hip): tickets, result, partials and whitened rows; grown
+    // on demand, so a handle that never asks for the base's gradient never allocates it
+    DevBuf<float> d_bg;
+    int fs_B = 0, fs_mode = 0;    // cnf_loss_grad / cnf_loss_grad_test on the recorded route: g_US[1] holds the final state of a batch
+                                  //   of fs_B samples solved in fs_mode (0: none); ends where a record ends
     PinnedBuf<float> h_sums;      // pinned, 4 floats
     std::string err;
 };
 
 static const int MAX_PARTIALS = 1024;
+// What a solve, an upload of parameters or conditioning, or a change of the base distribution ends: the record of
+// cnf_inference_record / cnf_generate_record and the final state a cnf_loss_grad* call left for cnf_base_logpdf_pullback.
+static inline void end_record(cnf_ctx* h) { h->rec_valid = false; h->fs_B = 0; }
 enum { REC_INFERENCE = 1, REC_GENERATE = 2 };
 
 #define HIPCHK(h, call)                                                                  \
@@ -355,7 +364,7 @@ static cnf_status params_uploaded(cnf_handle h, hipStream_t s, ParamsWait wait) 
     if (wait == PARAMS_WAIT_STREAM) HIPCHK(h, hipStreamSynchronize(s));
     if (wait == PARAMS_WAIT_DEVICE) HIPCHK(h, hipDeviceSynchronize());
     h->have_params = true;
-    h->rec_valid = false;
+    end_record(h);
     h->pt_valid = false;
     h->img_valid = false;
     h->bimg_valid = false;
@@ -474,7 +483,7 @@ extern "C" cnf_status cnf_set_basedist(cnf_handle h, int kind, const float* mean
     HIPCHK(h, hipDeviceSynchronize());
     h->d_bd.release();
     h->bd = BaseDist{};
-    h->rec_valid = false;
+    end_record(h);
     if (kind == 0) return CNF_OK;
     RESERVE(h, h->d_bd, host.size());
     HIPCHK(h, hipMemcpy(h->d_bd, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -504,7 +513,7 @@ extern "C" cnf_status cnf_set_cond(cnf_handle h, const float* ys, int B, void* s
     HIPCHK(h, hipSetDevice(h->device));
     // (a submitted inference reads d_cond until it ends, and its fallback would read it again: none may be outstanding)
     { const cnf_status ss = settle_submitted(h); if (ss != CNF_OK) return ss; }
-    h->rec_valid = false;
+    end_record(h);
     const int cbs = (h->nd.dims[1] + 15) & ~15;
     if (h->cond_B != B || h->cbs != cbs) {
         HIPCHK(h, hipDeviceSynchronize());
@@ -959,7 +968,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
                              bool final_sync, PostHook* post) {
     cnf_status s = check_call(h, mode, B);
     if (s != CNF_OK) return s;
-    h->rec_valid = false;                                  // (every solve may overwrite what a record consists of)
+    end_record(h);                     // (every solve may overwrite what a record consists of)
     if (!u0 || !opts) return fail(h, CNF_ERR_BAD_ARG, "null pointer");      // u_out may be null: the state stays in U[cur]
     const int train = mode == CNF_MODE_TRAIN;
     if (train && !eps) return fail(h, CNF_ERR_BAD_ARG, "eps is required in TrainMode");
@@ -1724,7 +1733,7 @@ static cnf_status ensure_grad_capacity(cnf_handle h, int B) {
     // As in ensure_capacity: what is carved from the arena exists only while it does, and neither does what was computed into
     // it -- the gradient cnf_grad_x hands out, a recorded solve, the trajectory.  A failed reserve leaves all of it cleared.
     const size_t cap = arena_alloc == hipSuccess ? want : 0;
-    h->grad_last_B = 0; h->gy_last_B = 0; h->rec_valid = false; h->traj_cap = 0;
+    h->grad_last_B = 0; h->gy_last_B = 0; end_record(h); h->traj_cap = 0;
     float* p = h->grad_arena;
     for (int i = 0; i < 5; ++i) { h->g_US[i] = p; p += D * cap; }
     for (int i = 0; i < 6; ++i) { h->g_W[i] = p; p += n_in * cap; }
@@ -2060,6 +2069,7 @@ extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* 
 
     if ((s = train_backward(h, eps, B, opts->kernel, rec.hs, nullptr, grad, st)) != CNF_OK) return s;
     HIPCHK(h, hipStreamSynchronize(st));
+    h->fs_B = B; h->fs_mode = mode;                        // (cnf_base_logpdf_pullback: the final state stays in g_US[1])
     if ((s = cnf_loss_from_sums(h, mode, sums, loss_out)) != CNF_OK) return s;
     if (stats) *stats = sst;
     return CNF_OK;
@@ -2161,6 +2171,7 @@ extern "C" cnf_status cnf_loss_grad_test(cnf_handle h, const float* xs, int B, c
     HIPCHK(h, hipMemcpyAsync(sums, h->d_sums, 5 * sizeof(float), hipMemcpyDeviceToHost, st));
     if ((s = test_backward(h, B, rec.hs, nullptr, grad, st)) != CNF_OK) return s;
     HIPCHK(h, hipStreamSynchronize(st));
+    h->fs_B = B; h->fs_mode = mode;                        // (cnf_base_logpdf_pullback: the final state stays in g_US[1])
     if ((s = cnf_loss_from_sums(h, mode, sums, loss_out)) != CNF_OK) return s;
     if (stats) { *stats = sst; stats->launches += 2; }
     return CNF_OK;
@@ -2328,6 +2339,58 @@ extern "C" cnf_status cnf_generate_pullback(cnf_handle h, const float* cot_z, co
         HIPCHK(h, hipGetLastError());
     }
     HIPCHK(h, hipStreamSynchronize(st));
+    return CNF_OK;
+}
+
+// ---- a learnable base distribution: the gradient w.r.t. mean and chol (include/cnfhip_basegrad.h, cnf_basegrad.hip) -------------
+// Both entry points are one batch contraction and a tail, enqueued on the caller's stream; the handle's buffer for them grows
+// behind a wait for the device and is cleared then (its ticket words must be zero before the first launch; their region does
+// not depend on the kind of the base, cnf_basegrad_plan.h, so a change of kind on a live handle finds them zero as well).
+static cnf_status base_grad_buffer(cnf_handle h, int B, BaseGradPlan& plan, hipStream_t st) {
+    plan = base_grad_plan(h->nd.n_in, h->bd.kind, B);
+    if (plan.ntiles > 65535) return fail(h, CNF_ERR_UNSUPPORTED, "base distribution too large for the gradient kernel's grid");
+    if (plan.floats > h->d_bg.capacity()) {
+        HIPCHK(h, hipDeviceSynchronize());                 // (an earlier pullback on ANY stream may still read the old buffer)
+        RESERVE(h, h->d_bg, (plan.floats + 4095) & ~(size_t)4095);
+        HIPCHK(h, hipMemsetAsync(h->d_bg, 0, h->d_bg.capacity() * sizeof(float), st));
+    }
+    return CNF_OK;
+}
+
+extern "C" cnf_status cnf_base_logpdf_pullback(cnf_handle h, const float* w, int B, float* g_mean, float* g_chol, void* stream) {
+    if (!h) return CNF_ERR_BAD_ARG;
+    if (!w || !g_mean || !g_chol) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    if (h->bd.kind == 0) return fail(h, CNF_ERR_BAD_ARG, "the default base distribution has no mean or chol to differentiate");
+    const float* src = nullptr;
+    int stride = 0;
+    if (h->rec_valid && B == h->rec_B && B >= 1) {
+        if (h->rec_kind == REC_GENERATE) { src = h->d_gz0; stride = h->nd.n_in; }
+        else { src = h->g_US[1]; stride = rows_of(h, h->rec_mode); }
+    } else if (h->fs_B >= 1 && B == h->fs_B) {
+        src = h->g_US[1]; stride = rows_of(h, h->fs_mode);
+    }
+    if (!src) return fail(h, CNF_ERR_BAD_ARG, "no recorded solve of a batch of this size: call cnf_inference_record or cnf_generate_record first");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    BaseGradPlan plan;
+    const cnf_status s = base_grad_buffer(h, B, plan, st);
+    if (s != CNF_OK) return s;
+    HIPCHK(h, launch_base_logpdf_pullback(h->nd.n_in, h->bd, src, stride, w, B, h->d_bg, plan, g_mean, g_chol, st));
+    return CNF_OK;
+}
+
+extern "C" cnf_status cnf_base_sample_pullback(cnf_handle h, const float* normals, const float* g_z0, int B, float* g_mean,
+                                               float* g_chol, void* stream) {
+    if (!h) return CNF_ERR_BAD_ARG;
+    if (!normals || !g_z0 || !g_mean || !g_chol) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    if (h->bd.kind == 0) return fail(h, CNF_ERR_BAD_ARG, "the default base distribution has no mean or chol to differentiate");
+    if (B < 1) return fail(h, CNF_ERR_BAD_ARG, "B must be >= 1");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    BaseGradPlan plan;
+    const cnf_status s = base_grad_buffer(h, B, plan, st);
+    if (s != CNF_OK) return s;
+    HIPCHK(h, launch_base_sample_pullback(h->nd.n_in, h->bd.kind, normals, g_z0, B, h->d_bg, plan, g_mean, g_chol, st));
     return CNF_OK;
 }
 

@@ -10,7 +10,19 @@ Every Gaussian reduces to ``(mu, W, c)``, computed once here in float64 and roun
     d logpdf / d z = -W' W (z - mu)
     sample         = mu + L n,   n ~ N(0, I)
 
-Nothing here is learnable: the loss has no gradient w.r.t. ``mu`` or ``Sigma``."""
+``MvNormal`` / ``DiagNormal`` are constants.  ``LearnableNormal(mean, scale_tril=... | std=...)`` is the same Gaussian held as
+torch tensors ``mu`` and ``L`` (the lower-triangular factor, or the vector ``sigma``): every call that solves uploads their
+current values (cnf_set_basedist) when a tensor's identity or in-place version changed, and the differentiable calls
+(``differentiable_inference``, ``icnf(xs, ps, st)``, ``differentiable_generate``, ``reverse_kl``; ``with_base=True`` of the
+pullbacks and of ``loss_and_grad``) return
+
+    d/d mu sum_b w_b logpdf(z_b) = W' sum_b w_b n_b,                                         n_b = W (z_b - mu)
+    d/d L  sum_b w_b logpdf(z_b) = tril(W' sum_b w_b n_b n_b') - (sum_b w_b) diag(1 / L_ii)
+
+(cnf_base_logpdf_pullback) and, for samples drawn as ``mu + L n``, the pullback of that draw (cnf_base_sample_pullback).
+Every upload is synchronous: one host wait per optimiser step on the base.  The built-in ``fit`` keeps the base constant and
+optimises ``ps`` only -- training a base goes through a custom loss and a torch optimiser; the ``_host`` entry points, the
+submitted gradients, the in-launch gradient of small networks and the Julia shims do not return the base's gradient."""
 from __future__ import annotations
 
 import numpy as np
@@ -118,6 +130,71 @@ class DiagNormal(MvNormal):
         self._set(mu, KIND_DIAG, s.copy(), 1.0 / s)
 
 
+class LearnableNormal(MvNormal):
+    """``LearnableNormal(mean, scale_tril=None, std=None)``: N(mean, L L') with ``L = tril(scale_tril)`` (``n x n``, positive
+    diagonal) or N(mean, diag(std)^2) (``std``: ``n`` entries > 0) -- exactly one of the two.  ``mean`` and the scale are torch
+    tensors on any device, leaves or not: ``std = log_std.exp()`` keeps the positivity constraint in the caller's graph.  The
+    model reads their current values before every call that solves; give a new pair with ``update`` (or a new
+    ``LearnableNormal`` assigned to ``icnf.basedist``) when the tensors themselves are recomputed each step."""
+
+    def __init__(self, mean, scale_tril=None, std=None):
+        self._seen = None
+        self.update(mean, scale_tril=scale_tril, std=std)
+
+    def update(self, mean, scale_tril=None, std=None):
+        """Replace the tensors (same length) and reduce their values; raises ``ValueError`` as ``MvNormal`` does."""
+        if (scale_tril is None) == (std is None):
+            raise ValueError("LearnableNormal takes exactly one of scale_tril and std")
+        scale = scale_tril if std is None else std
+        for name, t in (("mean", mean), ("scale_tril" if std is None else "std", scale)):
+            if not (hasattr(t, "detach") and hasattr(t, "_version")):
+                raise ValueError(f"LearnableNormal: {name} must be a torch tensor")
+        if getattr(self, "mean64", None) is not None and int(mean.numel()) != len(self):
+            raise ValueError(f"mean has {int(mean.numel())} entries, the distribution has {len(self)}")
+        self.mean_t, self.scale_t = mean, scale
+        self.kind = KIND_DIAG if scale_tril is None else KIND_DENSE
+        self._seen = None
+        self.refresh()
+
+    @property
+    def requires_grad(self):
+        return bool(self.mean_t.requires_grad or self.scale_t.requires_grad)
+
+    def refresh(self):
+        """Reduce the tensors' current values on the host in float64 (``MvNormal._set``) if a tensor's identity or in-place
+        version changed since the last time; returns whether it did."""
+        m, sc_t, p = self.mean_t, self.scale_t, self._seen
+        if p is not None and p[0] is m and p[1] == m._version and p[2] is sc_t and p[3] == sc_t._version:
+            return False
+        seen = (m, m._version, sc_t, sc_t._version)       # the caller's tensors, held: identity, not address (ICNF.set_cond)
+        mu = self._mean(self.mean_t.detach().cpu().double().numpy())
+        n = mu.size
+        sc = _finite(self.scale_t.detach().cpu().double().numpy(), "std" if self.kind == KIND_DIAG else "scale_tril")
+        if self.kind == KIND_DIAG:
+            if sc.ndim != 1 or sc.size != n:
+                raise ValueError(f"std must be a vector of {n} entries")
+            if not np.all(sc > 0):
+                raise ValueError("std must be > 0")
+            self._set(mu, KIND_DIAG, sc.copy(), 1.0 / sc)
+        else:
+            if sc.shape != (n, n):
+                raise ValueError(f"scale_tril must be {n} x {n}")
+            L = np.tril(sc)
+            if not np.all(np.diag(L) > 0):
+                raise ValueError("scale_tril: the diagonal must be > 0")
+            self._set(mu, KIND_DENSE, L, np.tril(np.linalg.solve(L, np.eye(n))))
+        self._seen = seen
+        self.generation = getattr(self, "generation", 0) + 1      # (what a model compares to know whether it holds these values)
+        return True
+
+
+def learnable(basedist):
+    """The ``LearnableNormal`` of a model, or ``ValueError``: what ``with_base=True`` needs."""
+    if not isinstance(basedist, LearnableNormal):
+        raise ValueError("with_base: the model's basedist is not a LearnableNormal (a constant base has no gradient)")
+    return basedist
+
+
 class StdNormal:
     """``epsdist``: N(0, I) probes -- the default, spelled out."""
 
@@ -133,7 +210,7 @@ class Rademacher:
         return "Rademacher()"
 
 
-SUPPORTED = "basedist: MvNormal(mean, cov), DiagNormal(mean, std) or None; epsdist: StdNormal(), Rademacher() or None"
+SUPPORTED = "basedist: MvNormal(mean, cov), DiagNormal(mean, std), LearnableNormal(mean, scale_tril | std) or None; epsdist: StdNormal(), Rademacher() or None"
 
 
 def check_basedist(basedist, n_in):

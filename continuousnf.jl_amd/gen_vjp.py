@@ -13,6 +13,12 @@ counterpart of what ``inference`` scores, not the marginal of its first ``nvars`
 it is the Hutchinson estimate for the ``eps`` used.  Gradients are taken w.r.t. ``ps``, the base draw ``z0`` and, for a
 conditional model, ``ys``; ``eps`` and the time span are constants, and the accepted step sizes are constants of the discrete
 adjoint, as everywhere in this package.
+
+With a ``distributions.LearnableNormal`` base the gradient also reaches its ``mean`` and scale.  ``generate_pullback`` returns
+the partial derivative at FIXED ``z0`` (``g_logq d logpdf(base, z0) / d base``, cnf_base_logpdf_pullback); when
+``differentiable_generate`` drew ``z0 = mean + L n`` itself it keeps the normals ``n`` and adds the pullback of that draw applied
+to ``grad_z0`` (cnf_base_sample_pullback), which is the total derivative.  A ``z0`` the caller passes is a leaf: the base gets
+the fixed-``z0`` partial only.
 """
 from __future__ import annotations
 
@@ -21,8 +27,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .base_icnf import (ICNF, _Buf, _as_colmajor, _generate_inputs, _is_torch, _mode_id, _solve_opts, grad_ys,
-                        n_augment_input, raise_if_no_gpu, set_grad_ys, steer_tspan)
+from .base_icnf import (ICNF, _Buf, _as_colmajor, _generate_inputs, _is_torch, _mode_id, _solve_opts, base_logpdf_pullback,
+                        base_sample_pullback, grad_ys, n_augment_input, raise_if_no_gpu, set_grad_ys, steer_tspan)
+from .distributions import learnable
+from .vjp import _base_grads, _base_key, _base_tensors, _base_unchanged
 
 
 def _device(icnf: ICNF):
@@ -109,13 +117,17 @@ def _cot_pair(icnf: ICNF, cot, dev):
     return cz, cl, B
 
 
-def generate_pullback(icnf: ICNF, cot, with_z0=False, with_ys=False):
+def generate_pullback(icnf: ICNF, cot, with_z0=False, with_ys=False, with_base=False):
     """``sum_b (<g_x[:, b], d xs_b / d ps> + g_logq[b] d logq_b / d ps)`` through the steps ``generate_record`` recorded, in the
     caller's parameter layout; with ``with_z0`` the same w.r.t. the base draw (``n_in x n``), with ``with_ys`` w.r.t. the
-    conditioning inputs (``n_cond x n``), appended in that order.  ``cot = (g_x, g_logq)``: ``g_x`` is ``nvars x n`` or
-    ``n_in x n`` (rows beyond ``nvars`` are zero when not given), ``None`` entries are zeros (not both).  May be called several
-    times on one record.  ``CNFError`` (``ERR_BAD_ARG``) when the record is gone or is not a sampling record."""
+    conditioning inputs (``n_cond x n``), with ``with_base`` the pair ``(/ d mean, / d scale)`` of a ``LearnableNormal`` base AT
+    FIXED ``z0`` (the pullback of the draw itself is ``base_sample_pullback`` of the ``with_z0`` result), appended in that
+    order.  ``cot = (g_x, g_logq)``: ``g_x`` is ``nvars x n`` or ``n_in x n`` (rows beyond ``nvars`` are zero when not given),
+    ``None`` entries are zeros (not both).  May be called several times on one record.  ``CNFError`` (``ERR_BAD_ARG``) when the
+    record is gone or is not a sampling record; ``ValueError`` for ``with_base`` with any other base."""
     import torch
+    if with_base:
+        learnable(icnf.basedist)
     l, h = _lib.lib(), icnf.handle()
     rec = getattr(icnf, "_record", None)
     dev = rec["xb"].arr.device if rec is not None else _device(icnf)
@@ -134,12 +146,16 @@ def generate_pullback(icnf: ICNF, cot, with_z0=False, with_ys=False):
     if with_z0:
         gz0 = gz0.view(B, n_in).t()
     gy = grad_ys(icnf, B, dev, stream, host) if with_ys else None
+    gb = None
+    if with_base:                                    # (only logq depends on the base at fixed z0)
+        gb = base_logpdf_pullback(icnf, cl if cl is not None else torch.zeros(B, dtype=torch.float32, device=dev))
     if host:
         grad = grad.cpu().numpy()
         gz0 = gz0.cpu().numpy() if gz0 is not None else None
-    if not with_z0 and not with_ys:
+        gb = tuple(g.cpu().numpy() for g in gb) if gb is not None else None
+    if not with_z0 and not with_ys and not with_base:
         return grad
-    return (grad,) + ((gz0,) if with_z0 else ()) + ((gy,) if with_ys else ())
+    return (grad,) + ((gz0,) if with_z0 else ()) + ((gy,) if with_ys else ()) + ((gb,) if with_base else ())
 
 
 def _autograd_function():
@@ -147,7 +163,9 @@ def _autograd_function():
 
     class _Generate(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, icnf, mode, ps, ys, z0, eps, tspan):
+        def forward(ctx, icnf, mode, ps, ys, z0, eps, tspan, normals, base_mean, base_scale):
+            # (base_mean / base_scale: the tensors of a LearnableNormal base, here so that autograd routes their gradient;
+            # normals: what z0 = mean + L n was drawn from inside differentiable_generate, None for a caller's z0)
             if _is_torch(ys) and ys.requires_grad:   # (a ys that asks for nothing stays the caller's object: set_cond knows it)
                 ys = ys.detach()
             n = z0.shape[1]
@@ -158,6 +176,8 @@ def _autograd_function():
             ctx.ps, ctx.ys, ctx.z0, ctx.eps, ctx.tspan = ps.detach(), ys, z0.detach(), eps, rec["tspan"]
             ctx.ys_shape = None if ys is None else ys.shape
             ctx.ps_shape = ps.shape
+            ctx.normals = normals
+            ctx.base_key = _base_key(icnf)
             ctx.set_materialize_grads(False)
             return xs.clone(), logq.clone()
 
@@ -165,10 +185,12 @@ def _autograd_function():
         def backward(ctx, g_x, g_logq):
             icnf = ctx.icnf
             need_ps, need_ys, need_z0 = ctx.needs_input_grad[2], bool(ctx.needs_input_grad[3]), ctx.needs_input_grad[4]
+            need_base = bool(ctx.needs_input_grad[8] or ctx.needs_input_grad[9])
             if g_x is None and g_logq is None:
-                return (None,) * 7
+                return (None,) * 10
 
             def record_again():
+                _base_unchanged(icnf, ctx.base_key)
                 generate_record(icnf, ctx.mode, ctx.ps, None, ctx.z0.shape[1], ys=ctx.ys, z0=ctx.z0, eps=ctx.eps, tspan=ctx.tspan)
                 ctx.token = icnf._record["token"]
 
@@ -176,16 +198,23 @@ def _autograd_function():
             if rec is None or rec["token"] is not ctx.token:
                 record_again()
             try:
-                res = generate_pullback(icnf, (g_x, g_logq), with_z0=True, with_ys=need_ys)
+                res = generate_pullback(icnf, (g_x, g_logq), with_z0=True, with_ys=need_ys, with_base=need_base)
             except _lib.CNFError as e:          # the record was displaced by another call on the handle: record again
                 if e.status != _lib.ERR_BAD_ARG:
                     raise
                 record_again()
-                res = generate_pullback(icnf, (g_x, g_logq), with_z0=True, with_ys=need_ys)
+                res = generate_pullback(icnf, (g_x, g_logq), with_z0=True, with_ys=need_ys, with_base=need_base)
             grad, gz0 = res[0], res[1]
             gy = res[2].reshape(ctx.ys_shape).contiguous() if need_ys else None
+            gm = gs = None
+            if need_base:
+                pm, psc = res[-1]                    # the partial at fixed z0 ...
+                if ctx.normals is not None:          # ... and the chain through z0 = mean + L n: the pullback of the draw
+                    sm, ssc = base_sample_pullback(icnf, ctx.normals, gz0)
+                    pm, psc = pm + sm, psc + ssc
+                gm, gs = _base_grads(icnf, (pm, psc), ctx.needs_input_grad[8], ctx.needs_input_grad[9])
             return (None, None, grad.reshape(ctx.ps_shape) if need_ps else None, gy, gz0.contiguous() if need_z0 else None,
-                    None, None)
+                    None, None, None, gm, gs)
 
     return _Generate
 
@@ -195,10 +224,12 @@ _FUNCTION = None
 
 def differentiable_generate(icnf: ICNF, mode, ps, st=None, n: int = 1, *, ys=None, z0=None, eps=None):
     """``generate`` with ``logq`` as a differentiable function of ``ps``, of ``z0`` when it requires grad (``z0 = g(context)``:
-    amortised inference) and, for a conditional model, of ``ys`` when it requires grad: forward = ``generate_record``, backward
-    = ``generate_pullback``.  Returns ``(xs [nvars x n], logq [n])`` attached to the autograd graph (device tensors).  ``z0``
-    and ``eps`` are drawn as ``generate`` draws them when not given.  If another call on the model displaced the record before
-    ``backward``, the solve is recorded again from the saved inputs (same outputs bit for bit) and then pulled back."""
+    amortised inference), for a conditional model of ``ys`` when it requires grad, and of the ``mean`` / scale tensors of a
+    ``LearnableNormal`` base when either requires grad (through the draw ``z0 = mean + L n`` too when ``z0`` is drawn here):
+    forward = ``generate_record``, backward = ``generate_pullback``.  Returns ``(xs [nvars x n], logq [n])`` attached to the
+    autograd graph (device tensors).  ``z0`` and ``eps`` are drawn as ``generate`` draws them when not given.  If another call on the model displaced the record before
+    ``backward``, the solve is recorded again from the saved inputs (same outputs bit for bit) and then pulled back; the values
+    of a ``LearnableNormal`` base are not saved, so ``RuntimeError`` if they changed in between."""
     global _FUNCTION
     import torch
     m = _mode_id(mode)
@@ -207,22 +238,27 @@ def differentiable_generate(icnf: ICNF, mode, ps, st=None, n: int = 1, *, ys=Non
         ps = torch.from_numpy(np.ascontiguousarray(np.asarray(ps, dtype=np.float32))).to(dev)
     if _is_torch(z0) and z0.shape[1] != n:
         raise ValueError("z0 must have n columns")
-    # the draws, in the order of generate_prob (z0, eps, the steered span), so that one seed gives one problem
+    bmean, bscale = _base_tensors(icnf)
+    kept = []
+    # the draws, in the order of generate_prob (z0, eps, the steered span), so that one seed gives one problem; the standard
+    # normals a z0 drawn here was made from are kept for the pullback of the draw
     zb, eb = _generate_inputs(icnf, mode, ps, n, ys.detach() if _is_torch(ys) and ys.requires_grad else ys,
-                              z0.detach() if _is_torch(z0) else z0, eps)
+                              z0.detach() if _is_torch(z0) else z0, eps, normals_out=kept)
+    n_in = icnf.nvars + n_augment_input(icnf)
+    normals = kept[0].view(n, n_in).t() if kept and bmean is not None else None
     tspan = steer_tspan(icnf, mode)
     if not (_is_torch(z0) and z0.requires_grad):
         z0 = _buf_to_device(icnf, zb).view()
     eps = _buf_to_device(icnf, eb).view() if m == _lib.MODE_TRAIN else None
     if _FUNCTION is None:
         _FUNCTION = _autograd_function()
-    return _FUNCTION.apply(icnf, mode, ps, ys, z0, eps, tspan)
+    return _FUNCTION.apply(icnf, mode, ps, ys, z0, eps, tspan, normals, bmean, bscale)
 
 
 def reverse_kl(icnf: ICNF, mode, ps, st, n, target_logpdf, **kw):
     """The reverse Kullback-Leibler divergence to an unnormalised target, estimated on ``n`` samples of the flow:
     ``mean(logq - target_logpdf(xs))`` with ``(xs, logq) = differentiable_generate(icnf, mode, ps, st, n)`` -- the variational
-    objective, differentiable w.r.t. ``ps`` (and ``z0`` / ``ys`` given through ``kw``).  ``target_logpdf``: a torch callable,
+    objective, differentiable w.r.t. ``ps`` (and ``z0`` / ``ys`` given through ``kw``, and the tensors of a ``LearnableNormal`` base).  ``target_logpdf``: a torch callable,
     ``nvars x n`` samples -> ``n`` log-densities."""
     xs, logq = differentiable_generate(icnf, mode, ps, st, n, **kw)
     return (logq - target_logpdf(xs).reshape(-1)).mean()

@@ -10,7 +10,8 @@ adjoint of the recorded solve with per-sample cotangents.
 Rows the model does not integrate carry no cotangent: with ``lambda1 = 0`` the E row is identically zero and its cotangent is
 ignored, likewise ``lambda2`` / n and ``lambda3`` / A, and all three in TestMode.  Gradients are taken w.r.t. ``ps``, ``xs`` and,
 for a conditional model, the conditioning inputs ``ys`` (cnf_set_grad_ys / cnf_grad_ys: ``ys = encoder(context)`` trains through
-the flow); ``eps`` and the time span are constants.
+the flow) and, with a ``distributions.LearnableNormal`` base, its ``mean`` and scale (cnf_base_logpdf_pullback: the final state
+does not depend on the base, so the cotangent of ``logpx`` is all it takes); ``eps`` and the time span are constants.
 """
 from __future__ import annotations
 
@@ -20,7 +21,8 @@ import numpy as np
 
 from . import _lib
 from .base_icnf import (ICNF, _as_colmajor, _is_torch, _mode_id, _solve_opts, _split_cond_args, _stream, _xs_colmajor,
-                        draw_eps, grad_ys, n_augment_input, raise_if_no_gpu, set_grad_ys, steer_tspan)
+                        base_logpdf_pullback, draw_eps, grad_ys, n_augment_input, raise_if_no_gpu, set_grad_ys, steer_tspan)
+from .distributions import LearnableNormal, learnable
 
 
 def _to_device(icnf: ICNF, a):
@@ -106,12 +108,15 @@ def _cot_matrix(cot, B, device):
     return out
 
 
-def inference_pullback(icnf: ICNF, cot, with_x=False, with_ys=False):
+def inference_pullback(icnf: ICNF, cot, with_x=False, with_ys=False, with_base=False):
     """``sum_b sum_r cot[r][b] d out_r[b] / d ps`` (and ``/ d xs`` with ``with_x``, ``/ d ys`` -- ``n_cond x B``, conditional
-    models only -- with ``with_ys``, appended in that order) through the steps ``inference_record`` recorded, in the caller's
-    parameter layout.  ``cot``: ``(g_logpx, (g_E, g_n, g_A))`` or a ``4 x B`` array; ``None`` entries are zeros.  May be called
-    several times on one record.  ``CNFError`` (``ERR_BAD_ARG``) when the record is gone."""
+    models only -- with ``with_ys``, and the pair ``(/ d mean, / d scale)`` of a ``LearnableNormal`` base with ``with_base``,
+    appended in that order) through the steps ``inference_record`` recorded, in the caller's parameter layout.  ``cot``:
+    ``(g_logpx, (g_E, g_n, g_A))`` or a ``4 x B`` array; ``None`` entries are zeros.  May be called several times on one
+    record.  ``CNFError`` (``ERR_BAD_ARG``) when the record is gone; ``ValueError`` for ``with_base`` with any other base."""
     import torch
+    if with_base:
+        learnable(icnf.basedist)
     l, h = _lib.lib(), icnf.handle()
     rec = getattr(icnf, "_record", None)
     dev = rec["xb"].arr.device if rec is not None else torch.device("cuda", icnf.device)
@@ -139,12 +144,14 @@ def inference_pullback(icnf: ICNF, cot, with_x=False, with_ys=False):
         _lib.check(l.cnf_grad_x(h, gx.data_ptr(), B, stream), h)
         gx = gx.view(B, icnf.nvars).t()
     gy = grad_ys(icnf, B, dev, stream, host) if with_ys else None
+    gb = base_logpdf_pullback(icnf, cm[0]) if with_base else None      # (row 0: the cotangent of logpx)
     if host:
         grad = grad.cpu().numpy()
         gx = gx.cpu().numpy() if gx is not None else None
-    if not with_x and not with_ys:
+        gb = tuple(g.cpu().numpy() for g in gb) if gb is not None else None
+    if not with_x and not with_ys and not with_base:
         return grad
-    return (grad,) + ((gx,) if with_x else ()) + ((gy,) if with_ys else ())
+    return (grad,) + ((gx,) if with_x else ()) + ((gy,) if with_ys else ()) + ((gb,) if with_base else ())
 
 
 def _autograd_function():
@@ -152,7 +159,9 @@ def _autograd_function():
 
     class _Inference(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, icnf, mode, xs, ys, ps, eps, tspan):
+        def forward(ctx, icnf, mode, xs, ys, ps, eps, tspan, base_mean, base_scale):
+            # (base_mean / base_scale: the tensors of a LearnableNormal base, here only so that autograd routes their gradient;
+            # their values were uploaded by the record's set_params)
             if _is_torch(ys) and ys.requires_grad:   # (a ys that asks for nothing stays the caller's object: set_cond knows it)
                 ys = ys.detach()
             args = (ys, ps, None) if icnf.cond else (ps, None)
@@ -163,6 +172,7 @@ def _autograd_function():
             ctx.xs, ctx.ys, ctx.ps, ctx.eb, ctx.tspan = xs.detach(), ys, ps.detach(), rec["eb"], rec["tspan"]
             ctx.ys_shape = None if ys is None else ys.shape
             ctx.ps_shape = ps.shape
+            ctx.base_key = _base_key(icnf)
             ctx.set_materialize_grads(False)
             return logpx.clone(), E.clone(), n.clone(), A.clone()
 
@@ -172,6 +182,7 @@ def _autograd_function():
             cot = (g_logpx, (g_E, g_n, g_A))
 
             def record_again():
+                _base_unchanged(icnf, ctx.base_key)
                 args = (ctx.ys, ctx.ps, None) if icnf.cond else (ctx.ps, None)
                 eps = ctx.eb.view() if ctx.eb is not None else None
                 inference_record(icnf, ctx.mode, ctx.xs, *args, eps=eps, tspan=ctx.tspan)
@@ -182,30 +193,67 @@ def _autograd_function():
                 record_again()
             # d / d ys is asked of the library only when whatever produced ys wants it (also after record_again)
             need_ys = bool(ctx.needs_input_grad[3])
+            need_base = bool(ctx.needs_input_grad[7] or ctx.needs_input_grad[8])
             try:
-                res = inference_pullback(icnf, cot, with_x=True, with_ys=need_ys)
+                res = inference_pullback(icnf, cot, with_x=True, with_ys=need_ys, with_base=need_base)
             except _lib.CNFError as e:          # the record was displaced by another call on the handle: record again
                 if e.status != _lib.ERR_BAD_ARG:
                     raise
                 record_again()
-                res = inference_pullback(icnf, cot, with_x=True, with_ys=need_ys)
+                res = inference_pullback(icnf, cot, with_x=True, with_ys=need_ys, with_base=need_base)
             grad, gx = res[0], res[1]
             gy = res[2].reshape(ctx.ys_shape).contiguous() if need_ys else None
+            gm, gs = _base_grads(icnf, res[-1], ctx.needs_input_grad[7], ctx.needs_input_grad[8]) if need_base else (None, None)
             need_x, need_ps = ctx.needs_input_grad[2], ctx.needs_input_grad[4]
             return (None, None, gx.contiguous() if need_x else None, gy,
-                    grad.reshape(ctx.ps_shape) if need_ps else None, None, None)
+                    grad.reshape(ctx.ps_shape) if need_ps else None, None, None, gm, gs)
 
     return _Inference
+
+
+def _base_grads(icnf: ICNF, pair, need_mean, need_scale):
+    """(g_mean, g_scale) of a pullback as the gradients of the base's own tensors: their device, dtype and shape."""
+    d = icnf.basedist
+    like = lambda g, t: g.to(device=t.device, dtype=t.dtype).reshape(t.shape)
+    return (like(pair[0], d.mean_t) if need_mean else None, like(pair[1], d.scale_t) if need_scale else None)
+
+
+def _base_key(icnf: ICNF):
+    """Which values of a LearnableNormal base a record was made with: (the object, its generation); None for any other base."""
+    d = icnf.basedist
+    return (d, d.generation) if isinstance(d, LearnableNormal) else None
+
+
+def _base_unchanged(icnf: ICNF, key):
+    """Before a displaced record is made again from saved inputs: the base's values are not among them, so they must still be
+    the ones of the first recording -- a second recording with another base would silently differentiate another function."""
+    d = icnf.basedist
+    if isinstance(d, LearnableNormal):
+        d.refresh()
+    cur = _base_key(icnf)
+    if (cur is None) != (key is None) or (cur is not None and (cur[0] is not key[0] or cur[1] != key[1])):
+        raise RuntimeError("the base distribution changed between forward and backward and the recorded solve was displaced by "
+                           "another call on the model: call backward before updating the base")
+
+
+def _base_tensors(icnf: ICNF):
+    """The tensors of a LearnableNormal base when either requires grad (what the autograd functions take), else (None, None)."""
+    d = icnf.basedist
+    if isinstance(d, LearnableNormal) and d.requires_grad:
+        return d.mean_t, d.scale_t
+    return None, None
 
 
 _FUNCTION = None
 
 
 def differentiable_inference(icnf: ICNF, mode, xs, *args, eps=None):
-    """``inference`` as a differentiable function of ``ps``, ``xs`` and (conditional models) ``ys`` (device tensors): forward
+    """``inference`` as a differentiable function of ``ps``, ``xs``, (conditional models) ``ys`` and the ``mean`` / scale tensors
+    of a ``LearnableNormal`` base when either requires grad (device tensors): forward
     = ``inference_record``, backward = ``inference_pullback`` (which is asked for d / d ys only when ``ys`` requires grad).  Returns ``(logpx, (E, n, A))`` attached to the autograd graph.  If another call on the
     model displaced the record before ``backward``, the solve is recorded again from the saved inputs (same outputs bit for
-    bit: the solve is deterministic) and then pulled back."""
+    bit: the solve is deterministic) and then pulled back; the values of a ``LearnableNormal`` base are not saved, so
+    ``RuntimeError`` if they changed in between."""
     global _FUNCTION
     import torch
     if not _is_torch(xs):
@@ -220,7 +268,7 @@ def differentiable_inference(icnf: ICNF, mode, xs, *args, eps=None):
     if m == _lib.MODE_TRAIN and eps is None:
         eps = draw_eps(icnf, _xs_colmajor(icnf, xs.detach()), xs.shape[1]).view()
     tspan = steer_tspan(icnf, mode)
-    logpx, E, n, A = _FUNCTION.apply(icnf, mode, xs, ys, ps, eps, tspan)
+    logpx, E, n, A = _FUNCTION.apply(icnf, mode, xs, ys, ps, eps, tspan, *_base_tensors(icnf))
     return logpx, (E, n, A)
 
 

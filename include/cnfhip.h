@@ -129,7 +129,9 @@ cnf_status cnf_set_cond_host(cnf_handle h, const float* ys, int B);
  *   kind 2: dense -- whiten = W and chol = L, lower triangular n_in x n_in, ROW-major (entry (i, j) at [i n_in + j]; entries
  *           above the diagonal are not read), diagonals finite and > 0.
  * HOST pointers, copied at the call (synchronous; outstanding submissions are completed first).  logconst is what the caller
- * computed in double, sum_i log W_ii - n_in / 2 log(2 pi), rounded once.  The base is not learnable: no gradient w.r.t. it.
+ * computed in double, sum_i log W_ii - n_in / 2 log(2 pi), rounded once.  The base is learnable from outside: cnf_base_logpdf_pullback /
+ * cnf_base_sample_pullback (cnfhip_basegrad.h) return the gradient w.r.t. `mean` and `chol`, and the caller uploads the updated
+ * arrays with this call (one host wait per update); the library itself keeps the base constant.
  * With a non-default base every solve keeps its N(0, I) post-processing and ONE small launch behind it on the same stream
  * recomputes logpx (and the loss sums) afresh from the final state; gradients take the recorded solve (never the gradient
  * inside the solve's launch), and cnf_loss_grad_submit returns CNF_ERR_UNSUPPORTED at once.
@@ -357,6 +359,9 @@ cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int B, float* 
 
 /* ---- differentiable sampling: cnf_generate_record / cnf_generate_pullback (declared in cnfhip_generate.h, part of this header) ---- */
 #include "cnfhip_generate.h"
+
+/* ---- a learnable base distribution: cnf_base_logpdf_pullback / cnf_base_sample_pullback (declared in cnfhip_basegrad.h, part of this header) ---- */
+#include "cnfhip_basegrad.h"
 
 /* ---- device random numbers ------------------------------------------
  *
