@@ -58,7 +58,8 @@ from .types import (FFJORD, RNODE, CondFFJORD, CondPlanar, CondRNODE, HIPJacVecM
                     HIPMatrixMode, HIPVecJacMatrixMode, Planar, TestMode, TrainMode)
 from .vjp import differentiable_inference, inference_pullback, inference_record, tempered_loss, weighted_loss
 from .gen_vjp import differentiable_generate, generate_pullback, generate_record, reverse_kl
-from . import gen_vjp, mlj, parallel, vjp
+from . import ensemble, gen_vjp, mlj, parallel, vjp
+from .ensemble import ensemble_capacity, ensemble_steps, fit_many, loss_and_grad_many
 from .mlj import (Adam, CondICNFModel, ICNFModel, Lion, Machine, fit, fit_, fitted_params, load_params, machine, save_params,
                   transform)
 

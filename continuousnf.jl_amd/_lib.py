@@ -135,6 +135,14 @@ _BASEGRAD_SIGNATURES = {
     "cnf_base_sample_pullback": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _fp, _fp, C.c_void_p]),
 }
 BASEGRAD_EXPORTS = tuple(_BASEGRAD_SIGNATURES)
+# ensembles (include/cnfhip_ensemble.h): likewise
+_ENSEMBLE_SIGNATURES = {
+    "cnf_ensemble_capacity": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "cnf_loss_grad_many": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), _fp, _fp, _fp,
+                                     _fp, C.c_void_p, C.c_void_p]),
+    "cnf_ensemble_steps": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int]),
+}
+ENSEMBLE_EXPORTS = tuple(_ENSEMBLE_SIGNATURES)
 
 _lib = None
 
@@ -172,7 +180,8 @@ def lib():
         except ImportError:
             pass
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) + list(_BASEGRAD_SIGNATURES.items()):
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) + list(_BASEGRAD_SIGNATURES.items()) + \
+                list(_ENSEMBLE_SIGNATURES.items()):
             f = getattr(l, name)
             f.restype, f.argtypes = res, args
         _lib = l

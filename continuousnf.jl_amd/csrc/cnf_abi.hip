@@ -167,6 +167,19 @@ struct cnf_ctx {
     int fs_B = 0, fs_mode = 0;    // cnf_loss_grad / cnf_loss_grad_test on the recorded route: g_US[1] holds the final state of a batch
                                   //   of fs_B samples solved in fs_mode (0: none); ends where a record ends
     PinnedBuf<float> h_sums;      // pinned, 4 floats
+    // cnf_loss_grad_many (k_solve_wave<.., ENS>): what one model's call has once, per member; sized for (M, B), grow-only
+    DevBuf<float> ens_traj;       // [M][cap] trajectory rows
+    DevBuf<float> ens_hs;         // [M][cap] signed step sizes (read back on demand: cnf_ensemble_steps)
+    DevBuf<float> ens_gpart;      // [M][tiles][n_params] the waves' partials
+    DevBuf<float> ens_cols;       // [M][B][D] final columns | [M][B] logpx | [M][3][B] regs | [M][B][n_in] d loss / d z(t0)
+    DevBuf<float> ens_part;       // [M] meeting words (WV_ENS_PART_FLOATS each), zero when allocated
+    DevBuf<unsigned> ens_words;   // [M] meeting bases | [M] abort words: set by every call in front of its launch
+    DevBuf<float> ens_fin;        // [M] final StepStates | [5 M] loss sums: one copy to the host per call
+    PinnedBuf<float> ens_hfin;    //   ... its landing place, and behind it [M] end times on their way to the device
+    DevBuf<float> ens_t1;
+    unsigned ens_base = 0;        // meeting indices the ensemble launches so far may have used (tags go on from there)
+    int ens_M = 0, ens_cap = 0;   // the last call: members, step slots per member
+    std::vector<int> ens_nacc;    //   accepted steps per member (-1: the member gave up)
     std::string err;
 };
 
@@ -963,6 +976,26 @@ extern "C" cnf_status cnf_solve_tsit5(cnf_handle h, int mode, const float* u0,
     return solve_core(h, mode, u0, eps, u_out, B, opts, stats, stream, nullptr);
 }
 
+// the bounds of a wait inside a one-launch solve of this handle (cnf_set_solve_wait; CNF_SOLVE_WAIT_US, CNF_SOLVE_POLL_LIMIT)
+static void set_wait_bounds(cnf_handle h, Solve3Args& sv) {
+    static const int spin_limit = [] { const char* e = getenv("CNF_SOLVE_POLL_LIMIT"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 0x7fffffff; }();
+    static const int wait_us = [] { const char* e = getenv("CNF_SOLVE_WAIT_US"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 2000; }();
+    sv.spin_limit = h->poll_limit > 0 ? h->poll_limit : spin_limit;
+    const int wus = h->wait_us > 0 ? h->wait_us : wait_us;
+    sv.wait_ticks = wus < 20000000 ? 100u * (unsigned)wus : 2000000000u;   // (per tile: the launcher scales it)
+}
+// what every solve asks of its options
+static cnf_status check_solve_opts(cnf_handle h, const cnf_solve_opts* opts) {
+    if (!(opts->t0 == opts->t0) || !(opts->t1 == opts->t1) || opts->t0 == opts->t1)
+        return fail(h, CNF_ERR_BAD_ARG, "empty or NaN time span");
+    if (!opts->adaptive && !(opts->dt > 0.f)) return fail(h, CNF_ERR_BAD_ARG, "fixed stepping needs dt > 0");
+    if (opts->adaptive && (!(opts->abstol >= 0.f) || !(opts->reltol >= 0.f) || (opts->abstol == 0.f && opts->reltol == 0.f)))
+        return fail(h, CNF_ERR_BAD_ARG, "bad tolerances");
+    if (opts->dt < 0.f) return fail(h, CNF_ERR_BAD_ARG, "dt must be >= 0 (direction comes from the span)");
+    if (opts->maxiters < 1) return fail(h, CNF_ERR_BAD_ARG, "maxiters must be >= 1");
+    return CNF_OK;
+}
+
 static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const float* eps, float* u_out, int B,
                              const cnf_solve_opts* opts, cnf_solve_stats* stats, void* stream, Recorder* rec,
                              bool final_sync, PostHook* post) {
@@ -972,13 +1005,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
     if (!u0 || !opts) return fail(h, CNF_ERR_BAD_ARG, "null pointer");      // u_out may be null: the state stays in U[cur]
     const int train = mode == CNF_MODE_TRAIN;
     if (train && !eps) return fail(h, CNF_ERR_BAD_ARG, "eps is required in TrainMode");
-    if (!(opts->t0 == opts->t0) || !(opts->t1 == opts->t1) || opts->t0 == opts->t1)
-        return fail(h, CNF_ERR_BAD_ARG, "empty or NaN time span");
-    if (!opts->adaptive && !(opts->dt > 0.f)) return fail(h, CNF_ERR_BAD_ARG, "fixed stepping needs dt > 0");
-    if (opts->adaptive && (!(opts->abstol >= 0.f) || !(opts->reltol >= 0.f) || (opts->abstol == 0.f && opts->reltol == 0.f)))
-        return fail(h, CNF_ERR_BAD_ARG, "bad tolerances");
-    if (opts->dt < 0.f) return fail(h, CNF_ERR_BAD_ARG, "dt must be >= 0 (direction comes from the span)");
-    if (opts->maxiters < 1) return fail(h, CNF_ERR_BAD_ARG, "maxiters must be >= 1");
+    if ((s = check_solve_opts(h, opts)) != CNF_OK) return s;
     if (stats) memset(stats, 0, sizeof *stats);
     if (B == 0) return CNF_OK;
     int k;
@@ -1011,18 +1038,12 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
     StepState* init = init_state(h);
     memset(init, 0, sizeof *init);
     init->t = init->t0 = opts->t0;
-    init->t1 = opts->t1;
-    init->tdir = opts->t1 >= opts->t0 ? 1.f : -1.f;
     init->dt = opts->dt;
     init->qold = 1e-4f;
     init->abstol = opts->abstol; init->reltol = opts->reltol;
     init->adaptive = opts->adaptive ? 1 : 0;
     init->n_partials = nblk;
-    {
-        float rem = fabsf(init->t1 - init->t);
-        float hh = init->dt < rem ? init->dt : rem;
-        init->h = init->tdir * hh;
-    }
+    step_state_set_t1(init, opts->t1);
     const bool hairer = opts->adaptive && opts->dt == 0.f;
     // The whole solve in ONE launch where the handle and the batch allow it (k_solve3b / k_solve3jb): the weights and the
     // Runge-Kutta rows stay on the CUs for all attempts, the workgroups exchange two floats per attempt.
@@ -1065,11 +1086,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
         // tile a workgroup carries (a meeting's arrivals are microseconds apart when every workgroup is placed; a workgroup
         // that is not placed because another tenant holds its CU makes the launch give up after that long, and the streamed
         // solve starts).  CNF_SOLVE_WAIT_US overrides; CNF_SOLVE_POLL_LIMIT bounds the number of polls instead (tests: 1).
-        static const int spin_limit = [] { const char* e = getenv("CNF_SOLVE_POLL_LIMIT"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 0x7fffffff; }();
-        static const int wait_us = [] { const char* e = getenv("CNF_SOLVE_WAIT_US"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 2000; }();
-        sv.spin_limit = h->poll_limit > 0 ? h->poll_limit : spin_limit;
-        const int wus = h->wait_us > 0 ? h->wait_us : wait_us;
-        sv.wait_ticks = wus < 20000000 ? 100u * (unsigned)wus : 2000000000u;   // (per tile: the launcher scales it)
+        set_wait_bounds(h, sv);
         sv.trace = h->step_trace; sv.trace_cap = h->step_trace_cap;
         // (k_trace3s<SOLVE> works on the integrator's buffers: u0 is assembled / copied into U[0] in front of it, the
         // post-processing follows it -- three launches per inference)
@@ -2505,4 +2522,170 @@ extern "C" cnf_status cnf_loss_grad_host(cnf_handle h, const float* xs, const fl
         if (e != hipSuccess) s = fail(h, CNF_ERR_HIP, hipGetErrorString(e));
     }
     return s;
+}
+
+// ---------------------------------------------------------------------------------------
+// Ensembles (include/cnfhip_ensemble.h): M independent models of the handle's architecture -- folds, replicas, seeds -- whose
+// losses and gradients come out of ONE launch of k_solve_wave<.., ENS> (cnf_wave.hip) and one launch of the partial sums.
+// Nothing of the handle's own model is touched: parameters, data and probes are the caller's arrays, every store is a buffer
+// of the ensemble's own.
+// ---------------------------------------------------------------------------------------
+// step slots per member: the single model's WV_GCAP, halved while the M trajectory stores exceed its budget of 1 GiB (>= 64)
+static int ens_step_slots(cnf_handle h, int M, int B) {
+    const size_t per_step = wave_grad_traj_floats(h->nd_wave, B);
+    int cap = WV_GCAP;
+    while (cap > 64 && per_step * cap * (size_t)M > ((size_t)1 << 28)) cap /= 2;
+    return cap;
+}
+extern "C" int cnf_ensemble_capacity(cnf_handle h, int mode, int B) {
+    if (!h || (mode != CNF_MODE_TEST && mode != CNF_MODE_TRAIN) || B < 1) return 0;
+    if (h->nd.n_cond > 0 || h->bd.kind || h->grad_ys || h->shard_reduce || h->shard_comm || h->no_persist) return 0;
+    if (hipSetDevice(h->device) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    int cap = wave_ens_capacity(h->nd_wave, mode == CNF_MODE_TRAIN, B);
+    // ... and no more members than keep 64 step slots each within the trajectory budget of one model's call
+    const size_t fit = ((size_t)1 << 28) / (wave_grad_traj_floats(h->nd_wave, B) * 64);
+    if ((size_t)cap > fit) cap = (int)fit;
+    return cap;
+}
+
+extern "C" cnf_status cnf_loss_grad_many(cnf_handle h, int mode, int M, const float* params_dev, const float* xs, const float* eps,
+                                         int B, const cnf_solve_opts* opts, const float* t1_host, float* loss_out, float* grad_dev,
+                                         int* status_out, cnf_solve_stats* stats_out, void* stream) {
+    // (the arguments first, the handle last: what is wrong with a call is said before anything asks for a device)
+    if (mode != CNF_MODE_TEST && mode != CNF_MODE_TRAIN) return fail(h, CNF_ERR_BAD_ARG, "unknown mode");
+    const bool train = mode == CNF_MODE_TRAIN;
+    if (!params_dev || !xs || !opts || !loss_out || !grad_dev || !status_out || (train && !eps)) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    if (M < 1) return fail(h, CNF_ERR_BAD_SHAPE, "an ensemble has at least one member");
+    if (B < 1) return fail(h, CNF_ERR_BAD_SHAPE, "the loss is a mean over the batch: B must be >= 1");
+    if (!h) return CNF_ERR_BAD_ARG;
+    cnf_status s = check_solve_opts(h, opts);
+    if (s != CNF_OK) return s;
+    if (t1_host)
+        for (int m = 0; m < M; ++m)
+            if (!std::isfinite(t1_host[m]) || t1_host[m] == opts->t0) return fail(h, CNF_ERR_BAD_ARG, "empty or NaN time span of a member");
+    while (!h->collecting && !h->submitted.empty())       // (as any other call: the inferences submitted on the handle end first)
+        if ((s = collect_one(h, nullptr)) != CNF_OK) return s;
+    if (opts->kernel == CNF_KERNEL_GENERIC) return fail(h, CNF_ERR_UNSUPPORTED, "the ensemble form exists on the wave kernels only");
+    const int capacity = cnf_ensemble_capacity(h, mode, B);
+    if (capacity < 1) return fail(h, CNF_ERR_UNSUPPORTED, "no ensemble form for this model, mode or batch");
+    if (M > capacity) return fail(h, CNF_ERR_UNSUPPORTED, "more members than one launch takes (cnf_ensemble_capacity)");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    const NetDesc& nd = h->nd_wave;
+    const size_t Mz = (size_t)M, Bz = (size_t)B, n_in = (size_t)nd.n_in, D = n_in + (train ? 3 : 1), np = h->n_params;
+    const int tiles = wave_grad_waves(B), cap = ens_step_slots(h, M, B);
+    const size_t per_step = wave_grad_traj_floats(nd, B);
+    const size_t st_f = (sizeof(StepState) + 3) / 4, fin_f = Mz * (st_f + 5);
+    // ---- the members' stores: grown behind a wait for the device, so that steady-state calls allocate nothing ----
+    const size_t cols_f = Mz * Bz * (D + 4 + n_in);
+    if (per_step * cap * Mz > h->ens_traj.capacity() || Mz * cap > h->ens_hs.capacity() || Mz * tiles * np > h->ens_gpart.capacity() ||
+        cols_f > h->ens_cols.capacity() || Mz * WV_ENS_PART_FLOATS > h->ens_part.capacity() || 2 * Mz > h->ens_words.capacity() ||
+        fin_f > h->ens_fin.capacity() || fin_f + Mz > h->ens_hfin.capacity() || Mz > h->ens_t1.capacity()) {
+        HIPCHK(h, hipDeviceSynchronize());
+        h->ens_M = 0;
+        RESERVE(h, h->ens_traj, per_step * cap * Mz);
+        RESERVE(h, h->ens_hs, Mz * cap);
+        RESERVE(h, h->ens_gpart, Mz * tiles * np);
+        RESERVE(h, h->ens_cols, cols_f);
+        RESERVE(h, h->ens_words, 2 * Mz);
+        RESERVE(h, h->ens_fin, fin_f);
+        RESERVE(h, h->ens_hfin, fin_f + Mz);
+        RESERVE(h, h->ens_t1, Mz);
+        if (Mz * WV_ENS_PART_FLOATS > h->ens_part.capacity()) {
+            RESERVE(h, h->ens_part, Mz * WV_ENS_PART_FLOATS);
+            HIPCHK(h, hipMemset(h->ens_part, 0, Mz * WV_ENS_PART_FLOATS * sizeof(float)));
+            h->ens_base = 0;
+        }
+    }
+    h->grad_last_B = 0; h->gy_last_B = 0; end_record(h);   // (as every gradient call; the handle's own model is not touched)
+    h->ens_M = 0;
+    StepState* fin_dev = reinterpret_cast<StepState*>(h->ens_fin.data());
+    float* sums_dev = h->ens_fin + Mz * st_f;
+
+    std::unique_lock<std::mutex> persist_lock(g_persist_mu);       // one one-launch solve at a time in this process
+    if (g_submitted_inflight > 0 && g_submitted_stream != st) HIPCHK(h, hipStreamSynchronize(g_submitted_stream));
+    // the meeting indices of this launch go on from where the earlier ones may have ended (a meeting per attempt, the two of the
+    // initial dt, the loss sums; twice that: a workgroup placed late reads a base its member has already advanced), so that no
+    // word an earlier call left can pass for news; when the 32 bits run out the words are cleared and the count starts again
+    const unsigned long long span = 2ull * ((unsigned long long)opts->maxiters + 8ull);
+    if ((unsigned long long)h->ens_base + span >= 0xffffffffull) {
+        HIPCHK(h, hipMemsetAsync(h->ens_part, 0, h->ens_part.capacity() * sizeof(float), st));
+        h->ens_base = 0;
+    }
+    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->ens_words.data(), (int)h->ens_base, Mz, st));
+    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(h->ens_words.data() + Mz), 0, Mz, st));
+    h->ens_base += (unsigned)(span < 0xffffffffull ? span : 0xfffffffeull);
+    float* t1_pin = h->ens_hfin + fin_f;
+    if (t1_host) {
+        memcpy(t1_pin, t1_host, Mz * sizeof(float));
+        HIPCHK(h, hipMemcpyAsync(h->ens_t1, t1_pin, Mz * sizeof(float), hipMemcpyHostToDevice, st));
+    }
+    StepState init{};
+    init.t = init.t0 = opts->t0;
+    init.dt = opts->dt;
+    init.qold = 1e-4f;
+    init.abstol = opts->abstol; init.reltol = opts->reltol;
+    init.adaptive = opts->adaptive ? 1 : 0;
+    init.n_partials = tiles;
+    step_state_set_t1(&init, opts->t1);
+    const bool hairer = opts->adaptive && opts->dt == 0.f;
+    Solve3Args sv{};
+    sv.part = h->ens_part; sv.base_dev = h->ens_words; sv.abort_flag = reinterpret_cast<int*>(h->ens_words.data() + Mz);
+    sv.maxiters = (int)opts->maxiters; sv.hairer = hairer ? 1 : 0; sv.init = init;
+    set_wait_bounds(h, sv);
+    float* cols = h->ens_cols;
+    sv.xs = xs; sv.logpx = cols + Mz * Bz * D; sv.regs = sv.logpx + Mz * Bz; sv.sums5 = sums_dev;
+    WaveGradArgs wg;
+    wg.traj = h->ens_traj; wg.traj_cap = cap; wg.hs_out = h->ens_hs; wg.gpart = h->ens_gpart;
+    wg.lam_out = cols + Mz * Bz * (D + 4); wg.n_params = (int)np;
+    wg.lam1 = h->lam[0]; wg.lam2 = h->lam[1]; wg.lam3 = h->lam[2];
+    WaveEnsLaunch ens;
+    ens.M = M; ens.t1 = t1_host ? h->ens_t1.data() : nullptr;
+    ens.p_stride = np; ens.traj_stride = per_step * cap; ens.part_stride = WV_ENS_PART_FLOATS;
+    int launches = 0;                                      // kernel launches of this call, counted where they are made
+    s = wave_solve_launch(nd, train, params_dev, nullptr, 0, fin_dev, cols, eps, B, st, nullptr, 0, sv, &wg, &ens);
+    if (s != CNF_OK) return fail(h, s, "the ensemble launch failed to start");
+    ++launches;
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch_grad_reduce_many(wg.gpart, grad_dev, (int)np, tiles, fin_dev, M, st));
+    ++launches;
+    HIPCHK(h, hipMemcpyAsync(h->ens_hfin, h->ens_fin, fin_f * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));                   // (no mirror is polled: the call waits for the stream)
+    persist_lock.unlock();
+
+    h->ens_nacc.assign(Mz, -1);
+    for (int m = 0; m < M; ++m) {
+        StepState fin;
+        memcpy(&fin, h->ens_hfin + (size_t)m * st_f, sizeof fin);
+        const int attempts = fin.naccept + fin.nreject;
+        fill_stats(stats_out ? stats_out + m : nullptr, fin, (hairer ? 2 : 1) + 6 * attempts, CNF_KERNEL_MFMA, launches);
+        loss_out[m] = NAN;
+        if (fin.n_partials < 0) status_out[m] = CNF_ERR_UNSUPPORTED;             // a wait ran out, or more steps than its store holds
+        else if (fin.nonfinite) status_out[m] = CNF_ERR_NONFINITE;
+        else if (!fin.done) status_out[m] = CNF_ERR_MAXITERS;
+        else {
+            // (a failure here is that member's status: the launch ran, so the call goes on and returns CNF_OK)
+            status_out[m] = cnf_loss_from_sums(h, mode, h->ens_hfin + Mz * st_f + 5 * (size_t)m, loss_out + m);
+            if (status_out[m] == CNF_OK) h->ens_nacc[m] = fin.naccept;
+            else loss_out[m] = NAN;
+        }
+    }
+    h->ens_M = M; h->ens_cap = cap;
+    return CNF_OK;
+}
+
+// the signed accepted step sizes of member `member` of the last cnf_loss_grad_many call (read from the device when asked for)
+extern "C" int cnf_ensemble_steps(cnf_handle h, int member, float* hs, int cap) {
+    if (!h || member < 0 || member >= h->ens_M) return -1;
+    const int n = h->ens_nacc[member];
+    if (n < 0) return -1;
+    const int take = n < cap ? n : cap;
+    if (hs && take > 0) {
+        if (hipSetDevice(h->device) != hipSuccess ||
+            hipMemcpy(hs, h->ens_hs + (size_t)member * h->ens_cap, (size_t)take * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+            (void)hipGetLastError();
+            return -1;
+        }
+    }
+    return n;
 }

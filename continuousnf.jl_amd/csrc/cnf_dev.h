@@ -41,6 +41,16 @@ struct StepState {
     int n_partials;         // entries of the error-partials array
 };
 
+// The end time of a solve and what follows from it: the direction and the first attempt's step, clamped to the span that is
+// left.  One copy for the host (solve_core sets up the initial state) and the device (an ensemble member's own end time).
+__host__ __device__ inline void step_state_set_t1(StepState* st, float t1) {
+    st->t1 = t1;
+    st->tdir = t1 >= st->t0 ? 1.f : -1.f;
+    const float rem = fabsf(st->t1 - st->t);
+    const float hh = st->dt < rem ? st->dt : rem;
+    st->h = st->tdir * hh;
+}
+
 #ifdef __HIPCC__
 // Integrator state -> pinned host mirror: one 8-byte system-scope store per state word, {tag = launch index, word}
 // (protocol and reader: cnf_mirror.h).  No wait, no fence: the reader validates the tags, and a release fence would

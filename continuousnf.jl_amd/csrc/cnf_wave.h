@@ -32,6 +32,21 @@ bool wave_solve_supported(const NetDesc& nd, bool train, int B);
 // sv as for mfma_solve_persistent (Solve3Args: the initial state by value, the meeting buffer and its index base, the wait
 // bounds; either sv.xs + the post-processing outputs, or sv.u0 / sv.u_out of a bare solve -- u_out null: the final columns
 // go to U0).  CNF_ERR_UNSUPPORTED: not this network / batch.
+// ens: M models in one launch (k_solve_wave<.., ENS>; cnf_loss_grad_many).  Every array of the other arguments is then the
+// first member's, with the members' copies behind it: [M][n_params] parameters (p_stride), [M][B][..] data, probes, logpx,
+// regs and final columns, [M] final states, 5 M sums, [M][traj_cap] step sizes, [M][tiles][n_params] partials, and
+// sv.base_dev / sv.abort_flag one word per member; no mirror, no trace, no clock, no rich store.
+struct WaveEnsLaunch {
+    int M = 0;
+    const float* t1 = nullptr;     // device, [M]: the members' own end times (null: sv.init.t1 for all)
+    size_t p_stride = 0;           // floats between two members' parameters
+    size_t traj_stride = 0;        // ... trajectory stores (traj_cap x wave_grad_traj_floats)
+    size_t part_stride = 0;        // ... meeting words, in floats (WV_ENS_PART_FLOATS)
+};
+#define WV_ENS_PART_FLOATS 8192    // a member's meeting words: 2 x 1024 of the meetings + 2048 of the loss-sum partials, 8 bytes each
+// the largest M a launch takes at batch B: workgroups the device holds at once / tiles (0: no ensemble form of this network
+// or mode, or the one-launch solves are switched off)
+int wave_ens_capacity(const NetDesc& nd, bool train, int B);
 cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_params, const float* cond, int cbs, StepState* st_out,
                              float* U0, const float* eps, int B, hipStream_t s, void* mirror, unsigned seq, const Solve3Args& sv,
-                             const WaveGradArgs* grad = nullptr);
+                             const WaveGradArgs* grad = nullptr, const WaveEnsLaunch* ens = nullptr);

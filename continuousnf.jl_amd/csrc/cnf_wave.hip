@@ -31,7 +31,8 @@
 //         factor tiles filed in LDS; RICH: the forward pass also files its evaluations' intermediates for the backward pass;
 //   ID2   the second activation is the identity (a PlanarLayer, or the identity layer cnf_create appends to a ONE-layer
 //         network: the network of the reference's benchmark suite);
-//   WGW   the tiles of a batch of at most 64 samples as the waves of one workgroup (LDS meeting), plain solves.
+//   WGW   the tiles of a batch of at most 64 samples as the waves of one workgroup (LDS meeting), plain solves;
+//   ENS   M independent models of one architecture in one launch (cnf_loss_grad_many): a GRAD form whose grid is M x tiles.
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -59,6 +60,15 @@ struct WaveArgs {
     void* mirror;
     unsigned seq;
     WaveGradArgs g;        // gradient path (GRAD instantiations): the discrete adjoint of the accepted steps in the same launch
+};
+// ENS instantiations: the grid is M members x `tiles` workgroups, member-major; everything a launch has ONE of, a member has its
+// own copy of, `member` strides further on (the strides that are not a product of two fields of the other arguments)
+struct WaveEnsArgs {
+    int tiles;             // 16-sample tiles (= workgroups, = meeting parties) of one member
+    const float* t1;       // null, or the members' own end times [M] (steer_tspan draws one per member)
+    size_t p_stride;       // floats between two members' flat parameters
+    size_t traj_stride;    // ... their trajectory stores
+    size_t part_stride;    // ... their meeting words (as floats)
 };
 
 __device__ __forceinline__ f32x4 mm4(const float (&A)[4], const f32x4& b, f32x4 acc) {
@@ -130,9 +140,16 @@ __device__ __forceinline__ float wv_quad_sum(float v) {
 // the weight-gradient contraction -- it keeps the Wbar tiles, reads the factor tiles the main wave files in LDS (two sets, one
 // workgroup barrier per stage evaluation) and issues the 48 MFMAs of a stage beside the main wave's next stage: the
 // contraction (a quarter of the backward pass: LDS round trip + MFMAs) leaves the main wave's dependent chain.
-template <int NI, int NH, int MODE, bool TANH, bool GRAD = false, bool ID2 = false, int WGW = 1, bool RICH = false>
-__global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wave(WaveArgs a, Solve3Args sv, const WvTab tab) {
+//
+// ENS (the recomputing GRAD forms): M independent models -- own parameters, data, probes, end time and step sequence -- in one
+// launch of M x tiles workgroups.  The prologue moves every pointer of the arguments on to its member's copy (scalar
+// arithmetic on the kernel arguments: nothing but the moved pointers outlives it); behind it the body is the single
+// model's, with `tiles` parties per meeting instead of the grid.  Members never meet: a member whose wait runs out sets its
+// own abort word and writes its own final state.
+template <int NI, int NH, int MODE, bool TANH, bool GRAD = false, bool ID2 = false, int WGW = 1, bool RICH = false, bool ENS = false>
+__global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wave(WaveArgs a, Solve3Args sv, const WvTab tab, const WaveEnsArgs en) {
     constexpr bool HELP = GRAD && WGW == 1;
+    static_assert(!ENS || (HELP && !RICH), "ENS is a form of the recomputing gradient, one tile per workgroup");
     static_assert(!RICH || (GRAD && MODE == WV_VJP), "RICH is a form of the TrainMode / VJP gradient");
     constexpr int RR = 3 * NH + 3 * NI;                     // f32x4 per lane and stage evaluation in the rich store
     f32x4* rich_ptr = nullptr;                             // where the next evaluation files them (null: nowhere)
@@ -146,7 +163,24 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
     // workgroups (large batches: up to 512 workgroups x WGW tiles): LDS inside the workgroup, the tagged words between them
     const int wloc = WGW > 1 ? (int)(threadIdx.x >> 6) : 0, nwg = WGW > 1 ? (int)(blockDim.x >> 6) : 1;
     const bool xwg = WGW > 1 && gridDim.x > 1;
-    const int wid = WGW > 1 ? (int)blockIdx.x * nwg + wloc : (int)blockIdx.x;      // this wave's tile
+    int wid_ = WGW > 1 ? (int)blockIdx.x * nwg + wloc : (int)blockIdx.x;
+    if constexpr (ENS) {
+        const int member = (int)blockIdx.x / en.tiles;
+        wid_ = (int)blockIdx.x - member * en.tiles;
+        const size_t mb = (size_t)member, Bz = (size_t)a.B, nz = (size_t)a.nd.n_in;
+        a.P += mb * en.p_stride;
+        sv.xs += mb * Bz * (size_t)sv.nvars;
+        if (a.eps) a.eps += mb * Bz * nz;
+        sv.logpx += mb * Bz; sv.regs += mb * 3 * Bz; sv.sums5 += mb * 5;
+        a.U0 += mb * Bz * (nz + (MODE != WV_TEST ? 3 : 1));
+        a.st_out += mb;
+        a.g.traj += mb * en.traj_stride; a.g.hs_out += mb * (size_t)a.g.traj_cap;
+        a.g.gpart += mb * (size_t)en.tiles * (size_t)a.g.n_params; a.g.lam_out += mb * Bz * nz;
+        sv.part += mb * en.part_stride; sv.base_dev += mb; sv.abort_flag += mb;
+        if (en.t1) step_state_set_t1(&sv.init, en.t1[mb]);
+    }
+    const int wid = wid_;                                  // this wave's tile
+    const int tiles = ENS ? en.tiles : (int)gridDim.x;     // (WGW == 1) tiles of the batch = parties of a meeting
     const NetDesc& nd = a.nd;
     const int n_in = nd.n_in, nh = nd.dims[1], D = n_in + NS;
     const int act1 = nd.acts[0], act2 = nd.acts[1];
@@ -439,7 +473,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
     float hstep = ns.h, abstol = ns.abstol, reltol = ns.reltol;
     int nsync = 0;
     const unsigned mbase = __builtin_amdgcn_readfirstlane(__hip_atomic_load(sv.base_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    const int G = WGW > 1 ? (int)gridDim.x * nwg : (int)gridDim.x;      // tiles
+    const int G = WGW > 1 ? (int)gridDim.x * nwg : tiles;               // tiles
     // the rich store's slot of (step, stage): [step][stage][wave][lane][RR]
     auto rich_slot = [&](int step, int stage) -> f32x4* {
         if (!RICH || !a.g.rich || step >= a.g.traj_cap) return nullptr;
@@ -516,7 +550,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
             ++nsync;
             return uni(bad) == 0.f;
         }
-        const bool ok = exchange(e, b, wid, (int)gridDim.x);
+        const bool ok = exchange(e, b, wid, tiles);
         ++nsync;
         return ok;
     };
@@ -1241,7 +1275,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
     }
 }
 
-typedef void (*wave_fn)(WaveArgs, Solve3Args, const WvTab);
+typedef void (*wave_fn)(WaveArgs, Solve3Args, const WvTab, const WaveEnsArgs);
 // one workgroup of up to four waves (B <= 64): the README / regression networks and the one-layer benchmark network, TrainMode
 // (VJP) and TestMode, plain solve and gradient
 wave_fn pick_wg(int ni, int nh, int mode, bool grad, bool id2, bool tanh2) {
@@ -1301,6 +1335,24 @@ wave_fn pick_grad(int ni, int nh, bool id2, bool test = false, bool jvp = false)
         case 3: return (wave_fn)k_solve_wave<1, 3, WV_VJP, true, true>;
         case 4: return (wave_fn)k_solve_wave<1, 4, WV_VJP, true, true>;
     }
+    return nullptr;
+}
+// the ENS forms of what pick_grad returns (no RICH form: its gradient is the recomputing form's bit for bit, and the ensemble
+// is there to fill the chip, not to save products)
+wave_fn pick_grad_ens(int ni, int nh, bool id2, bool test, bool jvp) {
+    if (ni != 1 || nh < 1 || nh > 4 || (id2 && nh != 1)) return nullptr;
+    const int mode = test ? WV_TEST : (jvp ? WV_JVP : WV_VJP);
+#define WV_ENS(NHV, ID2V) (mode == WV_VJP ? (wave_fn)k_solve_wave<1, NHV, WV_VJP, true, true, ID2V, 1, false, true> \
+                         : mode == WV_JVP ? (wave_fn)k_solve_wave<1, NHV, WV_JVP, true, true, ID2V, 1, false, true> \
+                                          : (wave_fn)k_solve_wave<1, NHV, WV_TEST, true, true, ID2V, 1, false, true>)
+    if (id2) return WV_ENS(1, true);
+    switch (nh) {
+        case 1: return WV_ENS(1, false);
+        case 2: return WV_ENS(2, false);
+        case 3: return WV_ENS(3, false);
+        case 4: return WV_ENS(4, false);
+    }
+#undef WV_ENS
     return nullptr;
 }
 template <int NI, int NH, bool TANH>
@@ -1378,10 +1430,36 @@ bool wave_grad_supported(const NetDesc& nd, int B, bool train) {
     return pick_grad((nd.n_in + 15) / 16, (nd.dims[1] + 15) / 16, is_id2(nd)) != nullptr && wave_grad_waves(B) <= 512;
 }
 
+// ---- the ensemble form (cnf_loss_grad_many): M x tiles workgroups, each member's tiles meeting among themselves ----
+// (the envelope below -- two layers, tanh then tanh or identity, one input tile, up to four hidden tiles, one with the identity --
+// is restated in continuousnf.jl_amd/ensemble.py `_refusal`, which has to refuse before a handle exists: change both together)
+static wave_fn ens_fn(const NetDesc& nd, bool train) {
+    if (nd.n_layers != 2 || nd.n_cond > 0 || nd.id2) return nullptr;      // (an APPENDED identity layer lives behind the handle's own parameters)
+    if (nd.acts[0] != 1 || !(nd.acts[1] == 1 || is_id2(nd))) return nullptr;
+    return pick_grad_ens((nd.n_in + 15) / 16, (nd.dims[1] + 15) / 16, is_id2(nd), !train, nd.jvp != 0);
+}
+int wave_ens_capacity(const NetDesc& nd, bool train, int B) {
+    static const bool off = [] { const char* e = getenv("CNF_PERSISTENT"); const char* w = getenv("CNF_WAVE"); return (e && e[0] == '0') || (w && w[0] == '0'); }();
+    wave_fn fn = ens_fn(nd, train);
+    if (off || !fn || B < 1 || !wave_grad_supported(nd, B, train)) return 0;
+    static std::mutex mu;
+    static std::map<const void*, int> cap;                 // workgroups (main wave + helper) the device holds at once
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cap.find((const void*)fn);
+    if (it == cap.end()) {
+        int dev = 0, n_cu = 0, per_cu = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)fn, 128, 0) != hipSuccess) { (void)hipGetLastError(); n_cu = per_cu = 0; }
+        it = cap.emplace((const void*)fn, n_cu * per_cu).first;
+    }
+    return it->second / wave_grad_waves(B);
+}
+
 cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_params, const float* cond, int cbs, StepState* st_out,
                              float* U0, const float* eps, int B, hipStream_t s, void* mirror, unsigned seq, const Solve3Args& sv_,
-                             const WaveGradArgs* grad) {
+                             const WaveGradArgs* grad, const WaveEnsLaunch* ens) {
     if (!wave_solve_supported(nd, train, B)) return CNF_ERR_UNSUPPORTED;
+    if (ens && (!grad || cond || mirror || ens->M < 1 || ens->M > wave_ens_capacity(nd, train, B))) return CNF_ERR_UNSUPPORTED;
     if (grad && nd.n_cond > 0 && !grad->ys) return CNF_ERR_BAD_ARG;
     if (grad && (!wave_grad_supported(nd, B, train) || !grad->traj || !grad->gpart || !grad->lam_out || !grad->hs_out || grad->traj_cap < 1))
         return CNF_ERR_UNSUPPORTED;
@@ -1402,6 +1480,7 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
     wave_fn wfn = ((grid <= 4 && !wg_off && !cond) || xwg) ? pick_wg(ni, nh, mode, grad != nullptr, is_id2(nd), nd.acts[0] == 1 && nd.acts[1] == 1) : nullptr;
     if (xwg && (!wfn || cond)) return CNF_ERR_UNSUPPORTED;
     const int waves = xwg ? 4 : grid;
+    if (ens) wfn = nullptr;                                // (one tile per workgroup and its helper, as every gradient)
     if (grad && grad->rich && mode == WV_VJP && ni == 1) {   // the forward pass files its intermediates: the RICH instantiations
         if (wave_fn r = pick_grad_rich(nh, is_id2(nd), wfn != nullptr)) { if (wfn) wfn = r; else fn = r; }
         else return CNF_ERR_BAD_ARG;                       // (wave_grad_rich_floats said it exists)
@@ -1417,7 +1496,14 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
     // (a bare solve reads u0 and writes u_out where the caller keeps them; an inference assembles u0 from sv.xs)
     if (!sv.xs && !sv.u0) return CNF_ERR_BAD_ARG;
     WvTab tab = kWvTab;
-    void* args[] = {&a, &sv, &tab};
+    WaveEnsArgs en{};
+    if (ens) {
+        if (grad->rich || sv.trace || sv.t_out || !sv.xs || !sv.logpx || !sv.regs || !sv.sums5 || sv.u_out) return CNF_ERR_BAD_ARG;
+        fn = ens_fn(nd, train);
+        en.tiles = grid; en.t1 = ens->t1; en.p_stride = ens->p_stride; en.traj_stride = ens->traj_stride; en.part_stride = ens->part_stride;
+        grid *= ens->M;
+    }
+    void* args[] = {&a, &sv, &tab, &en};
     // (a gradient: the tile's main wave and its helper)
     if (hipLaunchKernel((const void*)fn, dim3(grid), dim3(wfn ? 64 * waves : (grad ? 128 : 64)), args, 0, s) != hipSuccess) {
         (void)hipGetLastError();

@@ -363,6 +363,9 @@ cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int B, float* 
 /* ---- a learnable base distribution: cnf_base_logpdf_pullback / cnf_base_sample_pullback (declared in cnfhip_basegrad.h, part of this header) ---- */
 #include "cnfhip_basegrad.h"
 
+/* ---- ensembles: cnf_ensemble_capacity / cnf_loss_grad_many / cnf_ensemble_steps (declared in cnfhip_ensemble.h, part of this header) ---- */
+#include "cnfhip_ensemble.h"
+
 /* ---- device random numbers ------------------------------------------
  *
  * The library's own counter-based generator, the counterpart of the device RNG the reference draws eps and
