@@ -900,6 +900,71 @@ def grad_ys(icnf: ICNF, B, dev, stream, host=False):
     return gy.cpu().numpy() if host else gy
 
 
+def grad_x(icnf: ICNF, B, dev, stream, host=False):
+    """d / d xs of the last gradient call (the reference's call tests differentiate the loss w.r.t. the data too:
+    test/call_tests.jl, `diff2_loss`): the adjoint state at t0, left behind by the backward sweep (cnf_grad_x) -- ``nvars x B``,
+    where xs lives."""
+    import torch
+    l, h = _lib.lib(), icnf.handle()
+    gx = torch.empty(B * icnf.nvars, dtype=torch.float32, device=dev)
+    _lib.check(l.cnf_grad_x(h, gx.data_ptr(), B, stream), h)
+    gx = gx.view(B, icnf.nvars).t()
+    return gx.cpu().numpy() if host else gx
+
+
+def grad_steps(icnf: ICNF):
+    """``icnf.last_steps``: the signed step sizes the last gradient or recorded solve went through (cnf_grad_steps)."""
+    l, h = _lib.lib(), icnf.handle()
+    n = l.cnf_grad_steps(h, None, 0)
+    hs = np.empty(max(n, 1), dtype=np.float32)
+    l.cnf_grad_steps(h, hs.ctypes.data, n)
+    icnf.last_steps = hs[:n]
+
+
+def resolve_eps(icnf: ICNF, m, eps, xb: _Buf, B):
+    """The probes of a gradient or recording call in mode ``m``: none in TestMode, the caller's (one column per sample), or
+    drawn as ``inference`` draws them."""
+    if m != _lib.MODE_TRAIN:
+        return None
+    if eps is None:
+        return draw_eps(icnf, xb, B)
+    eb = _as_colmajor(eps, icnf.nvars + n_augment_input(icnf), "eps")
+    if eb.B != B:
+        raise ValueError("eps must have one column per sample")
+    return eb
+
+
+def to_device(icnf: ICNF, a, dev=None):
+    """A host array as a float32 tensor on ``dev`` (the model's device); a host ``_Buf`` as a device ``_Buf`` over the same
+    column-major storage.  None and what is on a device already pass through."""
+    import torch
+    if a is None or (isinstance(a, _Buf) and a.torch is not None):
+        return a
+    if isinstance(a, _Buf):
+        return _Buf(to_device(icnf, a.arr, dev), a.rows, a.B, torch)
+    raise_if_no_gpu()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32))).to(dev or torch.device("cuda", icnf.device))
+
+
+def device_and_stream(icnf: ICNF, buf: _Buf):
+    """Where the device side of a call on ``buf`` runs: the tensor's device (the model's for host arrays) and its current stream."""
+    import torch
+    dev = buf.arr.device if buf.torch is not None else torch.device("cuda", icnf.device)
+    return dev, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def grad_result(head, host, *optional):
+    """The result of a gradient call: ``head`` and then those of the optional results that were asked for -- ``(asked, value)``
+    in their one order: d / d xs (or z0), d / d ys, the base's pair -- as numpy arrays for a call on host arrays.  A lone
+    gradient is returned bare."""
+    def where(v):
+        if isinstance(v, tuple):
+            return tuple(where(a) for a in v)
+        return v.cpu().numpy() if host and _is_torch(v) else v
+    out = tuple(where(v) for v in head) + tuple(where(v) for asked, v in optional if asked)
+    return out[0] if len(out) == 1 else out
+
+
 def loss_and_grad(icnf: ICNF, mode, xs, *args, eps=None, with_x=False, with_ys=False, with_base=False):
     """``(loss, d loss / d ps)``: the pair ``MLJModelInterface.fit`` gets from Enzyme on
     ``loss(icnf, TrainMode(), xs, ps, st)`` (src/exts/mlj_ext/core_icnf.jl:59-73, src/icnf.jl:481-490),
@@ -909,70 +974,53 @@ def loss_and_grad(icnf: ICNF, mode, xs, *args, eps=None, with_x=False, with_ys=F
     d loss / d xs (``nvars x B``) and, for a conditional model, d loss / d ys (``n_cond x B``) to the result; with
     ``with_ys`` the gradient always takes the recorded solve.  ``with_base`` (a ``LearnableNormal`` base, device tensors)
     appends ``(d loss / d mean, d loss / d scale)`` last: the log-density of the final state pulled back with the loss's
-    cotangent ``-1/B`` (cnf_base_logpdf_pullback); ``ValueError`` with any other base."""
+    cotangent ``-1/B`` (cnf_base_logpdf_pullback); ``ValueError`` with any other base.
+
+    TestMode: ``loss(icnf, TestMode(), xs, ps, st)`` and its gradient through the exact-trace solve (cnf_loss_grad_test): what the
+    reference's call tests and benchmark suite differentiate besides the TrainMode loss (test/call_tests.jl ``diff_loss``,
+    benchmark/benchmarks.jl:60-99).  Small two-layer (or one-layer) tanh networks in the launch of the solve; every other Dense
+    chain through the recorded solve and the generic adjoint kernel (cnf_gradt.hip); ``NotImplementedError`` only where that
+    kernel's LDS budget is exceeded."""
     if with_base:
         learnable(icnf.basedist)
         if not _is_torch(xs):
             raise ValueError("with_base needs device tensors")
-    if _mode_id(mode) != _lib.MODE_TRAIN:
-        out = _loss_and_grad_test(icnf, mode, xs, *args, with_x=with_x, with_ys=with_ys)
-        return out + (_loss_base_grad(icnf, xs),) if with_base else out
+    m = _mode_id(mode)
     ys, ps, st = _split_cond_args(icnf, args)
     xb = _xs_colmajor(icnf, xs)
     B = xb.B
     icnf.set_params(ps)
     icnf.set_cond(ys, B)
     set_grad_ys(icnf, with_ys)
-    if eps is not None:
-        eb = _as_colmajor(eps, icnf.nvars + n_augment_input(icnf), "eps")
-        if eb.B != B:
-            raise ValueError("eps must have one column per sample")
-    else:
-        eb = draw_eps(icnf, xb, B)
+    eb = resolve_eps(icnf, m, eps, xb, B)
     opts = _solve_opts(icnf, steer_tspan(icnf, mode))
     stats = _lib.cnf_solve_stats()
     val = C.c_float()
     l, h = _lib.lib(), icnf.handle()
-    n_params = icnf.nn.n_params_internal
-    if xb.torch is not None:
-        t = xb.torch
-        grad = t.empty(n_params, dtype=t.float32, device=xb.arr.device)
-        _lib.check(l.cnf_loss_grad(h, xb.ptr, eb.ptr, B, C.byref(opts), C.byref(val), grad.data_ptr(),
-                                   C.byref(stats), _stream(xb)), h)
+    host = xb.torch is None                                # host arrays in, host gradient out
+    dev, stream = device_and_stream(icnf, xb)
+    # the two modes differ in the pair of entry points (TrainMode's take eps) ...
+    if m == _lib.MODE_TRAIN:
+        fn, lead = (l.cnf_loss_grad_host if host else l.cnf_loss_grad), (h, xb.ptr, eb.ptr, B)
     else:
-        grad = np.empty(n_params, dtype=np.float32)
-        _lib.check(l.cnf_loss_grad_host(h, xb.ptr, eb.ptr, B, C.byref(opts), C.byref(val), grad.ctypes.data,
-                                        C.byref(stats)), h)
+        fn, lead = (l.cnf_loss_grad_test_host if host else l.cnf_loss_grad_test), (h, xb.ptr, B)
+    if host:
+        grad = np.empty(icnf.nn.n_params_internal, dtype=np.float32)
+        rc = fn(*lead, C.byref(opts), C.byref(val), grad.ctypes.data, C.byref(stats))
+    else:
+        grad = xb.torch.empty(icnf.nn.n_params_internal, dtype=xb.torch.float32, device=dev)
+        rc = fn(*lead, C.byref(opts), C.byref(val), grad.data_ptr(), C.byref(stats), stream)
+    # ... and in that TestMode has networks without a gradient
+    if m != _lib.MODE_TRAIN and rc == _lib.ERR_UNSUPPORTED:
+        raise NotImplementedError("TestMode gradient: network too wide for the adjoint kernels: " + l.cnf_last_error(h).decode())
+    _lib.check(rc, h)
     icnf.last_stats = stats.as_dict()
-    n = l.cnf_grad_steps(h, None, 0)
-    hs = np.empty(max(n, 1), dtype=np.float32)
-    l.cnf_grad_steps(h, hs.ctypes.data, n)
-    icnf.last_steps = hs[:n]             # signed step sizes the gradient was taken through
+    grad_steps(icnf)                     # signed step sizes the gradient was taken through
     grad = icnf.nn.grad_to_external(grad)  # (PlanarLayer: back to the (u, w, b) order; identity for Dense chains)
-    if with_x:
-        # d loss / d xs (the reference's call tests differentiate the loss w.r.t. the data too: test/call_tests.jl,
-        # `diff2_loss`): the adjoint state at t0, left behind by the backward sweep (cnf_grad_x) -- nvars x B, where xs lives
-        if xb.torch is not None:
-            gx = xb.torch.empty(B * icnf.nvars, dtype=xb.torch.float32, device=xb.arr.device)
-            _lib.check(l.cnf_grad_x(h, gx.data_ptr(), B, _stream(xb)), h)
-            gx = gx.view(B, icnf.nvars).t()
-        else:
-            import torch
-            dev = torch.device("cuda", icnf.device)
-            gd = torch.empty(B * icnf.nvars, dtype=torch.float32, device=dev)
-            _lib.check(l.cnf_grad_x(h, gd.data_ptr(), B, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), h)
-            gx = gd.cpu().numpy().reshape(B, icnf.nvars).T
-    out = (float(val.value), grad) + ((gx,) if with_x else ())
-    if with_ys:
-        if xb.torch is not None:
-            out += (grad_ys(icnf, B, xb.arr.device, _stream(xb)),)
-        else:
-            import torch
-            dev = torch.device("cuda", icnf.device)
-            out += (grad_ys(icnf, B, dev, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), host=True),)
-    if with_base:
-        out += (_loss_base_grad(icnf, xs),)
-    return out
+    return grad_result((float(val.value), grad), host,
+                       (with_x, grad_x(icnf, B, dev, stream, host) if with_x else None),
+                       (with_ys, grad_ys(icnf, B, dev, stream, host) if with_ys else None),
+                       (with_base, _loss_base_grad(icnf, xs) if with_base else None))
 
 
 def _loss_base_grad(icnf: ICNF, xs):
@@ -1003,12 +1051,7 @@ def loss_and_grad_submit(icnf: ICNF, mode, xs, *args, eps=None):
     icnf.set_params_async(ps)
     icnf.set_cond(ys, B)
     set_grad_ys(icnf, False)            # (a submitted gradient carries no d / d ys: the switch would refuse it)
-    if m != _lib.MODE_TRAIN:
-        eb = None
-    elif eps is not None:
-        eb = _as_colmajor(eps, icnf.nvars + n_augment_input(icnf), "eps")
-    else:
-        eb = draw_eps(icnf, xb, B)
+    eb = resolve_eps(icnf, m, eps, xb, B)
     opts = _solve_opts(icnf, steer_tspan(icnf, mode))
     l, h = _lib.lib(), icnf.handle()
     out = torch.empty(icnf.nn.n_params_internal + 1, dtype=torch.float32, device=xb.arr.device)
@@ -1027,55 +1070,6 @@ def loss_and_grad_collect(icnf: ICNF):
     """Completes the oldest submitted gradient (cnf_loss_grad_collect); returns its statistics.  Raises ``RuntimeError`` if that
     launch gave up (it delivered zeros and a NaN loss): run the batch again with ``loss_and_grad``."""
     return inference_collect(icnf)
-
-
-def _loss_and_grad_test(icnf: ICNF, mode, xs, *args, with_x=False, with_ys=False):
-    """``loss(icnf, TestMode(), xs, ps, st)`` and its gradient through the exact-trace solve (cnf_loss_grad_test): what the
-    reference's call tests and benchmark suite differentiate besides the TrainMode loss (test/call_tests.jl ``diff_loss``,
-    benchmark/benchmarks.jl:60-99).  Small two-layer (or one-layer) tanh networks in the launch of the solve; every other Dense
-    chain through the recorded solve and the generic adjoint kernel (cnf_gradt.hip); ``NotImplementedError`` only where that
-    kernel's LDS budget is exceeded."""
-    import torch
-    ys, ps, st = _split_cond_args(icnf, args)
-    xb = _xs_colmajor(icnf, xs)
-    B = xb.B
-    icnf.set_params(ps)
-    icnf.set_cond(ys, B)
-    set_grad_ys(icnf, with_ys)
-    opts = _solve_opts(icnf, steer_tspan(icnf, mode))
-    stats = _lib.cnf_solve_stats()
-    val = C.c_float()
-    l, h = _lib.lib(), icnf.handle()
-    n_params = icnf.nn.n_params_internal
-    if xb.torch is not None:
-        dev, stream = xb.arr.device, _stream(xb)
-        grad = torch.empty(n_params, dtype=torch.float32, device=dev)
-        rc = l.cnf_loss_grad_test(h, xb.ptr, B, C.byref(opts), C.byref(val), grad.data_ptr(), C.byref(stats), stream)
-    else:                                                  # host arrays in, host gradient out
-        dev = torch.device("cuda", icnf.device)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        grad = np.empty(n_params, dtype=np.float32)
-        rc = l.cnf_loss_grad_test_host(h, xb.ptr, B, C.byref(opts), C.byref(val), grad.ctypes.data, C.byref(stats))
-    if rc == _lib.ERR_UNSUPPORTED:
-        raise NotImplementedError("TestMode gradient: network too wide for the adjoint kernels: " + l.cnf_last_error(h).decode())
-    _lib.check(rc, h)
-    icnf.last_stats = stats.as_dict()
-    n = l.cnf_grad_steps(h, None, 0)
-    hs = np.empty(max(n, 1), dtype=np.float32)
-    l.cnf_grad_steps(h, hs.ctypes.data, n)
-    icnf.last_steps = hs[:n]
-    gx = None
-    if with_x:
-        gx = torch.empty(B * icnf.nvars, dtype=torch.float32, device=dev)
-        _lib.check(l.cnf_grad_x(h, gx.data_ptr(), B, stream), h)
-        gx = gx.view(B, icnf.nvars).t()
-    if xb.torch is None and gx is not None:
-        gx = gx.cpu().numpy()
-    grad = icnf.nn.grad_to_external(grad)
-    out = (float(val.value), grad) + ((gx,) if with_x else ())
-    if with_ys:
-        out += (grad_ys(icnf, B, dev, stream, host=xb.torch is None),)
-    return out
 
 
 def loss_sums(icnf: ICNF, logpx, regs):

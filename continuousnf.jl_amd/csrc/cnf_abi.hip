@@ -8,6 +8,7 @@
 #include "cnf_trace.h"
 #include "cnf_mirror.h"
 #include "cnf_buf.h"
+#include "cnf_record.h"
 #include "cnf_wave.h"
 #include "cnf_bcast.h"
 #include "cnf_gradt.h"
@@ -142,18 +143,14 @@ struct cnf_ctx {
     DevBuf<float> wg_traj;        // k_solve_wave<GRAD>: z rows of u_n per accepted step, as the lanes hold them; + WV_GCAP step sizes
     float* g_grad = nullptr;      // n_params (host-pointer variant)
     std::vector<float> last_hs;   // signed step sizes of the last cnf_loss_grad solve
-    int grad_last_B = 0;          // batch of the last cnf_loss_grad call (g_lam holds its d loss / d u(t0))
-    // cnf_inference_record / cnf_inference_pullback: the record is the trajectory store, g_US[1], last_hs and these; any solve,
-    // parameter or conditioning upload or change of the base distribution on the handle ends it (rec_valid = false)
-    bool rec_valid = false;
-    int rec_mode = 0, rec_B = 0, rec_kernel = 0;
-    const float* rec_eps = nullptr;
-    int rec_kind = 0;             // whose record it is: REC_INFERENCE (cnf_inference_record) or REC_GENERATE (cnf_generate_record)
+    // What the last calls left in the trajectory store, g_US[1], last_hs, g_lam and d_gy for cnf_inference_pullback,
+    // cnf_generate_pullback, cnf_base_logpdf_pullback, cnf_grad_x and cnf_grad_ys -- and which events end which piece of it:
+    // cnf_record.h.  Every change of it below is one of that type's named transitions.
+    CnfRecord rec;
     DevBuf<float> d_gz0;          // cnf_generate_record: the handle's copy of the base draw z0 [B][n_in] (read again by the pullback)
     DevBuf<float> d_cw;           // [3][B] per-sample cotangents of the scalar rows, packed by k_vjp_cotangent
     // cnf_set_grad_ys / cnf_grad_ys: the gradient w.r.t. the conditioning inputs (cnf_condgrad.hip; k_adj_test's own in TestMode)
     bool grad_ys = false;         // the switch: gradient calls also accumulate d / d ys
-    int gy_last_B = 0;            // batch of the last gradient call that did (0: none, or the switch was off during it)
     DevBuf<float> d_gy;           // [B][dims[1]] row sums of abar_1, then [B][n_cond] the result
     DevBuf<float> d_ys;           // conditional models: copy of ys (n_cond x cond_B), kept for the weight gradient
     DevBuf<float> stage;          // device staging area of the *_host entry points, owned by the handle, grown on demand:
@@ -164,8 +161,6 @@ struct cnf_ctx {
     // cnf_base_logpdf_pullback / cnf_base_sample_pullback (cnf_basegrad.hip): tickets, result, partials and whitened rows; grown
     // on demand, so a handle that never asks for the base's gradient never allocates it
     DevBuf<float> d_bg;
-    int fs_B = 0, fs_mode = 0;    // cnf_loss_grad / cnf_loss_grad_test on the recorded route: g_US[1] holds the final state of a batch
-                                  //   of fs_B samples solved in fs_mode (0: none); ends where a record ends
     PinnedBuf<float> h_sums;      // pinned, 4 floats
     // cnf_loss_grad_many (k_solve_wave<.., ENS>): what one model's call has once, per member; sized for (M, B), grow-only
     DevBuf<float> ens_traj;       // [M][cap] trajectory rows
@@ -184,10 +179,6 @@ struct cnf_ctx {
 };
 
 static const int MAX_PARTIALS = 1024;
-// What a solve, an upload of parameters or conditioning, or a change of the base distribution ends: the record of
-// cnf_inference_record / cnf_generate_record and the final state a cnf_loss_grad* call left for cnf_base_logpdf_pullback.
-static inline void end_record(cnf_ctx* h) { h->rec_valid = false; h->fs_B = 0; }
-enum { REC_INFERENCE = 1, REC_GENERATE = 2 };
 
 #define HIPCHK(h, call)                                                                  \
     do {                                                                                 \
@@ -377,7 +368,7 @@ static cnf_status params_uploaded(cnf_handle h, hipStream_t s, ParamsWait wait) 
     if (wait == PARAMS_WAIT_STREAM) HIPCHK(h, hipStreamSynchronize(s));
     if (wait == PARAMS_WAIT_DEVICE) HIPCHK(h, hipDeviceSynchronize());
     h->have_params = true;
-    end_record(h);
+    h->rec.end();
     h->pt_valid = false;
     h->img_valid = false;
     h->bimg_valid = false;
@@ -496,7 +487,7 @@ extern "C" cnf_status cnf_set_basedist(cnf_handle h, int kind, const float* mean
     HIPCHK(h, hipDeviceSynchronize());
     h->d_bd.release();
     h->bd = BaseDist{};
-    end_record(h);
+    h->rec.end();
     if (kind == 0) return CNF_OK;
     RESERVE(h, h->d_bd, host.size());
     HIPCHK(h, hipMemcpy(h->d_bd, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -526,7 +517,7 @@ extern "C" cnf_status cnf_set_cond(cnf_handle h, const float* ys, int B, void* s
     HIPCHK(h, hipSetDevice(h->device));
     // (a submitted inference reads d_cond until it ends, and its fallback would read it again: none may be outstanding)
     { const cnf_status ss = settle_submitted(h); if (ss != CNF_OK) return ss; }
-    end_record(h);
+    h->rec.end();
     const int cbs = (h->nd.dims[1] + 15) & ~15;
     if (h->cond_B != B || h->cbs != cbs) {
         HIPCHK(h, hipDeviceSynchronize());
@@ -1001,7 +992,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
                              bool final_sync, PostHook* post) {
     cnf_status s = check_call(h, mode, B);
     if (s != CNF_OK) return s;
-    end_record(h);                     // (every solve may overwrite what a record consists of)
+    h->rec.end();                      // (every solve may overwrite what a record consists of)
     if (!u0 || !opts) return fail(h, CNF_ERR_BAD_ARG, "null pointer");      // u_out may be null: the state stays in U[cur]
     const int train = mode == CNF_MODE_TRAIN;
     if (train && !eps) return fail(h, CNF_ERR_BAD_ARG, "eps is required in TrainMode");
@@ -1750,7 +1741,7 @@ static cnf_status ensure_grad_capacity(cnf_handle h, int B) {
     // As in ensure_capacity: what is carved from the arena exists only while it does, and neither does what was computed into
     // it -- the gradient cnf_grad_x hands out, a recorded solve, the trajectory.  A failed reserve leaves all of it cleared.
     const size_t cap = arena_alloc == hipSuccess ? want : 0;
-    h->grad_last_B = 0; h->gy_last_B = 0; end_record(h); h->traj_cap = 0;
+    h->rec.clear(); h->traj_cap = 0;
     float* p = h->grad_arena;
     for (int i = 0; i < 5; ++i) { h->g_US[i] = p; p += D * cap; }
     for (int i = 0; i < 6; ++i) { h->g_W[i] = p; p += n_in * cap; }
@@ -1774,7 +1765,7 @@ static cnf_status wave_loss_grad(cnf_handle h, int mode, const float* xs, const 
                                  float* loss_out, float* grad, cnf_solve_stats* stats, void* stream, bool* done,
                                  float* loss_dev = nullptr /* submit: the loss goes here (device), nothing is waited for */) {
     *done = false;
-    h->gy_last_B = 0;                                      // (the in-launch gradient carries no d / d ys)
+    h->rec.backward_begins();                              // (the in-launch gradient carries no d / d ys)
     cnf_status s = CNF_OK;
     hipStream_t st = (hipStream_t)stream;
     const bool train = mode == CNF_MODE_TRAIN;
@@ -1812,7 +1803,7 @@ static cnf_status wave_loss_grad(cnf_handle h, int mode, const float* xs, const 
         if (rec.wg_submitted) {
             HIPCHK(h, launch_grad_finish(wg.gpart, grad, (int)h->n_params, waves, h->d_state, h->d_sums, h->lam[0], h->lam[1], h->lam[2],
                                          train ? 1 : 0, loss_dev, st));
-            h->grad_last_B = B;
+            h->rec.backward_done(B, false);
             *done = true;
             return CNF_OK;
         }
@@ -1822,13 +1813,56 @@ static cnf_status wave_loss_grad(cnf_handle h, int mode, const float* xs, const 
             HIPCHK(h, hipMemcpyAsync(sums, h->d_sums, 5 * sizeof(float), hipMemcpyDeviceToHost, st));
             HIPCHK(h, hipStreamSynchronize(st));
             h->last_hs = rec.hs;
-            h->grad_last_B = B;
+            h->rec.backward_done(B, false);
             sst.launches += 1;
             if ((s = cnf_loss_from_sums(h, mode, sums, loss_out)) != CNF_OK) return s;
             if (stats) *stats = sst;
             *done = true;
         }
     }
+    return CNF_OK;
+}
+
+// What the five gradient entry points begin with (cnf_loss_grad, cnf_loss_grad_test, cnf_inference_record, cnf_generate_record,
+// cnf_loss_grad_submit): the call's checks in their one order, then room for B samples.  ptrs_ok: none of the pointers THIS
+// entry point needs is null; width: the TrainMode pullback kernels must take the network; cw / gz0: the call packs per-sample
+// cotangents / keeps the base draw (d_cw, d_gz0; grown behind a wait for the stream).
+static cnf_status grad_prologue(cnf_handle h, int mode, int B, bool ptrs_ok, const char* empty_batch, bool width, hipStream_t st,
+                                bool cw = false, bool gz0 = false) {
+    cnf_status s = check_call(h, mode, B);
+    if (s != CNF_OK) return s;
+    if (!ptrs_ok) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    if (B < 1) return fail(h, CNF_ERR_BAD_SHAPE, empty_batch);
+    if (width && !grad_supported(h->nd, grad_layout(h->nd))) return fail(h, CNF_ERR_UNSUPPORTED, "network too wide for the gradient kernels");
+    if ((s = ensure_capacity(h, B)) != CNF_OK) return s;
+    if ((s = ensure_grad_capacity(h, B)) != CNF_OK) return s;
+    const size_t nw = cw ? (size_t)3 * B : 0, nz = gz0 ? (size_t)h->nd.n_in * B : 0;
+    if (nw > h->d_cw.capacity() || nz > h->d_gz0.capacity()) {
+        HIPCHK(h, hipStreamSynchronize(st));
+        RESERVE(h, h->d_cw, (nw + 1023) & ~(size_t)1023);
+        RESERVE(h, h->d_gz0, (nz + 1023) & ~(size_t)1023);
+    }
+    return CNF_OK;
+}
+static const char* const EMPTY_LOSS_BATCH = "the loss is a mean over the batch: B must be >= 1";
+
+// The RECORDED solve of the gradient entry points, from u0: stage states in the trajectory store, the final state in g_US[1],
+// the signed step sizes in last_hs.  A solve of more steps than the store has slots grows it and runs again.
+// TestMode records in solve_core's recording branch of the streamed driver (host-driven, one attempt at a time), the one place
+// where a TestMode solve records: networks whose TestMode otherwise runs inside the fused step kernels (two layers, closed-form
+// trace) take the generic right-hand side there.
+static cnf_status record_solve(cnf_handle h, int mode, const float* u0, const float* eps, int B, const cnf_solve_opts* opts, Recorder& rec,
+                               cnf_solve_stats& sst, void* stream, PostHook* ph = nullptr) {
+    cnf_status s = CNF_OK;
+    cnf_solve_opts ropts = *opts;
+    if (mode == CNF_MODE_TEST && mfma_supported(h->mfma, h->nd, false, B)) ropts.kernel = CNF_KERNEL_GENERIC;
+    for (;;) {
+        if (ph) ph->launched = false;
+        if ((s = solve_core(h, mode, u0, eps, h->g_US[1], B, &ropts, &sst, stream, &rec, true, ph)) != CNF_OK) return s;
+        if (!rec.overflow) break;
+        if ((s = traj_reserve(h, rec.n + 8)) != CNF_OK) return s;       // more steps than slots: grow, solve again
+    }
+    h->last_hs = rec.hs;
     return CNF_OK;
 }
 
@@ -1846,13 +1880,7 @@ static cnf_status train_forward(cnf_handle h, const float* xs, const float* eps,
     // straight to fsol where the kernel can write it there)
     float* fsol = h->g_US[1];
     PostHook ph{h->tmp_logpx, h->tmp_regs, h->d_sums, xs};
-    for (;;) {
-        ph.launched = false;
-        if ((s = solve_core(h, mode, h->U[0], eps, fsol, B, opts, &sst, stream, &rec, true, &ph)) != CNF_OK) return s;
-        if (!rec.overflow) break;
-        if ((s = traj_reserve(h, rec.n + 8)) != CNF_OK) return s;       // more steps than slots: grow, solve again
-    }
-    h->last_hs = rec.hs;
+    if ((s = record_solve(h, mode, h->U[0], eps, B, opts, rec, sst, stream, &ph)) != CNF_OK) return s;
     if (!ph.launched) {                                    // (the one-attempt-at-a-time drivers leave it to the caller)
         enqueue_post(h, 1, h->last_state, ph, B, false, st);
         HIPCHK(h, hipGetLastError());
@@ -1879,13 +1907,20 @@ static cnf_status ensure_gy(cnf_handle h, int B, hipStream_t st) {
 
 // The backward half of cnf_loss_grad (and cnf_inference_pullback in TrainMode): the discrete adjoint of the recorded steps `hs`
 // (sizes; their stage states lie in the trajectory store, the final state in g_US[1]) into grad, d / d u(t0) into g_lam.
-// cot == null: the cotangent of the loss -- three launch-wide scalars and k_final_cotangent / k_base_cotangent, the arithmetic
-// cnf_loss_grad has always had.  cot = [4][B] (rows logpx, E, n, A): k_vjp_cotangent forms the terminal cotangent and packs the
-// per-sample weights of the scalar rows into d_cw, which every pullback kernel then reads in place of the scalars.
-// gen != null (cnf_generate_pullback; cot is null then): the same per-sample pullback seeded by k_generate_cotangent instead.
-struct GenCot { const float* cot_z; const float* cot_logq; };
-static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kernel, const std::vector<float>& rec_hs, const float* cot,
-                                 float* grad, hipStream_t st, const GenCot* gen = nullptr) {
+// The cotangent it starts from is one of three (Cotangent).  LOSS: of the loss -- three launch-wide scalars and
+// k_final_cotangent / k_base_cotangent, the arithmetic cnf_loss_grad has always had.  ROWS = [4][B] (rows logpx, E, n, A):
+// k_vjp_cotangent forms the terminal cotangent and packs the per-sample weights of the scalar rows into d_cw, which every
+// pullback kernel then reads in place of the scalars.  SAMPLE (cnf_generate_pullback): the same per-sample pullback seeded by
+// k_generate_cotangent instead.
+struct Cotangent {
+    enum Kind { LOSS, ROWS, SAMPLE } kind;
+    const float* rows;             // ROWS: [4][B]
+    const float *z, *logq;         // SAMPLE: [B][n_in], [B]; one of them may be null
+    bool per_sample() const { return kind != LOSS; }
+};
+static const Cotangent COT_LOSS{Cotangent::LOSS, nullptr, nullptr, nullptr};
+static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kernel, const std::vector<float>& rec_hs, const Cotangent& cot,
+                                 float* grad, hipStream_t st) {
     cnf_status s = CNF_OK;
     const NetDesc& nd = h->nd;
     const int n_in = nd.n_in, D = n_in + 3;
@@ -1895,9 +1930,9 @@ static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kern
     // the pullback kernel follows the kernel choice of the solve: GENERIC -> VALU, otherwise MFMA when it fits
     const bool adj_mfma = kernel != CNF_KERNEL_GENERIC && adj_mfma_supported(nd, am);
     const int rec_n = (int)rec_hs.size();
-    const float* cw = (cot || gen) ? h->d_cw : nullptr;
+    const float* cw = cot.per_sample() ? h->d_cw : nullptr;
     // d / d ys: the layer-1 segment of the AB rows of every run, summed per sample beside the run's contraction (gy_runs counts them)
-    h->gy_last_B = 0;
+    h->rec.backward_begins();
     const bool want_gy = h->grad_ys;
     int gy_runs = 0;
     if (want_gy && (s = ensure_gy(h, B, st)) != CNF_OK) return s;
@@ -1911,10 +1946,13 @@ static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kern
     int ksplit = 1, filed = 0;
     HIPCHK(h, hipMemsetAsync(h->g_part, 0, (size_t)GRAD_MAX_KSPLIT * h->n_params * sizeof(float), st));
     const float* fsol = h->g_US[1];
-    if (gen) { launch_generate_cotangent(n_in, gen->cot_z, gen->cot_logq, h->g_lam, h->d_cw, B, st); HIPCHK(h, hipGetLastError()); }
-    else if (cot) { launch_vjp_cotangent(nd, D, h->bd, 1, fsol, cot, h->g_lam, h->d_cw, B, st); HIPCHK(h, hipGetLastError()); }
-    else if (h->bd.kind) { launch_base_cotangent(nd, D, h->bd, h->lam[2], fsol, h->g_lam, B, st); HIPCHK(h, hipGetLastError()); }
-    else HIPCHK(h, launch_final_cotangent(nd, h->lam[2], fsol, h->g_lam, B, st));
+    switch (cot.kind) {
+        case Cotangent::SAMPLE: launch_generate_cotangent(n_in, cot.z, cot.logq, h->g_lam, h->d_cw, B, st); HIPCHK(h, hipGetLastError()); break;
+        case Cotangent::ROWS: launch_vjp_cotangent(nd, D, h->bd, 1, fsol, cot.rows, h->g_lam, h->d_cw, B, st); HIPCHK(h, hipGetLastError()); break;
+        case Cotangent::LOSS:
+            if (h->bd.kind) { launch_base_cotangent(nd, D, h->bd, h->lam[2], fsol, h->g_lam, B, st); HIPCHK(h, hipGetLastError()); }
+            else HIPCHK(h, launch_final_cotangent(nd, h->lam[2], fsol, h->g_lam, B, st));
+    }
     const float invB = 1.0f / (float)B;
     // constant scalar rows; with per-sample weights the kernels multiply cw[r][b] in where these scalars stand, so they are 1
     const float lam_l = cw ? 1.0f : invB, lam_E = cw ? 1.0f : h->lam[0] * invB, lam_n = cw ? 1.0f : h->lam[1] * invB;
@@ -2037,11 +2075,11 @@ static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kern
     }
     }
     HIPCHK(h, launch_grad_reduce(h->g_part, grad, (int)h->n_params, ksplit, st));
-    h->grad_last_B = B;                                    // (g_lam now holds d loss / d u(t0): cnf_grad_x)
+    h->rec.backward_done(B, false);                        // (g_lam now holds d loss / d u(t0): cnf_grad_x)
     if (want_gy) {                                         // gy = W_1y' S1, once per pullback  (no run at all: no step, gy = 0)
         if (!gy_runs) HIPCHK(h, hipMemsetAsync(h->d_gy, 0, (size_t)B * nd.dims[1] * sizeof(float), st));
         HIPCHK(h, launch_cond_project(nd, h->d_params, h->d_gy, gy_result(h, B), B, st));
-        h->gy_last_B = B;                                  // (cnf_grad_ys)
+        h->rec.backward_done(B, true);                     // (cnf_grad_ys)
     }
     return CNF_OK;
 }
@@ -2061,15 +2099,9 @@ extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* 
                                     const cnf_solve_opts* opts, float* loss_out, float* grad,
                                     cnf_solve_stats* stats, void* stream) {
     const int mode = CNF_MODE_TRAIN;
-    cnf_status s = check_call(h, mode, B);
-    if (s != CNF_OK) return s;
-    if (!xs || !eps || !opts || !loss_out || !grad) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
-    if (B < 1) return fail(h, CNF_ERR_BAD_SHAPE, "the loss is a mean over the batch: B must be >= 1");
-    const GradLayout gl = grad_layout(h->nd);
-    if (!grad_supported(h->nd, gl)) return fail(h, CNF_ERR_UNSUPPORTED, "network too wide for the gradient kernels");
-    if ((s = ensure_capacity(h, B)) != CNF_OK) return s;
-    if ((s = ensure_grad_capacity(h, B)) != CNF_OK) return s;
     hipStream_t st = (hipStream_t)stream;
+    cnf_status s = grad_prologue(h, mode, B, xs && eps && opts && loss_out && grad, EMPTY_LOSS_BATCH, true, st);
+    if (s != CNF_OK) return s;
     if ((s = ensure_pullback_params(h, st)) != CNF_OK) return s;
 
     if (!h->bd.kind && !h->grad_ys) {   // small batches of a small two-layer tanh network: everything in one launch (wave_loss_grad above)
@@ -2084,9 +2116,9 @@ extern "C" cnf_status cnf_loss_grad(cnf_handle h, const float* xs, const float* 
     float* sums = loss_sums_host(h);
     HIPCHK(h, hipMemcpyAsync(sums, h->d_sums, 5 * sizeof(float), hipMemcpyDeviceToHost, st));
 
-    if ((s = train_backward(h, eps, B, opts->kernel, rec.hs, nullptr, grad, st)) != CNF_OK) return s;
+    if ((s = train_backward(h, eps, B, opts->kernel, rec.hs, COT_LOSS, grad, st)) != CNF_OK) return s;
     HIPCHK(h, hipStreamSynchronize(st));
-    h->fs_B = B; h->fs_mode = mode;                        // (cnf_base_logpdf_pullback: the final state stays in g_US[1])
+    h->rec.begin(REC_LOSS, mode, B);                       // (cnf_base_logpdf_pullback: the final state stays in g_US[1])
     if ((s = cnf_loss_from_sums(h, mode, sums, loss_out)) != CNF_OK) return s;
     if (stats) *stats = sst;
     return CNF_OK;
@@ -2103,18 +2135,9 @@ static cnf_status test_forward(cnf_handle h, const float* xs, int B, const cnf_s
     const int n_in = nd.n_in, D = n_in + 1;
     float* u0 = h->g_US[0];
     launch_build_u0(xs, u0, nd.nvars, D, B, st);
-    // the recorded forward pass files u_n after every accepted step (host-driven, one attempt at a time: solve_core's recording
-    // branch of the streamed driver).  Networks whose TestMode runs inside the fused step kernels (two layers, closed-form trace)
-    // take the generic right-hand side there: that branch is the one place where a TestMode solve records.
-    cnf_solve_opts ropts = *opts;
-    if (mfma_supported(h->mfma, nd, false, B)) ropts.kernel = CNF_KERNEL_GENERIC;
+    // (the recorded forward pass files u_n after every accepted step: record_solve)
     float* fsol = h->g_US[1];
-    for (;;) {
-        if ((s = solve_core(h, mode, u0, nullptr, fsol, B, &ropts, &sst, stream, &rec)) != CNF_OK) return s;
-        if (!rec.overflow) break;
-        if ((s = traj_reserve(h, rec.n + 8)) != CNF_OK) return s;
-    }
-    h->last_hs = rec.hs;
+    if ((s = record_solve(h, mode, u0, nullptr, B, opts, rec, sst, stream)) != CNF_OK) return s;
     launch_post(nd, 0, fsol, h->tmp_logpx, h->tmp_regs, B, st);
     if (h->bd.kind) {          // a non-default base distribution: its log-density, and its d loss / d z(t1) for k_adj_test
         launch_base_post(n_in, D, h->bd, nullptr, fsol, nullptr, h->tmp_logpx, h->tmp_regs, B, nullptr, nullptr, nullptr, st);
@@ -2124,18 +2147,20 @@ static cnf_status test_forward(cnf_handle h, const float* xs, int B, const cnf_s
     return CNF_OK;
 }
 
-// The backward half: k_adj_test (cnf_gradt.hip) over all recorded steps in one launch, then the sum of its partials.  cot == null:
-// the cotangent of the loss (1 / B per sample); cot = [4][B]: k_vjp_cotangent leaves d / d z(t1) in g_W[0] and w_l = -cot_l in d_cw
-// (rows E, n, A do not exist in TestMode: their cotangents are not read); gen != null: k_generate_cotangent leaves them instead.
-static cnf_status test_backward(cnf_handle h, int B, const std::vector<float>& rec_hs, const float* cot, float* grad, hipStream_t st,
-                                const GenCot* gen = nullptr) {
+// The backward half: k_adj_test (cnf_gradt.hip) over all recorded steps in one launch, then the sum of its partials.  LOSS: the
+// cotangent of the loss (1 / B per sample); ROWS: k_vjp_cotangent leaves d / d z(t1) in g_W[0] and w_l = -cot_l in d_cw
+// (rows E, n, A do not exist in TestMode: their cotangents are not read); SAMPLE: k_generate_cotangent leaves them instead.
+static cnf_status test_backward(cnf_handle h, int B, const std::vector<float>& rec_hs, const Cotangent& cot, float* grad, hipStream_t st) {
     cnf_status s = CNF_OK;
     const NetDesc& nd = h->nd;
     const int rec_n = (int)rec_hs.size();
-    h->gy_last_B = 0;
+    h->rec.backward_begins();
     if (h->grad_ys && (s = ensure_gy(h, B, st)) != CNF_OK) return s;
-    if (gen) { launch_generate_cotangent(nd.n_in, gen->cot_z, gen->cot_logq, h->g_W[0], h->d_cw, B, st); HIPCHK(h, hipGetLastError()); }
-    else if (cot) { launch_vjp_cotangent(nd, nd.n_in + 1, h->bd, 0, h->g_US[1], cot, h->g_W[0], h->d_cw, B, st); HIPCHK(h, hipGetLastError()); }
+    switch (cot.kind) {
+        case Cotangent::SAMPLE: launch_generate_cotangent(nd.n_in, cot.z, cot.logq, h->g_W[0], h->d_cw, B, st); HIPCHK(h, hipGetLastError()); break;
+        case Cotangent::ROWS: launch_vjp_cotangent(nd, nd.n_in + 1, h->bd, 0, h->g_US[1], cot.rows, h->g_W[0], h->d_cw, B, st); HIPCHK(h, hipGetLastError()); break;
+        case Cotangent::LOSS: break;       // (test_forward has left the base's d loss / d z(t1) in g_W[0], if there is one)
+    }
     // the step sizes to the device (behind the steps in the trajectory store's step-size array), scratch and partials of the kernel
     if ((s = traj_reserve(h, rec_n + 1)) != CNF_OK) return s;
     if (rec_n > 0) HIPCHK(h, hipMemcpyAsync(h->traj_hs, rec_hs.data(), (size_t)rec_n * sizeof(float), hipMemcpyHostToDevice, st));
@@ -2150,15 +2175,14 @@ static cnf_status test_backward(cnf_handle h, int B, const std::vector<float>& r
     AdjTestArgs ta{};
     ta.P = h->d_params; ta.traj = first; ta.slot_stride = traj_slot_floats(h); ta.hs = h->traj_hs; ta.nsteps = rec_n;
     ta.ys = nd.n_cond > 0 ? h->d_ys : nullptr; ta.lam_l = 1.0f / (float)B; ta.lam_out = h->g_lam;
-    ta.lam_init = (cot || gen || h->bd.kind) ? h->g_W[0] : nullptr;
-    ta.w_l = (cot || gen) ? h->d_cw : nullptr;
+    ta.lam_init = (cot.per_sample() || h->bd.kind) ? h->g_W[0] : nullptr;
+    ta.w_l = cot.per_sample() ? h->d_cw : nullptr;
     ta.gy = h->grad_ys ? gy_result(h, B) : nullptr;
     ta.gpart = h->d_gt; ta.scratch = h->d_gt + (size_t)G * h->n_params; ta.scratch_per_wg = adj_test_scratch_floats(nd);
     ta.B = B; ta.n_params = (int)h->n_params;
     if (launch_adj_test(nd, ta, st) != hipSuccess) { (void)hipGetLastError(); return fail(h, CNF_ERR_UNSUPPORTED, "network too wide for the TestMode adjoint kernel"); }
     HIPCHK(h, launch_grad_reduce(h->d_gt, grad, (int)h->n_params, G, st));
-    h->grad_last_B = B;                                    // (g_lam holds d loss / d z(t0): cnf_grad_x)
-    if (h->grad_ys) h->gy_last_B = B;                      // (k_adj_test left d / d ys behind: cnf_grad_ys)
+    h->rec.backward_done(B, h->grad_ys);                   // (g_lam holds d loss / d z(t0): cnf_grad_x; k_adj_test left d / d ys: cnf_grad_ys)
     return CNF_OK;
 }
 
@@ -2170,44 +2194,55 @@ static cnf_status test_backward(cnf_handle h, int B, const std::vector<float>& r
 extern "C" cnf_status cnf_loss_grad_test(cnf_handle h, const float* xs, int B, const cnf_solve_opts* opts, float* loss_out,
                                          float* grad, cnf_solve_stats* stats, void* stream) {
     const int mode = CNF_MODE_TEST;
-    cnf_status s = check_call(h, mode, B);
+    hipStream_t st = (hipStream_t)stream;
+    cnf_status s = grad_prologue(h, mode, B, xs && opts && loss_out && grad, EMPTY_LOSS_BATCH, false, st);
     if (s != CNF_OK) return s;
-    if (!xs || !opts || !loss_out || !grad) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
-    if (B < 1) return fail(h, CNF_ERR_BAD_SHAPE, "the loss is a mean over the batch: B must be >= 1");
-    if ((s = ensure_capacity(h, B)) != CNF_OK) return s;
-    if ((s = ensure_grad_capacity(h, B)) != CNF_OK) return s;
     bool done = false;
     if (!h->bd.kind && !h->grad_ys && (s = wave_loss_grad(h, mode, xs, nullptr, B, opts, loss_out, grad, stats, stream, &done)) != CNF_OK) return s;
     if (done) return CNF_OK;
     // ---- every other network: the recorded exact-trace solve, then k_adj_test (cnf_gradt.hip) over all of its steps in one launch ----
-    hipStream_t st = (hipStream_t)stream;
     Recorder rec;
     cnf_solve_stats sst{};
     if ((s = test_forward(h, xs, B, opts, rec, sst, stream)) != CNF_OK) return s;
     float* sums = loss_sums_host(h);
     HIPCHK(h, hipMemcpyAsync(sums, h->d_sums, 5 * sizeof(float), hipMemcpyDeviceToHost, st));
-    if ((s = test_backward(h, B, rec.hs, nullptr, grad, st)) != CNF_OK) return s;
+    if ((s = test_backward(h, B, rec.hs, COT_LOSS, grad, st)) != CNF_OK) return s;
     HIPCHK(h, hipStreamSynchronize(st));
-    h->fs_B = B; h->fs_mode = mode;                        // (cnf_base_logpdf_pullback: the final state stays in g_US[1])
+    h->rec.begin(REC_LOSS, mode, B);                       // (cnf_base_logpdf_pullback: the final state stays in g_US[1])
     if ((s = cnf_loss_from_sums(h, mode, sums, loss_out)) != CNF_OK) return s;
     if (stats) { *stats = sst; stats->launches += 2; }
     return CNF_OK;
 }
 
-extern "C" cnf_status cnf_loss_grad_test_host(cnf_handle h, const float* xs, int B, const cnf_solve_opts* opts, float* loss_out,
-                                              float* grad, cnf_solve_stats* stats) {
-    cnf_status s = check_call(h, CNF_MODE_TEST, B);
+// The host-array forms of the two: xs (and in TrainMode eps) through the handle's staging area, the gradient through g_grad.
+static cnf_status loss_grad_staged(cnf_handle h, int mode, const float* xs, const float* eps, int B, const cnf_solve_opts* opts,
+                                   float* loss_out, float* grad, cnf_solve_stats* stats) {
+    const bool train = mode == CNF_MODE_TRAIN;
+    cnf_status s = check_call(h, mode, B);
     if (s != CNF_OK) return s;
-    if (!xs || !grad) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
-    if (B < 1) return fail(h, CNF_ERR_BAD_SHAPE, "the loss is a mean over the batch: B must be >= 1");
+    if (!xs || !grad || (train && !eps)) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    if (B < 1) return fail(h, CNF_ERR_BAD_SHAPE, EMPTY_LOSS_BATCH);
     HIPCHK(h, hipSetDevice(h->device));
     if ((s = ensure_grad_capacity(h, B)) != CNF_OK) return s;
-    const size_t nx = (size_t)h->nd.nvars * B;
-    if ((s = ensure_stage(h, nx)) != CNF_OK) return s;
-    HIPCHK(h, hipMemcpy(h->stage, xs, nx * sizeof(float), hipMemcpyHostToDevice));
-    if ((s = cnf_loss_grad_test(h, h->stage, B, opts, loss_out, h->g_grad, stats, nullptr)) != CNF_OK) return s;
+    const size_t nx = (size_t)h->nd.nvars * B, ne = train ? (size_t)h->nd.n_in * B : 0;
+    if ((s = ensure_stage(h, nx + ne)) != CNF_OK) return s;
+    float* x_d = h->stage;
+    float* e_d = x_d + nx;
+    HIPCHK(h, hipMemcpy(x_d, xs, nx * sizeof(float), hipMemcpyHostToDevice));
+    if (train) HIPCHK(h, hipMemcpy(e_d, eps, ne * sizeof(float), hipMemcpyHostToDevice));
+    s = train ? cnf_loss_grad(h, x_d, e_d, B, opts, loss_out, h->g_grad, stats, nullptr)
+              : cnf_loss_grad_test(h, x_d, B, opts, loss_out, h->g_grad, stats, nullptr);
+    if (s != CNF_OK) return s;
     HIPCHK(h, hipMemcpy(grad, h->g_grad, h->n_params * sizeof(float), hipMemcpyDeviceToHost));
     return CNF_OK;
+}
+extern "C" cnf_status cnf_loss_grad_host(cnf_handle h, const float* xs, const float* eps, int B, const cnf_solve_opts* opts,
+                                         float* loss_out, float* grad, cnf_solve_stats* stats) {
+    return loss_grad_staged(h, CNF_MODE_TRAIN, xs, eps, B, opts, loss_out, grad, stats);
+}
+extern "C" cnf_status cnf_loss_grad_test_host(cnf_handle h, const float* xs, int B, const cnf_solve_opts* opts, float* loss_out,
+                                              float* grad, cnf_solve_stats* stats) {
+    return loss_grad_staged(h, CNF_MODE_TEST, xs, nullptr, B, opts, loss_out, grad, stats);
 }
 
 // ---- differentiable inference: the two halves of cnf_loss_grad / cnf_loss_grad_test as entry points of their own -----------------
@@ -2222,22 +2257,10 @@ extern "C" cnf_status cnf_loss_grad_test_host(cnf_handle h, const float* xs, int
 // lambda3 / A, and rows 1-3 in TestMode.  A caller who wants d E builds the model with lambda1 != 0.
 extern "C" cnf_status cnf_inference_record(cnf_handle h, int mode, const float* xs, const float* eps, int B, const cnf_solve_opts* opts,
                                            float* logpx, float* regs, cnf_solve_stats* stats, void* stream) {
-    cnf_status s = check_call(h, mode, B);
-    if (s != CNF_OK) return s;
     const bool train = mode == CNF_MODE_TRAIN;
-    if (!xs || !opts || !logpx || !regs || (train && !eps)) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
-    if (B < 1) return fail(h, CNF_ERR_BAD_SHAPE, "a recorded inference needs B >= 1");
-    if (train) {
-        const GradLayout gl = grad_layout(h->nd);
-        if (!grad_supported(h->nd, gl)) return fail(h, CNF_ERR_UNSUPPORTED, "network too wide for the gradient kernels");
-    }
-    if ((s = ensure_capacity(h, B)) != CNF_OK) return s;
-    if ((s = ensure_grad_capacity(h, B)) != CNF_OK) return s;
     hipStream_t st = (hipStream_t)stream;
-    if ((size_t)3 * B > h->d_cw.capacity()) {
-        HIPCHK(h, hipStreamSynchronize(st));
-        RESERVE(h, h->d_cw, ((size_t)3 * B + 1023) & ~(size_t)1023);
-    }
+    cnf_status s = grad_prologue(h, mode, B, xs && opts && logpx && regs && (!train || eps), "a recorded inference needs B >= 1", train, st, true);
+    if (s != CNF_OK) return s;
     Recorder rec;
     cnf_solve_stats sst{};
     if (train) s = train_forward(h, xs, eps, B, opts, rec, sst, stream);
@@ -2246,28 +2269,37 @@ extern "C" cnf_status cnf_inference_record(cnf_handle h, int mode, const float* 
     HIPCHK(h, hipMemcpyAsync(logpx, h->tmp_logpx, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, st));
     HIPCHK(h, hipMemcpyAsync(regs, h->tmp_regs, (size_t)3 * B * sizeof(float), hipMemcpyDeviceToDevice, st));
     HIPCHK(h, hipStreamSynchronize(st));
-    h->rec_valid = true; h->rec_mode = mode; h->rec_B = B; h->rec_kernel = opts->kernel; h->rec_eps = train ? eps : nullptr;
-    h->rec_kind = REC_INFERENCE;
+    h->rec.begin(REC_INFERENCE, mode, B, opts->kernel, train ? eps : nullptr);
     if (stats) *stats = sst;
     return CNF_OK;
+}
+
+// What the two pullbacks share: the record of `kind` at this batch size, or the entry point's refusal (which changes nothing);
+// then the backward half of the record's mode for the cotangent given, enqueued on `st`.  A pullback that fails half way has
+// overwritten part of the record: it is gone.
+static cnf_status record_pullback(cnf_handle h, CnfRecKind kind, const Cotangent& cot, int B, float* grad, hipStream_t st, const char* refusal) {
+    if (!h->rec.pullable(kind, B) || (size_t)h->last_hs.size() == 0 || !h->d_cw || (kind == REC_GENERATE && !h->d_gz0))
+        return fail(h, CNF_ERR_BAD_ARG, refusal);
+    HIPCHK(h, hipSetDevice(h->device));
+    cnf_status s;
+    const std::vector<float> hs = h->last_hs;
+    if (h->rec.mode() == CNF_MODE_TRAIN) {
+        if ((s = ensure_pullback_params(h, st)) != CNF_OK) return s;
+        s = train_backward(h, h->rec.eps(), B, h->rec.kernel(), hs, cot, grad, st);
+    } else {
+        s = test_backward(h, B, hs, cot, grad, st);
+    }
+    if (s != CNF_OK) h->rec.pullback_failed();
+    return s;
 }
 
 extern "C" cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int B, float* grad, void* stream) {
     if (!h) return CNF_ERR_BAD_ARG;
     if (!cot || !grad) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
-    if (!h->rec_valid || h->rec_kind != REC_INFERENCE || B != h->rec_B || (size_t)h->last_hs.size() == 0 || !h->d_cw)
-        return fail(h, CNF_ERR_BAD_ARG, "no recorded inference of a batch of this size: call cnf_inference_record first");
-    HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
-    cnf_status s;
-    const std::vector<float> hs = h->last_hs;
-    if (h->rec_mode == CNF_MODE_TRAIN) {
-        if ((s = ensure_pullback_params(h, st)) != CNF_OK) return s;
-        s = train_backward(h, h->rec_eps, B, h->rec_kernel, hs, cot, grad, st);
-    } else {
-        s = test_backward(h, B, hs, cot, grad, st);
-    }
-    if (s != CNF_OK) { h->rec_valid = false; return s; }
+    const cnf_status s = record_pullback(h, REC_INFERENCE, Cotangent{Cotangent::ROWS, cot, nullptr, nullptr}, B, grad, st,
+                                         "no recorded inference of a batch of this size: call cnf_inference_record first");
+    if (s != CNF_OK) return s;
     HIPCHK(h, hipStreamSynchronize(st));
     return CNF_OK;
 }
@@ -2282,26 +2314,13 @@ extern "C" cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int
 // d / d z0 is what they leave in g_lam plus cot_logq d logpdf(basedist, z0) / d z0 (k_generate_z0_grad).
 extern "C" cnf_status cnf_generate_record(cnf_handle h, int mode, const float* z0, const float* eps, int B, const cnf_solve_opts* opts,
                                           float* z_out, float* logq, cnf_solve_stats* stats, void* stream) {
-    cnf_status s = check_call(h, mode, B);
-    if (s != CNF_OK) return s;
     const bool train = mode == CNF_MODE_TRAIN;
-    if (!z0 || !opts || !z_out || !logq || (train && !eps)) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
-    if (B < 1) return fail(h, CNF_ERR_BAD_SHAPE, "a recorded sampling solve needs B >= 1");
-    if (train) {
-        const GradLayout gl = grad_layout(h->nd);
-        if (!grad_supported(h->nd, gl)) return fail(h, CNF_ERR_UNSUPPORTED, "network too wide for the gradient kernels");
-    }
-    if ((s = ensure_capacity(h, B)) != CNF_OK) return s;
-    if ((s = ensure_grad_capacity(h, B)) != CNF_OK) return s;
     hipStream_t st = (hipStream_t)stream;
-    const NetDesc& nd = h->nd;
-    const int n_in = nd.n_in, D = rows_of(h, mode);
+    cnf_status s = grad_prologue(h, mode, B, z0 && opts && z_out && logq && (!train || eps), "a recorded sampling solve needs B >= 1", train, st,
+                                 true, true);
+    if (s != CNF_OK) return s;
+    const int n_in = h->nd.n_in, D = rows_of(h, mode);
     const size_t nz = (size_t)n_in * B;
-    if ((size_t)3 * B > h->d_cw.capacity() || nz > h->d_gz0.capacity()) {
-        HIPCHK(h, hipStreamSynchronize(st));
-        RESERVE(h, h->d_cw, ((size_t)3 * B + 1023) & ~(size_t)1023);
-        RESERVE(h, h->d_gz0, (nz + 1023) & ~(size_t)1023);
-    }
     // u0 = [z0; 0] in g_US[0] (not in the integrator's own U[0]: a one-launch solve that gives up is run again from it), and the
     // handle's copy of z0 for the pullback
     float* u0 = h->g_US[0];
@@ -2309,24 +2328,13 @@ extern "C" cnf_status cnf_generate_record(cnf_handle h, int mode, const float* z
     HIPCHK(h, hipMemcpy2DAsync(u0, (size_t)D * sizeof(float), z0, (size_t)n_in * sizeof(float), (size_t)n_in * sizeof(float), (size_t)B,
                                hipMemcpyDeviceToDevice, st));
     HIPCHK(h, hipMemcpyAsync(h->d_gz0, z0, nz * sizeof(float), hipMemcpyDeviceToDevice, st));
-    // (TestMode records on the generic right-hand side where it otherwise runs inside the fused step kernels: test_forward)
-    cnf_solve_opts ropts = *opts;
-    if (!train && mfma_supported(h->mfma, nd, false, B)) ropts.kernel = CNF_KERNEL_GENERIC;
-    float* fsol = h->g_US[1];
     Recorder rec;
     cnf_solve_stats sst{};
-    for (;;) {
-        if ((s = solve_core(h, mode, u0, train ? eps : nullptr, fsol, B, &ropts, &sst, stream, &rec, true, nullptr)) != CNF_OK) return s;
-        if (!rec.overflow) break;
-        if ((s = traj_reserve(h, rec.n + 8)) != CNF_OK) return s;       // more steps than slots: grow, solve again
-    }
-    h->last_hs = rec.hs;
-    launch_generate_post(n_in, D, h->bd, fsol, h->d_gz0, z_out, logq, B, st);
+    if ((s = record_solve(h, mode, u0, train ? eps : nullptr, B, opts, rec, sst, stream)) != CNF_OK) return s;
+    launch_generate_post(n_in, D, h->bd, h->g_US[1], h->d_gz0, z_out, logq, B, st);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(st));
-    h->grad_last_B = 0; h->gy_last_B = 0;
-    h->rec_valid = true; h->rec_mode = mode; h->rec_B = B; h->rec_kernel = opts->kernel; h->rec_eps = train ? eps : nullptr;
-    h->rec_kind = REC_GENERATE;
+    h->rec.begin(REC_GENERATE, mode, B, opts->kernel, train ? eps : nullptr);      // (and no cnf_grad_x / cnf_grad_ys any more)
     if (stats) { *stats = sst; stats->launches += 1; }
     return CNF_OK;
 }
@@ -2336,21 +2344,11 @@ extern "C" cnf_status cnf_generate_pullback(cnf_handle h, const float* cot_z, co
     if (!h) return CNF_ERR_BAD_ARG;
     if (!grad) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
     if (!cot_z && !cot_logq) return fail(h, CNF_ERR_BAD_ARG, "both cotangents are null");
-    if (!h->rec_valid || h->rec_kind != REC_GENERATE || B != h->rec_B || (size_t)h->last_hs.size() == 0 || !h->d_cw || !h->d_gz0)
-        return fail(h, CNF_ERR_BAD_ARG, "no recorded sampling solve of a batch of this size: call cnf_generate_record first");
-    HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
-    cnf_status s;
-    const std::vector<float> hs = h->last_hs;
-    const GenCot gen{cot_z, cot_logq};
-    if (h->rec_mode == CNF_MODE_TRAIN) {
-        if ((s = ensure_pullback_params(h, st)) != CNF_OK) return s;
-        s = train_backward(h, h->rec_eps, B, h->rec_kernel, hs, nullptr, grad, st, &gen);
-    } else {
-        s = test_backward(h, B, hs, nullptr, grad, st, &gen);
-    }
-    if (s != CNF_OK) { h->rec_valid = false; return s; }
-    h->grad_last_B = 0;                                    // (g_lam is d / d u(t_start) of a SAMPLING solve: cnf_grad_x is not defined for it)
+    const cnf_status s = record_pullback(h, REC_GENERATE, Cotangent{Cotangent::SAMPLE, nullptr, cot_z, cot_logq}, B, grad, st,
+                                         "no recorded sampling solve of a batch of this size: call cnf_generate_record first");
+    if (s != CNF_OK) return s;
+    h->rec.sampling_pullback_done();                       // (g_lam is d / d u(t_start) of a SAMPLING solve: cnf_grad_x is not defined for it)
     if (grad_z0) {
         launch_generate_z0_grad(h->nd.n_in, h->bd, h->g_lam, cot_logq, h->d_gz0, grad_z0, B, st);
         HIPCHK(h, hipGetLastError());
@@ -2380,11 +2378,10 @@ extern "C" cnf_status cnf_base_logpdf_pullback(cnf_handle h, const float* w, int
     if (h->bd.kind == 0) return fail(h, CNF_ERR_BAD_ARG, "the default base distribution has no mean or chol to differentiate");
     const float* src = nullptr;
     int stride = 0;
-    if (h->rec_valid && B == h->rec_B && B >= 1) {
-        if (h->rec_kind == REC_GENERATE) { src = h->d_gz0; stride = h->nd.n_in; }
-        else { src = h->g_US[1]; stride = rows_of(h, h->rec_mode); }
-    } else if (h->fs_B >= 1 && B == h->fs_B) {
-        src = h->g_US[1]; stride = rows_of(h, h->fs_mode);
+    switch (h->rec.base_source(B)) {
+        case CnfRecord::SRC_Z0: src = h->d_gz0; stride = h->nd.n_in; break;
+        case CnfRecord::SRC_FINAL_STATE: src = h->g_US[1]; stride = rows_of(h, h->rec.mode()); break;
+        case CnfRecord::SRC_NONE: break;
     }
     if (!src) return fail(h, CNF_ERR_BAD_ARG, "no recorded solve of a batch of this size: call cnf_inference_record or cnf_generate_record first");
     HIPCHK(h, hipSetDevice(h->device));
@@ -2427,11 +2424,8 @@ extern "C" cnf_status cnf_loss_grad_submit(cnf_handle h, int mode, const float* 
     if (h->bd.kind) return fail(h, CNF_ERR_UNSUPPORTED, "no in-launch gradient with a non-default base distribution: use cnf_loss_grad");
     if (h->grad_ys) return fail(h, CNF_ERR_UNSUPPORTED, "no in-launch gradient w.r.t. ys (cnf_set_grad_ys is on): use cnf_loss_grad");
     h->collecting = true;
-    cnf_status s = check_call(h, mode, B);
-    if (s == CNF_OK && (!xs || !opts || !loss_dev || !grad || (mode == CNF_MODE_TRAIN && !eps))) s = fail(h, CNF_ERR_BAD_ARG, "null pointer");
-    if (s == CNF_OK && B < 1) s = fail(h, CNF_ERR_BAD_SHAPE, "the loss is a mean over the batch: B must be >= 1");
-    if (s == CNF_OK) s = ensure_capacity(h, B);
-    if (s == CNF_OK) s = ensure_grad_capacity(h, B);
+    cnf_status s = grad_prologue(h, mode, B, xs && opts && loss_dev && grad && (mode != CNF_MODE_TRAIN || eps), EMPTY_LOSS_BATCH, false,
+                                 (hipStream_t)stream);
     bool done = false;
     if (s == CNF_OK) {
         h->submitting = true; h->sub_taken = false;
@@ -2468,7 +2462,7 @@ extern "C" cnf_status cnf_set_params_async(cnf_handle h, const float* flat_dev, 
 // nvars rows, [B][nvars] as xs is laid out.  (The backward sweep leaves it in g_lam; nothing is recomputed.)
 extern "C" cnf_status cnf_grad_x(cnf_handle h, float* gx, int B, void* stream) {
     if (!h || !gx) return CNF_ERR_BAD_ARG;
-    if (B < 1 || B != h->grad_last_B || !h->g_lam) return fail(h, CNF_ERR_BAD_ARG, "cnf_grad_x: no gradient of a batch of this size has been computed");
+    if (!h->rec.grad_x_ok(B) || !h->g_lam) return fail(h, CNF_ERR_BAD_ARG, "cnf_grad_x: no gradient of a batch of this size has been computed");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpy2DAsync(gx, (size_t)h->nd.nvars * sizeof(float), h->g_lam, (size_t)h->nd.n_in * sizeof(float),
                                (size_t)h->nd.nvars * sizeof(float), (size_t)B, hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -2486,7 +2480,7 @@ extern "C" cnf_status cnf_set_grad_ys(cnf_handle h, int enable) {
 // d / d ys of the last gradient call, [B][n_cond] as cnf_set_cond takes ys (left behind by k_cond_project / k_adj_test).
 extern "C" cnf_status cnf_grad_ys(cnf_handle h, float* gy, int B, void* stream) {
     if (!h || !gy) return CNF_ERR_BAD_ARG;
-    if (B < 1 || B != h->gy_last_B || !h->d_gy)
+    if (!h->rec.grad_ys_ok(B) || !h->d_gy)
         return fail(h, CNF_ERR_BAD_ARG, "cnf_grad_ys: no gradient of a batch of this size has been computed with cnf_set_grad_ys on");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpyAsync(gy, gy_result(h, B), (size_t)B * h->nd.n_cond * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -2498,30 +2492,6 @@ extern "C" int cnf_grad_steps(cnf_handle h, float* hs, int cap) {
     const int n = (int)h->last_hs.size();
     if (hs) for (int i = 0; i < n && i < cap; ++i) hs[i] = h->last_hs[i];
     return n;
-}
-
-extern "C" cnf_status cnf_loss_grad_host(cnf_handle h, const float* xs, const float* eps, int B,
-                                         const cnf_solve_opts* opts, float* loss_out, float* grad,
-                                         cnf_solve_stats* stats) {
-    cnf_status s = check_call(h, CNF_MODE_TRAIN, B);
-    if (s != CNF_OK) return s;
-    if (!xs || !eps || !grad) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
-    if (B < 1) return fail(h, CNF_ERR_BAD_SHAPE, "the loss is a mean over the batch: B must be >= 1");
-    HIPCHK(h, hipSetDevice(h->device));
-    if ((s = ensure_grad_capacity(h, B)) != CNF_OK) return s;
-    const size_t nx = (size_t)h->nd.nvars * B, ne = (size_t)h->nd.n_in * B;
-    if ((s = ensure_stage(h, nx + ne)) != CNF_OK) return s;
-    float* x_d = h->stage;
-    float* e_d = x_d + nx;
-    hipError_t e = hipMemcpy(x_d, xs, nx * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(e_d, eps, ne * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) s = fail(h, CNF_ERR_HIP, hipGetErrorString(e));
-    if (s == CNF_OK) s = cnf_loss_grad(h, x_d, e_d, B, opts, loss_out, h->g_grad, stats, nullptr);
-    if (s == CNF_OK) {
-        e = hipMemcpy(grad, h->g_grad, h->n_params * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) s = fail(h, CNF_ERR_HIP, hipGetErrorString(e));
-    }
-    return s;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2597,7 +2567,7 @@ extern "C" cnf_status cnf_loss_grad_many(cnf_handle h, int mode, int M, const fl
             h->ens_base = 0;
         }
     }
-    h->grad_last_B = 0; h->gy_last_B = 0; end_record(h);   // (as every gradient call; the handle's own model is not touched)
+    h->rec.clear();                                        // (as every gradient call; the handle's own model is not touched)
     h->ens_M = 0;
     StepState* fin_dev = reinterpret_cast<StepState*>(h->ens_fin.data());
     float* sums_dev = h->ens_fin + Mz * st_f;

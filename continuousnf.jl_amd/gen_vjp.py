@@ -27,24 +27,16 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .base_icnf import (ICNF, _Buf, _as_colmajor, _generate_inputs, _is_torch, _mode_id, _solve_opts, base_logpdf_pullback,
-                        base_sample_pullback, grad_ys, n_augment_input, raise_if_no_gpu, set_grad_ys, steer_tspan)
+from .base_icnf import (ICNF, _generate_inputs, _is_torch, _mode_id, _solve_opts, base_logpdf_pullback, base_sample_pullback,
+                        grad_result, grad_steps, grad_ys, n_augment_input, raise_if_no_gpu, set_grad_ys, steer_tspan, to_device)
 from .distributions import learnable
-from .vjp import _base_grads, _base_key, _base_tensors, _base_unchanged
+from .vjp import _base_grads, _base_key, _base_tensors, _pull_recorded
 
 
 def _device(icnf: ICNF):
     import torch
     raise_if_no_gpu()
     return torch.device("cuda", icnf.device)
-
-
-def _buf_to_device(icnf: ICNF, b: _Buf):
-    """A host _Buf on the model's device (same column-major storage)."""
-    import torch
-    if b is None or b.torch is not None:
-        return b
-    return _Buf(torch.from_numpy(np.ascontiguousarray(b.arr, dtype=np.float32)).to(_device(icnf)), b.rows, b.B, torch)
 
 
 def generate_record(icnf: ICNF, mode, ps, st=None, n: int = 1, *, ys=None, z0=None, eps=None, tspan=None):
@@ -61,7 +53,7 @@ def generate_record(icnf: ICNF, mode, ps, st=None, n: int = 1, *, ys=None, z0=No
     if eb.B != n:
         raise ValueError("eps must have one column per sample")
     host = zb.torch is None
-    zb, eb = _buf_to_device(icnf, zb), _buf_to_device(icnf, eb)
+    zb, eb = to_device(icnf, zb), to_device(icnf, eb)
     if tspan is None:
         tspan = steer_tspan(icnf, mode)
     t0, t1 = tspan
@@ -76,10 +68,7 @@ def generate_record(icnf: ICNF, mode, ps, st=None, n: int = 1, *, ys=None, z0=No
     _lib.check(l.cnf_generate_record(h, m, zb.ptr, eb.ptr if m == _lib.MODE_TRAIN else None, n, C.byref(opts), z.data_ptr(),
                                      logq.data_ptr(), C.byref(stats), stream), h)
     icnf.last_stats = stats.as_dict()
-    k = l.cnf_grad_steps(h, None, 0)
-    hs = np.empty(max(k, 1), dtype=np.float32)
-    l.cnf_grad_steps(h, hs.ctypes.data, k)
-    icnf.last_steps = hs[:k]
+    grad_steps(icnf)
     zfull = z.view(n, n_in).t()
     # ("xb": the buffer the density direction's pullback looks its device up in -- the library then refuses the wrong kind)
     icnf._record = {"kind": "generate", "xb": zb, "zb": zb, "eb": eb, "B": n, "host": host, "tspan": tuple(tspan), "z": zfull,
@@ -149,13 +138,7 @@ def generate_pullback(icnf: ICNF, cot, with_z0=False, with_ys=False, with_base=F
     gb = None
     if with_base:                                    # (only logq depends on the base at fixed z0)
         gb = base_logpdf_pullback(icnf, cl if cl is not None else torch.zeros(B, dtype=torch.float32, device=dev))
-    if host:
-        grad = grad.cpu().numpy()
-        gz0 = gz0.cpu().numpy() if gz0 is not None else None
-        gb = tuple(g.cpu().numpy() for g in gb) if gb is not None else None
-    if not with_z0 and not with_ys and not with_base:
-        return grad
-    return (grad,) + ((gz0,) if with_z0 else ()) + ((gy,) if with_ys else ()) + ((gb,) if with_base else ())
+    return grad_result((grad,), host, (with_z0, gz0), (with_ys, gy), (with_base, gb))
 
 
 def _autograd_function():
@@ -190,20 +173,10 @@ def _autograd_function():
                 return (None,) * 10
 
             def record_again():
-                _base_unchanged(icnf, ctx.base_key)
                 generate_record(icnf, ctx.mode, ctx.ps, None, ctx.z0.shape[1], ys=ctx.ys, z0=ctx.z0, eps=ctx.eps, tspan=ctx.tspan)
-                ctx.token = icnf._record["token"]
 
-            rec = getattr(icnf, "_record", None)
-            if rec is None or rec["token"] is not ctx.token:
-                record_again()
-            try:
-                res = generate_pullback(icnf, (g_x, g_logq), with_z0=True, with_ys=need_ys, with_base=need_base)
-            except _lib.CNFError as e:          # the record was displaced by another call on the handle: record again
-                if e.status != _lib.ERR_BAD_ARG:
-                    raise
-                record_again()
-                res = generate_pullback(icnf, (g_x, g_logq), with_z0=True, with_ys=need_ys, with_base=need_base)
+            res = _pull_recorded(icnf, ctx, record_again,
+                                 lambda: generate_pullback(icnf, (g_x, g_logq), with_z0=True, with_ys=need_ys, with_base=need_base))
             grad, gz0 = res[0], res[1]
             gy = res[2].reshape(ctx.ys_shape).contiguous() if need_ys else None
             gm = gs = None
@@ -234,8 +207,7 @@ def differentiable_generate(icnf: ICNF, mode, ps, st=None, n: int = 1, *, ys=Non
     import torch
     m = _mode_id(mode)
     dev = _device(icnf)
-    if not _is_torch(ps):
-        ps = torch.from_numpy(np.ascontiguousarray(np.asarray(ps, dtype=np.float32))).to(dev)
+    ps = ps if _is_torch(ps) else to_device(icnf, ps, dev)
     if _is_torch(z0) and z0.shape[1] != n:
         raise ValueError("z0 must have n columns")
     bmean, bscale = _base_tensors(icnf)
@@ -248,8 +220,8 @@ def differentiable_generate(icnf: ICNF, mode, ps, st=None, n: int = 1, *, ys=Non
     normals = kept[0].view(n, n_in).t() if kept and bmean is not None else None
     tspan = steer_tspan(icnf, mode)
     if not (_is_torch(z0) and z0.requires_grad):
-        z0 = _buf_to_device(icnf, zb).view()
-    eps = _buf_to_device(icnf, eb).view() if m == _lib.MODE_TRAIN else None
+        z0 = to_device(icnf, zb).view()
+    eps = to_device(icnf, eb).view() if m == _lib.MODE_TRAIN else None
     if _FUNCTION is None:
         _FUNCTION = _autograd_function()
     return _FUNCTION.apply(icnf, mode, ps, ys, z0, eps, tspan, normals, bmean, bscale)

@@ -20,15 +20,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .base_icnf import (ICNF, _as_colmajor, _is_torch, _mode_id, _solve_opts, _split_cond_args, _stream, _xs_colmajor,
-                        base_logpdf_pullback, draw_eps, grad_ys, n_augment_input, raise_if_no_gpu, set_grad_ys, steer_tspan)
+from .base_icnf import (ICNF, _is_torch, _mode_id, _solve_opts, _split_cond_args, _stream, _xs_colmajor, base_logpdf_pullback,
+                        draw_eps, grad_result, grad_steps, grad_x, grad_ys, resolve_eps, set_grad_ys, steer_tspan, to_device)
 from .distributions import LearnableNormal, learnable
-
-
-def _to_device(icnf: ICNF, a):
-    import torch
-    raise_if_no_gpu()
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32))).to(torch.device("cuda", icnf.device))
 
 
 def inference_record(icnf: ICNF, mode, xs, *args, eps=None, tspan=None):
@@ -41,23 +35,12 @@ def inference_record(icnf: ICNF, mode, xs, *args, eps=None, tspan=None):
     ys, ps, st = _split_cond_args(icnf, args)
     m = _mode_id(mode)
     if host:
-        xs = _to_device(icnf, xs)
-        if ys is not None:
-            ys = _to_device(icnf, ys)
-        if eps is not None:
-            eps = _to_device(icnf, eps)
+        xs, ys, eps = to_device(icnf, xs), to_device(icnf, ys), to_device(icnf, eps)
     xb = _xs_colmajor(icnf, xs)
     B = xb.B
     icnf.set_params(ps)
     icnf.set_cond(ys, B)
-    if m != _lib.MODE_TRAIN:
-        eb = None
-    elif eps is not None:
-        eb = _as_colmajor(eps, icnf.nvars + n_augment_input(icnf), "eps")
-        if eb.B != B:
-            raise ValueError("eps must have one column per sample")
-    else:
-        eb = draw_eps(icnf, xb, B)
+    eb = resolve_eps(icnf, m, eps, xb, B)
     if tspan is None:
         tspan = steer_tspan(icnf, mode)
     t = xb.torch
@@ -70,10 +53,7 @@ def inference_record(icnf: ICNF, mode, xs, *args, eps=None, tspan=None):
     _lib.check(l.cnf_inference_record(h, m, xb.ptr, eb.ptr if eb is not None else None, B, C.byref(opts), logpx.data_ptr(),
                                       regs.data_ptr(), C.byref(stats), _stream(xb)), h)
     icnf.last_stats = stats.as_dict()
-    n = l.cnf_grad_steps(h, None, 0)
-    hs = np.empty(max(n, 1), dtype=np.float32)
-    l.cnf_grad_steps(h, hs.ctypes.data, n)
-    icnf.last_steps = hs[:n]
+    grad_steps(icnf)
     # (the library reads eps again in the pullback: the record keeps its buffers alive, and says whose record it is)
     icnf._record = {"xb": xb, "eb": eb, "B": B, "host": host, "tspan": tuple(tspan), "token": object()}
     r = regs.view(3, B)
@@ -138,20 +118,10 @@ def inference_pullback(icnf: ICNF, cot, with_x=False, with_ys=False, with_base=F
     set_grad_ys(icnf, with_ys)
     _lib.check(l.cnf_inference_pullback(h, cm.data_ptr(), B, grad.data_ptr(), stream), h)
     grad = icnf.nn.grad_to_external(grad)
-    gx = None
-    if with_x:
-        gx = torch.empty(B * icnf.nvars, dtype=torch.float32, device=dev)
-        _lib.check(l.cnf_grad_x(h, gx.data_ptr(), B, stream), h)
-        gx = gx.view(B, icnf.nvars).t()
-    gy = grad_ys(icnf, B, dev, stream, host) if with_ys else None
-    gb = base_logpdf_pullback(icnf, cm[0]) if with_base else None      # (row 0: the cotangent of logpx)
-    if host:
-        grad = grad.cpu().numpy()
-        gx = gx.cpu().numpy() if gx is not None else None
-        gb = tuple(g.cpu().numpy() for g in gb) if gb is not None else None
-    if not with_x and not with_ys and not with_base:
-        return grad
-    return (grad,) + ((gx,) if with_x else ()) + ((gy,) if with_ys else ()) + ((gb,) if with_base else ())
+    return grad_result((grad,), host,
+                       (with_x, grad_x(icnf, B, dev, stream, host) if with_x else None),
+                       (with_ys, grad_ys(icnf, B, dev, stream, host) if with_ys else None),
+                       (with_base, base_logpdf_pullback(icnf, cm[0]) if with_base else None))      # (row 0: the cotangent of logpx)
 
 
 def _autograd_function():
@@ -182,25 +152,15 @@ def _autograd_function():
             cot = (g_logpx, (g_E, g_n, g_A))
 
             def record_again():
-                _base_unchanged(icnf, ctx.base_key)
                 args = (ctx.ys, ctx.ps, None) if icnf.cond else (ctx.ps, None)
                 eps = ctx.eb.view() if ctx.eb is not None else None
                 inference_record(icnf, ctx.mode, ctx.xs, *args, eps=eps, tspan=ctx.tspan)
-                ctx.token = icnf._record["token"]
 
-            rec = getattr(icnf, "_record", None)
-            if rec is None or rec["token"] is not ctx.token:
-                record_again()
             # d / d ys is asked of the library only when whatever produced ys wants it (also after record_again)
             need_ys = bool(ctx.needs_input_grad[3])
             need_base = bool(ctx.needs_input_grad[7] or ctx.needs_input_grad[8])
-            try:
-                res = inference_pullback(icnf, cot, with_x=True, with_ys=need_ys, with_base=need_base)
-            except _lib.CNFError as e:          # the record was displaced by another call on the handle: record again
-                if e.status != _lib.ERR_BAD_ARG:
-                    raise
-                record_again()
-                res = inference_pullback(icnf, cot, with_x=True, with_ys=need_ys, with_base=need_base)
+            res = _pull_recorded(icnf, ctx, record_again,
+                                 lambda: inference_pullback(icnf, cot, with_x=True, with_ys=need_ys, with_base=need_base))
             grad, gx = res[0], res[1]
             gy = res[2].reshape(ctx.ys_shape).contiguous() if need_ys else None
             gm, gs = _base_grads(icnf, res[-1], ctx.needs_input_grad[7], ctx.needs_input_grad[8]) if need_base else (None, None)
@@ -209,6 +169,27 @@ def _autograd_function():
                     grad.reshape(ctx.ps_shape) if need_ps else None, None, None, gm, gs)
 
     return _Inference
+
+
+def _pull_recorded(icnf: ICNF, ctx, record_again, pull):
+    """``pull()`` on the record ``ctx.token`` names -- what both autograd functions' ``backward`` do.  A record another call on
+    the model has displaced (its token is gone, or the library refuses the pullback with ``ERR_BAD_ARG``) is made again from
+    the saved inputs first, with the base's values checked to be those of the first recording, and pulled once more."""
+    def again():
+        _base_unchanged(icnf, ctx.base_key)
+        record_again()
+        ctx.token = icnf._record["token"]
+
+    rec = getattr(icnf, "_record", None)
+    if rec is None or rec["token"] is not ctx.token:
+        again()
+    try:
+        return pull()
+    except _lib.CNFError as e:          # the record was displaced by another call on the handle: record again
+        if e.status != _lib.ERR_BAD_ARG:
+            raise
+        again()
+        return pull()
 
 
 def _base_grads(icnf: ICNF, pair, need_mean, need_scale):
@@ -259,8 +240,7 @@ def differentiable_inference(icnf: ICNF, mode, xs, *args, eps=None):
     if not _is_torch(xs):
         raise ValueError("differentiable_inference needs device tensors")
     ys, ps, st = _split_cond_args(icnf, args)
-    if not _is_torch(ps):
-        ps = torch.from_numpy(np.ascontiguousarray(np.asarray(ps, dtype=np.float32))).to(xs.device)
+    ps = ps if _is_torch(ps) else to_device(icnf, ps, xs.device)
     if _FUNCTION is None:
         _FUNCTION = _autograd_function()
     # eps first and then the steered t1: the order in which loss_and_grad draws, so that one seed gives one problem

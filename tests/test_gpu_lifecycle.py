@@ -227,3 +227,97 @@ def test_destroy_and_recreate():
     assert ic._handle is None
     _same(_np(cnf.inference(ic, TRAIN, *_args(ic, d), eps=d["eps"])), ref, "after destroy and re-create")     # (a new handle, made on demand)
     ic.close()
+
+
+# ---- what a call leaves behind for the calls that may follow it -----------------------------------------------------------------
+def _probe(ic, d, B, seen):
+    """The five follow-up calls at batch B, in this order: cnf_grad_x, cnf_grad_ys, base_logpdf_pullback (which change nothing),
+    then inference_pullback and generate_pullback (an accepted one is a backward pass: it leaves its own d / d u(t0) and d / d ys
+    behind).  Returns the accepted ones as a string of their letters; `seen` remembers every accepted result under what it
+    must be a result OF (the caller's label), and a second result under one label must repeat the first bit for bit."""
+    l, h = _lib.lib(), ic.handle()
+    st = torch.cuda.current_stream().cuda_stream
+    ok, got = "", {}
+    gx, gy = torch.empty(B * ic.nvars, device="cuda"), torch.empty(B * ic.n_cond, device="cuda")
+    for key, rc, out in (("x", l.cnf_grad_x(h, gx.data_ptr(), B, st), gx.view(B, ic.nvars).t()),
+                         ("y", l.cnf_grad_ys(h, gy.data_ptr(), B, st), gy.view(B, ic.n_cond).t())):
+        assert rc in (_lib.OK, _lib.ERR_BAD_ARG), (key, rc)
+        if rc == _lib.OK:
+            got[key] = _np(out)
+    w = torch.full((B,), -1.0 / B, device="cuda")
+    for key, call in (("b", lambda: cnf.base_logpdf_pullback(ic, w)),
+                      ("i", lambda: cnf.inference_pullback(ic, d["cot"], with_ys=True)[0]),
+                      ("g", lambda: cnf.generate_pullback(ic, (d["cot"][:ic.nvars], d["cot"][3]), with_ys=True)[0])):
+        try:
+            got[key] = _np(call())
+        except cnf.CNFError as e:
+            assert e.status == _lib.ERR_BAD_ARG, (key, e.status)
+    for key, v in got.items():
+        ok += key
+        label = d["labels"].get(key)
+        if label in seen:
+            _same(v, seen[label], f"{label} again")
+        elif label is not None:
+            seen[label] = v
+    return ok
+
+
+@pytest.mark.parametrize("mode", [TRAIN, TEST], ids=["train", "test"])
+def test_what_each_call_leaves_behind(mode):
+    """One handle through every event that begins or ends a piece of what the gradient calls leave on it, and after each event
+    which of the five follow-up calls it accepts (x: cnf_grad_x, y: cnf_grad_ys, b: base_logpdf_pullback, i: inference_pullback,
+    g: generate_pullback; every other answer must be ERR_BAD_ARG).  The expected strings are the table of csrc/cnf_record.h.
+    Besides the nine events there are two re-recordings (marked +), so that set_params and set_cond find something to end."""
+    n = 4
+    base = cnf.LearnableNormal(torch.linspace(-0.2, 0.3, n).cuda(), std=torch.linspace(0.7, 1.4, n).cuda())
+    ic = _model(WAVE_NET, n, n_cond=2, kernel="generic", basedist=base)
+    B, B2 = 5, 7
+    d, d2 = _inputs(ic, B), _inputs(ic, B2)
+    eps = lambda dd: dd["eps"] if mode is TRAIN else None
+    seen = {}
+
+    def record(dd):
+        return cnf.inference_record(ic, mode, *_args(ic, dd), eps=eps(dd))
+
+    def rearm():
+        record(d)
+        cnf.inference_pullback(ic, d["cot"], with_ys=True)
+
+    def check(event, want, dd, nB, **labels):
+        dd["labels"] = labels
+        got = _probe(ic, dd, nB, seen)
+        print(f"after {event}, B = {nB}: accepted '{got}', expected '{want}'")
+        assert got == want, (event, nB, got, want)
+
+    out = cnf.loss_and_grad(ic, mode, *_args(ic, d), eps=eps(d), with_x=True, with_ys=True)
+    seen["gx of the loss"], seen["gy of the loss"] = _np(out[2]), _np(out[3])
+    check("1 loss_and_grad", "xyb", d, B, x="gx of the loss", y="gy of the loss", b="base at the final state")
+    record(d)                    # a solve ends the LOSS record, not what the backward pass left; the pullback is a new backward pass
+    check("2 inference_record", "xybi", d, B, x="gx of the loss", y="gy of the loss", b="base at the final state", i="pullback")
+    out = cnf.inference_pullback(ic, d["cot"], with_x=True, with_ys=True)
+    _same(_np(out[0]), seen["pullback"], "3 inference_pullback against the probe's")
+    seen["gx of the pullback"], seen["gy of the pullback"] = _np(out[1]), _np(out[2])
+    check("3 inference_pullback", "xybi", d, B, x="gx of the pullback", y="gy of the pullback", b="base at the final state", i="pullback")
+    gen = dict(ys=d["ys"], z0=d["xs"], eps=eps(d))
+    cnf.generate_record(ic, mode, d["ps"], None, B, **gen)
+    check("4 generate_record", "bg", d, B, b="base at z0", g="sampling pullback")
+    out = cnf.generate_pullback(ic, (d["cot"][:n], d["cot"][3]), with_ys=True)
+    _same(_np(out[0]), seen["sampling pullback"], "5 generate_pullback against the probe's")
+    seen["gy of the sampling pullback"] = _np(out[1])
+    check("5 generate_pullback", "ybg", d, B, y="gy of the sampling pullback", b="base at z0", g="sampling pullback")
+    cnf.inference(ic, mode, *_args(ic, d), eps=eps(d))
+    check("6 inference", "y", d, B, y="gy of the sampling pullback")
+    rearm()                      # +
+    d["ps"] = d["ps"].clone()    # (another tensor with the same values: uploaded again)
+    ic.set_params(d["ps"])
+    check("7 set_params", "xy", d, B, x="gx of the pullback", y="gy of the pullback")
+    rearm()                      # +
+    d["ys"] = d["ys"].clone()
+    ic.set_cond(d["ys"], B)
+    check("8 set_cond", "xy", d, B, x="gx of the pullback", y="gy of the pullback")
+    d2["ps"] = d["ps"]
+    record(d2)                   # (within the capacity the first call reserved: nothing is cleared)
+    check("9 a larger record, the smaller batch", "xy", d, B, x="gx of the pullback", y="gy of the pullback")
+    check("9 a larger record, its own batch", "bi", d2, B2, b="base at the larger final state", i="larger pullback")
+    check("9 ... and after its pullback", "xybi", d2, B2, b="base at the larger final state", i="larger pullback")
+    ic.close()
