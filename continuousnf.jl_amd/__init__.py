@@ -60,6 +60,8 @@ from .vjp import differentiable_inference, inference_pullback, inference_record,
 from .gen_vjp import differentiable_generate, generate_pullback, generate_record, reverse_kl
 from . import ensemble, gen_vjp, mlj, parallel, vjp
 from .ensemble import ensemble_capacity, ensemble_steps, fit_many, loss_and_grad_many
+from .ensemble import EnsembleDist, ensemble_eval_capacity, ensemble_eval_steps, generate_many, inference_many, logpdf_members, \
+    loss_many
 from .mlj import (Adam, CondICNFModel, ICNFModel, Lion, Machine, fit, fit_, fitted_params, load_params, machine, save_params,
                   transform)
 

@@ -143,6 +143,16 @@ _ENSEMBLE_SIGNATURES = {
     "cnf_ensemble_steps": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int]),
 }
 ENSEMBLE_EXPORTS = tuple(_ENSEMBLE_SIGNATURES)
+# ensemble inference and sampling (include/cnfhip_ensemble_eval.h): likewise
+_ENSEMBLE_EVAL_SIGNATURES = {
+    "cnf_ensemble_eval_capacity": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "cnf_inference_many": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), _fp, _fp, _fp, _fp,
+                                     _fp, C.c_void_p, C.c_int, C.c_void_p]),
+    "cnf_generate_many": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), _fp, _fp, _fp,
+                                    _fp, C.c_void_p, C.c_int, C.c_void_p]),
+    "cnf_ensemble_eval_steps": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int]),
+}
+ENSEMBLE_EVAL_EXPORTS = tuple(_ENSEMBLE_EVAL_SIGNATURES)
 
 _lib = None
 
@@ -181,7 +191,7 @@ def lib():
             pass
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in list(_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) + list(_BASEGRAD_SIGNATURES.items()) + \
-                list(_ENSEMBLE_SIGNATURES.items()):
+                list(_ENSEMBLE_SIGNATURES.items()) + list(_ENSEMBLE_EVAL_SIGNATURES.items()):
             f = getattr(l, name)
             f.restype, f.argtypes = res, args
         _lib = l

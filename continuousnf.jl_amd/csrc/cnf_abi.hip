@@ -175,6 +175,10 @@ struct cnf_ctx {
     unsigned ens_base = 0;        // meeting indices the ensemble launches so far may have used (tags go on from there)
     int ens_M = 0, ens_cap = 0;   // the last call: members, step slots per member
     std::vector<int> ens_nacc;    //   accepted steps per member (-1: the member gave up)
+    // cnf_inference_many / cnf_generate_many share the meeting words, bases, final states and columns above; their own:
+    DevBuf<float> ens_trace;      // [M][trace_cap][4] the members' step attempts (cnf_ensemble_eval_steps)
+    int ensv_M = 0, ensv_tcap = 0;   // the last call that kept a trace: members, rows per member
+    std::vector<int> ensv_att;    //   attempts per member (-1: the member gave up)
     std::string err;
 };
 
@@ -2653,6 +2657,190 @@ extern "C" int cnf_ensemble_steps(cnf_handle h, int member, float* hs, int cap) 
     if (hs && take > 0) {
         if (hipSetDevice(h->device) != hipSuccess ||
             hipMemcpy(hs, h->ens_hs + (size_t)member * h->ens_cap, (size_t)take * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+            (void)hipGetLastError();
+            return -1;
+        }
+    }
+    return n;
+}
+
+// ---------------------------------------------------------------------------------------
+// Ensemble inference and sampling (include/cnfhip_ensemble_eval.h): the M members scored (cnf_inference_many) or sampled
+// (cnf_generate_many) by ONE launch of the plain ENS form of k_solve_wave.  The meeting words, bases, final states and column
+// store are the ensemble's own buffers above; nothing of the handle's model, solver state or record is touched.
+// ---------------------------------------------------------------------------------------
+extern "C" int cnf_ensemble_eval_capacity(cnf_handle h, int mode, int B) {
+    if (!h || (mode != CNF_MODE_TEST && mode != CNF_MODE_TRAIN) || B < 1) return 0;
+    if (h->nd.n_cond > 0 || h->bd.kind || h->grad_ys || h->shard_reduce || h->shard_comm || h->no_persist) return 0;
+    if (hipSetDevice(h->device) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    return wave_ens_eval_capacity(h->nd_wave, mode == CNF_MODE_TRAIN, B);
+}
+
+// What the two calls share.  gen = false: src = xs [M][B][nvars], out0 = logpx [M][B], out1 = regs [M][3][B], times = the end
+// times; gen = true: src = z0 [M][B][n_in], out0 = xs_out [M][B][nvars], out1 = logq [M][B] or null, times = the start times.
+static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float* params_dev, const float* src, const float* eps, int B,
+                           const cnf_solve_opts* opts, const float* times_host, float* out0, float* out1, float* loss_out,
+                           int* status_out, cnf_solve_stats* stats_out, int trace_cap, void* stream) {
+    // (the arguments first, the handle last: what is wrong with a call is said before anything asks for a device)
+    if (mode != CNF_MODE_TEST && mode != CNF_MODE_TRAIN) return fail(h, CNF_ERR_BAD_ARG, "unknown mode");
+    const bool train = mode == CNF_MODE_TRAIN;
+    if (!params_dev || !src || !opts || !out0 || (!gen && !out1) || !status_out || (train && !eps)) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    if (M < 1) return fail(h, CNF_ERR_BAD_SHAPE, "an ensemble has at least one member");
+    if (B < 1) return fail(h, CNF_ERR_BAD_SHAPE, "B must be >= 1");
+    if (trace_cap < 0) return fail(h, CNF_ERR_BAD_ARG, "trace_cap must be >= 0");
+    if (!h) return CNF_ERR_BAD_ARG;
+    cnf_status s = check_solve_opts(h, opts);
+    if (s != CNF_OK) return s;
+    if (times_host)
+        for (int m = 0; m < M; ++m)
+            if (!std::isfinite(times_host[m]) || times_host[m] == (gen ? opts->t1 : opts->t0))
+                return fail(h, CNF_ERR_BAD_ARG, "empty or NaN time span of a member");
+    while (!h->collecting && !h->submitted.empty())       // (as any other call: the inferences submitted on the handle end first)
+        if ((s = collect_one(h, nullptr)) != CNF_OK) return s;
+    if (opts->kernel == CNF_KERNEL_GENERIC) return fail(h, CNF_ERR_UNSUPPORTED, "the ensemble form exists on the wave kernels only");
+    const int capacity = cnf_ensemble_eval_capacity(h, mode, B);
+    if (capacity < 1) return fail(h, CNF_ERR_UNSUPPORTED, "no ensemble form for this model, mode or batch");
+    if (M > capacity) return fail(h, CNF_ERR_UNSUPPORTED, "more members than one launch takes (cnf_ensemble_eval_capacity)");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    const NetDesc& nd = h->nd_wave;
+    const size_t Mz = (size_t)M, Bz = (size_t)B, n_in = (size_t)nd.n_in, nv = (size_t)nd.nvars, D = n_in + (train ? 3 : 1);
+    const int tiles = (B + 15) / 16;
+    const size_t st_f = (sizeof(StepState) + 3) / 4, fin_f = Mz * (st_f + 5);
+    // ---- the members' stores: grown behind a wait for the device, so that steady-state calls allocate nothing ----
+    const size_t cols_f = Mz * Bz * (gen ? 2 * D : D);     // final columns (an inference) | u0 and the final columns (sampling)
+    const size_t trace_f = Mz * 4 * (size_t)trace_cap;
+    if (cols_f > h->ens_cols.capacity() || Mz * WV_ENS_PART_FLOATS > h->ens_part.capacity() || 2 * Mz > h->ens_words.capacity() ||
+        fin_f > h->ens_fin.capacity() || fin_f + Mz > h->ens_hfin.capacity() || Mz > h->ens_t1.capacity() ||
+        trace_f > h->ens_trace.capacity()) {
+        HIPCHK(h, hipDeviceSynchronize());
+        if (trace_f > h->ens_trace.capacity()) h->ensv_M = 0;
+        RESERVE(h, h->ens_cols, cols_f);
+        RESERVE(h, h->ens_words, 2 * Mz);
+        RESERVE(h, h->ens_fin, fin_f);
+        RESERVE(h, h->ens_hfin, fin_f + Mz);
+        RESERVE(h, h->ens_t1, Mz);
+        RESERVE(h, h->ens_trace, trace_f);
+        if (Mz * WV_ENS_PART_FLOATS > h->ens_part.capacity()) {
+            RESERVE(h, h->ens_part, Mz * WV_ENS_PART_FLOATS);
+            HIPCHK(h, hipMemset(h->ens_part, 0, Mz * WV_ENS_PART_FLOATS * sizeof(float)));
+            h->ens_base = 0;
+        }
+    }
+    if (trace_cap > 0) h->ensv_M = 0;                      // (the trace on record is about to be overwritten)
+    StepState* fin_dev = reinterpret_cast<StepState*>(h->ens_fin.data());
+    float* sums_dev = h->ens_fin + Mz * st_f;
+
+    std::unique_lock<std::mutex> persist_lock(g_persist_mu);       // one one-launch solve at a time in this process
+    if (g_submitted_inflight > 0 && g_submitted_stream != st) HIPCHK(h, hipStreamSynchronize(g_submitted_stream));
+    // the meeting indices go on from where the earlier ensemble launches may have ended (cnf_loss_grad_many has the reasons)
+    const unsigned long long span = 2ull * ((unsigned long long)opts->maxiters + 8ull);
+    if ((unsigned long long)h->ens_base + span >= 0xffffffffull) {
+        HIPCHK(h, hipMemsetAsync(h->ens_part, 0, h->ens_part.capacity() * sizeof(float), st));
+        h->ens_base = 0;
+    }
+    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->ens_words.data(), (int)h->ens_base, Mz, st));
+    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(h->ens_words.data() + Mz), 0, Mz, st));
+    h->ens_base += (unsigned)(span < 0xffffffffull ? span : 0xfffffffeull);
+    if (times_host) {
+        float* pin = h->ens_hfin + fin_f;
+        memcpy(pin, times_host, Mz * sizeof(float));
+        HIPCHK(h, hipMemcpyAsync(h->ens_t1, pin, Mz * sizeof(float), hipMemcpyHostToDevice, st));
+    }
+    StepState init{};
+    init.t = init.t0 = opts->t0;
+    init.dt = opts->dt;
+    init.qold = 1e-4f;
+    init.abstol = opts->abstol; init.reltol = opts->reltol;
+    init.adaptive = opts->adaptive ? 1 : 0;
+    init.n_partials = tiles;
+    step_state_set_t1(&init, opts->t1);
+    const bool hairer = opts->adaptive && opts->dt == 0.f;
+    Solve3Args sv{};
+    sv.part = h->ens_part; sv.base_dev = h->ens_words; sv.abort_flag = reinterpret_cast<int*>(h->ens_words.data() + Mz);
+    sv.maxiters = (int)opts->maxiters; sv.hairer = hairer ? 1 : 0; sv.init = init;
+    set_wait_bounds(h, sv);
+    if (trace_cap > 0) { sv.trace = h->ens_trace; sv.trace_cap = trace_cap; }
+    float* cols = h->ens_cols;
+    float* fsol = cols + Mz * Bz * D;                      // sampling: the final columns behind u0
+    if (gen) {
+        // u0 = [z0; 0] of all M B columns (the members' columns are contiguous)
+        HIPCHK(h, hipMemsetAsync(cols, 0, Mz * Bz * D * sizeof(float), st));
+        HIPCHK(h, hipMemcpy2DAsync(cols, D * sizeof(float), src, n_in * sizeof(float), n_in * sizeof(float), Mz * Bz, hipMemcpyDeviceToDevice, st));
+        sv.u0 = cols; sv.u_out = fsol;
+    } else {
+        sv.xs = src; sv.logpx = out0; sv.regs = out1; sv.sums5 = sums_dev;
+    }
+    WaveEnsLaunch ens;
+    ens.M = M;
+    (gen ? ens.t0 : ens.t1) = times_host ? h->ens_t1.data() : nullptr;
+    ens.p_stride = h->n_params; ens.part_stride = WV_ENS_PART_FLOATS;
+    int launches = 0;
+    s = wave_solve_launch(nd, train, params_dev, nullptr, 0, fin_dev, cols, eps, B, st, nullptr, 0, sv, nullptr, &ens);
+    if (s != CNF_OK) return fail(h, s, "the ensemble launch failed to start");
+    ++launches;
+    HIPCHK(h, hipGetLastError());
+    if (gen) {
+        launch_generate_post_rows((int)n_in, (int)nv, (int)D, fsol, src, out0, out1, Mz * Bz, st);
+        HIPCHK(h, hipGetLastError());
+        ++launches;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->ens_hfin, h->ens_fin, fin_f * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));                   // (no mirror is polled: the call waits for the stream)
+    persist_lock.unlock();
+
+    std::vector<int> att(Mz, -1);
+    bool any_bad = false;
+    for (int m = 0; m < M; ++m) {
+        StepState fin;
+        memcpy(&fin, h->ens_hfin + (size_t)m * st_f, sizeof fin);
+        const int attempts = fin.naccept + fin.nreject;
+        fill_stats(stats_out ? stats_out + m : nullptr, fin, (hairer ? 2 : 1) + 6 * attempts, CNF_KERNEL_MFMA, launches);
+        float loss = NAN;
+        if (fin.n_partials < 0) status_out[m] = CNF_ERR_UNSUPPORTED;             // a wait ran out
+        else if (fin.nonfinite) status_out[m] = CNF_ERR_NONFINITE;
+        else if (!fin.done) status_out[m] = CNF_ERR_MAXITERS;
+        else {
+            // (a failure here is that member's status: the launch ran, so the call goes on and returns CNF_OK)
+            status_out[m] = gen ? CNF_OK : cnf_loss_from_sums(h, mode, h->ens_hfin + Mz * st_f + 5 * (size_t)m, &loss);
+            if (status_out[m] == CNF_OK) att[m] = attempts; else loss = NAN;
+        }
+        if (loss_out) loss_out[m] = loss;
+        if (status_out[m] != CNF_OK) {                     // nothing of such a member is valid: NaN, whatever the kernel left
+            any_bad = true;
+            const size_t n0 = gen ? Bz * nv : Bz, n1 = gen ? Bz : 3 * Bz;
+            HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(out0 + (size_t)m * n0), 0x7fc00000, n0, st));
+            if (out1) HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(out1 + (size_t)m * n1), 0x7fc00000, n1, st));
+        }
+    }
+    if (any_bad) HIPCHK(h, hipStreamSynchronize(st));
+    if (trace_cap > 0) { h->ensv_att.swap(att); h->ensv_M = M; h->ensv_tcap = trace_cap; }
+    return CNF_OK;
+}
+
+extern "C" cnf_status cnf_inference_many(cnf_handle h, int mode, int M, const float* params_dev, const float* xs, const float* eps, int B,
+                                         const cnf_solve_opts* opts, const float* t1_host, float* logpx_dev, float* regs_dev,
+                                         float* loss_out, int* status_out, cnf_solve_stats* stats_out, int trace_cap, void* stream) {
+    return ens_eval(h, false, mode, M, params_dev, xs, eps, B, opts, t1_host, logpx_dev, regs_dev, loss_out, status_out, stats_out,
+                    trace_cap, stream);
+}
+
+extern "C" cnf_status cnf_generate_many(cnf_handle h, int mode, int M, const float* params_dev, const float* z0, const float* eps, int B,
+                                        const cnf_solve_opts* opts, const float* t0_host, float* xs_out, float* logq_out,
+                                        int* status_out, cnf_solve_stats* stats_out, int trace_cap, void* stream) {
+    return ens_eval(h, true, mode, M, params_dev, z0, eps, B, opts, t0_host, xs_out, logq_out, nullptr, status_out, stats_out,
+                    trace_cap, stream);
+}
+
+extern "C" int cnf_ensemble_eval_steps(cnf_handle h, int member, float* rows, int cap) {
+    if (!h || member < 0 || member >= h->ensv_M || h->ensv_tcap < 1) return -1;
+    const int n = h->ensv_att[member];
+    if (n < 0) return -1;
+    int take = n < cap ? n : cap;
+    if (take > h->ensv_tcap) take = h->ensv_tcap;
+    if (rows && take > 0) {
+        if (hipSetDevice(h->device) != hipSuccess ||
+            hipMemcpy(rows, h->ens_trace + (size_t)member * 4 * h->ensv_tcap, (size_t)take * 4 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
             (void)hipGetLastError();
             return -1;
         }

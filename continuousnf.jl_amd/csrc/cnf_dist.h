@@ -38,6 +38,9 @@ void launch_vjp_cotangent(const NetDesc& nd, int D, const BaseDist& bd, int with
 // z_out[b] = rows 1..n_in of fsol[b] (D floats per sample), logq[b] = logpdf(base, z0_b) + dlogp_b
 void launch_generate_post(int n_in, int D, const BaseDist& bd, const float* fsol, const float* z0, float* z_out, float* logq, int B,
                           hipStream_t s);
+// cnf_generate_many: the M B columns of an ensemble as one batch, N(0, I) base: x_out[b] = the first n_out rows, logq may be null
+void launch_generate_post_rows(int n_in, int n_out, int D, const float* fsol, const float* z0, float* x_out, float* logq, size_t B,
+                               hipStream_t s);
 // The terminal cotangent: lam = cot_z, cw = [3][B]: w_l = +cot_logq, w_E = w_n = 0 (null cotangents: zeros).  n_in >= 1.
 void launch_generate_cotangent(int n_in, const float* cot_z, const float* cot_logq, float* lam, float* cw, int B, hipStream_t s);
 // gz0 = lam0 + cot_logq d logpdf(base, z0) / d z0   (cot_logq null: a copy; gz0 must not alias lam0)

@@ -199,6 +199,28 @@ k_generate_post(int n_in, int D, BaseDist bd, const float* __restrict__ fsol, co
     }
 }
 
+// cnf_generate_many: the same for the M B columns of an ensemble (the members' columns are contiguous: one batch), N(0, I) base;
+// only the first n_out = nvars rows of the sample are written, logq (may be null) with k_generate_post's arithmetic.
+__global__ void __launch_bounds__(256)
+k_generate_post_rows(int n_in, int n_out, int D, const float* __restrict__ fsol, const float* __restrict__ z0,
+                     float* __restrict__ x_out, float* __restrict__ logq, size_t B) {
+    const int tid = threadIdx.x, p = tid & 3;
+    const size_t b = (size_t)blockIdx.x * 64 + (tid >> 2);
+    const size_t bb = b < B ? b : B - 1;
+    const float* c = fsol + bb * D;
+    const float* z = z0 + bb * n_in;
+    float ss = 0.f;
+    for (int i = p; i < n_in; i += 4) ss = fmaf(z[i], z[i], ss);
+    ss += __shfl_xor(ss, 1, 64);
+    ss += __shfl_xor(ss, 2, 64);
+    if (b >= B) return;
+    for (int i = p; i < n_out; i += 4) x_out[bb * n_out + i] = c[i];
+    if (p == 0 && logq) {
+        const float log2pi = 1.8378770664093453f;
+        logq[b] = -0.5f * fmaf((float)n_in, log2pi, ss) + c[n_in];
+    }
+}
+
 // The terminal cotangent of sampling: lam = cot_z (null: zeros), and the [3][B] weights of the scalar rows -- +cot_logq (null:
 // zeros) on the dlogp row, zero on the E and n rows, which are integrated but are not outputs of sampling.
 __global__ void __launch_bounds__(256)
@@ -266,6 +288,11 @@ void launch_base_sample(int n_in, const BaseDist& bd, const float* normals, floa
 void launch_generate_post(int n_in, int D, const BaseDist& bd, const float* fsol, const float* z0, float* z_out, float* logq, int B,
                           hipStream_t s) {
     hipLaunchKernelGGL(k_generate_post, dim3((B + 63) / 64), dim3(256), 0, s, n_in, D, bd, fsol, z0, z_out, logq, B);
+}
+
+void launch_generate_post_rows(int n_in, int n_out, int D, const float* fsol, const float* z0, float* x_out, float* logq, size_t B,
+                               hipStream_t s) {
+    hipLaunchKernelGGL(k_generate_post_rows, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, s, n_in, n_out, D, fsol, z0, x_out, logq, B);
 }
 
 void launch_generate_cotangent(int n_in, const float* cot_z, const float* cot_logq, float* lam, float* cw, int B, hipStream_t s) {

@@ -39,6 +39,7 @@ bool wave_solve_supported(const NetDesc& nd, bool train, int B);
 struct WaveEnsLaunch {
     int M = 0;
     const float* t1 = nullptr;     // device, [M]: the members' own end times (null: sv.init.t1 for all)
+    const float* t0 = nullptr;     // device, [M]: the members' own start times (plain forms only; null: sv.init.t0 for all)
     size_t p_stride = 0;           // floats between two members' parameters
     size_t traj_stride = 0;        // ... trajectory stores (traj_cap x wave_grad_traj_floats)
     size_t part_stride = 0;        // ... meeting words, in floats (WV_ENS_PART_FLOATS)
@@ -47,6 +48,10 @@ struct WaveEnsLaunch {
 // the largest M a launch takes at batch B: workgroups the device holds at once / tiles (0: no ensemble form of this network
 // or mode, or the one-launch solves are switched off)
 int wave_ens_capacity(const NetDesc& nd, bool train, int B);
+// Without `grad`, `ens` launches the PLAIN ensemble form (cnf_inference_many / cnf_generate_many): either an inference (sv.xs,
+// sv.logpx [M][B], sv.regs [M][3][B], sv.sums5 [5 M]) or a bare solve (sv.u0 -> sv.u_out, [M][B][D] each); sv.trace, when
+// set, is [M][sv.trace_cap][4].  Its capacity: workgroups of one wave the device holds at once / tiles, at most 512 tiles.
+int wave_ens_eval_capacity(const NetDesc& nd, bool train, int B);
 cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_params, const float* cond, int cbs, StepState* st_out,
                              float* U0, const float* eps, int B, hipStream_t s, void* mirror, unsigned seq, const Solve3Args& sv,
                              const WaveGradArgs* grad = nullptr, const WaveEnsLaunch* ens = nullptr);

@@ -32,7 +32,8 @@
 //   ID2   the second activation is the identity (a PlanarLayer, or the identity layer cnf_create appends to a ONE-layer
 //         network: the network of the reference's benchmark suite);
 //   WGW   the tiles of a batch of at most 64 samples as the waves of one workgroup (LDS meeting), plain solves;
-//   ENS   M independent models of one architecture in one launch (cnf_loss_grad_many): a GRAD form whose grid is M x tiles.
+//   ENS   M independent models of one architecture in one launch, the grid M x tiles: the recomputing GRAD forms
+//         (cnf_loss_grad_many) and the plain one-tile-per-workgroup forms (cnf_inference_many, cnf_generate_many).
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -69,6 +70,8 @@ struct WaveEnsArgs {
     size_t p_stride;       // floats between two members' flat parameters
     size_t traj_stride;    // ... their trajectory stores
     size_t part_stride;    // ... their meeting words (as floats)
+    const float* t0;       // plain forms: null, or the members' own start times [M] (sampling runs over reverse(steer_tspan));
+                           // (last: the fields the gradient forms read keep their places among the kernel arguments)
 };
 
 __device__ __forceinline__ f32x4 mm4(const float (&A)[4], const f32x4& b, f32x4 acc) {
@@ -146,10 +149,12 @@ __device__ __forceinline__ float wv_quad_sum(float v) {
 // arithmetic on the kernel arguments: nothing but the moved pointers outlives it); behind it the body is the single
 // model's, with `tiles` parties per meeting instead of the grid.  Members never meet: a member whose wait runs out sets its
 // own abort word and writes its own final state.
+// Plain ENS forms (!GRAD: cnf_inference_many, cnf_generate_many): the same prologue without the gradient's stores; it also
+// moves the columns of a bare solve (sv.u0 / sv.u_out) and the member's step trace, and takes the member's own START time.
 template <int NI, int NH, int MODE, bool TANH, bool GRAD = false, bool ID2 = false, int WGW = 1, bool RICH = false, bool ENS = false>
 __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wave(WaveArgs a, Solve3Args sv, const WvTab tab, const WaveEnsArgs en) {
     constexpr bool HELP = GRAD && WGW == 1;
-    static_assert(!ENS || (HELP && !RICH), "ENS is a form of the recomputing gradient, one tile per workgroup");
+    static_assert(!ENS || (WGW == 1 && !RICH), "ENS forms have one tile per workgroup and no rich store");
     static_assert(!RICH || (GRAD && MODE == WV_VJP), "RICH is a form of the TrainMode / VJP gradient");
     constexpr int RR = 3 * NH + 3 * NI;                     // f32x4 per lane and stage evaluation in the rich store
     f32x4* rich_ptr = nullptr;                             // where the next evaluation files them (null: nowhere)
@@ -169,15 +174,28 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
         wid_ = (int)blockIdx.x - member * en.tiles;
         const size_t mb = (size_t)member, Bz = (size_t)a.B, nz = (size_t)a.nd.n_in;
         a.P += mb * en.p_stride;
-        sv.xs += mb * Bz * (size_t)sv.nvars;
+        if (GRAD || sv.xs) {                               // (a bare solve of the plain forms has none of these: null stays null)
+            sv.xs += mb * Bz * (size_t)sv.nvars;
+            sv.logpx += mb * Bz; sv.regs += mb * 3 * Bz; sv.sums5 += mb * 5;
+        }
         if (a.eps) a.eps += mb * Bz * nz;
-        sv.logpx += mb * Bz; sv.regs += mb * 3 * Bz; sv.sums5 += mb * 5;
         a.U0 += mb * Bz * (nz + (MODE != WV_TEST ? 3 : 1));
         a.st_out += mb;
-        a.g.traj += mb * en.traj_stride; a.g.hs_out += mb * (size_t)a.g.traj_cap;
-        a.g.gpart += mb * (size_t)en.tiles * (size_t)a.g.n_params; a.g.lam_out += mb * Bz * nz;
+        if constexpr (GRAD) {
+            a.g.traj += mb * en.traj_stride; a.g.hs_out += mb * (size_t)a.g.traj_cap;
+            a.g.gpart += mb * (size_t)en.tiles * (size_t)a.g.n_params; a.g.lam_out += mb * Bz * nz;
+        }
         sv.part += mb * en.part_stride; sv.base_dev += mb; sv.abort_flag += mb;
-        if (en.t1) step_state_set_t1(&sv.init, en.t1[mb]);
+        if constexpr (GRAD) {
+            if (en.t1) step_state_set_t1(&sv.init, en.t1[mb]);
+        } else {
+            const size_t Dz = nz + (MODE != WV_TEST ? 3 : 1);
+            if (sv.u0) sv.u0 += mb * Bz * Dz;
+            if (sv.u_out) sv.u_out += mb * Bz * Dz;
+            if (sv.trace) sv.trace += mb * 4 * (size_t)sv.trace_cap;
+            if (en.t0) sv.init.t = sv.init.t0 = en.t0[mb];
+            if (en.t0 || en.t1) step_state_set_t1(&sv.init, en.t1 ? en.t1[mb] : sv.init.t1);
+        }
     }
     const int wid = wid_;                                  // this wave's tile
     const int tiles = ENS ? en.tiles : (int)gridDim.x;     // (WGW == 1) tiles of the batch = parties of a meeting
@@ -1355,6 +1373,24 @@ wave_fn pick_grad_ens(int ni, int nh, bool id2, bool test, bool jvp) {
 #undef WV_ENS
     return nullptr;
 }
+// the plain ENS forms (cnf_inference_many, cnf_generate_many): the envelope of pick_grad_ens, so that every ensemble that can
+// be trained in one launch can be scored and sampled in one
+wave_fn pick_ens_plain(int ni, int nh, bool id2, bool test, bool jvp) {
+    if (ni != 1 || nh < 1 || nh > 4 || (id2 && nh != 1)) return nullptr;
+    const int mode = test ? WV_TEST : (jvp ? WV_JVP : WV_VJP);
+#define WV_ENSP(NHV, ID2V) (mode == WV_VJP ? (wave_fn)k_solve_wave<1, NHV, WV_VJP, true, false, ID2V, 1, false, true> \
+                          : mode == WV_JVP ? (wave_fn)k_solve_wave<1, NHV, WV_JVP, true, false, ID2V, 1, false, true> \
+                                           : (wave_fn)k_solve_wave<1, NHV, WV_TEST, true, false, ID2V, 1, false, true>)
+    if (id2) return WV_ENSP(1, true);
+    switch (nh) {
+        case 1: return WV_ENSP(1, false);
+        case 2: return WV_ENSP(2, false);
+        case 3: return WV_ENSP(3, false);
+        case 4: return WV_ENSP(4, false);
+    }
+#undef WV_ENSP
+    return nullptr;
+}
 template <int NI, int NH, bool TANH>
 wave_fn pick_mode(int mode) {
     return mode == WV_VJP ? (wave_fn)k_solve_wave<NI, NH, WV_VJP, TANH>
@@ -1438,28 +1474,47 @@ static wave_fn ens_fn(const NetDesc& nd, bool train) {
     if (nd.acts[0] != 1 || !(nd.acts[1] == 1 || is_id2(nd))) return nullptr;
     return pick_grad_ens((nd.n_in + 15) / 16, (nd.dims[1] + 15) / 16, is_id2(nd), !train, nd.jvp != 0);
 }
-int wave_ens_capacity(const NetDesc& nd, bool train, int B) {
+static bool ens_off() {
     static const bool off = [] { const char* e = getenv("CNF_PERSISTENT"); const char* w = getenv("CNF_WAVE"); return (e && e[0] == '0') || (w && w[0] == '0'); }();
-    wave_fn fn = ens_fn(nd, train);
-    if (off || !fn || B < 1 || !wave_grad_supported(nd, B, train)) return 0;
+    return off;
+}
+// workgroups of `threads` threads of an ENS instantiation that the current device holds at once (asked once per instantiation)
+static int ens_resident_workgroups(wave_fn fn, int threads) {
     static std::mutex mu;
-    static std::map<const void*, int> cap;                 // workgroups (main wave + helper) the device holds at once
+    static std::map<const void*, int> cap;
     std::lock_guard<std::mutex> lk(mu);
     auto it = cap.find((const void*)fn);
     if (it == cap.end()) {
         int dev = 0, n_cu = 0, per_cu = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)fn, 128, 0) != hipSuccess) { (void)hipGetLastError(); n_cu = per_cu = 0; }
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)fn, threads, 0) != hipSuccess) { (void)hipGetLastError(); n_cu = per_cu = 0; }
         it = cap.emplace((const void*)fn, n_cu * per_cu).first;
     }
-    return it->second / wave_grad_waves(B);
+    return it->second;
+}
+int wave_ens_capacity(const NetDesc& nd, bool train, int B) {
+    wave_fn fn = ens_fn(nd, train);
+    if (ens_off() || !fn || B < 1 || !wave_grad_supported(nd, B, train)) return 0;
+    return ens_resident_workgroups(fn, 128) / wave_grad_waves(B);      // (main wave + helper)
+}
+
+// ... and its plain form (cnf_inference_many, cnf_generate_many): the same envelope, 64 threads per workgroup
+static wave_fn ens_plain_fn(const NetDesc& nd, bool train) {
+    if (!ens_fn(nd, train)) return nullptr;
+    return pick_ens_plain((nd.n_in + 15) / 16, (nd.dims[1] + 15) / 16, is_id2(nd), !train, nd.jvp != 0);
+}
+int wave_ens_eval_capacity(const NetDesc& nd, bool train, int B) {
+    wave_fn fn = ens_plain_fn(nd, train);
+    if (ens_off() || !fn || B < 1 || B > 16 * 512) return 0;     // (a member's meeting has at most 512 parties)
+    return ens_resident_workgroups(fn, 64) / ((B + 15) / 16);
 }
 
 cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_params, const float* cond, int cbs, StepState* st_out,
                              float* U0, const float* eps, int B, hipStream_t s, void* mirror, unsigned seq, const Solve3Args& sv_,
                              const WaveGradArgs* grad, const WaveEnsLaunch* ens) {
     if (!wave_solve_supported(nd, train, B)) return CNF_ERR_UNSUPPORTED;
-    if (ens && (!grad || cond || mirror || ens->M < 1 || ens->M > wave_ens_capacity(nd, train, B))) return CNF_ERR_UNSUPPORTED;
+    if (ens && (cond || mirror || ens->M < 1 || ens->M > (grad ? wave_ens_capacity(nd, train, B) : wave_ens_eval_capacity(nd, train, B))))
+        return CNF_ERR_UNSUPPORTED;
     if (grad && nd.n_cond > 0 && !grad->ys) return CNF_ERR_BAD_ARG;
     if (grad && (!wave_grad_supported(nd, B, train) || !grad->traj || !grad->gpart || !grad->lam_out || !grad->hs_out || grad->traj_cap < 1))
         return CNF_ERR_UNSUPPORTED;
@@ -1497,7 +1552,15 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
     if (!sv.xs && !sv.u0) return CNF_ERR_BAD_ARG;
     WvTab tab = kWvTab;
     WaveEnsArgs en{};
-    if (ens) {
+    if (ens && !grad) {
+        // an inference (xs and all of its outputs) or a bare solve between the caller's columns; a trace needs its stride
+        const bool inf = sv.xs && sv.logpx && sv.regs && sv.sums5 && !sv.u0 && !sv.u_out;
+        const bool bare = !sv.xs && !sv.logpx && !sv.regs && !sv.sums5 && sv.u0 && sv.u_out;
+        if (!(inf || bare) || sv.t_out || (sv.trace && sv.trace_cap < 1) || grid > 512) return CNF_ERR_BAD_ARG;
+        fn = ens_plain_fn(nd, train);
+        en.tiles = grid; en.t1 = ens->t1; en.t0 = ens->t0; en.p_stride = ens->p_stride; en.part_stride = ens->part_stride;
+        grid *= ens->M;
+    } else if (ens) {
         if (grad->rich || sv.trace || sv.t_out || !sv.xs || !sv.logpx || !sv.regs || !sv.sums5 || sv.u_out) return CNF_ERR_BAD_ARG;
         fn = ens_fn(nd, train);
         en.tiles = grid; en.t1 = ens->t1; en.p_stride = ens->p_stride; en.traj_stride = ens->traj_stride; en.part_stride = ens->part_stride;

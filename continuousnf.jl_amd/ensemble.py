@@ -4,8 +4,12 @@ regression networks at ``batch_size = 32`` (src/exts/mlj_ext/core_icnf.jl:59-73)
 workgroups of the device; here M of them run side by side on M times as many (measured: tools/prof_ensemble.py).
 
 ``loss_and_grad_many`` is ``loss_and_grad`` for M members with their own parameters, data, probes and end times;
-``fit_many`` is ``mlj.fit`` for M data sets trained side by side.  Inference and ``logpdf`` of the members go through the
-existing calls, one member at a time."""
+``fit_many`` is ``mlj.fit`` for M data sets trained side by side.
+
+The other half of that workflow (include/cnfhip_ensemble_eval.h): ``inference_many`` / ``loss_many`` score the M members --
+each on its own held-out data, or all on one data set -- and ``generate_many`` samples them, each in ONE launch of the plain
+ensemble form of the same kernel; ``EnsembleDist`` is the bagged density: a weighted mixture of the members with ``logpdf``,
+``pdf`` and ``rand``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,7 +18,8 @@ import time
 import numpy as np
 
 from . import _lib
-from .base_icnf import ICNF, _Buf, _is_torch, _mode_id, _solve_opts, draw_eps, loss_and_grad, n_augment_input, steer_tspan
+from .base_icnf import ICNF, _Buf, _is_torch, _mode_id, _solve_opts, draw_eps, generate, inference, loss_and_grad, n_augment_input, \
+    steer_tspan
 from .layers import setup
 from .rng import HIPRNG
 from .types import TrainMode
@@ -48,13 +53,13 @@ def ensemble_capacity(icnf: ICNF, mode, B: int) -> int:
     return int(_lib.lib().cnf_ensemble_capacity(icnf.handle(), m, int(B)))
 
 
-def _check_inputs(icnf: ICNF, mode, xs, ps, eps, t1):
+def _check_inputs(icnf: ICNF, mode, xs, ps, eps, t1, who="loss_and_grad_many", single="loss_and_grad"):
     m = _mode_id(mode)
     why = _refusal(icnf)
     if why is not None:
-        raise NotImplementedError("loss_and_grad_many: " + why)
+        raise NotImplementedError(f"{who}: " + why)
     if not (_is_torch(xs) and _is_torch(ps)):
-        raise NotImplementedError("loss_and_grad_many takes device tensors (host arrays: loss_and_grad, one member at a time)")
+        raise NotImplementedError(f"{who} takes device tensors (host arrays: {single}, one member at a time)")
     if xs.dim() != 3 or xs.shape[1] != icnf.nvars or xs.shape[0] < 1 or xs.shape[2] < 1:
         raise ValueError(f"xs must be (M, nvars = {icnf.nvars}, B), got {tuple(xs.shape)}")
     M, _, B = xs.shape
@@ -74,6 +79,34 @@ def _check_inputs(icnf: ICNF, mode, xs, ps, eps, t1):
         if not np.isfinite(t1).all() or (t1 == np.float32(icnf.tspan[0])).any():
             raise ValueError("t1: every member needs a finite end time different from tspan[0]")
     return m, M, B, n_in, t1
+
+
+def _probes_and_ends(icnf: ICNF, mode, train, M, B, n_in, xr, eps, t1):
+    """The members' probes ([M][B][n_in] on the device of ``xr``; None in TestMode) and end times (None: ``tspan[1]`` for all),
+    given or drawn in the order ``loss_and_grad_many`` documents."""
+    import torch
+    if not train:
+        er = None
+    elif eps is not None:
+        er = _rows(eps)
+    elif isinstance(icnf.rng, HIPRNG):                     # one draw of M B columns
+        er = draw_eps(icnf, _Buf(xr.view(-1), icnf.nvars, M * B, torch), M * B).arr.view(M, B, n_in)
+    else:
+        # the host generator, member by member in the order a loop of ``loss_and_grad`` consumes it (the member's probes, then
+        # its end time: base_icnf.loss_and_grad), so that one seed gives the members the draws that loop would; one upload
+        host, draws = _Buf(None, icnf.nvars, B, None), []
+        steer = t1 is None and icnf.STEER
+        ends = []
+        for _ in range(M):
+            draws.append(draw_eps(icnf, host, B).arr.reshape(B, n_in))
+            if steer:
+                ends.append(steer_tspan(icnf, mode)[1])
+        er = torch.from_numpy(np.stack(draws)).to(xr.device)
+        if steer:
+            t1 = np.asarray(ends, dtype=np.float32)
+    if t1 is None and icnf.STEER and train:                # (given probes, TestMode never steers, or a device generator: M draws)
+        t1 = np.asarray([steer_tspan(icnf, mode)[1] for _ in range(M)], dtype=np.float32)
+    return er, t1
 
 
 def _rows(x):
@@ -109,27 +142,7 @@ def loss_and_grad_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, wit
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     xr = _rows(xs)
     pr = ps.detach().to(torch.float32).contiguous()
-    if not train:
-        er = None
-    elif eps is not None:
-        er = _rows(eps)
-    elif isinstance(icnf.rng, HIPRNG):                     # one draw of M B columns
-        er = draw_eps(icnf, _Buf(xr.view(-1), icnf.nvars, M * B, torch), M * B).arr.view(M, B, n_in)
-    else:
-        # the host generator, member by member in the order a loop of ``loss_and_grad`` consumes it (the member's probes, then
-        # its end time: base_icnf.loss_and_grad), so that one seed gives the members the draws that loop would; one upload
-        host, draws = _Buf(None, icnf.nvars, B, None), []
-        steer = t1 is None and icnf.STEER
-        ends = []
-        for _ in range(M):
-            draws.append(draw_eps(icnf, host, B).arr.reshape(B, n_in))
-            if steer:
-                ends.append(steer_tspan(icnf, mode)[1])
-        er = torch.from_numpy(np.stack(draws)).to(dev)
-        if steer:
-            t1 = np.asarray(ends, dtype=np.float32)
-    if t1 is None and icnf.STEER and train:                # (given probes, TestMode never steers, or a device generator: M draws)
-        t1 = np.asarray([steer_tspan(icnf, mode)[1] for _ in range(M)], dtype=np.float32)
+    er, t1 = _probes_and_ends(icnf, mode, train, M, B, n_in, xr, eps, t1)
     opts = _solve_opts(icnf, icnf.tspan)
     n_params = pr.shape[1]
     grads = torch.empty((M, n_params), dtype=torch.float32, device=dev)
@@ -244,3 +257,334 @@ def fit_many(model, verbosity: int, Xs, *, seeds=None):
     report = {"stats": {"time": time.perf_counter() - t0, "iterations": it}, "losses": np.stack(losses, axis=1) if losses else np.zeros((M, 0))}
     host = ps.cpu().numpy()
     return [(host[m].copy(), st) for m in range(M)], report
+
+
+# ---------------------------------------------------------------------------------------
+# scoring and sampling the members (include/cnfhip_ensemble_eval.h)
+# ---------------------------------------------------------------------------------------
+def ensemble_eval_capacity(icnf: ICNF, mode, B: int) -> int:
+    """The largest M one ``inference_many`` / ``generate_many`` launch takes for this model, mode and batch size
+    (cnf_ensemble_eval_capacity); 0: no ensemble form."""
+    m = _mode_id(mode)
+    if _refusal(icnf) is not None:
+        return 0
+    return int(_lib.lib().cnf_ensemble_eval_capacity(icnf.handle(), m, int(B)))
+
+
+def ensemble_eval_steps(icnf: ICNF, member: int):
+    """The step attempts of ``member`` in the last ``inference_many(with_steps=True)`` / ``generate_many(with_steps=True)``
+    CALL on this model (cnf_ensemble_eval_steps; the index counts within that call): rows ``(t, signed h, EEst, accepted)``.
+    A member that made more attempts than the call kept rows for (1024) returns the rows that were kept: its first ones."""
+    l, h = _lib.lib(), icnf.handle()
+    n = l.cnf_ensemble_eval_steps(h, int(member), None, 0)
+    if n < 0:
+        raise ValueError(f"no step attempts on record for ensemble member {member}")
+    kept = min(n, _TRACE_ROWS)                             # (what the library copies: min(attempts, cap, trace_cap))
+    rows = np.zeros((max(kept, 1), 4), dtype=np.float32)
+    l.cnf_ensemble_eval_steps(h, int(member), rows.ctypes.data, kept)
+    return rows[:kept]
+
+
+_TRACE_ROWS = 1024                                         # rows of step trace a member keeps at most
+
+
+def _trace_cap(opts, with_steps):
+    """Rows of step trace per member: a member that makes more attempts than this keeps its first ones."""
+    return min(int(opts.maxiters), _TRACE_ROWS) if with_steps else 0
+
+
+def _raise_failed(status):
+    l = _lib.lib()
+    for i, s in enumerate(status):
+        if s in (_lib.ERR_NONFINITE, _lib.ERR_MAXITERS):
+            raise _lib.CNFError(int(s), f"ensemble member {i}: " + l.cnf_status_string(int(s)).decode())
+
+
+def inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, with_steps=False):
+    """``inference`` of M members in one launch (cnf_inference_many).  ``xs`` (M, nvars, B): one data set per member (the
+    held-out folds), or (nvars, B): one data set scored by every member (bagging; expanded here, the kernel reads M copies);
+    ``ps`` (M, n_params); ``eps`` (M, n_in, B; TrainMode) and ``t1`` as ``loss_and_grad_many`` takes and draws them, in its
+    order.  Returns ``(logpx (M, B), (E, n, A) each (M, B), info)``, device tensors; ``info`` has ``stats`` and ``status`` per
+    member, ``losses`` (M,), the end times ``t1``, ``launches`` (kernel launches per ensemble call: 1, whatever M), ``calls``
+    (more than one when M exceeds ``ensemble_eval_capacity``), ``rerun`` (the members whose part of the launch gave up and
+    that were run again with ``inference``) and, with ``with_steps``, ``steps``: per member the rows ``(t, signed h, EEst,
+    accepted)`` of its step attempts (None for a member that was run again).  A member whose solve went non-finite or hit maxiters raises ``CNFError`` naming it;
+    ``NotImplementedError`` -- before anything is drawn -- for what ``loss_and_grad_many`` refuses."""
+    import torch
+    who = "inference_many"
+    if _is_torch(xs) and _is_torch(ps) and xs.dim() == 2 and ps.dim() == 2 and _refusal(icnf) is None:
+        xs = xs.unsqueeze(0).expand(ps.shape[0], *xs.shape)                # shared data: every member reads its own copy
+    m, M, B, n_in, t1 = _check_inputs(icnf, mode, xs, ps, eps, t1, who, "inference")
+    l, h = _lib.lib(), icnf.handle()
+    if not (xs.is_cuda and ps.is_cuda and (eps is None or eps.is_cuda)):
+        raise ValueError(f"{who}: torch tensors must live on the GPU")
+    cap = int(l.cnf_ensemble_eval_capacity(h, m, B))
+    if cap < 1:
+        raise NotImplementedError(f"{who}: no ensemble form for this model, mode or batch on this device "
+                                  "(cnf_ensemble_eval_capacity is 0)")
+    train = m == _lib.MODE_TRAIN
+    dev = xs.device
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    xr = _rows(xs)
+    pr = ps.detach().to(torch.float32).contiguous()
+    er, t1 = _probes_and_ends(icnf, mode, train, M, B, n_in, xr, eps, t1)
+    opts = _solve_opts(icnf, icnf.tspan)
+    logpx, regs = torch.empty((M, B), dtype=torch.float32, device=dev), torch.empty((M, 3, B), dtype=torch.float32, device=dev)
+    losses = np.empty(M, dtype=np.float32)
+    status = np.empty(M, dtype=np.int32)
+    stats = (_lib.cnf_solve_stats * M)()
+    tc = _trace_cap(opts, with_steps)
+    calls, steps = 0, []
+    for lo in range(0, M, cap):                            # M above the capacity: consecutive launches
+        n = min(cap, M - lo)
+        _lib.check(l.cnf_inference_many(
+            h, m, n, pr[lo].data_ptr(), xr[lo].data_ptr(), er[lo].data_ptr() if er is not None else None, B, C.byref(opts),
+            t1[lo:].ctypes.data if t1 is not None else None, logpx[lo].data_ptr(), regs[lo].data_ptr(), losses[lo:].ctypes.data,
+            status[lo:].ctypes.data, C.byref(stats, lo * C.sizeof(_lib.cnf_solve_stats)), tc, stream), h)
+        calls += 1
+        if with_steps:
+            steps += [ensemble_eval_steps(icnf, i) if status[lo + i] == _lib.OK else None for i in range(n)]
+    info = {"stats": [s.as_dict() for s in stats], "status": status, "launches": max(s.launches for s in stats), "calls": calls,
+            "rerun": [], "losses": losses, "t1": t1 if t1 is not None else np.full(M, icnf.tspan[1], dtype=np.float32)}
+    _raise_failed(status)
+    gave_up = [i for i in range(M) if status[i] != _lib.OK]
+    if gave_up:
+        # the existing route, its fallbacks included, on the member's own end time
+        from .base_icnf import loss_from_sums
+        span, steer = icnf.tspan, icnf.steer_rate
+        try:
+            icnf.steer_rate = 0.0
+            for i in gave_up:
+                if t1 is not None:
+                    icnf.tspan = (span[0], float(t1[i]))
+                args = dict(eps=er[i].t()) if train else {}
+                lp, rg, sums = inference(icnf, mode, xr[i].t(), pr[i], st, with_sums=True, **args)
+                logpx[i].copy_(lp)
+                regs[i].copy_(torch.stack(list(rg)))
+                losses[i] = loss_from_sums(icnf, mode, sums)
+                status[i] = _lib.OK
+                info["stats"][i] = dict(icnf.last_stats)
+        finally:
+            icnf.tspan, icnf.steer_rate = span, steer
+        info["rerun"] = gave_up
+    if with_steps:
+        info["steps"] = steps
+    icnf.last_stats = info["stats"][0]
+    return logpx, (regs[:, 0], regs[:, 1], regs[:, 2]), info
+
+
+def loss_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None):
+    """The M members' losses (``loss`` of each on its own data): ``inference_many(...)[2]["losses"]``, a numpy vector."""
+    return inference_many(icnf, mode, xs, ps, st, eps=eps, t1=t1)[2]["losses"]
+
+
+def _host_gen(icnf: ICNF):
+    """The numpy generator behind the model's scalar and index draws (a ``HIPRNG`` keeps one for them)."""
+    return icnf.rng._host if isinstance(icnf.rng, HIPRNG) else icnf.rng
+
+
+def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, t0=None, with_logp=False, with_steps=False):
+    """``generate`` of M members in one launch (cnf_generate_many): ``ps`` (M, n_params) on the device, ``z0`` and ``eps``
+    (M, n_in, n) device tensors or drawn as ``generate_prob`` draws them -- on a host generator member by member: the member's
+    base sample, its probes (drawn in TestMode too, and not used there), then its steered time; with a ``HIPRNG`` ONE draw of
+    M n columns for the base samples, one for the probes, then the M steered times from the generator's host side.  ``t0``:
+    the members' start times of the reversed span (what ``steer_tspan`` would return as the end time); every member ends at
+    ``tspan[0]``.  Returns ``xs (M, nvars, n)``, with ``with_logp`` ``(xs, logq (M, n))``: the log-density of each sample under
+    its member (``generate(..., with_logp=True)``).  ``icnf.last_ensemble_info`` holds ``stats``, ``status``, ``launches`` (2:
+    the solve and the column kernel), ``calls``, ``rerun``, ``t0`` and the inputs used (``z0``, ``eps``); after ``with_steps``
+    the members' step attempts are read with ``ensemble_eval_steps`` (``info["steps"]``).  Failures and refusals as
+    ``inference_many``."""
+    import torch
+    who = "generate_many"
+    m = _mode_id(mode)
+    why = _refusal(icnf)
+    if why is not None:
+        raise NotImplementedError(f"{who}: " + why)
+    if not _is_torch(ps):
+        raise NotImplementedError(f"{who} takes device tensors (host arrays: generate, one member at a time)")
+    n_params = icnf.nn.n_params_internal
+    if ps.dim() != 2 or ps.shape[0] < 1 or ps.shape[1] != n_params:
+        raise ValueError(f"ps must be (M, n_params = {n_params}), got {tuple(ps.shape)}")
+    M, n = int(ps.shape[0]), int(n)
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    n_in = icnf.nvars + n_augment_input(icnf)
+    train = m == _lib.MODE_TRAIN
+    for name, a in (("z0", z0), ("eps", eps)):
+        if a is not None and (not _is_torch(a) or tuple(a.shape) != (M, n_in, n)):
+            raise ValueError(f"{name} must be a device tensor (M = {M}, n_in = {n_in}, n = {n})")
+    if t0 is not None:
+        t0 = np.asarray(t0, dtype=np.float32).reshape(-1)
+        if t0.shape[0] != M:
+            raise ValueError(f"t0 must have one start time per member (M = {M}), got {t0.shape[0]}")
+        if not np.isfinite(t0).all() or (t0 == np.float32(icnf.tspan[0])).any():
+            raise ValueError("t0: every member needs a finite start time different from tspan[0]")
+    l, h = _lib.lib(), icnf.handle()
+    if not (ps.is_cuda and (z0 is None or z0.is_cuda) and (eps is None or eps.is_cuda)):
+        raise ValueError(f"{who}: torch tensors must live on the GPU")
+    cap = int(l.cnf_ensemble_eval_capacity(h, m, n))
+    if cap < 1:
+        raise NotImplementedError(f"{who}: no ensemble form for this model, mode or batch on this device "
+                                  "(cnf_ensemble_eval_capacity is 0)")
+    dev = ps.device
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    pr = ps.detach().to(torch.float32).contiguous()
+    zr = _rows(z0) if z0 is not None else None
+    er = _rows(eps) if eps is not None else None
+    steer = t0 is None and icnf.STEER and train
+    if isinstance(icnf.rng, HIPRNG):
+        if zr is None:
+            zr = icnf.rng.normal(n_in * M * n, dev.index if dev.index is not None else icnf.device).view(M, n, n_in)
+        if er is None:
+            er = draw_eps(icnf, _Buf(zr.reshape(-1), n_in, M * n, torch), M * n).arr.view(M, n, n_in)
+        if steer:
+            t0 = np.asarray([steer_tspan(icnf, mode)[1] for _ in range(M)], dtype=np.float32)
+    else:
+        host, zs, es, starts = _Buf(None, n_in, n, None), [], [], []
+        for _ in range(M):                                 # generate_prob's order, member by member
+            if zr is None:
+                zs.append(icnf.rng.standard_normal((n, n_in)).astype(np.float32))
+            if er is None:
+                es.append(draw_eps(icnf, host, n).arr.reshape(n, n_in))
+            if steer:
+                starts.append(steer_tspan(icnf, mode)[1])
+        if zr is None:
+            zr = torch.from_numpy(np.stack(zs)).to(dev)
+        if er is None:
+            er = torch.from_numpy(np.stack(es)).to(dev)
+        if steer:
+            t0 = np.asarray(starts, dtype=np.float32)
+    opts = _solve_opts(icnf, (icnf.tspan[1], icnf.tspan[0]))              # reverse(tspan)
+    xo = torch.empty((M, n, icnf.nvars), dtype=torch.float32, device=dev)
+    lq = torch.empty((M, n), dtype=torch.float32, device=dev) if with_logp else None
+    status = np.empty(M, dtype=np.int32)
+    stats = (_lib.cnf_solve_stats * M)()
+    tc = _trace_cap(opts, with_steps)
+    calls, steps = 0, []
+    for lo in range(0, M, cap):
+        k = min(cap, M - lo)
+        _lib.check(l.cnf_generate_many(
+            h, m, k, pr[lo].data_ptr(), zr[lo].data_ptr(), er[lo].data_ptr() if train else None, n, C.byref(opts),
+            t0[lo:].ctypes.data if t0 is not None else None, xo[lo].data_ptr(), lq[lo].data_ptr() if with_logp else None,
+            status[lo:].ctypes.data, C.byref(stats, lo * C.sizeof(_lib.cnf_solve_stats)), tc, stream), h)
+        calls += 1
+        if with_steps:
+            steps += [ensemble_eval_steps(icnf, i) if status[lo + i] == _lib.OK else None for i in range(k)]
+    info = {"stats": [s.as_dict() for s in stats], "status": status, "launches": max(s.launches for s in stats), "calls": calls,
+            "rerun": [], "t0": t0 if t0 is not None else np.full(M, icnf.tspan[1], dtype=np.float32),
+            "z0": zr.permute(0, 2, 1), "eps": er.permute(0, 2, 1)}
+    icnf.last_ensemble_info = info
+    _raise_failed(status)
+    gave_up = [i for i in range(M) if status[i] != _lib.OK]
+    if gave_up:
+        span, rate = icnf.tspan, icnf.steer_rate
+        try:
+            icnf.steer_rate = 0.0
+            for i in gave_up:
+                if t0 is not None:
+                    icnf.tspan = (span[0], float(t0[i]))
+                r = generate(icnf, mode, pr[i], st, n, z0=zr[i].t(), eps=er[i].t(), with_logp=with_logp)
+                xs_i = r[0] if with_logp else r
+                xo[i].copy_(torch.as_tensor(xs_i, device=dev)[: icnf.nvars].t())
+                if with_logp:
+                    lq[i].copy_(torch.as_tensor(r[1], device=dev))
+                status[i] = _lib.OK
+        finally:
+            icnf.tspan, icnf.steer_rate = span, rate
+        info["rerun"] = gave_up
+    if with_steps:
+        info["steps"] = steps
+    xs = xo.permute(0, 2, 1)
+    return (xs, lq) if with_logp else xs
+
+
+# ---- the bagged density: a mixture of the members ----
+def mixture_logpdf(logp, weights):
+    """``logsumexp_m(log w_m + logp[m, :])`` of an (M, n) matrix of the members' log-densities (numpy array or torch tensor;
+    the result is of the same kind).  A member of weight 0 or of log-density -inf contributes nothing; a column in which every
+    member does is -inf."""
+    if _is_torch(logp):
+        import torch
+        w = torch.as_tensor(np.asarray(weights, dtype=np.float64), device=logp.device).to(logp.dtype)
+        a = logp + torch.log(w)[:, None]
+        mx = a.max(dim=0).values
+        safe = torch.where(torch.isfinite(mx), mx, torch.zeros_like(mx))
+        return safe + torch.log(torch.exp(a - safe).sum(dim=0))
+    logp = np.asarray(logp)
+    with np.errstate(divide="ignore"):
+        a = logp + np.log(np.asarray(weights, dtype=logp.dtype))[:, None]
+        mx = a.max(axis=0)
+        safe = np.where(np.isfinite(mx), mx, 0)
+        return safe + np.log(np.exp(a - safe).sum(axis=0))
+
+
+def split_counts(rng, n: int, weights):
+    """How many of ``n`` draws of a mixture come from each member: ONE multinomial draw of the numpy generator ``rng``.  Returns
+    an int64 vector that sums to n; members may get none."""
+    w = check_weights(weights, len(weights))
+    return np.asarray(rng.multinomial(int(n), w), dtype=np.int64)
+
+
+def check_weights(weights, M):
+    """Mixture weights as float64: M finite values >= 0 that sum to 1 (within 1e-6: they are normalised); None: uniform."""
+    if weights is None:
+        return np.full(M, 1.0 / M)
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.shape[0] != M or not np.isfinite(w).all() or (w < 0).any() or abs(w.sum() - 1.0) > 1e-6:
+        raise ValueError(f"weights: {M} values >= 0 that sum to 1")
+    return w / w.sum()
+
+
+class EnsembleDist:
+    """The bagged density of M members of one architecture: ``sum_m w_m p_m`` (``weights``: uniform by default).  ``ps`` is the
+    (M, n_params) device tensor ``fit_many`` trains (or a list of its ``(ps_m, st)`` results)."""
+
+    def __init__(self, icnf: ICNF, mode, ps, st=None, weights=None):
+        why = _refusal(icnf)
+        if why is not None:
+            raise NotImplementedError("EnsembleDist: " + why)
+        _mode_id(mode)
+        if isinstance(ps, (list, tuple)):
+            import torch
+            ps = torch.from_numpy(np.stack([np.asarray(p[0] if isinstance(p, tuple) else p, dtype=np.float32) for p in ps]))
+            ps = ps.to(torch.device("cuda", icnf.device))
+        if not _is_torch(ps) or ps.dim() != 2:
+            raise ValueError("ps must be an (M, n_params) tensor")
+        self.m, self.mode, self.ps, self.st = icnf, mode, ps, st
+        self.weights = check_weights(weights, int(ps.shape[0]))
+
+    def __len__(self):
+        return self.m.nvars
+
+    def logpdf_members(self, A, *, eps=None):
+        """Every member's ``logpdf`` of the columns of ``A`` (nvars, n): (M, n), one launch."""
+        return inference_many(self.m, self.mode, A, self.ps, self.st, eps=eps)[0]
+
+    def logpdf(self, A, *, eps=None):
+        return mixture_logpdf(self.logpdf_members(A, eps=eps), self.weights)
+
+    def pdf(self, A, *, eps=None):
+        return self.logpdf(A, eps=eps).exp()
+
+    def rand(self, n: int, *, with_members=False):
+        """``n`` draws of the mixture, (nvars, n) on the device: the members' counts from one multinomial draw on the model's
+        host generator (``split_counts``), then ONE ``generate_many`` with ``B = max count`` columns per member, of which member
+        m keeps its first ``count_m``; the draws are ordered by member.  The launch computes M max(count) columns for n kept
+        ones: M max(count) - n are wasted (about (M - 1) / M of them for a one-hot mixture, few for uniform weights and
+        n >> M).  ``with_members``: also the member index of every column."""
+        import torch
+        if int(n) < 1:                                     # (nothing is drawn, nothing is launched)
+            if int(n) < 0:
+                raise ValueError("n must be >= 0")
+            out = torch.empty((self.m.nvars, 0), dtype=torch.float32, device=self.ps.device)
+            return (out, np.zeros(0, dtype=np.int64)) if with_members else out
+        counts = split_counts(_host_gen(self.m), n, self.weights)
+        xs = generate_many(self.m, self.mode, self.ps, self.st, int(counts.max()))
+        out = torch.cat([xs[i, :, :c] for i, c in enumerate(counts)], dim=1)
+        if with_members:
+            return out, np.repeat(np.arange(len(counts)), counts)
+        return out
+
+
+def logpdf_members(d: EnsembleDist, A, *, eps=None):
+    return d.logpdf_members(A, eps=eps)

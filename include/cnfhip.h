@@ -366,6 +366,10 @@ cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int B, float* 
 /* ---- ensembles: cnf_ensemble_capacity / cnf_loss_grad_many / cnf_ensemble_steps (declared in cnfhip_ensemble.h, part of this header) ---- */
 #include "cnfhip_ensemble.h"
 
+/* ---- ensemble inference and sampling: cnf_ensemble_eval_capacity / cnf_inference_many / cnf_generate_many /
+ * cnf_ensemble_eval_steps (declared in cnfhip_ensemble_eval.h, part of this header) ---- */
+#include "cnfhip_ensemble_eval.h"
+
 /* ---- device random numbers ------------------------------------------
  *
  * The library's own counter-based generator, the counterpart of the device RNG the reference draws eps and
