@@ -153,6 +153,13 @@ _ENSEMBLE_EVAL_SIGNATURES = {
     "cnf_ensemble_eval_steps": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int]),
 }
 ENSEMBLE_EVAL_EXPORTS = tuple(_ENSEMBLE_EVAL_SIGNATURES)
+# flow paths (include/cnfhip_path.h): likewise
+_PATH_SIGNATURES = {
+    "cnf_solve_path": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), _fp, C.c_int, _fp,
+                                 C.POINTER(cnf_solve_stats), C.c_void_p]),
+    "cnf_path_steps": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int]),
+}
+PATH_EXPORTS = tuple(_PATH_SIGNATURES)
 
 _lib = None
 
@@ -191,7 +198,7 @@ def lib():
             pass
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in list(_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) + list(_BASEGRAD_SIGNATURES.items()) + \
-                list(_ENSEMBLE_SIGNATURES.items()) + list(_ENSEMBLE_EVAL_SIGNATURES.items()):
+                list(_ENSEMBLE_SIGNATURES.items()) + list(_ENSEMBLE_EVAL_SIGNATURES.items()) + list(_PATH_SIGNATURES.items()):
             f = getattr(l, name)
             f.restype, f.argtypes = res, args
         _lib = l

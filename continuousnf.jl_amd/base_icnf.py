@@ -517,10 +517,11 @@ def _split_cond_args(icnf: ICNF, args):
     return None, args[0], (args[1] if len(args) > 1 else None)
 
 
-def inference_prob(icnf: ICNF, mode, xs, *args, eps=None) -> ODEProblem:
+def inference_prob(icnf: ICNF, mode, xs, *args, eps=None, tspan=None) -> ODEProblem:
     """src/base_icnf.jl:266-286 (``(xs, ps, st)``) and :288-309 (conditional: ``(xs, ys, ps, st)``).
     ``eps`` may be supplied (n_in x B) to make the call deterministic; by default it is drawn
-    from icnf.rng as the reference does."""
+    from icnf.rng as the reference does.  ``tspan``: the span to integrate instead of ``steer_tspan(icnf, mode)`` (no steer
+    variate is drawn then)."""
     ys, ps, st = _split_cond_args(icnf, args)
     m = _mode_id(mode)
     xb = _xs_colmajor(icnf, xs)
@@ -541,7 +542,7 @@ def inference_prob(icnf: ICNF, mode, xs, *args, eps=None) -> ODEProblem:
             raise ValueError("eps must have one column per sample")
     else:
         eb = draw_eps(icnf, xb, B)
-    return ODEProblem(icnf, mode, u0, eb, steer_tspan(icnf, mode), ps)
+    return ODEProblem(icnf, mode, u0, eb, tuple(tspan) if tspan is not None else steer_tspan(icnf, mode), ps)
 
 
 def _solve_opts(icnf: ICNF, tspan):
@@ -627,14 +628,15 @@ def _post(icnf, mode, fsol: _Buf):
     return logpx, (r[0], r[1], r[2])
 
 
-def generate_prob(icnf: ICNF, mode, ps, st, n: int, *, ys=None, z0=None, eps=None) -> ODEProblem:
+def generate_prob(icnf: ICNF, mode, ps, st, n: int, *, ys=None, z0=None, eps=None, tspan=None) -> ODEProblem:
     """src/base_icnf.jl:358-380 (first row of SURVEY.md 8f): the sampling problem -- the same
     right-hand side integrated over ``reverse(tspan)`` from a draw of the base distribution.
     ``z0`` ((nvars+naugs) x n) and ``eps`` may be supplied to make the call deterministic;
     by default both are drawn from icnf.rng (``rand!(rng, icnf.basedist, new_xs)``, ``rand!(rng, icnf.epsdist, eps)``); with a
     ``HIPRNG`` on the device, z0 first and eps from the elements after it, and the sample comes back as a device tensor.  A
     non-default ``basedist`` takes the standard normals the default would have drawn through ``mu + L n`` on the device
-    (cnf_base_sample), wherever they were drawn; a ``z0`` given by the caller is used as it is."""
+    (cnf_base_sample), wherever they were drawn; a ``z0`` given by the caller is used as it is.  ``tspan``: the span whose
+    reverse is integrated instead of ``steer_tspan(icnf, mode)`` (no steer variate is drawn then)."""
     n_in = icnf.nvars + n_augment_input(icnf)
     D = n_in + 1 + n_augment(icnf, mode)
     zb, eb = _generate_inputs(icnf, mode, ps, n, ys, z0, eps)
@@ -643,7 +645,7 @@ def generate_prob(icnf: ICNF, mode, ps, st, n: int, *, ys=None, z0=None, eps=Non
     src = zb.flat2d() if zb.torch is not None else zb.arr.reshape(n, n_in)
     v[:, :n_in] = src
     v[:, n_in:] = 0.0                                   # zrs = zeros(n_aug + 1, n)  (:367-368)
-    t0, t1 = steer_tspan(icnf, mode)
+    t0, t1 = tspan if tspan is not None else steer_tspan(icnf, mode)
     return ODEProblem(icnf, mode, u0, eb, (t1, t0), ps)  # reverse(tspan)  (:377)
 
 

@@ -179,8 +179,15 @@ struct cnf_ctx {
     DevBuf<float> ens_trace;      // [M][trace_cap][4] the members' step attempts (cnf_ensemble_eval_steps)
     int ensv_M = 0, ensv_tcap = 0;   // the last call that kept a trace: members, rows per member
     std::vector<int> ensv_att;    //   attempts per member (-1: the member gave up)
+    // cnf_solve_path (include/cnfhip_path.h): the save times on the device and the step pairs the in-launch route files (both
+    // allocated on first use), and the accepted steps of the last call on either route (cnf_path_steps)
+    DevBuf<float> d_saveat;
+    DevBuf<float> d_path_steps;   // [PATH_STEPS_CAP][2]
+    std::vector<float> path_t, path_h;
+    bool path_valid = false;
     std::string err;
 };
+static const int PATH_STEPS_CAP = 16384;
 
 static const int MAX_PARTIALS = 1024;
 
@@ -902,9 +909,16 @@ static void enqueue_post(cnf_handle h, int train, const StepState* state, const 
     launch_post_state(h->nd, train, state, h->U[0], h->U[1], ph.logpx, ph.regs, B, st, need_done, ph.sums5, h->post_part,
                       sums_word<unsigned>(h, SUMS_POST_TICKET));
 }
+// The path of a bare solve (cnf_solve_path): the caller's save times and where their slices go.  In the launch of the wave
+// kernel where it has a PATH form; else one attempt at a time on the per-stage kernels, k_dense_out behind every accepted step.
+struct PathHook {
+    const float* saveat;           // host, [K]: checked by the caller (finite, monotone along the span, inside it)
+    int K;
+    float* out;                    // device, [K][B][D]
+};
 static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const float* eps, float* u_out, int B,
                              const cnf_solve_opts* opts, cnf_solve_stats* stats, void* stream, Recorder* rec,
-                             bool final_sync = true, PostHook* post = nullptr);
+                             bool final_sync = true, PostHook* post = nullptr, PathHook* path = nullptr);
 
 // One-launch solves of this process: one at a time (two would each hold CUs the other is waiting for), except that
 // submitted launches may queue up behind each other on ONE stream.
@@ -993,7 +1007,7 @@ static cnf_status check_solve_opts(cnf_handle h, const cnf_solve_opts* opts) {
 
 static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const float* eps, float* u_out, int B,
                              const cnf_solve_opts* opts, cnf_solve_stats* stats, void* stream, Recorder* rec,
-                             bool final_sync, PostHook* post) {
+                             bool final_sync, PostHook* post, PathHook* path) {
     cnf_status s = check_call(h, mode, B);
     if (s != CNF_OK) return s;
     h->rec.end();                      // (every solve may overwrite what a record consists of)
@@ -1012,11 +1026,14 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
     const size_t n = (size_t)D * B;
     int launches = 0;
 
-    const bool use_mfma = k == CNF_KERNEL_MFMA && mfma_supported(h->mfma, h->nd, train, B);
+    // (a path needs k_2 .. k_6 of every accepted step in the handle's buffers: where the fused step kernel would run, its solve
+    // takes the per-stage generic kernel instead)
+    const bool mfma_ok = k == CNF_KERNEL_MFMA && mfma_supported(h->mfma, h->nd, train, B);
+    const bool use_mfma = mfma_ok && !path;
     // generic driver + an auxiliary MFMA kernel per stage.  Not for the recorded TrainMode solve of the gradient path: k_jvp_mfma
     // does not file the stage states the pullback starts from (k_mfma and the generic stage kernel do), so that solve runs the
     // generic stage kernel
-    h->trace_on = k == CNF_KERNEL_MFMA && !use_mfma && !(rec && train);
+    h->trace_on = k == CNF_KERNEL_MFMA && !mfma_ok && !(rec && train);
     h->aux_train = train != 0; h->aux_eps = eps;
     if (h->trace_on && (s = ensure_adj_images(h, (hipStream_t)stream)) != CNF_OK) return s;
     // lock-step over shards only matters when the controller decides something
@@ -1026,7 +1043,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
     if (nblk > 256) nblk = 256;
     if (use_mfma) nblk = mfma_grid_for(h->mfma, B, rec != nullptr, train != 0);
     // TestMode on k_trace3s: the trace launches write the error partials themselves (one pair per workgroup)
-    const bool trace_fused = h->trace_on && !lockstep && !rec && trace_fused_ok(h, B);
+    const bool trace_fused = h->trace_on && !lockstep && !rec && !path && trace_fused_ok(h, B);
     if (trace_fused) nblk = trace_fused_grid(B);
 
     // initial state
@@ -1052,7 +1069,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
     // ... or of config 5's network at eight columns per CU (k_solve_bcast, cnf_bcast.hip)
     // (the gradient's recorded forward too, where one tile per workgroup holds the batch)
     const bool bcast_rec = rec && !rec->wg && train && bcast_store_floats(B, h->device) == 0;
-    const bool bcast_ok = k == CNF_KERNEL_MFMA && (!rec || bcast_rec) && !wave_ok && bcast_solve_supported(h->nd, train != 0, B, h->device);
+    const bool bcast_ok = k == CNF_KERNEL_MFMA && (!rec || bcast_rec) && !wave_ok && !path && bcast_solve_supported(h->nd, train != 0, B, h->device);
     if (bcast_ok && !lockstep && !h->no_persist) {
         RESERVE(h, h->d_bimg, bcast_img_floats());          // (allocated on first use)
         if (!h->bimg_valid) { bcast_pack(h->nd, h->d_params, h->d_bimg, st); HIPCHK(h, hipGetLastError()); h->bimg_valid = true; }
@@ -1102,9 +1119,16 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
             dump = h->traj + n;                      // stage area of slot 0; u_n sits one array before
         }
         s = CNF_ERR_UNSUPPORTED;
+        WavePathArgs wp{};
+        if (path && wave_ok) {                           // the save times to the device; the launch files its accepted steps
+            RESERVE(h, h->d_saveat, (size_t)path->K);
+            RESERVE(h, h->d_path_steps, (size_t)2 * PATH_STEPS_CAP);
+            HIPCHK(h, hipMemcpyAsync(h->d_saveat, path->saveat, (size_t)path->K * sizeof(float), hipMemcpyHostToDevice, st));
+            wp.times = h->d_saveat; wp.K = path->K; wp.out = path->out; wp.steps = h->d_path_steps; wp.steps_cap = PATH_STEPS_CAP;
+        }
         if (wave_ok)
             s = wave_solve_launch(h->nd_wave, train != 0, h->d_params, h->nd.n_cond > 0 ? h->d_cond : nullptr, h->cbs, h->d_state, h->U[0],
-                                  eps, B, st, h->d_mirror + mslot, base, sv, rec ? rec->wg : nullptr);
+                                  eps, B, st, h->d_mirror + mslot, base, sv, rec ? rec->wg : nullptr, nullptr, path ? &wp : nullptr);
         // (the gradient in the launch of the solve exists on the wave kernel only: if that launch could not start, the caller
         // runs the streamed gradient path)
         if (rec && rec->wg && s != CNF_OK) { rec->wg_failed = true; return CNF_OK; }
@@ -1178,6 +1202,15 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
                                                  hipMemcpyDeviceToHost, st));
                     if (rec->wg) rec->wg_done = true;
                     else final_sync = true;
+                }
+                if (path && fin.naccept <= PATH_STEPS_CAP) {   // the accepted steps back from the device (cnf_path_steps)
+                    std::vector<float> pairs((size_t)2 * fin.naccept);
+                    if (fin.naccept > 0)
+                        HIPCHK(h, hipMemcpyAsync(pairs.data(), h->d_path_steps, pairs.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+                    HIPCHK(h, hipStreamSynchronize(st));
+                    h->path_t.resize((size_t)fin.naccept); h->path_h.resize((size_t)fin.naccept);
+                    for (int i = 0; i < fin.naccept; ++i) { h->path_t[i] = pairs[2 * i]; h->path_h[i] = pairs[2 * i + 1]; }
+                    h->path_valid = !fin.nonfinite;
                 }
                 if (final_sync) HIPCHK(h, hipStreamSynchronize(st));
                 fill_stats(stats, fin, (hairer ? 2 : 1) + 6 * attempts, wave_ok ? CNF_KERNEL_MFMA : k, launches);
@@ -1293,13 +1326,23 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
 
     StepState* cur_state = h->d_state;   // slot holding the live integrator state
     int pp = 0;                          // partials buffer the NEXT launch reads
-    if (lockstep || (rec && !use_mfma)) {
+    if (lockstep || (rec && !use_mfma) || path) {
         // one attempt at a time.  Lock-step: every shard must see the same global error norm before
         // the next attempt is sized.  Recording (gradient path): the host files the state after
-        // every accepted step.
+        // every accepted step.  A path: the host enqueues the interpolation of an accepted step (k_dense_out) before the next
+        // attempt overwrites k_2 .. k_6.
         StepState* snap = &h->h_state[0];
-        float h_attempt = 0.f;
+        float h_attempt = 0.f, t_attempt = 0.f;
         int seen_accept = 0;
+        int pcur = 0;                                    // the next save time
+        std::vector<float> path_t, path_h;
+        if (path) {
+            HIPCHK(h, hipMemcpyAsync(snap, h->d_state, sizeof(StepState), hipMemcpyDeviceToHost, st));
+            HIPCHK(h, hipStreamSynchronize(st));
+            h_attempt = snap->h; t_attempt = snap->t;
+            for (; pcur < path->K && path->saveat[pcur] == opts->t0; ++pcur)      // save times at the start: u0 itself
+                HIPCHK(h, hipMemcpyAsync(path->out + (size_t)pcur * n, h->U[0], n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        }
         if (rec) {
             float* slot0;
             if ((s = traj_slot(h, 0, &slot0)) != CNF_OK) return s;
@@ -1349,9 +1392,32 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
                 rec->hs.push_back(h_attempt);
                 rec->n = seen_accept;
             }
-            h_attempt = snap->h;
+            if (path && snap->naccept > seen_accept) {
+                // the accepted step (t_attempt, h_attempt) serves every save time up to its end -- the last step everything left;
+                // u_n, k_1 sit in the buffer set the controller has just left, u_{n+1}, k_7 in the current one
+                seen_accept = snap->naccept;
+                path_t.push_back(t_attempt); path_h.push_back(h_attempt);
+                const float t_end = snap->t, tdir = snap->tdir;
+                const int cur = snap->cur;
+                DenseOutArgs da{};
+                da.u = h->U[cur ^ 1]; da.unew = h->U[cur]; da.k[0] = h->K1[cur ^ 1]; da.k[6] = h->K1[cur];
+                for (int i = 0; i < 5; ++i) da.k[1 + i] = h->Ks[i];
+                da.n = n; da.out = path->out; da.h = h_attempt;
+                for (; pcur < path->K; ++pcur) {
+                    const float tau = path->saveat[pcur];
+                    if (!snap->done && tdir * (tau - t_end) > 0.f) break;
+                    const float th = (tau - t_attempt) / h_attempt;
+                    const int c = da.count++;
+                    da.slice[c] = pcur; da.exact[c] = (tau == t_end || !(th < 1.f)) ? 1 : 0;
+                    tsit5_dense_b(th, da.b[c]);
+                    if (da.count == DENSE_OUT_MAX) { launch_dense_out(da, st); ++launches; da.count = 0; }
+                }
+                if (da.count > 0) { launch_dense_out(da, st); ++launches; }
+            }
+            h_attempt = snap->h; t_attempt = snap->t;
             if (snap->done) break;
         }
+        if (path) { h->path_t.swap(path_t); h->path_h.swap(path_h); h->path_valid = !snap->nonfinite; }
         h->last_state = h->d_state;
         if (u_out) {
             launch_copy_final(h->d_state, h->U[0], h->U[1], u_out, n, st);
@@ -1465,6 +1531,44 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
     fill_stats(stats, fin, nf + 6 * (fin.naccept + fin.nreject), k, launches);
     if (fin.nonfinite) return fail(h, CNF_ERR_NONFINITE, "solver state became NaN/Inf");
     return CNF_OK;
+}
+
+// ---- flow paths (include/cnfhip_path.h) ----
+extern "C" cnf_status cnf_solve_path(cnf_handle h, int mode, const float* u0, const float* eps, float* u_out, int B,
+                                     const cnf_solve_opts* opts, const float* saveat_host, int K, float* path_out_dev,
+                                     cnf_solve_stats* stats, void* stream) {
+    // the save times against the span, before the handle is looked at
+    const char* bad = nullptr;
+    if (!opts || !saveat_host || !path_out_dev) bad = "null pointer";
+    else if (K < 1) bad = "saveat is empty";
+    else if (!std::isfinite(opts->t0) || !std::isfinite(opts->t1) || opts->t0 == opts->t1) bad = "empty or non-finite time span";
+    else {
+        const float dir = opts->t1 >= opts->t0 ? 1.f : -1.f;
+        for (int i = 0; i < K && !bad; ++i) {
+            const float tau = saveat_host[i];
+            if (!std::isfinite(tau)) bad = "saveat must be finite";
+            else if (dir * (tau - opts->t0) < 0.f || dir * (opts->t1 - tau) < 0.f) bad = "saveat must lie inside the time span";
+            else if (i > 0 && dir * (tau - saveat_host[i - 1]) < 0.f) bad = "saveat must be monotone along the direction of integration";
+        }
+    }
+    if (bad) return h ? fail(h, CNF_ERR_BAD_ARG, bad) : CNF_ERR_BAD_ARG;
+    if (!h) return CNF_ERR_BAD_ARG;
+    if (!u_out) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    if (h->shard_reduce != nullptr || h->shard_comm != nullptr)
+        return fail(h, CNF_ERR_UNSUPPORTED, "cnf_solve_path: lock-step shards have no path");
+    h->path_valid = false;
+    PathHook ph{saveat_host, K, path_out_dev};
+    return solve_core(h, mode, u0, eps, u_out, B, opts, stats, stream, nullptr, true, nullptr, &ph);
+}
+
+extern "C" int cnf_path_steps(cnf_handle h, float* t_host, float* h_host, int cap) {
+    if (!h || !h->path_valid) return -1;
+    const int n = (int)h->path_t.size();
+    for (int i = 0; i < n && i < cap; ++i) {
+        if (t_host) t_host[i] = h->path_t[i];
+        if (h_host) h_host[i] = h->path_h[i];
+    }
+    return n;
 }
 
 extern "C" cnf_status cnf_solve_tsit5_host(cnf_handle h, int mode, const float* u0, const float* eps,

@@ -109,6 +109,22 @@ __host__ __device__ inline void tsit5_row(int s, float* a) {
     for (int j = 0; j < 6; ++j) a[j] = A[s][j];
 }
 
+// Tsit5's free 4th-order interpolant (Tsitouras 2011, as OrdinaryDiffEq's Tsit5 uses it; third party in the reference, restated):
+// u(t_n + theta h) = u_n + h sum_i b_i(theta) k_i,  b_i(theta) = theta (r_i1 + theta (r_i2 + theta (r_i3 + theta r_i4))).
+// b_i(1) = a_7i and b_7(1) = 0; tests/test_path_host.py checks the digits against the tableau and the order conditions.
+// One copy for the host (the streamed path: cnf_solve_path) and the device (k_solve_wave<.., PATH>): fp32 Horner forms.
+__host__ __device__ inline void tsit5_dense_b(float th, float* b) {
+    const float R[7][4] = {
+        {1.0f, -2.763706197274826f, 2.9132554618219126f, -1.0530884977290216f},
+        {0.f, 0.13169999999999998f, -0.2234f, 0.1017f},
+        {0.f, 3.9302962368947516f, -5.941033872131505f, 2.490627285651253f},
+        {0.f, -12.411077166933676f, 30.33818863028232f, -16.548102889244902f},
+        {0.f, 37.50931341651104f, -88.1789048947664f, 47.37952196281928f},
+        {0.f, -27.896526289197286f, 65.09189467479366f, -34.87065786149661f},
+        {0.f, 1.5f, -4.0f, 2.5f}};
+    for (int i = 0; i < 7; ++i) b[i] = th * (R[i][0] + th * (R[i][1] + th * (R[i][2] + th * R[i][3])));
+}
+
 #ifdef __HIPCC__
 // ---- step controller (shared by k_controller and the fused MFMA step kernel) -----------------
 // OrdinaryDiffEq-style PI controller for Tsit5 (third party in the

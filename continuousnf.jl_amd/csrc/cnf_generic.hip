@@ -416,6 +416,49 @@ __global__ void k_copy_final(const StepState* st, const float* U0, const float* 
         out[i] = src[i];
 }
 
+// Dense output of one accepted step (cnf_solve_path, streamed route): u_n + h sum_i b_i(theta_s) k_i for every save time s the
+// step serves, from the integrator's buffers -- every element of u_n, k_1 .. k_7 read once, 16 bytes per request, whatever the
+// number of slices; `exact` slices are the accepted state itself.  Four consecutive elements per lane; the tail and any
+// operand that is not 16-byte aligned take scalar requests.
+__global__ void __launch_bounds__(256) k_dense_out(const DenseOutArgs a) {
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= a.n) return;
+    const int m = a.n - i < 4 ? (int)(a.n - i) : 4;
+    float u[4] = {0.f, 0.f, 0.f, 0.f}, un[4] = {0.f, 0.f, 0.f, 0.f}, k[7][4];
+    if (m == 4 && a.vec_in) {
+        const float4 t = *reinterpret_cast<const float4*>(a.u + i), w = *reinterpret_cast<const float4*>(a.unew + i);
+        u[0] = t.x; u[1] = t.y; u[2] = t.z; u[3] = t.w;
+        un[0] = w.x; un[1] = w.y; un[2] = w.z; un[3] = w.w;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            const float4 v = *reinterpret_cast<const float4*>(a.k[j] + i);
+            k[j][0] = v.x; k[j][1] = v.y; k[j][2] = v.z; k[j][3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const bool ok = e < m;
+            u[e] = ok ? a.u[i + e] : 0.f; un[e] = ok ? a.unew[i + e] : 0.f;
+#pragma unroll
+            for (int j = 0; j < 7; ++j) k[j][e] = ok ? a.k[j][i + e] : 0.f;
+        }
+    }
+    for (int s = 0; s < a.count; ++s) {
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float acc = a.b[s][0] * k[0][e];
+#pragma unroll
+            for (int j = 1; j < 7; ++j) acc += a.b[s][j] * k[j][e];
+            v[e] = a.exact[s] ? un[e] : u[e] + a.h * acc;
+        }
+        float* o = a.out + (size_t)a.slice[s] * a.n + i;
+        if (m == 4 && (reinterpret_cast<uintptr_t>(o) & 15) == 0) *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
+        else
+            for (int e = 0; e < m; ++e) o[e] = v[e];
+    }
+}
+
 // inference_sol (src/base_icnf.jl:167-189), one lane per column
 __global__ void k_post(NetDesc nd, int train, const float* __restrict__ fsol,
                        float* __restrict__ logpx, float* __restrict__ regs, int B) {
@@ -587,6 +630,14 @@ void launch_copy_final(const StepState* st, const float* U0, const float* U1, fl
     unsigned nb = (unsigned)((n + 255) / 256);
     if (nb > 2048) nb = 2048;
     hipLaunchKernelGGL(k_copy_final, dim3(nb), dim3(256), 0, s, st, U0, U1, out, n);
+}
+void launch_dense_out(const DenseOutArgs& a_, hipStream_t s) {
+    DenseOutArgs a = a_;
+    uintptr_t bits = reinterpret_cast<uintptr_t>(a.u) | reinterpret_cast<uintptr_t>(a.unew);
+    for (int j = 0; j < 7; ++j) bits |= reinterpret_cast<uintptr_t>(a.k[j]);
+    a.vec_in = (bits & 15) == 0 ? 1 : 0;
+    const size_t lanes = (a.n + 3) / 4;
+    hipLaunchKernelGGL(k_dense_out, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, a);
 }
 void launch_post(const NetDesc& nd, int train, const float* fsol, float* logpx, float* regs,
                  int B, hipStream_t s) {

@@ -42,6 +42,23 @@ struct NormArgs {
     unsigned seq;           //   with this tag
 };
 
+// Dense output of one accepted step at up to DENSE_OUT_MAX save times (k_dense_out; cnf_solve_path, streamed route)
+#define DENSE_OUT_MAX 8
+struct DenseOutArgs {
+    const float* u;         // u_n
+    const float* unew;      // the accepted state u_{n+1}
+    const float* k[7];      // k_1 .. k_7
+    size_t n;               // D*B
+    float* out;             // [K][n]
+    float h;                // signed step
+    int count;              // slices of this launch
+    int vec_in;             // every operand is 16-byte aligned (set by the launcher)
+    int slice[DENSE_OUT_MAX];     // which of the K slices
+    int exact[DENSE_OUT_MAX];     // the slice is the accepted state itself
+    float b[DENSE_OUT_MAX][7];    // b_i(theta) (tsit5_dense_b)
+};
+void launch_dense_out(const DenseOutArgs& a, hipStream_t s);
+
 void launch_rhs_generic(const NetDesc& nd, const float* P, const RhsArgs& a, hipStream_t s);
 void launch_norm_partials(const NormArgs& a, int nblocks, hipStream_t s);
 void launch_controller(StepState* st, const float* partials, int phase, float n_total,

@@ -52,6 +52,17 @@ int wave_ens_capacity(const NetDesc& nd, bool train, int B);
 // sv.logpx [M][B], sv.regs [M][3][B], sv.sums5 [5 M]) or a bare solve (sv.u0 -> sv.u_out, [M][B][D] each); sv.trace, when
 // set, is [M][sv.trace_cap][4].  Its capacity: workgroups of one wave the device holds at once / tiles, at most 512 tiles.
 int wave_ens_eval_capacity(const NetDesc& nd, bool train, int B);
+// The path of a plain solve in the same launch (k_solve_wave<.., PATH>; cnf_solve_path): every accepted step evaluates Tsit5's
+// interpolant at the save times it serves, from the k_1 .. k_7 it holds in registers, and stores those columns.
+struct WavePathArgs {
+    const float* times = nullptr;      // device, [K]: the save times, monotone along the direction of integration, inside the span
+    int K = 0;
+    float* out = nullptr;              // [K][B][D]: slice k in the layout of u_out
+    float* steps = nullptr;            // [steps_cap][2]: (t_n, signed h_n) of accepted step n (steps beyond the capacity are not filed)
+    int steps_cap = 0;
+};
+// `path`: the PATH form -- a plain solve (no grad, no ens) of one tile per workgroup, whatever the batch (B <= 8192), on the
+// tanh networks with one input tile; CNF_ERR_UNSUPPORTED for everything else (the caller takes the streamed path).
 cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_params, const float* cond, int cbs, StepState* st_out,
                              float* U0, const float* eps, int B, hipStream_t s, void* mirror, unsigned seq, const Solve3Args& sv,
-                             const WaveGradArgs* grad = nullptr, const WaveEnsLaunch* ens = nullptr);
+                             const WaveGradArgs* grad = nullptr, const WaveEnsLaunch* ens = nullptr, const WavePathArgs* path = nullptr);

@@ -33,7 +33,9 @@
 //         network: the network of the reference's benchmark suite);
 //   WGW   the tiles of a batch of at most 64 samples as the waves of one workgroup (LDS meeting), plain solves;
 //   ENS   M independent models of one architecture in one launch, the grid M x tiles: the recomputing GRAD forms
-//         (cnf_loss_grad_many) and the plain one-tile-per-workgroup forms (cnf_inference_many, cnf_generate_many).
+//         (cnf_loss_grad_many) and the plain one-tile-per-workgroup forms (cnf_inference_many, cnf_generate_many);
+//   PATH  the plain one-tile-per-workgroup solve that also stores the flow at the caller's save times, from Tsit5's interpolant
+//         over the k_1 .. k_7 of every accepted step (cnf_solve_path).
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -151,9 +153,15 @@ __device__ __forceinline__ float wv_quad_sum(float v) {
 // own abort word and writes its own final state.
 // Plain ENS forms (!GRAD: cnf_inference_many, cnf_generate_many): the same prologue without the gradient's stores; it also
 // moves the columns of a bare solve (sv.u0 / sv.u_out) and the member's step trace, and takes the member's own START time.
-template <int NI, int NH, int MODE, bool TANH, bool GRAD = false, bool ID2 = false, int WGW = 1, bool RICH = false, bool ENS = false>
-__global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wave(WaveArgs a, Solve3Args sv, const WvTab tab, const WaveEnsArgs en) {
+//
+// PATH (cnf_solve_path: plain solves, one tile per workgroup): an accepted step also stores the columns of every save time it
+// serves -- t_n < tau <= t_n + h along the direction, the last step everything left -- from Tsit5's interpolant over the k_1 .. k_7
+// in its registers (tsit5_dense_b: wave-uniform fp32 Horner forms), each lane its own rows, before u <- u_new.  A cursor into the
+// save times is kept across attempts; the step sequence is the plain form's, bit for bit.
+template <int NI, int NH, int MODE, bool TANH, bool GRAD = false, bool ID2 = false, int WGW = 1, bool RICH = false, bool ENS = false, bool PATH = false>
+__global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wave(WaveArgs a, Solve3Args sv, const WvTab tab, const WaveEnsArgs en, const WavePathArgs pa) {
     constexpr bool HELP = GRAD && WGW == 1;
+    static_assert(!PATH || (!GRAD && !ENS && WGW == 1), "PATH is a form of the plain solve with one tile per workgroup");
     static_assert(!ENS || (WGW == 1 && !RICH), "ENS forms have one tile per workgroup and no rich store");
     static_assert(!RICH || (GRAD && MODE == WV_VJP), "RICH is a form of the TrainMode / VJP gradient");
     constexpr int RR = 3 * NH + 3 * NI;                     // f32x4 per lane and stage evaluation in the rich store
@@ -618,6 +626,21 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
             if (alive) { ctrl_phase(&ns, 1, p0, p1, a.n_total); after_ctrl(); }
         }
     }
+    // ---- PATH: one slice of the path (this lane's z rows; the scalar rows from the lane groups that own them) ----
+    int pcur = 0;                                          // the next save time: the same in every lane and wave
+    auto path_store = [&](int k, const f32x4 (&z)[NI], float s) __attribute__((always_inline)) {
+        if (!live) return;
+        float* o = pa.out + ((size_t)k * (size_t)a.B + (size_t)smp) * D;
+#pragma unroll
+        for (int m = 0; m < NI; ++m)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const int r = 16 * m + 4 * q + j; if (r < n_in) o[r] = z[m][j]; }
+        if (sown) o[n_in + q] = s;
+    };
+    if constexpr (PATH) {                                  // save times at the start of the span: u0 itself
+        const float t_start = uni(ns.t0);
+        while (pcur < pa.K && uni(pa.times[pcur]) == t_start) { path_store(pcur, uz, us); ++pcur; }
+    }
     // ---- step attempts ----
     constexpr float BT[7] = {TS_BT1, TS_BT2, TS_BT3, TS_BT4, TS_BT5, TS_BT6, TS_BT7};
     f32x4 zt[NI];
@@ -724,6 +747,37 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
                 hsL[acc0] = h_att;
                 if (wid == 0 && lane == 0) a.g.hs_out[acc0] = h_att;
             } else gover = true;
+        }
+        if constexpr (PATH) {
+            if (accepted) {
+                if (wid == 0 && lane == 0 && acc0 < pa.steps_cap) { pa.steps[2 * acc0] = t_att; pa.steps[2 * acc0 + 1] = h_att; }
+                const float t_end = uni(ns.t), tdir = uni(ns.tdir);       // (the last step's end is t1 itself)
+                const bool last = __builtin_amdgcn_readfirstlane(ns.done) != 0;
+                while (pcur < pa.K) {
+                    const float tau = uni(pa.times[pcur]);
+                    if (!last && tdir * (tau - t_end) > 0.f) break;
+                    const float th = (tau - t_att) / h_att;
+                    if (tau == t_end || !(th < 1.f)) {     // the end of the step: the accepted state itself
+                        path_store(pcur, zt, uns);
+                    } else {
+                        float bth[7];
+                        tsit5_dense_b(th, bth);
+                        f32x4 zi[NI];
+#pragma unroll
+                        for (int m = 0; m < NI; ++m) {
+                            f32x4 acc = bth[0] * kz[0][m];
+#pragma unroll
+                            for (int j = 1; j < 7; ++j) acc += bth[j] * kz[j][m];
+                            zi[m] = uz[m] + h_att * acc;
+                        }
+                        float si = bth[0] * ks[0];
+#pragma unroll
+                        for (int j = 1; j < 7; ++j) si += bth[j] * ks[j];
+                        path_store(pcur, zi, us + h_att * si);
+                    }
+                    ++pcur;
+                }
+            }
         }
         if (accepted) {                                    // u <- u_new, k1 <- k7
 #pragma unroll
@@ -1293,7 +1347,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
     }
 }
 
-typedef void (*wave_fn)(WaveArgs, Solve3Args, const WvTab, const WaveEnsArgs);
+typedef void (*wave_fn)(WaveArgs, Solve3Args, const WvTab, const WaveEnsArgs, const WavePathArgs);
 // one workgroup of up to four waves (B <= 64): the README / regression networks and the one-layer benchmark network, TrainMode
 // (VJP) and TestMode, plain solve and gradient
 wave_fn pick_wg(int ni, int nh, int mode, bool grad, bool id2, bool tanh2) {
@@ -1389,6 +1443,22 @@ wave_fn pick_ens_plain(int ni, int nh, bool id2, bool test, bool jvp) {
         case 4: return WV_ENSP(4, false);
     }
 #undef WV_ENSP
+    return nullptr;
+}
+// the PATH forms (cnf_solve_path): tanh networks with one input tile, up to four hidden tiles -- one with the identity second
+wave_fn pick_path(int ni, int nh, int mode, bool tanh2, bool id2) {
+    if (ni != 1 || nh < 1 || nh > 4 || !(tanh2 || id2) || (id2 && nh != 1)) return nullptr;
+#define WV_PATH(NHV, ID2V) (mode == WV_VJP ? (wave_fn)k_solve_wave<1, NHV, WV_VJP, true, false, ID2V, 1, false, false, true> \
+                          : mode == WV_JVP ? (wave_fn)k_solve_wave<1, NHV, WV_JVP, true, false, ID2V, 1, false, false, true> \
+                                           : (wave_fn)k_solve_wave<1, NHV, WV_TEST, true, false, ID2V, 1, false, false, true>)
+    if (id2) return WV_PATH(1, true);
+    switch (nh) {
+        case 1: return WV_PATH(1, false);
+        case 2: return WV_PATH(2, false);
+        case 3: return WV_PATH(3, false);
+        case 4: return WV_PATH(4, false);
+    }
+#undef WV_PATH
     return nullptr;
 }
 template <int NI, int NH, bool TANH>
@@ -1511,8 +1581,9 @@ int wave_ens_eval_capacity(const NetDesc& nd, bool train, int B) {
 
 cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_params, const float* cond, int cbs, StepState* st_out,
                              float* U0, const float* eps, int B, hipStream_t s, void* mirror, unsigned seq, const Solve3Args& sv_,
-                             const WaveGradArgs* grad, const WaveEnsLaunch* ens) {
+                             const WaveGradArgs* grad, const WaveEnsLaunch* ens, const WavePathArgs* path) {
     if (!wave_solve_supported(nd, train, B)) return CNF_ERR_UNSUPPORTED;
+    if (path && (grad || ens || !path->times || !path->out || path->K < 1 || (path->steps_cap > 0 && !path->steps))) return CNF_ERR_BAD_ARG;
     if (ens && (cond || mirror || ens->M < 1 || ens->M > (grad ? wave_ens_capacity(nd, train, B) : wave_ens_eval_capacity(nd, train, B))))
         return CNF_ERR_UNSUPPORTED;
     if (grad && nd.n_cond > 0 && !grad->ys) return CNF_ERR_BAD_ARG;
@@ -1540,6 +1611,11 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
         if (wave_fn r = pick_grad_rich(nh, is_id2(nd), wfn != nullptr)) { if (wfn) wfn = r; else fn = r; }
         else return CNF_ERR_BAD_ARG;                       // (wave_grad_rich_floats said it exists)
     }
+    if (path) {                                            // one tile per workgroup, whatever the batch
+        fn = pick_path(ni, nh, mode, nd.acts[0] == 1 && nd.acts[1] == 1, is_id2(nd));
+        wfn = nullptr;
+        if (!fn || grid > 512) return CNF_ERR_UNSUPPORTED;
+    }
     if (wfn) { fn = wfn; grid = xwg ? (grid + 3) / 4 : 1; }
     WaveArgs a{};
     a.nd = nd; a.P = d_params; a.eps = eps; a.cond = cond; a.cbs = cbs; a.B = B;
@@ -1566,7 +1642,12 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
         en.tiles = grid; en.t1 = ens->t1; en.p_stride = ens->p_stride; en.traj_stride = ens->traj_stride; en.part_stride = ens->part_stride;
         grid *= ens->M;
     }
-    void* args[] = {&a, &sv, &tab, &en};
+    WavePathArgs pa{};
+    if (path) {
+        if (sv.xs || !sv.u0) return CNF_ERR_BAD_ARG;       // (a bare solve: the path starts from the caller's columns)
+        pa = *path;
+    }
+    void* args[] = {&a, &sv, &tab, &en, &pa};
     // (a gradient: the tile's main wave and its helper)
     if (hipLaunchKernel((const void*)fn, dim3(grid), dim3(wfn ? 64 * waves : (grad ? 128 : 64)), args, 0, s) != hipSuccess) {
         (void)hipGetLastError();

@@ -370,6 +370,10 @@ cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int B, float* 
  * cnf_ensemble_eval_steps (declared in cnfhip_ensemble_eval.h, part of this header) ---- */
 #include "cnfhip_ensemble_eval.h"
 
+/* ---- flow paths: the solve's columns at caller-given times, from Tsit5's interpolant (declared in cnfhip_path.h, part of this
+ * header) ---- */
+#include "cnfhip_path.h"
+
 /* ---- device random numbers ------------------------------------------
  *
  * The library's own counter-based generator, the counterpart of the device RNG the reference draws eps and
