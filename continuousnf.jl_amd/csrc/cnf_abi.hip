@@ -1004,6 +1004,19 @@ static cnf_status check_solve_opts(cnf_handle h, const cnf_solve_opts* opts) {
     if (opts->maxiters < 1) return fail(h, CNF_ERR_BAD_ARG, "maxiters must be >= 1");
     return CNF_OK;
 }
+// the state a solve starts from; n_partials: the error partials (blocks, tiles) that meet per attempt
+static StepState init_step_state(const cnf_solve_opts* opts, int n_partials) {
+    StepState init;
+    memset(&init, 0, sizeof init);
+    init.t = init.t0 = opts->t0;
+    init.dt = opts->dt;
+    init.qold = 1e-4f;
+    init.abstol = opts->abstol; init.reltol = opts->reltol;
+    init.adaptive = opts->adaptive ? 1 : 0;
+    init.n_partials = n_partials;
+    step_state_set_t1(&init, opts->t1);
+    return init;
+}
 
 static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const float* eps, float* u_out, int B,
                              const cnf_solve_opts* opts, cnf_solve_stats* stats, void* stream, Recorder* rec,
@@ -1048,14 +1061,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
 
     // initial state
     StepState* init = init_state(h);
-    memset(init, 0, sizeof *init);
-    init->t = init->t0 = opts->t0;
-    init->dt = opts->dt;
-    init->qold = 1e-4f;
-    init->abstol = opts->abstol; init->reltol = opts->reltol;
-    init->adaptive = opts->adaptive ? 1 : 0;
-    init->n_partials = nblk;
-    step_state_set_t1(init, opts->t1);
+    *init = init_step_state(opts, nblk);
     const bool hairer = opts->adaptive && opts->dt == 0.f;
     // The whole solve in ONE launch where the handle and the batch allow it (k_solve3b / k_solve3jb): the weights and the
     // Runge-Kutta rows stay on the CUs for all attempts, the workgroups exchange two floats per attempt.
@@ -1865,6 +1871,18 @@ static cnf_status ensure_grad_capacity(cnf_handle h, int B) {
     return CNF_OK;
 }
 
+// Step slots of an in-launch gradient's trajectory store of `per_step` floats per accepted step (one model's, or all the members'
+// of an ensemble): WV_GCAP, halved while the store exceeds 2^28 floats = 1 GiB (B = 8192: 256 steps), but 64 at least.
+// *fit: how many such stores keep those 64 slots each within that budget.
+static int traj_step_slots(size_t per_step, size_t* fit = nullptr) {
+    constexpr size_t budget = (size_t)1 << 28;
+    constexpr int least = 64;
+    if (fit) *fit = budget / (per_step * least);
+    int cap = WV_GCAP;
+    while (cap > least && per_step * cap > budget) cap /= 2;
+    return cap;
+}
+
 // loss_and_grad of small batches of a small two-layer tanh network (or a one-layer one through its appended identity layer):
 // the solve, the loss sums and the whole discrete adjoint in ONE launch, one wave per 16 samples (k_solve_wave<GRAD>,
 // cnf_wave.hip), then the sum of the waves' partials.  TrainMode (VJP compute mode) and TestMode (exact trace).  *done = false:
@@ -1880,8 +1898,7 @@ static cnf_status wave_loss_grad(cnf_handle h, int mode, const float* xs, const 
     if (opts->kernel == CNF_KERNEL_GENERIC || !wave_grad_supported(h->nd_wave, B, train)) return CNF_OK;
     {
         const size_t per_step = wave_grad_traj_floats(h->nd_wave, B);
-        int cap = WV_GCAP;
-        while (cap > 64 && per_step * cap > ((size_t)1 << 28)) cap /= 2;       // <= 1 GiB of trajectory (B = 8192: 256 steps)
+        int cap = traj_step_slots(per_step);
         // behind the trajectory: the step sizes, and one partial of the flat gradient per wave when there are more waves than
         // the arena's GRAD_MAX_KSPLIT partials
         const int waves = wave_grad_waves(B);
@@ -2608,111 +2625,174 @@ extern "C" int cnf_grad_steps(cnf_handle h, float* hs, int cap) {
 // Nothing of the handle's own model is touched: parameters, data and probes are the caller's arrays, every store is a buffer
 // of the ensemble's own.
 // ---------------------------------------------------------------------------------------
-// step slots per member: the single model's WV_GCAP, halved while the M trajectory stores exceed its budget of 1 GiB (>= 64)
-static int ens_step_slots(cnf_handle h, int M, int B) {
-    const size_t per_step = wave_grad_traj_floats(h->nd_wave, B);
-    int cap = WV_GCAP;
-    while (cap > 64 && per_step * cap * (size_t)M > ((size_t)1 << 28)) cap /= 2;
-    return cap;
+// the handles that take an ensemble call at all (both capacity calls answer 0 for the others)
+static bool ens_handle_ok(cnf_handle h, int mode) {
+    if (!h || (mode != CNF_MODE_TEST && mode != CNF_MODE_TRAIN)) return false;
+    return !(h->nd.n_cond > 0 || h->bd.kind || h->grad_ys || h->shard_reduce || h->shard_comm || h->no_persist);
 }
 extern "C" int cnf_ensemble_capacity(cnf_handle h, int mode, int B) {
-    if (!h || (mode != CNF_MODE_TEST && mode != CNF_MODE_TRAIN) || B < 1) return 0;
-    if (h->nd.n_cond > 0 || h->bd.kind || h->grad_ys || h->shard_reduce || h->shard_comm || h->no_persist) return 0;
+    if (B < 1 || !ens_handle_ok(h, mode)) return 0;
     if (hipSetDevice(h->device) != hipSuccess) { (void)hipGetLastError(); return 0; }
     int cap = wave_ens_capacity(h->nd_wave, mode == CNF_MODE_TRAIN, B);
     // ... and no more members than keep 64 step slots each within the trajectory budget of one model's call
-    const size_t fit = ((size_t)1 << 28) / (wave_grad_traj_floats(h->nd_wave, B) * 64);
+    size_t fit = 0;
+    traj_step_slots(wave_grad_traj_floats(h->nd_wave, B), &fit);
     if ((size_t)cap > fit) cap = (int)fit;
     return cap;
 }
 
-extern "C" cnf_status cnf_loss_grad_many(cnf_handle h, int mode, int M, const float* params_dev, const float* xs, const float* eps,
-                                         int B, const cnf_solve_opts* opts, const float* t1_host, float* loss_out, float* grad_dev,
-                                         int* status_out, cnf_solve_stats* stats_out, void* stream) {
+// ---- What cnf_loss_grad_many and ens_eval (cnf_inference_many, cnf_generate_many: further down) share, each step once: the
+// checks, the growth of the stores, the launch preamble and the read-back.  EnsCall is one call's arguments and, from ens_begin
+// to ens_finish, its lock and the common part of its Solve3Args. ----
+struct EnsCall {
+    bool grad, gen;                // cnf_loss_grad_many | ens_eval: sampling (times are the members' START times) or inference
+    int mode, M, B, trace_cap;
+    const cnf_solve_opts* opts;
+    const float* times;            // the members' own end (gen: start) times on the host, or null: opts' for all
+    hipStream_t st;
+    std::unique_lock<std::mutex> lock;     // g_persist_mu
+    bool hairer = false;
+    Solve3Args sv{};
+};
+constexpr size_t ENS_ST_F = (sizeof(StepState) + 3) / 4;     // floats of one member's final state in ens_fin / ens_hfin ...
+static size_t ens_fin_floats(int M) { return (size_t)M * (ENS_ST_F + 5); }      // ... and of all M, their five loss sums behind them
+
+static cnf_status ens_check(cnf_handle h, const EnsCall& c, bool null_ptr, const char* b_msg, const char* capacity_fn) {
     // (the arguments first, the handle last: what is wrong with a call is said before anything asks for a device)
-    if (mode != CNF_MODE_TEST && mode != CNF_MODE_TRAIN) return fail(h, CNF_ERR_BAD_ARG, "unknown mode");
-    const bool train = mode == CNF_MODE_TRAIN;
-    if (!params_dev || !xs || !opts || !loss_out || !grad_dev || !status_out || (train && !eps)) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
-    if (M < 1) return fail(h, CNF_ERR_BAD_SHAPE, "an ensemble has at least one member");
-    if (B < 1) return fail(h, CNF_ERR_BAD_SHAPE, "the loss is a mean over the batch: B must be >= 1");
+    if (c.mode != CNF_MODE_TEST && c.mode != CNF_MODE_TRAIN) return fail(h, CNF_ERR_BAD_ARG, "unknown mode");
+    if (null_ptr) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    if (c.M < 1) return fail(h, CNF_ERR_BAD_SHAPE, "an ensemble has at least one member");
+    if (c.B < 1) return fail(h, CNF_ERR_BAD_SHAPE, b_msg);
+    if (c.trace_cap < 0) return fail(h, CNF_ERR_BAD_ARG, "trace_cap must be >= 0");
     if (!h) return CNF_ERR_BAD_ARG;
-    cnf_status s = check_solve_opts(h, opts);
+    cnf_status s = check_solve_opts(h, c.opts);
     if (s != CNF_OK) return s;
-    if (t1_host)
-        for (int m = 0; m < M; ++m)
-            if (!std::isfinite(t1_host[m]) || t1_host[m] == opts->t0) return fail(h, CNF_ERR_BAD_ARG, "empty or NaN time span of a member");
+    if (c.times)
+        for (int m = 0; m < c.M; ++m)
+            if (!std::isfinite(c.times[m]) || c.times[m] == (c.gen ? c.opts->t1 : c.opts->t0))
+                return fail(h, CNF_ERR_BAD_ARG, "empty or NaN time span of a member");
     while (!h->collecting && !h->submitted.empty())       // (as any other call: the inferences submitted on the handle end first)
         if ((s = collect_one(h, nullptr)) != CNF_OK) return s;
-    if (opts->kernel == CNF_KERNEL_GENERIC) return fail(h, CNF_ERR_UNSUPPORTED, "the ensemble form exists on the wave kernels only");
-    const int capacity = cnf_ensemble_capacity(h, mode, B);
+    if (c.opts->kernel == CNF_KERNEL_GENERIC) return fail(h, CNF_ERR_UNSUPPORTED, "the ensemble form exists on the wave kernels only");
+    const int capacity = c.grad ? cnf_ensemble_capacity(h, c.mode, c.B) : cnf_ensemble_eval_capacity(h, c.mode, c.B);
     if (capacity < 1) return fail(h, CNF_ERR_UNSUPPORTED, "no ensemble form for this model, mode or batch");
-    if (M > capacity) return fail(h, CNF_ERR_UNSUPPORTED, "more members than one launch takes (cnf_ensemble_capacity)");
+    if (c.M > capacity)
+        return fail(h, CNF_ERR_UNSUPPORTED, (std::string("more members than one launch takes (") + capacity_fn + ")").c_str());
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    const NetDesc& nd = h->nd_wave;
-    const size_t Mz = (size_t)M, Bz = (size_t)B, n_in = (size_t)nd.n_in, D = n_in + (train ? 3 : 1), np = h->n_params;
-    const int tiles = wave_grad_waves(B), cap = ens_step_slots(h, M, B);
-    const size_t per_step = wave_grad_traj_floats(nd, B);
-    const size_t st_f = (sizeof(StepState) + 3) / 4, fin_f = Mz * (st_f + 5);
-    // ---- the members' stores: grown behind a wait for the device, so that steady-state calls allocate nothing ----
-    const size_t cols_f = Mz * Bz * (D + 4 + n_in);
-    if (per_step * cap * Mz > h->ens_traj.capacity() || Mz * cap > h->ens_hs.capacity() || Mz * tiles * np > h->ens_gpart.capacity() ||
-        cols_f > h->ens_cols.capacity() || Mz * WV_ENS_PART_FLOATS > h->ens_part.capacity() || 2 * Mz > h->ens_words.capacity() ||
-        fin_f > h->ens_fin.capacity() || fin_f + Mz > h->ens_hfin.capacity() || Mz > h->ens_t1.capacity()) {
-        HIPCHK(h, hipDeviceSynchronize());
-        h->ens_M = 0;
-        RESERVE(h, h->ens_traj, per_step * cap * Mz);
-        RESERVE(h, h->ens_hs, Mz * cap);
-        RESERVE(h, h->ens_gpart, Mz * tiles * np);
-        RESERVE(h, h->ens_cols, cols_f);
-        RESERVE(h, h->ens_words, 2 * Mz);
-        RESERVE(h, h->ens_fin, fin_f);
-        RESERVE(h, h->ens_hfin, fin_f + Mz);
-        RESERVE(h, h->ens_t1, Mz);
-        if (Mz * WV_ENS_PART_FLOATS > h->ens_part.capacity()) {
-            RESERVE(h, h->ens_part, Mz * WV_ENS_PART_FLOATS);
-            HIPCHK(h, hipMemset(h->ens_part, 0, Mz * WV_ENS_PART_FLOATS * sizeof(float)));
-            h->ens_base = 0;
-        }
-    }
-    h->rec.clear();                                        // (as every gradient call; the handle's own model is not touched)
-    h->ens_M = 0;
-    StepState* fin_dev = reinterpret_cast<StepState*>(h->ens_fin.data());
-    float* sums_dev = h->ens_fin + Mz * st_f;
+    return CNF_OK;
+}
 
-    std::unique_lock<std::mutex> persist_lock(g_persist_mu);       // one one-launch solve at a time in this process
-    if (g_submitted_inflight > 0 && g_submitted_stream != st) HIPCHK(h, hipStreamSynchronize(g_submitted_stream));
+// The members' stores: grown behind a wait for the device, so that steady-state calls allocate nothing.  cols_f: the column
+// store; traj_f, hs_f, gpart_f: the gradient's trajectories, step sizes and partials; trace_f: the eval calls' trace (floats)
+static cnf_status ens_grow(cnf_handle h, const EnsCall& c, size_t cols_f, size_t traj_f, size_t hs_f, size_t gpart_f, size_t trace_f) {
+    const size_t Mz = (size_t)c.M, fin_f = ens_fin_floats(c.M), part_f = Mz * WV_ENS_PART_FLOATS;
+    if (traj_f <= h->ens_traj.capacity() && hs_f <= h->ens_hs.capacity() && gpart_f <= h->ens_gpart.capacity() &&
+        trace_f <= h->ens_trace.capacity() && cols_f <= h->ens_cols.capacity() && part_f <= h->ens_part.capacity() &&
+        2 * Mz <= h->ens_words.capacity() && fin_f <= h->ens_fin.capacity() && fin_f + Mz <= h->ens_hfin.capacity() &&
+        Mz <= h->ens_t1.capacity())
+        return CNF_OK;
+    HIPCHK(h, hipDeviceSynchronize());
+    if (c.grad) h->ens_M = 0;
+    if (trace_f > h->ens_trace.capacity()) h->ensv_M = 0;
+    RESERVE(h, h->ens_traj, traj_f);
+    RESERVE(h, h->ens_hs, hs_f);
+    RESERVE(h, h->ens_gpart, gpart_f);
+    RESERVE(h, h->ens_cols, cols_f);
+    RESERVE(h, h->ens_words, 2 * Mz);
+    RESERVE(h, h->ens_fin, fin_f);
+    RESERVE(h, h->ens_hfin, fin_f + Mz);
+    RESERVE(h, h->ens_t1, Mz);
+    RESERVE(h, h->ens_trace, trace_f);
+    if (part_f > h->ens_part.capacity()) {
+        RESERVE(h, h->ens_part, part_f);
+        HIPCHK(h, hipMemset(h->ens_part, 0, part_f * sizeof(float)));
+        h->ens_base = 0;
+    }
+    return CNF_OK;
+}
+
+// The launch preamble: the lock, the meeting words, the members' times, the common part of c.sv.  (An early return of the
+// caller lets go of the lock with c.)
+static cnf_status ens_begin(cnf_handle h, EnsCall& c) {
+    const size_t Mz = (size_t)c.M;
+    const cnf_solve_opts* opts = c.opts;
+    c.lock = std::unique_lock<std::mutex>(g_persist_mu);   // one one-launch solve at a time in this process
+    if (g_submitted_inflight > 0 && g_submitted_stream != c.st) HIPCHK(h, hipStreamSynchronize(g_submitted_stream));
     // the meeting indices of this launch go on from where the earlier ones may have ended (a meeting per attempt, the two of the
     // initial dt, the loss sums; twice that: a workgroup placed late reads a base its member has already advanced), so that no
     // word an earlier call left can pass for news; when the 32 bits run out the words are cleared and the count starts again
     const unsigned long long span = 2ull * ((unsigned long long)opts->maxiters + 8ull);
     if ((unsigned long long)h->ens_base + span >= 0xffffffffull) {
-        HIPCHK(h, hipMemsetAsync(h->ens_part, 0, h->ens_part.capacity() * sizeof(float), st));
+        HIPCHK(h, hipMemsetAsync(h->ens_part, 0, h->ens_part.capacity() * sizeof(float), c.st));
         h->ens_base = 0;
     }
-    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->ens_words.data(), (int)h->ens_base, Mz, st));
-    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(h->ens_words.data() + Mz), 0, Mz, st));
+    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->ens_words.data(), (int)h->ens_base, Mz, c.st));
+    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(h->ens_words.data() + Mz), 0, Mz, c.st));
     h->ens_base += (unsigned)(span < 0xffffffffull ? span : 0xfffffffeull);
-    float* t1_pin = h->ens_hfin + fin_f;
-    if (t1_host) {
-        memcpy(t1_pin, t1_host, Mz * sizeof(float));
-        HIPCHK(h, hipMemcpyAsync(h->ens_t1, t1_pin, Mz * sizeof(float), hipMemcpyHostToDevice, st));
+    if (c.times) {                                         // (through the pinned tail of ens_hfin)
+        float* pin = h->ens_hfin + ens_fin_floats(c.M);
+        memcpy(pin, c.times, Mz * sizeof(float));
+        HIPCHK(h, hipMemcpyAsync(h->ens_t1, pin, Mz * sizeof(float), hipMemcpyHostToDevice, c.st));
     }
-    StepState init{};
-    init.t = init.t0 = opts->t0;
-    init.dt = opts->dt;
-    init.qold = 1e-4f;
-    init.abstol = opts->abstol; init.reltol = opts->reltol;
-    init.adaptive = opts->adaptive ? 1 : 0;
-    init.n_partials = tiles;
-    step_state_set_t1(&init, opts->t1);
-    const bool hairer = opts->adaptive && opts->dt == 0.f;
-    Solve3Args sv{};
+    c.hairer = opts->adaptive && opts->dt == 0.f;
+    Solve3Args& sv = c.sv;
     sv.part = h->ens_part; sv.base_dev = h->ens_words; sv.abort_flag = reinterpret_cast<int*>(h->ens_words.data() + Mz);
-    sv.maxiters = (int)opts->maxiters; sv.hairer = hairer ? 1 : 0; sv.init = init;
+    sv.maxiters = (int)opts->maxiters; sv.hairer = c.hairer ? 1 : 0; sv.init = init_step_state(opts, (c.B + 15) / 16);
     set_wait_bounds(h, sv);
+    return CNF_OK;
+}
+
+// The tail: the final states come back, the call waits for the stream (no mirror is polled) and lets go of the lock.  Then per
+// member its stats, its status and -- sums: the call has loss sums -- its loss.  steps[m]: the accepted steps (attempts: all
+// attempts) of a member that succeeded, -1 of the others.
+static cnf_status ens_finish(cnf_handle h, EnsCall& c, int launches, bool sums, float* loss_out, int* status_out,
+                             cnf_solve_stats* stats_out, std::vector<int>& steps, bool attempts) {
+    const size_t Mz = (size_t)c.M;
+    HIPCHK(h, hipMemcpyAsync(h->ens_hfin, h->ens_fin, ens_fin_floats(c.M) * sizeof(float), hipMemcpyDeviceToHost, c.st));
+    HIPCHK(h, hipStreamSynchronize(c.st));
+    c.lock.unlock();
+    steps.assign(Mz, -1);
+    for (int m = 0; m < c.M; ++m) {
+        StepState fin;
+        memcpy(&fin, h->ens_hfin + (size_t)m * ENS_ST_F, sizeof fin);
+        const int natt = fin.naccept + fin.nreject;
+        fill_stats(stats_out ? stats_out + m : nullptr, fin, (c.hairer ? 2 : 1) + 6 * natt, CNF_KERNEL_MFMA, launches);
+        float loss = NAN;
+        if (fin.n_partials < 0) status_out[m] = CNF_ERR_UNSUPPORTED;             // a wait ran out, or more steps than its store holds
+        else if (fin.nonfinite) status_out[m] = CNF_ERR_NONFINITE;
+        else if (!fin.done) status_out[m] = CNF_ERR_MAXITERS;
+        else {
+            // (a failure here is that member's status: the launch ran, so the call goes on and returns CNF_OK)
+            status_out[m] = sums ? cnf_loss_from_sums(h, c.mode, h->ens_hfin + Mz * ENS_ST_F + 5 * (size_t)m, &loss) : CNF_OK;
+            if (status_out[m] == CNF_OK) steps[m] = attempts ? natt : fin.naccept;
+            else loss = NAN;
+        }
+        if (loss_out) loss_out[m] = loss;
+    }
+    return CNF_OK;
+}
+
+extern "C" cnf_status cnf_loss_grad_many(cnf_handle h, int mode, int M, const float* params_dev, const float* xs, const float* eps,
+                                         int B, const cnf_solve_opts* opts, const float* t1_host, float* loss_out, float* grad_dev,
+                                         int* status_out, cnf_solve_stats* stats_out, void* stream) {
+    const bool train = mode == CNF_MODE_TRAIN;
+    EnsCall c{true, false, mode, M, B, 0, opts, t1_host, (hipStream_t)stream};
+    cnf_status s = ens_check(h, c, !params_dev || !xs || !opts || !loss_out || !grad_dev || !status_out || (train && !eps),
+                             "the loss is a mean over the batch: B must be >= 1", "cnf_ensemble_capacity");
+    if (s != CNF_OK) return s;
+    const NetDesc& nd = h->nd_wave;
+    const size_t Mz = (size_t)M, Bz = (size_t)B, n_in = (size_t)nd.n_in, D = n_in + (train ? 3 : 1), np = h->n_params;
+    const size_t per_step = wave_grad_traj_floats(nd, B);
+    // step slots per member: the single model's, for the M trajectory stores together
+    const int tiles = wave_grad_waves(B), cap = traj_step_slots(per_step * Mz);
+    if ((s = ens_grow(h, c, Mz * Bz * (D + 4 + n_in), per_step * cap * Mz, Mz * cap, Mz * tiles * np, 0)) != CNF_OK) return s;
+    h->rec.clear();                                        // (as every gradient call; the handle's own model is not touched)
+    h->ens_M = 0;
+    if ((s = ens_begin(h, c)) != CNF_OK) return s;
+    StepState* fin_dev = reinterpret_cast<StepState*>(h->ens_fin.data());
     float* cols = h->ens_cols;
-    sv.xs = xs; sv.logpx = cols + Mz * Bz * D; sv.regs = sv.logpx + Mz * Bz; sv.sums5 = sums_dev;
+    Solve3Args& sv = c.sv;
+    sv.xs = xs; sv.logpx = cols + Mz * Bz * D; sv.regs = sv.logpx + Mz * Bz; sv.sums5 = h->ens_fin + Mz * ENS_ST_F;
     WaveGradArgs wg;
     wg.traj = h->ens_traj; wg.traj_cap = cap; wg.hs_out = h->ens_hs; wg.gpart = h->ens_gpart;
     wg.lam_out = cols + Mz * Bz * (D + 4); wg.n_params = (int)np;
@@ -2721,33 +2801,13 @@ extern "C" cnf_status cnf_loss_grad_many(cnf_handle h, int mode, int M, const fl
     ens.M = M; ens.t1 = t1_host ? h->ens_t1.data() : nullptr;
     ens.p_stride = np; ens.traj_stride = per_step * cap; ens.part_stride = WV_ENS_PART_FLOATS;
     int launches = 0;                                      // kernel launches of this call, counted where they are made
-    s = wave_solve_launch(nd, train, params_dev, nullptr, 0, fin_dev, cols, eps, B, st, nullptr, 0, sv, &wg, &ens);
+    s = wave_solve_launch(nd, train, params_dev, nullptr, 0, fin_dev, cols, eps, B, c.st, nullptr, 0, sv, &wg, &ens);
     if (s != CNF_OK) return fail(h, s, "the ensemble launch failed to start");
     ++launches;
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, launch_grad_reduce_many(wg.gpart, grad_dev, (int)np, tiles, fin_dev, M, st));
+    HIPCHK(h, launch_grad_reduce_many(wg.gpart, grad_dev, (int)np, tiles, fin_dev, M, c.st));
     ++launches;
-    HIPCHK(h, hipMemcpyAsync(h->ens_hfin, h->ens_fin, fin_f * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));                   // (no mirror is polled: the call waits for the stream)
-    persist_lock.unlock();
-
-    h->ens_nacc.assign(Mz, -1);
-    for (int m = 0; m < M; ++m) {
-        StepState fin;
-        memcpy(&fin, h->ens_hfin + (size_t)m * st_f, sizeof fin);
-        const int attempts = fin.naccept + fin.nreject;
-        fill_stats(stats_out ? stats_out + m : nullptr, fin, (hairer ? 2 : 1) + 6 * attempts, CNF_KERNEL_MFMA, launches);
-        loss_out[m] = NAN;
-        if (fin.n_partials < 0) status_out[m] = CNF_ERR_UNSUPPORTED;             // a wait ran out, or more steps than its store holds
-        else if (fin.nonfinite) status_out[m] = CNF_ERR_NONFINITE;
-        else if (!fin.done) status_out[m] = CNF_ERR_MAXITERS;
-        else {
-            // (a failure here is that member's status: the launch ran, so the call goes on and returns CNF_OK)
-            status_out[m] = cnf_loss_from_sums(h, mode, h->ens_hfin + Mz * st_f + 5 * (size_t)m, loss_out + m);
-            if (status_out[m] == CNF_OK) h->ens_nacc[m] = fin.naccept;
-            else loss_out[m] = NAN;
-        }
-    }
+    if ((s = ens_finish(h, c, launches, true, loss_out, status_out, stats_out, h->ens_nacc, false)) != CNF_OK) return s;
     h->ens_M = M; h->ens_cap = cap;
     return CNF_OK;
 }
@@ -2774,8 +2834,7 @@ extern "C" int cnf_ensemble_steps(cnf_handle h, int member, float* hs, int cap) 
 // store are the ensemble's own buffers above; nothing of the handle's model, solver state or record is touched.
 // ---------------------------------------------------------------------------------------
 extern "C" int cnf_ensemble_eval_capacity(cnf_handle h, int mode, int B) {
-    if (!h || (mode != CNF_MODE_TEST && mode != CNF_MODE_TRAIN) || B < 1) return 0;
-    if (h->nd.n_cond > 0 || h->bd.kind || h->grad_ys || h->shard_reduce || h->shard_comm || h->no_persist) return 0;
+    if (B < 1 || !ens_handle_ok(h, mode)) return 0;
     if (hipSetDevice(h->device) != hipSuccess) { (void)hipGetLastError(); return 0; }
     return wave_ens_eval_capacity(h->nd_wave, mode == CNF_MODE_TRAIN, B);
 }
@@ -2785,85 +2844,19 @@ extern "C" int cnf_ensemble_eval_capacity(cnf_handle h, int mode, int B) {
 static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float* params_dev, const float* src, const float* eps, int B,
                            const cnf_solve_opts* opts, const float* times_host, float* out0, float* out1, float* loss_out,
                            int* status_out, cnf_solve_stats* stats_out, int trace_cap, void* stream) {
-    // (the arguments first, the handle last: what is wrong with a call is said before anything asks for a device)
-    if (mode != CNF_MODE_TEST && mode != CNF_MODE_TRAIN) return fail(h, CNF_ERR_BAD_ARG, "unknown mode");
     const bool train = mode == CNF_MODE_TRAIN;
-    if (!params_dev || !src || !opts || !out0 || (!gen && !out1) || !status_out || (train && !eps)) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
-    if (M < 1) return fail(h, CNF_ERR_BAD_SHAPE, "an ensemble has at least one member");
-    if (B < 1) return fail(h, CNF_ERR_BAD_SHAPE, "B must be >= 1");
-    if (trace_cap < 0) return fail(h, CNF_ERR_BAD_ARG, "trace_cap must be >= 0");
-    if (!h) return CNF_ERR_BAD_ARG;
-    cnf_status s = check_solve_opts(h, opts);
+    EnsCall c{false, gen, mode, M, B, trace_cap, opts, times_host, (hipStream_t)stream};
+    cnf_status s = ens_check(h, c, !params_dev || !src || !opts || !out0 || (!gen && !out1) || !status_out || (train && !eps),
+                             "B must be >= 1", "cnf_ensemble_eval_capacity");
     if (s != CNF_OK) return s;
-    if (times_host)
-        for (int m = 0; m < M; ++m)
-            if (!std::isfinite(times_host[m]) || times_host[m] == (gen ? opts->t1 : opts->t0))
-                return fail(h, CNF_ERR_BAD_ARG, "empty or NaN time span of a member");
-    while (!h->collecting && !h->submitted.empty())       // (as any other call: the inferences submitted on the handle end first)
-        if ((s = collect_one(h, nullptr)) != CNF_OK) return s;
-    if (opts->kernel == CNF_KERNEL_GENERIC) return fail(h, CNF_ERR_UNSUPPORTED, "the ensemble form exists on the wave kernels only");
-    const int capacity = cnf_ensemble_eval_capacity(h, mode, B);
-    if (capacity < 1) return fail(h, CNF_ERR_UNSUPPORTED, "no ensemble form for this model, mode or batch");
-    if (M > capacity) return fail(h, CNF_ERR_UNSUPPORTED, "more members than one launch takes (cnf_ensemble_eval_capacity)");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
     const NetDesc& nd = h->nd_wave;
     const size_t Mz = (size_t)M, Bz = (size_t)B, n_in = (size_t)nd.n_in, nv = (size_t)nd.nvars, D = n_in + (train ? 3 : 1);
-    const int tiles = (B + 15) / 16;
-    const size_t st_f = (sizeof(StepState) + 3) / 4, fin_f = Mz * (st_f + 5);
-    // ---- the members' stores: grown behind a wait for the device, so that steady-state calls allocate nothing ----
-    const size_t cols_f = Mz * Bz * (gen ? 2 * D : D);     // final columns (an inference) | u0 and the final columns (sampling)
-    const size_t trace_f = Mz * 4 * (size_t)trace_cap;
-    if (cols_f > h->ens_cols.capacity() || Mz * WV_ENS_PART_FLOATS > h->ens_part.capacity() || 2 * Mz > h->ens_words.capacity() ||
-        fin_f > h->ens_fin.capacity() || fin_f + Mz > h->ens_hfin.capacity() || Mz > h->ens_t1.capacity() ||
-        trace_f > h->ens_trace.capacity()) {
-        HIPCHK(h, hipDeviceSynchronize());
-        if (trace_f > h->ens_trace.capacity()) h->ensv_M = 0;
-        RESERVE(h, h->ens_cols, cols_f);
-        RESERVE(h, h->ens_words, 2 * Mz);
-        RESERVE(h, h->ens_fin, fin_f);
-        RESERVE(h, h->ens_hfin, fin_f + Mz);
-        RESERVE(h, h->ens_t1, Mz);
-        RESERVE(h, h->ens_trace, trace_f);
-        if (Mz * WV_ENS_PART_FLOATS > h->ens_part.capacity()) {
-            RESERVE(h, h->ens_part, Mz * WV_ENS_PART_FLOATS);
-            HIPCHK(h, hipMemset(h->ens_part, 0, Mz * WV_ENS_PART_FLOATS * sizeof(float)));
-            h->ens_base = 0;
-        }
-    }
+    // the column store: final columns (an inference) | u0 and the final columns (sampling)
+    if ((s = ens_grow(h, c, Mz * Bz * (gen ? 2 * D : D), 0, 0, 0, Mz * 4 * (size_t)trace_cap)) != CNF_OK) return s;
     if (trace_cap > 0) h->ensv_M = 0;                      // (the trace on record is about to be overwritten)
-    StepState* fin_dev = reinterpret_cast<StepState*>(h->ens_fin.data());
-    float* sums_dev = h->ens_fin + Mz * st_f;
-
-    std::unique_lock<std::mutex> persist_lock(g_persist_mu);       // one one-launch solve at a time in this process
-    if (g_submitted_inflight > 0 && g_submitted_stream != st) HIPCHK(h, hipStreamSynchronize(g_submitted_stream));
-    // the meeting indices go on from where the earlier ensemble launches may have ended (cnf_loss_grad_many has the reasons)
-    const unsigned long long span = 2ull * ((unsigned long long)opts->maxiters + 8ull);
-    if ((unsigned long long)h->ens_base + span >= 0xffffffffull) {
-        HIPCHK(h, hipMemsetAsync(h->ens_part, 0, h->ens_part.capacity() * sizeof(float), st));
-        h->ens_base = 0;
-    }
-    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->ens_words.data(), (int)h->ens_base, Mz, st));
-    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(h->ens_words.data() + Mz), 0, Mz, st));
-    h->ens_base += (unsigned)(span < 0xffffffffull ? span : 0xfffffffeull);
-    if (times_host) {
-        float* pin = h->ens_hfin + fin_f;
-        memcpy(pin, times_host, Mz * sizeof(float));
-        HIPCHK(h, hipMemcpyAsync(h->ens_t1, pin, Mz * sizeof(float), hipMemcpyHostToDevice, st));
-    }
-    StepState init{};
-    init.t = init.t0 = opts->t0;
-    init.dt = opts->dt;
-    init.qold = 1e-4f;
-    init.abstol = opts->abstol; init.reltol = opts->reltol;
-    init.adaptive = opts->adaptive ? 1 : 0;
-    init.n_partials = tiles;
-    step_state_set_t1(&init, opts->t1);
-    const bool hairer = opts->adaptive && opts->dt == 0.f;
-    Solve3Args sv{};
-    sv.part = h->ens_part; sv.base_dev = h->ens_words; sv.abort_flag = reinterpret_cast<int*>(h->ens_words.data() + Mz);
-    sv.maxiters = (int)opts->maxiters; sv.hairer = hairer ? 1 : 0; sv.init = init;
-    set_wait_bounds(h, sv);
+    if ((s = ens_begin(h, c)) != CNF_OK) return s;
+    hipStream_t st = c.st;
+    Solve3Args& sv = c.sv;
     if (trace_cap > 0) { sv.trace = h->ens_trace; sv.trace_cap = trace_cap; }
     float* cols = h->ens_cols;
     float* fsol = cols + Mz * Bz * D;                      // sampling: the final columns behind u0
@@ -2873,14 +2866,15 @@ static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float*
         HIPCHK(h, hipMemcpy2DAsync(cols, D * sizeof(float), src, n_in * sizeof(float), n_in * sizeof(float), Mz * Bz, hipMemcpyDeviceToDevice, st));
         sv.u0 = cols; sv.u_out = fsol;
     } else {
-        sv.xs = src; sv.logpx = out0; sv.regs = out1; sv.sums5 = sums_dev;
+        sv.xs = src; sv.logpx = out0; sv.regs = out1; sv.sums5 = h->ens_fin + Mz * ENS_ST_F;
     }
     WaveEnsLaunch ens;
     ens.M = M;
     (gen ? ens.t0 : ens.t1) = times_host ? h->ens_t1.data() : nullptr;
     ens.p_stride = h->n_params; ens.part_stride = WV_ENS_PART_FLOATS;
     int launches = 0;
-    s = wave_solve_launch(nd, train, params_dev, nullptr, 0, fin_dev, cols, eps, B, st, nullptr, 0, sv, nullptr, &ens);
+    s = wave_solve_launch(nd, train, params_dev, nullptr, 0, reinterpret_cast<StepState*>(h->ens_fin.data()), cols, eps, B, st, nullptr, 0,
+                          sv, nullptr, &ens);
     if (s != CNF_OK) return fail(h, s, "the ensemble launch failed to start");
     ++launches;
     HIPCHK(h, hipGetLastError());
@@ -2889,34 +2883,16 @@ static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float*
         HIPCHK(h, hipGetLastError());
         ++launches;
     }
-    HIPCHK(h, hipMemcpyAsync(h->ens_hfin, h->ens_fin, fin_f * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));                   // (no mirror is polled: the call waits for the stream)
-    persist_lock.unlock();
-
-    std::vector<int> att(Mz, -1);
+    std::vector<int> att;
+    if ((s = ens_finish(h, c, launches, !gen, loss_out, status_out, stats_out, att, true)) != CNF_OK) return s;
     bool any_bad = false;
-    for (int m = 0; m < M; ++m) {
-        StepState fin;
-        memcpy(&fin, h->ens_hfin + (size_t)m * st_f, sizeof fin);
-        const int attempts = fin.naccept + fin.nreject;
-        fill_stats(stats_out ? stats_out + m : nullptr, fin, (hairer ? 2 : 1) + 6 * attempts, CNF_KERNEL_MFMA, launches);
-        float loss = NAN;
-        if (fin.n_partials < 0) status_out[m] = CNF_ERR_UNSUPPORTED;             // a wait ran out
-        else if (fin.nonfinite) status_out[m] = CNF_ERR_NONFINITE;
-        else if (!fin.done) status_out[m] = CNF_ERR_MAXITERS;
-        else {
-            // (a failure here is that member's status: the launch ran, so the call goes on and returns CNF_OK)
-            status_out[m] = gen ? CNF_OK : cnf_loss_from_sums(h, mode, h->ens_hfin + Mz * st_f + 5 * (size_t)m, &loss);
-            if (status_out[m] == CNF_OK) att[m] = attempts; else loss = NAN;
-        }
-        if (loss_out) loss_out[m] = loss;
+    for (int m = 0; m < M; ++m)
         if (status_out[m] != CNF_OK) {                     // nothing of such a member is valid: NaN, whatever the kernel left
             any_bad = true;
             const size_t n0 = gen ? Bz * nv : Bz, n1 = gen ? Bz : 3 * Bz;
             HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(out0 + (size_t)m * n0), 0x7fc00000, n0, st));
             if (out1) HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(out1 + (size_t)m * n1), 0x7fc00000, n1, st));
         }
-    }
     if (any_bad) HIPCHK(h, hipStreamSynchronize(st));
     if (trace_cap > 0) { h->ensv_att.swap(att); h->ensv_M = M; h->ensv_tcap = trace_cap; }
     return CNF_OK;

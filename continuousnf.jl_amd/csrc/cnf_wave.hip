@@ -1347,144 +1347,97 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
     }
 }
 
+}  // namespace
+
+// ---- which instantiation runs a call: cnf_wave_variants.h says which exist, wave_instance maps its answer to the kernel ----
+#include <tuple>
+#include "cnf_wave_variants.h"
+
+namespace {
+
+static_assert(WV_VJP == WVM_VJP && WV_JVP == WVM_JVP && WV_TEST == WVM_TEST, "cnf_wave_variants.h numbers the modes as the kernel does");
 typedef void (*wave_fn)(WaveArgs, Solve3Args, const WvTab, const WaveEnsArgs, const WavePathArgs);
-// one workgroup of up to four waves (B <= 64): the README / regression networks and the one-layer benchmark network, TrainMode
-// (VJP) and TestMode, plain solve and gradient
-wave_fn pick_wg(int ni, int nh, int mode, bool grad, bool id2, bool tanh2) {
-    if (grad) return nullptr;            // (gradients: one tile per workgroup + its helper wave, whatever the batch)
-    if (ni != 1 || !(tanh2 || id2)) return nullptr;
-    const bool t = mode == WV_TEST;
-    if (id2)
-        return (nh != 1 || mode == WV_JVP) ? nullptr
-             : (t ? (wave_fn)k_solve_wave<1, 1, WV_TEST, true, false, true, 4> : (wave_fn)k_solve_wave<1, 1, WV_VJP, true, false, true, 4>);
-#define WV_WG(NHV) (mode == WV_VJP ? (wave_fn)k_solve_wave<1, NHV, WV_VJP, true, false, false, 4> \
-                  : mode == WV_JVP ? (wave_fn)k_solve_wave<1, NHV, WV_JVP, true, false, false, 4> : (wave_fn)k_solve_wave<1, NHV, WV_TEST, true, false, false, 4>)
-    switch (nh) {
-        case 1: return WV_WG(1);
-        case 2: return WV_WG(2);
-        case 3: return WV_WG(3);
-        case 4: return WV_WG(4);
-    }
-#undef WV_WG
+constexpr int WV_M_VJP = 1, WV_M_TEST = 4, WV_M_ALL = 7;     // the modes a row of wave_instance is instantiated for: bit 1 << MODE
+
+// the mode, among those of MODES
+template <int MODES, int NI, int NH, bool TANH, bool GRAD, bool ID2, int WGW, bool RICH, bool ENS, bool PATH>
+wave_fn wave_instance_mode(int mode) {
+    if constexpr ((MODES & (1 << WV_VJP)) != 0) if (mode == WV_VJP) return (wave_fn)k_solve_wave<NI, NH, WV_VJP, TANH, GRAD, ID2, WGW, RICH, ENS, PATH>;
+    if constexpr ((MODES & (1 << WV_JVP)) != 0) if (mode == WV_JVP) return (wave_fn)k_solve_wave<NI, NH, WV_JVP, TANH, GRAD, ID2, WGW, RICH, ENS, PATH>;
+    if constexpr ((MODES & (1 << WV_TEST)) != 0) if (mode == WV_TEST) return (wave_fn)k_solve_wave<NI, NH, WV_TEST, TANH, GRAD, ID2, WGW, RICH, ENS, PATH>;
     return nullptr;
 }
-// the RICH form of the TrainMode / VJP gradient (the forward pass files its intermediates)
-wave_fn pick_grad_rich(int nh, bool id2, bool wg) {
-    if (wg) return nullptr;
-    if (id2) return nh == 1 ? (wave_fn)k_solve_wave<1, 1, WV_VJP, true, true, true, 1, true> : nullptr;
-    switch (nh) {
-        case 1: return (wave_fn)k_solve_wave<1, 1, WV_VJP, true, true, false, 1, true>;
-        case 2: return (wave_fn)k_solve_wave<1, 2, WV_VJP, true, true, false, 1, true>;
-        case 3: return (wave_fn)k_solve_wave<1, 3, WV_VJP, true, true, false, 1, true>;
-        case 4: return (wave_fn)k_solve_wave<1, 4, WV_VJP, true, true, false, 1, true>;
+// the tiles: (1, 1..4) -- (1, 1) alone with the identity compiled out -- and, on the plain form, (2, 6)
+template <int MODES, bool TANH, bool GRAD, bool ID2, int WGW, bool RICH, bool ENS, bool PATH>
+wave_fn wave_instance_tiles(int ni, int nh, int mode) {
+#define WV_TILES(NIV, NHV) if (ni == NIV && nh == NHV) return wave_instance_mode<MODES, NIV, NHV, TANH, GRAD, ID2, WGW, RICH, ENS, PATH>(mode)
+    WV_TILES(1, 1);
+    if constexpr (!ID2) {
+        WV_TILES(1, 2);
+        WV_TILES(1, 3);
+        WV_TILES(1, 4);
+        if constexpr (!GRAD && WGW == 1 && !ENS && !PATH) WV_TILES(2, 6);
     }
+#undef WV_TILES
     return nullptr;
 }
-wave_fn pick_grad(int ni, int nh, bool id2, bool test = false, bool jvp = false) {
-    if (ni != 1) return nullptr;
-    if (jvp && !test) {
-        if (id2) return nh == 1 ? (wave_fn)k_solve_wave<1, 1, WV_JVP, true, true, true> : nullptr;
-        switch (nh) {
-            case 1: return (wave_fn)k_solve_wave<1, 1, WV_JVP, true, true>;
-            case 2: return (wave_fn)k_solve_wave<1, 2, WV_JVP, true, true>;
-            case 3: return (wave_fn)k_solve_wave<1, 3, WV_JVP, true, true>;
-            case 4: return (wave_fn)k_solve_wave<1, 4, WV_JVP, true, true>;
-            default: return nullptr;
-        }
-    }
-    if (id2) return nh != 1 ? nullptr : test ? (wave_fn)k_solve_wave<1, 1, WV_TEST, true, true, true> : (wave_fn)k_solve_wave<1, 1, WV_VJP, true, true, true>;
-    if (test)
-        switch (nh) {
-            case 1: return (wave_fn)k_solve_wave<1, 1, WV_TEST, true, true>;
-            case 2: return (wave_fn)k_solve_wave<1, 2, WV_TEST, true, true>;
-            case 3: return (wave_fn)k_solve_wave<1, 3, WV_TEST, true, true>;
-            case 4: return (wave_fn)k_solve_wave<1, 4, WV_TEST, true, true>;
-            default: return nullptr;
-        }
-    switch (nh) {
-        case 1: return (wave_fn)k_solve_wave<1, 1, WV_VJP, true, true>;
-        case 2: return (wave_fn)k_solve_wave<1, 2, WV_VJP, true, true>;
-        case 3: return (wave_fn)k_solve_wave<1, 3, WV_VJP, true, true>;
-        case 4: return (wave_fn)k_solve_wave<1, 4, WV_VJP, true, true>;
-    }
+// One row per set of flags that is instantiated, each for the tiles above and the modes it names: these rows ARE the library's
+// k_solve_wave kernels (112 of them).  nullptr: no such kernel -- wave_variant does not return such a tuple.
+wave_fn wave_instance(const WaveVariant& v) {
+#define WV_ROW(MODES, TANH, GRAD, ID2, WGW, RICH, ENS, PATH)                                                                         \
+    if (v.tanh == TANH && v.grad == GRAD && v.id2 == ID2 && v.wgw == WGW && v.rich == RICH && v.ens == ENS && v.path == PATH) \
+        return wave_instance_tiles<MODES, TANH, GRAD, ID2, WGW, RICH, ENS, PATH>(v.ni, v.nh, v.mode)
+    //     modes      TANH   GRAD   ID2    WGW RICH   ENS    PATH
+    WV_ROW(WV_M_ALL,  true,  false, false, 1, false, false, false);     // WF_PLAIN
+    WV_ROW(WV_M_ALL,  false, false, false, 1, false, false, false);
+    WV_ROW(WV_M_ALL,  true,  false, true,  1, false, false, false);
+    WV_ROW(WV_M_ALL,  true,  false, false, 4, false, false, false);     // WF_WG4
+    WV_ROW(WV_M_VJP | WV_M_TEST, true, false, true, 4, false, false, false);
+    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, false, false);     // WF_GRAD
+    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, false, false);
+    WV_ROW(WV_M_VJP,  true,  true,  false, 1, true,  false, false);     // WF_GRAD_RICH
+    WV_ROW(WV_M_VJP,  true,  true,  true,  1, true,  false, false);
+    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, true,  false);     // WF_ENS_GRAD
+    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, true,  false);
+    WV_ROW(WV_M_ALL,  true,  false, false, 1, false, true,  false);     // WF_ENS_PLAIN
+    WV_ROW(WV_M_ALL,  true,  false, true,  1, false, true,  false);
+    WV_ROW(WV_M_ALL,  true,  false, false, 1, false, false, true);      // WF_PATH
+    WV_ROW(WV_M_ALL,  true,  false, true,  1, false, false, true);
+#undef WV_ROW
     return nullptr;
-}
-// the ENS forms of what pick_grad returns (no RICH form: its gradient is the recomputing form's bit for bit, and the ensemble
-// is there to fill the chip, not to save products)
-wave_fn pick_grad_ens(int ni, int nh, bool id2, bool test, bool jvp) {
-    if (ni != 1 || nh < 1 || nh > 4 || (id2 && nh != 1)) return nullptr;
-    const int mode = test ? WV_TEST : (jvp ? WV_JVP : WV_VJP);
-#define WV_ENS(NHV, ID2V) (mode == WV_VJP ? (wave_fn)k_solve_wave<1, NHV, WV_VJP, true, true, ID2V, 1, false, true> \
-                         : mode == WV_JVP ? (wave_fn)k_solve_wave<1, NHV, WV_JVP, true, true, ID2V, 1, false, true> \
-                                          : (wave_fn)k_solve_wave<1, NHV, WV_TEST, true, true, ID2V, 1, false, true>)
-    if (id2) return WV_ENS(1, true);
-    switch (nh) {
-        case 1: return WV_ENS(1, false);
-        case 2: return WV_ENS(2, false);
-        case 3: return WV_ENS(3, false);
-        case 4: return WV_ENS(4, false);
-    }
-#undef WV_ENS
-    return nullptr;
-}
-// the plain ENS forms (cnf_inference_many, cnf_generate_many): the envelope of pick_grad_ens, so that every ensemble that can
-// be trained in one launch can be scored and sampled in one
-wave_fn pick_ens_plain(int ni, int nh, bool id2, bool test, bool jvp) {
-    if (ni != 1 || nh < 1 || nh > 4 || (id2 && nh != 1)) return nullptr;
-    const int mode = test ? WV_TEST : (jvp ? WV_JVP : WV_VJP);
-#define WV_ENSP(NHV, ID2V) (mode == WV_VJP ? (wave_fn)k_solve_wave<1, NHV, WV_VJP, true, false, ID2V, 1, false, true> \
-                          : mode == WV_JVP ? (wave_fn)k_solve_wave<1, NHV, WV_JVP, true, false, ID2V, 1, false, true> \
-                                           : (wave_fn)k_solve_wave<1, NHV, WV_TEST, true, false, ID2V, 1, false, true>)
-    if (id2) return WV_ENSP(1, true);
-    switch (nh) {
-        case 1: return WV_ENSP(1, false);
-        case 2: return WV_ENSP(2, false);
-        case 3: return WV_ENSP(3, false);
-        case 4: return WV_ENSP(4, false);
-    }
-#undef WV_ENSP
-    return nullptr;
-}
-// the PATH forms (cnf_solve_path): tanh networks with one input tile, up to four hidden tiles -- one with the identity second
-wave_fn pick_path(int ni, int nh, int mode, bool tanh2, bool id2) {
-    if (ni != 1 || nh < 1 || nh > 4 || !(tanh2 || id2) || (id2 && nh != 1)) return nullptr;
-#define WV_PATH(NHV, ID2V) (mode == WV_VJP ? (wave_fn)k_solve_wave<1, NHV, WV_VJP, true, false, ID2V, 1, false, false, true> \
-                          : mode == WV_JVP ? (wave_fn)k_solve_wave<1, NHV, WV_JVP, true, false, ID2V, 1, false, false, true> \
-                                           : (wave_fn)k_solve_wave<1, NHV, WV_TEST, true, false, ID2V, 1, false, false, true>)
-    if (id2) return WV_PATH(1, true);
-    switch (nh) {
-        case 1: return WV_PATH(1, false);
-        case 2: return WV_PATH(2, false);
-        case 3: return WV_PATH(3, false);
-        case 4: return WV_PATH(4, false);
-    }
-#undef WV_PATH
-    return nullptr;
-}
-template <int NI, int NH, bool TANH>
-wave_fn pick_mode(int mode) {
-    return mode == WV_VJP ? (wave_fn)k_solve_wave<NI, NH, WV_VJP, TANH>
-         : mode == WV_JVP ? (wave_fn)k_solve_wave<NI, NH, WV_JVP, TANH> : (wave_fn)k_solve_wave<NI, NH, WV_TEST, TANH>;
-}
-template <bool TANH>
-wave_fn pick_shape_t(int ni, int nh, int mode) {
-    if (ni == 1 && nh == 1) return pick_mode<1, 1, TANH>(mode);
-    if (ni == 1 && nh == 2) return pick_mode<1, 2, TANH>(mode);
-    if (ni == 1 && nh == 3) return pick_mode<1, 3, TANH>(mode);
-    if (ni == 1 && nh == 4) return pick_mode<1, 4, TANH>(mode);
-    if (ni == 2 && nh == 6) return pick_mode<2, 6, TANH>(mode);
-    return nullptr;
-}
-wave_fn pick_shape(int ni, int nh, int mode, bool tanh2 = true, bool id2 = false) {
-    if (id2 && ni == 1 && nh == 1)       // (tanh, identity) with one tile each: the activation compiled out
-        return mode == WV_VJP ? (wave_fn)k_solve_wave<1, 1, WV_VJP, true, false, true>
-             : mode == WV_JVP ? (wave_fn)k_solve_wave<1, 1, WV_JVP, true, false, true> : (wave_fn)k_solve_wave<1, 1, WV_TEST, true, false, true>;
-    return tanh2 ? pick_shape_t<true>(ni, nh, mode) : pick_shape_t<false>(ni, nh, mode);
 }
 // a one-layer tanh network seen as (tanh layer, identity layer): cnf_abi.hip appends W_2 = I, b_2 = 0 behind the parameters
 // ... or a real second layer with the identity activation (PlanarLayer: tanh(w'z + b) u): the same instantiations, its
 // gradient is written (nd.id2 = 0)
 bool is_id2(const NetDesc& nd) { return nd.n_layers == 2 && nd.acts[0] == 1 && nd.acts[1] == 0; }
+int wave_mode(const NetDesc& nd, bool train) { return !train ? WV_TEST : (nd.jvp ? WV_JVP : WV_VJP); }
+// the kernel of `form` for this two-layer network and mode (nullptr: there is none)
+wave_fn wave_kernel(WaveForm form, const NetDesc& nd, bool train) {
+    const auto v = wave_variant(form, (nd.n_in + 15) / 16, (nd.dims[1] + 15) / 16, wave_mode(nd, train), nd.acts[0] == 1 && nd.acts[1] == 1, is_id2(nd));
+    return v ? wave_instance(*v) : nullptr;
+}
+// CNF_PERSISTENT=0 / CNF_WAVE=0: no one-launch solve / none of this file's
+bool wave_off() {
+    static const bool off = [] { const char* e = getenv("CNF_PERSISTENT"); const char* w = getenv("CNF_WAVE"); return (e && e[0] == '0') || (w && w[0] == '0'); }();
+    return off;
+}
+// workgroups of `threads` threads of an instantiation that the current device holds at once (asked once per device, kernel and
+// block size)
+int wave_resident_workgroups(wave_fn fn, int threads) {
+    int dev = 0, n_cu = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    static std::mutex mu;
+    static std::map<std::tuple<int, const void*, int>, int> cap;
+    std::lock_guard<std::mutex> lk(mu);
+    const auto key = std::make_tuple(dev, (const void*)fn, threads);
+    auto it = cap.find(key);
+    if (it == cap.end()) {
+        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)fn, threads, 0) != hipSuccess) { (void)hipGetLastError(); n_cu = per_cu = 0; }
+        it = cap.emplace(key, n_cu * per_cu).first;
+    }
+    return it->second;
+}
 
 }  // namespace
 
@@ -1493,29 +1446,13 @@ bool is_id2(const NetDesc& nd) { return nd.n_layers == 2 && nd.acts[0] == 1 && n
 // word pair per wave: up to 512 x 16 columns.
 // Beyond 512 tiles (B > 8192): four tiles per workgroup where that form is instantiated (n_in <= 16, tanh networks, no
 // conditioning) -- up to 512 workgroups = 32768 columns, provided the device holds them all at once.
-static int wave_xwg_capacity(wave_fn fn) {                 // workgroups of four waves the current device holds at once
-    int dev = 0, n_cu = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)fn, 256, 0) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    return n_cu * per_cu;
-}
 static bool wave_xwg_ok(const NetDesc& nd, bool train, int B) {
     if (B > 16 * 4 * 512 || nd.n_cond > 0) return false;
-    const int ni = (nd.n_in + 15) / 16, nh = (nd.dims[1] + 15) / 16;
-    const int mode = !train ? WV_TEST : (nd.jvp ? WV_JVP : WV_VJP);
-    wave_fn fn = pick_wg(ni, nh, mode, false, is_id2(nd), nd.acts[0] == 1 && nd.acts[1] == 1);
-    if (!fn) return false;
-    static std::mutex mu;
-    static std::map<const void*, int> cap;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = cap.find((const void*)fn);
-    if (it == cap.end()) it = cap.emplace((const void*)fn, wave_xwg_capacity(fn)).first;
-    return (B + 63) / 64 <= it->second;
+    wave_fn fn = wave_kernel(WF_WG4, nd, train);
+    return fn && (B + 63) / 64 <= wave_resident_workgroups(fn, 256);
 }
 bool wave_solve_supported(const NetDesc& nd, bool train, int B) {
-    if (nd.n_layers != 2 || B < 1) return false;
-    const int ni = (nd.n_in + 15) / 16, nh = (nd.dims[1] + 15) / 16;
-    if (pick_shape(ni, nh, 0) == nullptr) return false;
+    if (nd.n_layers != 2 || B < 1 || !wave_kernel(WF_PLAIN, nd, train)) return false;
     return B <= 16 * 512 || wave_xwg_ok(nd, train, B);
 }
 
@@ -1533,50 +1470,27 @@ bool wave_grad_supported(const NetDesc& nd, int B, bool train) {
     if (off || !wave_solve_supported(nd, train, B)) return false;
     if (nd.acts[0] != 1 || !(nd.acts[1] == 1 || is_id2(nd))) return false;
     if (nd.n_cond > 0 && nd.n_in + nd.n_cond > 16 * ((nd.n_in + 15) / 16)) return false;       // [z; ys] within the input tiles
-    return pick_grad((nd.n_in + 15) / 16, (nd.dims[1] + 15) / 16, is_id2(nd)) != nullptr && wave_grad_waves(B) <= 512;
+    return wave_kernel(WF_GRAD, nd, train) != nullptr && wave_grad_waves(B) <= 512;
 }
 
 // ---- the ensemble form (cnf_loss_grad_many): M x tiles workgroups, each member's tiles meeting among themselves ----
 // (the envelope below -- two layers, tanh then tanh or identity, one input tile, up to four hidden tiles, one with the identity --
 // is restated in continuousnf.jl_amd/ensemble.py `_refusal`, which has to refuse before a handle exists: change both together)
-static wave_fn ens_fn(const NetDesc& nd, bool train) {
+static wave_fn ens_fn(WaveForm form, const NetDesc& nd, bool train) {
     if (nd.n_layers != 2 || nd.n_cond > 0 || nd.id2) return nullptr;      // (an APPENDED identity layer lives behind the handle's own parameters)
     if (nd.acts[0] != 1 || !(nd.acts[1] == 1 || is_id2(nd))) return nullptr;
-    return pick_grad_ens((nd.n_in + 15) / 16, (nd.dims[1] + 15) / 16, is_id2(nd), !train, nd.jvp != 0);
-}
-static bool ens_off() {
-    static const bool off = [] { const char* e = getenv("CNF_PERSISTENT"); const char* w = getenv("CNF_WAVE"); return (e && e[0] == '0') || (w && w[0] == '0'); }();
-    return off;
-}
-// workgroups of `threads` threads of an ENS instantiation that the current device holds at once (asked once per instantiation)
-static int ens_resident_workgroups(wave_fn fn, int threads) {
-    static std::mutex mu;
-    static std::map<const void*, int> cap;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = cap.find((const void*)fn);
-    if (it == cap.end()) {
-        int dev = 0, n_cu = 0, per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)fn, threads, 0) != hipSuccess) { (void)hipGetLastError(); n_cu = per_cu = 0; }
-        it = cap.emplace((const void*)fn, n_cu * per_cu).first;
-    }
-    return it->second;
+    return wave_kernel(form, nd, train);
 }
 int wave_ens_capacity(const NetDesc& nd, bool train, int B) {
-    wave_fn fn = ens_fn(nd, train);
-    if (ens_off() || !fn || B < 1 || !wave_grad_supported(nd, B, train)) return 0;
-    return ens_resident_workgroups(fn, 128) / wave_grad_waves(B);      // (main wave + helper)
+    wave_fn fn = ens_fn(WF_ENS_GRAD, nd, train);
+    if (wave_off() || !fn || B < 1 || !wave_grad_supported(nd, B, train)) return 0;
+    return wave_resident_workgroups(fn, 128) / wave_grad_waves(B);     // (main wave + helper)
 }
-
 // ... and its plain form (cnf_inference_many, cnf_generate_many): the same envelope, 64 threads per workgroup
-static wave_fn ens_plain_fn(const NetDesc& nd, bool train) {
-    if (!ens_fn(nd, train)) return nullptr;
-    return pick_ens_plain((nd.n_in + 15) / 16, (nd.dims[1] + 15) / 16, is_id2(nd), !train, nd.jvp != 0);
-}
 int wave_ens_eval_capacity(const NetDesc& nd, bool train, int B) {
-    wave_fn fn = ens_plain_fn(nd, train);
-    if (ens_off() || !fn || B < 1 || B > 16 * 512) return 0;     // (a member's meeting has at most 512 parties)
-    return ens_resident_workgroups(fn, 64) / ((B + 15) / 16);
+    wave_fn fn = ens_fn(WF_ENS_PLAIN, nd, train);
+    if (wave_off() || !fn || B < 1 || B > 16 * 512) return 0;    // (a member's meeting has at most 512 parties)
+    return wave_resident_workgroups(fn, 64) / ((B + 15) / 16);
 }
 
 cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_params, const float* cond, int cbs, StepState* st_out,
@@ -1589,34 +1503,34 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
     if (grad && nd.n_cond > 0 && !grad->ys) return CNF_ERR_BAD_ARG;
     if (grad && (!wave_grad_supported(nd, B, train) || !grad->traj || !grad->gpart || !grad->lam_out || !grad->hs_out || grad->traj_cap < 1))
         return CNF_ERR_UNSUPPORTED;
-    static const bool off = [] { const char* e = getenv("CNF_PERSISTENT"); const char* w = getenv("CNF_WAVE"); return (e && e[0] == '0') || (w && w[0] == '0'); }();
-    if (off) return CNF_ERR_UNSUPPORTED;
-    const int ni = (nd.n_in + 15) / 16, nh = (nd.dims[1] + 15) / 16;
-    int grid = (B + 15) / 16;
-    const int mode = !train ? WV_TEST : (nd.jvp ? WV_JVP : WV_VJP);
-    wave_fn fn = grad ? pick_grad(ni, nh, is_id2(nd), !train, nd.jvp != 0) : pick_shape(ni, nh, mode, nd.acts[0] == 1 && nd.acts[1] == 1, is_id2(nd));
-    if (!fn || (grid > 512 && grad)) return CNF_ERR_UNSUPPORTED;
-    // at most four tiles: the waves of ONE workgroup (they meet through LDS), where that form is instantiated; more than 512
-    // tiles: workgroups of four tiles (LDS inside, the tagged words between them: wave_solve_supported has checked that they fit)
-    static const bool wg_off = [] { const char* e = getenv("CNF_WAVE_WG"); return e && e[0] == '0'; }();
-    // (CNF_WAVE_XWG_MIN=<tiles>: take the four-tile workgroups from that many tiles on -- measurements; the default is what 512
-    // meeting words force)
-    static const int xwg_min = [] { const char* e = getenv("CNF_WAVE_XWG_MIN"); const int v = e ? atoi(e) : 0; return v > 4 ? v : 513; }();
-    const bool xwg = grid > 512 || (grid >= xwg_min && !cond && !grad && pick_wg(ni, nh, mode, false, is_id2(nd), nd.acts[0] == 1 && nd.acts[1] == 1));
-    wave_fn wfn = ((grid <= 4 && !wg_off && !cond) || xwg) ? pick_wg(ni, nh, mode, grad != nullptr, is_id2(nd), nd.acts[0] == 1 && nd.acts[1] == 1) : nullptr;
-    if (xwg && (!wfn || cond)) return CNF_ERR_UNSUPPORTED;
-    const int waves = xwg ? 4 : grid;
-    if (ens) wfn = nullptr;                                // (one tile per workgroup and its helper, as every gradient)
-    if (grad && grad->rich && mode == WV_VJP && ni == 1) {   // the forward pass files its intermediates: the RICH instantiations
-        if (wave_fn r = pick_grad_rich(nh, is_id2(nd), wfn != nullptr)) { if (wfn) wfn = r; else fn = r; }
-        else return CNF_ERR_BAD_ARG;                       // (wave_grad_rich_floats said it exists)
+    if (wave_off()) return CNF_ERR_UNSUPPORTED;
+    // ---- the form ----
+    const int tiles = (B + 15) / 16;
+    bool xwg = false;                                      // WF_WG4: workgroups of four tiles (false: one workgroup of `tiles` waves)
+    WaveForm form = WF_PLAIN;
+    if (path) form = WF_PATH;                              // one tile per workgroup, whatever the batch
+    else if (ens) form = grad ? WF_ENS_GRAD : WF_ENS_PLAIN;       // (one tile per workgroup -- and its helper, as every gradient)
+    else if (grad)                                         // the forward pass files its intermediates: the RICH instantiations
+        form = grad->rich && wave_mode(nd, train) == WV_VJP && nd.n_in <= 16 ? WF_GRAD_RICH : WF_GRAD;
+    else {
+        // at most four tiles: the waves of ONE workgroup (they meet through LDS), where that form is instantiated; more than 512
+        // tiles: workgroups of four tiles (LDS inside, the tagged words between them: wave_solve_supported has checked that they fit)
+        static const bool wg_off = [] { const char* e = getenv("CNF_WAVE_WG"); return e && e[0] == '0'; }();
+        // (CNF_WAVE_XWG_MIN=<tiles>: take the four-tile workgroups from that many tiles on -- measurements; the default is what 512
+        // meeting words force)
+        static const int xwg_min = [] { const char* e = getenv("CNF_WAVE_XWG_MIN"); const int v = e ? atoi(e) : 0; return v > 4 ? v : 513; }();
+        const bool wg = wave_kernel(WF_WG4, nd, train) != nullptr;
+        xwg = tiles > 512 || (tiles >= xwg_min && !cond && wg);
+        if (xwg && (!wg || cond)) return CNF_ERR_UNSUPPORTED;
+        if (wg && (xwg || (tiles <= 4 && !wg_off && !cond))) form = WF_WG4;
     }
-    if (path) {                                            // one tile per workgroup, whatever the batch
-        fn = pick_path(ni, nh, mode, nd.acts[0] == 1 && nd.acts[1] == 1, is_id2(nd));
-        wfn = nullptr;
-        if (!fn || grid > 512) return CNF_ERR_UNSUPPORTED;
-    }
-    if (wfn) { fn = wfn; grid = xwg ? (grid + 3) / 4 : 1; }
+    if (tiles > 512 && !xwg) return CNF_ERR_UNSUPPORTED;     // (a meeting has at most 512 parties)
+    // ---- the kernel ----
+    wave_fn fn = wave_kernel(form, nd, train);
+    if (!fn) return form == WF_GRAD_RICH ? CNF_ERR_BAD_ARG : CNF_ERR_UNSUPPORTED;       // (wave_grad_rich_floats said it exists)
+    // ---- grid and block: a gradient's tile has its main wave and its helper ----
+    int grid = form == WF_WG4 ? (xwg ? (tiles + 3) / 4 : 1) : tiles;
+    const int block = form == WF_WG4 ? 64 * (xwg ? 4 : tiles) : (grad ? 128 : 64);
     WaveArgs a{};
     a.nd = nd; a.P = d_params; a.eps = eps; a.cond = cond; a.cbs = cbs; a.B = B;
     a.n_total = (float)((size_t)(nd.n_in + (train ? 3 : 1)) * B);
@@ -1632,14 +1546,14 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
         // an inference (xs and all of its outputs) or a bare solve between the caller's columns; a trace needs its stride
         const bool inf = sv.xs && sv.logpx && sv.regs && sv.sums5 && !sv.u0 && !sv.u_out;
         const bool bare = !sv.xs && !sv.logpx && !sv.regs && !sv.sums5 && sv.u0 && sv.u_out;
-        if (!(inf || bare) || sv.t_out || (sv.trace && sv.trace_cap < 1) || grid > 512) return CNF_ERR_BAD_ARG;
-        fn = ens_plain_fn(nd, train);
-        en.tiles = grid; en.t1 = ens->t1; en.t0 = ens->t0; en.p_stride = ens->p_stride; en.part_stride = ens->part_stride;
-        grid *= ens->M;
+        if (!(inf || bare) || sv.t_out || (sv.trace && sv.trace_cap < 1)) return CNF_ERR_BAD_ARG;
+        en.t0 = ens->t0;
     } else if (ens) {
         if (grad->rich || sv.trace || sv.t_out || !sv.xs || !sv.logpx || !sv.regs || !sv.sums5 || sv.u_out) return CNF_ERR_BAD_ARG;
-        fn = ens_fn(nd, train);
-        en.tiles = grid; en.t1 = ens->t1; en.p_stride = ens->p_stride; en.traj_stride = ens->traj_stride; en.part_stride = ens->part_stride;
+        en.traj_stride = ens->traj_stride;
+    }
+    if (ens) {                                             // M x tiles workgroups
+        en.tiles = tiles; en.t1 = ens->t1; en.p_stride = ens->p_stride; en.part_stride = ens->part_stride;
         grid *= ens->M;
     }
     WavePathArgs pa{};
@@ -1648,8 +1562,7 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
         pa = *path;
     }
     void* args[] = {&a, &sv, &tab, &en, &pa};
-    // (a gradient: the tile's main wave and its helper)
-    if (hipLaunchKernel((const void*)fn, dim3(grid), dim3(wfn ? 64 * waves : (grad ? 128 : 64)), args, 0, s) != hipSuccess) {
+    if (hipLaunchKernel((const void*)fn, dim3(grid), dim3(block), args, 0, s) != hipSuccess) {
         (void)hipGetLastError();
         return CNF_ERR_UNSUPPORTED;
     }

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import time
+from contextlib import contextmanager
 
 import numpy as np
 
@@ -27,7 +28,8 @@ from .types import TrainMode
 
 def _refusal(icnf: ICNF):
     """Why this model has no ensemble form, or None.  Host logic only: nothing is drawn, no handle is made.  The network
-    envelope restates `ens_fn` / `pick_grad_ens` of csrc/cnf_wave.hip (which decides for the C ABI): change both together."""
+    envelope restates `ens_fn` of csrc/cnf_wave.hip and the WF_ENS_GRAD form of csrc/cnf_wave_variants.h (which decide for the
+    C ABI): change both together."""
     if icnf.cond:
         return "conditional models are evaluated one member at a time"
     if icnf.basedist is not None:
@@ -115,6 +117,63 @@ def _rows(x):
     return x.detach().to(torch.float32).permute(0, 2, 1).contiguous()
 
 
+def _device_capacity(who, capacity_fn, h, m, B):
+    """The members one launch takes on this device (``capacity_fn`` of the C ABI), or ``NotImplementedError``."""
+    cap = int(getattr(_lib.lib(), capacity_fn)(h, m, B))
+    if cap < 1:
+        raise NotImplementedError(f"{who}: no ensemble form for this model, mode or batch on this device ({capacity_fn} is 0)")
+    return cap
+
+
+def _chunked_calls(icnf: ICNF, M, cap, call, steps_of=None):
+    """The ensemble call in launches of at most ``cap`` members (M above the capacity: consecutive launches).
+    ``call(lo, n, status, stats)`` makes the ABI call for the members ``lo .. lo + n - 1`` with the two pointers as its
+    ``status_out`` and ``stats_out``; ``steps_of(icnf, i)`` reads the steps of member i of the call just made (asked for the
+    members that succeeded; None: no steps).  Returns ``(stats, status, calls, steps)``."""
+    h = icnf.handle()
+    status = np.empty(M, dtype=np.int32)
+    stats = (_lib.cnf_solve_stats * M)()
+    calls, steps = 0, []
+    for lo in range(0, M, cap):
+        n = min(cap, M - lo)
+        _lib.check(call(lo, n, status[lo:].ctypes.data, C.byref(stats, lo * C.sizeof(_lib.cnf_solve_stats))), h)
+        calls += 1
+        if steps_of is not None:
+            steps += [steps_of(icnf, i) if status[lo + i] == _lib.OK else None for i in range(n)]
+    return stats, status, calls, steps
+
+
+def _info(icnf: ICNF, stats, status, calls, times_key, times, **more):
+    """What every ensemble call reports; ``times``: the members' own times (None: ``tspan[1]`` for all)."""
+    if times is None:
+        times = np.full(len(status), icnf.tspan[1], dtype=np.float32)
+    return {"stats": [s.as_dict() for s in stats], "status": status, "launches": max(s.launches for s in stats), "calls": calls,
+            "rerun": [], times_key: times, **more}
+
+
+def _raise_failed(status):
+    l = _lib.lib()
+    for i, s in enumerate(status):
+        if s in (_lib.ERR_NONFINITE, _lib.ERR_MAXITERS):
+            raise _lib.CNFError(int(s), f"ensemble member {i}: " + l.cnf_status_string(int(s)).decode())
+
+
+@contextmanager
+def _one_member_at_a_time(icnf: ICNF, times):
+    """For the re-run of the members whose part of the launch gave up -- the existing route, its fallbacks included: ``tspan``
+    and ``steer_rate`` are set aside and restored; ``member(i)`` of the yielded function puts member i's own time in."""
+    span, steer = icnf.tspan, icnf.steer_rate
+
+    def member(i):
+        if times is not None:
+            icnf.tspan = (span[0], float(times[i]))
+    try:
+        icnf.steer_rate = 0.0
+        yield member
+    finally:
+        icnf.tspan, icnf.steer_rate = span, steer
+
+
 def loss_and_grad_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, with_steps=False):
     """``loss_and_grad`` of M members at once: ``xs`` (M, nvars, B) and ``ps`` (M, n_params) device tensors, ``eps``
     (M, n_in, B; TrainMode, drawn with ``draw_eps`` when not given), ``t1`` one end time per member (with ``steer_rate > 0``
@@ -133,10 +192,7 @@ def loss_and_grad_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, wit
     l, h = _lib.lib(), icnf.handle()                       # (no device: cnf_create's error, as everywhere)
     if not (xs.is_cuda and ps.is_cuda and (eps is None or eps.is_cuda)):
         raise ValueError("loss_and_grad_many: torch tensors must live on the GPU")
-    cap = int(l.cnf_ensemble_capacity(h, m, B))
-    if cap < 1:
-        raise NotImplementedError("loss_and_grad_many: no ensemble form for this model, mode or batch on this device "
-                                  "(cnf_ensemble_capacity is 0)")
+    cap = _device_capacity("loss_and_grad_many", "cnf_ensemble_capacity", h, m, B)
     train = m == _lib.MODE_TRAIN
     dev = xs.device
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
@@ -147,45 +203,25 @@ def loss_and_grad_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, wit
     n_params = pr.shape[1]
     grads = torch.empty((M, n_params), dtype=torch.float32, device=dev)
     losses = np.empty(M, dtype=np.float32)
-    status = np.empty(M, dtype=np.int32)
-    stats = (_lib.cnf_solve_stats * M)()
-    calls, steps = 0, []
-    for lo in range(0, M, cap):                            # M above the capacity: consecutive launches
-        n = min(cap, M - lo)
-        _lib.check(l.cnf_loss_grad_many(
-            h, m, n, pr[lo].data_ptr(), xr[lo].data_ptr(), er[lo].data_ptr() if er is not None else None, B, C.byref(opts),
-            t1[lo:].ctypes.data if t1 is not None else None, losses[lo:].ctypes.data, grads[lo].data_ptr(),
-            status[lo:].ctypes.data, C.byref(stats, lo * C.sizeof(_lib.cnf_solve_stats)), stream), h)
-        calls += 1
-        if with_steps:
-            steps += [ensemble_steps(icnf, i) if status[lo + i] == _lib.OK else None for i in range(n)]
-    info = {"stats": [s.as_dict() for s in stats], "status": status, "launches": max(s.launches for s in stats), "calls": calls, "rerun": [],
-            "t1": t1 if t1 is not None else np.full(M, icnf.tspan[1], dtype=np.float32)}
-    for i in range(M):
-        if status[i] in (_lib.ERR_NONFINITE, _lib.ERR_MAXITERS):
-            raise _lib.CNFError(int(status[i]), f"ensemble member {i}: " + l.cnf_status_string(int(status[i])).decode())
+    stats, status, calls, steps = _chunked_calls(icnf, M, cap, lambda lo, n, status, stats: l.cnf_loss_grad_many(
+        h, m, n, pr[lo].data_ptr(), xr[lo].data_ptr(), er[lo].data_ptr() if er is not None else None, B, C.byref(opts),
+        t1[lo:].ctypes.data if t1 is not None else None, losses[lo:].ctypes.data, grads[lo].data_ptr(), status, stats, stream),
+        ensemble_steps if with_steps else None)
+    info = _info(icnf, stats, status, calls, "t1", t1)
+    _raise_failed(status)
     gave_up = [i for i in range(M) if status[i] != _lib.OK]
     if gave_up:
-        # the existing route, its fallbacks included, on the member's own end time
-        span = icnf.tspan
-        try:
+        with _one_member_at_a_time(icnf, t1) as member:
             for i in gave_up:
-                if t1 is not None:
-                    icnf.tspan = (span[0], float(t1[i]))
-                steer, icnf.steer_rate = icnf.steer_rate, 0.0
-                try:
-                    args = dict(eps=er[i].t()) if train else {}
-                    val, g = loss_and_grad(icnf, mode, xr[i].t(), pr[i], st, **args)
-                finally:
-                    icnf.steer_rate = steer
+                member(i)
+                args = dict(eps=er[i].t()) if train else {}
+                val, g = loss_and_grad(icnf, mode, xr[i].t(), pr[i], st, **args)
                 losses[i] = val
                 grads[i].copy_(g)
                 status[i] = _lib.OK
                 info["stats"][i] = dict(icnf.last_stats)
                 if with_steps:
                     steps[i] = np.array(icnf.last_steps, dtype=np.float32)
-        finally:
-            icnf.tspan = span
         info["rerun"] = gave_up
     if with_steps:
         info["steps"] = steps
@@ -293,13 +329,6 @@ def _trace_cap(opts, with_steps):
     return min(int(opts.maxiters), _TRACE_ROWS) if with_steps else 0
 
 
-def _raise_failed(status):
-    l = _lib.lib()
-    for i, s in enumerate(status):
-        if s in (_lib.ERR_NONFINITE, _lib.ERR_MAXITERS):
-            raise _lib.CNFError(int(s), f"ensemble member {i}: " + l.cnf_status_string(int(s)).decode())
-
-
 def inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, with_steps=False):
     """``inference`` of M members in one launch (cnf_inference_many).  ``xs`` (M, nvars, B): one data set per member (the
     held-out folds), or (nvars, B): one data set scored by every member (bagging; expanded here, the kernel reads M copies);
@@ -318,10 +347,7 @@ def inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, with_st
     l, h = _lib.lib(), icnf.handle()
     if not (xs.is_cuda and ps.is_cuda and (eps is None or eps.is_cuda)):
         raise ValueError(f"{who}: torch tensors must live on the GPU")
-    cap = int(l.cnf_ensemble_eval_capacity(h, m, B))
-    if cap < 1:
-        raise NotImplementedError(f"{who}: no ensemble form for this model, mode or batch on this device "
-                                  "(cnf_ensemble_eval_capacity is 0)")
+    cap = _device_capacity(who, "cnf_ensemble_eval_capacity", h, m, B)
     train = m == _lib.MODE_TRAIN
     dev = xs.device
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
@@ -331,32 +357,19 @@ def inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, with_st
     opts = _solve_opts(icnf, icnf.tspan)
     logpx, regs = torch.empty((M, B), dtype=torch.float32, device=dev), torch.empty((M, 3, B), dtype=torch.float32, device=dev)
     losses = np.empty(M, dtype=np.float32)
-    status = np.empty(M, dtype=np.int32)
-    stats = (_lib.cnf_solve_stats * M)()
     tc = _trace_cap(opts, with_steps)
-    calls, steps = 0, []
-    for lo in range(0, M, cap):                            # M above the capacity: consecutive launches
-        n = min(cap, M - lo)
-        _lib.check(l.cnf_inference_many(
-            h, m, n, pr[lo].data_ptr(), xr[lo].data_ptr(), er[lo].data_ptr() if er is not None else None, B, C.byref(opts),
-            t1[lo:].ctypes.data if t1 is not None else None, logpx[lo].data_ptr(), regs[lo].data_ptr(), losses[lo:].ctypes.data,
-            status[lo:].ctypes.data, C.byref(stats, lo * C.sizeof(_lib.cnf_solve_stats)), tc, stream), h)
-        calls += 1
-        if with_steps:
-            steps += [ensemble_eval_steps(icnf, i) if status[lo + i] == _lib.OK else None for i in range(n)]
-    info = {"stats": [s.as_dict() for s in stats], "status": status, "launches": max(s.launches for s in stats), "calls": calls,
-            "rerun": [], "losses": losses, "t1": t1 if t1 is not None else np.full(M, icnf.tspan[1], dtype=np.float32)}
+    stats, status, calls, steps = _chunked_calls(icnf, M, cap, lambda lo, n, status, stats: l.cnf_inference_many(
+        h, m, n, pr[lo].data_ptr(), xr[lo].data_ptr(), er[lo].data_ptr() if er is not None else None, B, C.byref(opts),
+        t1[lo:].ctypes.data if t1 is not None else None, logpx[lo].data_ptr(), regs[lo].data_ptr(), losses[lo:].ctypes.data,
+        status, stats, tc, stream), ensemble_eval_steps if with_steps else None)
+    info = _info(icnf, stats, status, calls, "t1", t1, losses=losses)
     _raise_failed(status)
     gave_up = [i for i in range(M) if status[i] != _lib.OK]
     if gave_up:
-        # the existing route, its fallbacks included, on the member's own end time
         from .base_icnf import loss_from_sums
-        span, steer = icnf.tspan, icnf.steer_rate
-        try:
-            icnf.steer_rate = 0.0
+        with _one_member_at_a_time(icnf, t1) as member:
             for i in gave_up:
-                if t1 is not None:
-                    icnf.tspan = (span[0], float(t1[i]))
+                member(i)
                 args = dict(eps=er[i].t()) if train else {}
                 lp, rg, sums = inference(icnf, mode, xr[i].t(), pr[i], st, with_sums=True, **args)
                 logpx[i].copy_(lp)
@@ -364,8 +377,6 @@ def inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, with_st
                 losses[i] = loss_from_sums(icnf, mode, sums)
                 status[i] = _lib.OK
                 info["stats"][i] = dict(icnf.last_stats)
-        finally:
-            icnf.tspan, icnf.steer_rate = span, steer
         info["rerun"] = gave_up
     if with_steps:
         info["steps"] = steps
@@ -422,10 +433,7 @@ def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, 
     l, h = _lib.lib(), icnf.handle()
     if not (ps.is_cuda and (z0 is None or z0.is_cuda) and (eps is None or eps.is_cuda)):
         raise ValueError(f"{who}: torch tensors must live on the GPU")
-    cap = int(l.cnf_ensemble_eval_capacity(h, m, n))
-    if cap < 1:
-        raise NotImplementedError(f"{who}: no ensemble form for this model, mode or batch on this device "
-                                  "(cnf_ensemble_eval_capacity is 0)")
+    cap = _device_capacity(who, "cnf_ensemble_eval_capacity", h, m, n)
     dev = ps.device
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     pr = ps.detach().to(torch.float32).contiguous()
@@ -457,40 +465,25 @@ def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, 
     opts = _solve_opts(icnf, (icnf.tspan[1], icnf.tspan[0]))              # reverse(tspan)
     xo = torch.empty((M, n, icnf.nvars), dtype=torch.float32, device=dev)
     lq = torch.empty((M, n), dtype=torch.float32, device=dev) if with_logp else None
-    status = np.empty(M, dtype=np.int32)
-    stats = (_lib.cnf_solve_stats * M)()
     tc = _trace_cap(opts, with_steps)
-    calls, steps = 0, []
-    for lo in range(0, M, cap):
-        k = min(cap, M - lo)
-        _lib.check(l.cnf_generate_many(
-            h, m, k, pr[lo].data_ptr(), zr[lo].data_ptr(), er[lo].data_ptr() if train else None, n, C.byref(opts),
-            t0[lo:].ctypes.data if t0 is not None else None, xo[lo].data_ptr(), lq[lo].data_ptr() if with_logp else None,
-            status[lo:].ctypes.data, C.byref(stats, lo * C.sizeof(_lib.cnf_solve_stats)), tc, stream), h)
-        calls += 1
-        if with_steps:
-            steps += [ensemble_eval_steps(icnf, i) if status[lo + i] == _lib.OK else None for i in range(k)]
-    info = {"stats": [s.as_dict() for s in stats], "status": status, "launches": max(s.launches for s in stats), "calls": calls,
-            "rerun": [], "t0": t0 if t0 is not None else np.full(M, icnf.tspan[1], dtype=np.float32),
-            "z0": zr.permute(0, 2, 1), "eps": er.permute(0, 2, 1)}
+    stats, status, calls, steps = _chunked_calls(icnf, M, cap, lambda lo, k, status, stats: l.cnf_generate_many(
+        h, m, k, pr[lo].data_ptr(), zr[lo].data_ptr(), er[lo].data_ptr() if train else None, n, C.byref(opts),
+        t0[lo:].ctypes.data if t0 is not None else None, xo[lo].data_ptr(), lq[lo].data_ptr() if with_logp else None,
+        status, stats, tc, stream), ensemble_eval_steps if with_steps else None)
+    info = _info(icnf, stats, status, calls, "t0", t0, z0=zr.permute(0, 2, 1), eps=er.permute(0, 2, 1))
     icnf.last_ensemble_info = info
     _raise_failed(status)
     gave_up = [i for i in range(M) if status[i] != _lib.OK]
     if gave_up:
-        span, rate = icnf.tspan, icnf.steer_rate
-        try:
-            icnf.steer_rate = 0.0
+        with _one_member_at_a_time(icnf, t0) as member:
             for i in gave_up:
-                if t0 is not None:
-                    icnf.tspan = (span[0], float(t0[i]))
+                member(i)
                 r = generate(icnf, mode, pr[i], st, n, z0=zr[i].t(), eps=er[i].t(), with_logp=with_logp)
                 xs_i = r[0] if with_logp else r
                 xo[i].copy_(torch.as_tensor(xs_i, device=dev)[: icnf.nvars].t())
                 if with_logp:
                     lq[i].copy_(torch.as_tensor(r[1], device=dev))
                 status[i] = _lib.OK
-        finally:
-            icnf.tspan, icnf.steer_rate = span, rate
         info["rerun"] = gave_up
     if with_steps:
         info["steps"] = steps

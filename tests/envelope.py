@@ -160,7 +160,7 @@ def trace_mfma_supported(dims, n_cond=0):
 
 
 def wave_shape(dims):
-    """cnf_wave.hip ``pick_shape``: two-layer networks of (input tiles, hidden tiles) = (1, 1..4) or (2, 6)."""
+    """csrc/cnf_wave_variants.h ``WF_PLAIN``: two-layer networks of (input tiles, hidden tiles) = (1, 1..4) or (2, 6)."""
     if len(dims) != 3:
         return False
     ni, nh = (dims[0] + 15) // 16, (dims[1] + 15) // 16
