@@ -153,6 +153,13 @@ _ENSEMBLE_EVAL_SIGNATURES = {
     "cnf_ensemble_eval_steps": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int]),
 }
 ENSEMBLE_EVAL_EXPORTS = tuple(_ENSEMBLE_EVAL_SIGNATURES)
+# differentiable ensembles (include/cnfhip_ensemble_vjp.h): likewise
+_ENSEMBLE_VJP_SIGNATURES = {
+    "cnf_ensemble_vjp_capacity": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "cnf_inference_vjp_many": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), _fp, _fp, _fp,
+                                         _fp, _fp, _fp, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+ENSEMBLE_VJP_EXPORTS = tuple(_ENSEMBLE_VJP_SIGNATURES)
 # flow paths (include/cnfhip_path.h): likewise
 _PATH_SIGNATURES = {
     "cnf_solve_path": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), _fp, C.c_int, _fp,
@@ -198,7 +205,8 @@ def lib():
             pass
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in list(_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) + list(_BASEGRAD_SIGNATURES.items()) + \
-                list(_ENSEMBLE_SIGNATURES.items()) + list(_ENSEMBLE_EVAL_SIGNATURES.items()) + list(_PATH_SIGNATURES.items()):
+                list(_ENSEMBLE_SIGNATURES.items()) + list(_ENSEMBLE_EVAL_SIGNATURES.items()) + list(_ENSEMBLE_VJP_SIGNATURES.items()) + \
+                list(_PATH_SIGNATURES.items()):
             f = getattr(l, name)
             f.restype, f.argtypes = res, args
         _lib = l

@@ -2630,16 +2630,19 @@ static bool ens_handle_ok(cnf_handle h, int mode) {
     if (!h || (mode != CNF_MODE_TEST && mode != CNF_MODE_TRAIN)) return false;
     return !(h->nd.n_cond > 0 || h->bd.kind || h->grad_ys || h->shard_reduce || h->shard_comm || h->no_persist);
 }
-extern "C" int cnf_ensemble_capacity(cnf_handle h, int mode, int B) {
+// cw: of the per-sample-cotangent form (cnf_inference_vjp_many), whose kernels have their own register budget
+static int ens_grad_capacity(cnf_handle h, int mode, int B, bool cw) {
     if (B < 1 || !ens_handle_ok(h, mode)) return 0;
     if (hipSetDevice(h->device) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    int cap = wave_ens_capacity(h->nd_wave, mode == CNF_MODE_TRAIN, B);
+    int cap = wave_ens_capacity(h->nd_wave, mode == CNF_MODE_TRAIN, B, cw);
     // ... and no more members than keep 64 step slots each within the trajectory budget of one model's call
     size_t fit = 0;
     traj_step_slots(wave_grad_traj_floats(h->nd_wave, B), &fit);
     if ((size_t)cap > fit) cap = (int)fit;
     return cap;
 }
+extern "C" int cnf_ensemble_capacity(cnf_handle h, int mode, int B) { return ens_grad_capacity(h, mode, B, false); }
+extern "C" int cnf_ensemble_vjp_capacity(cnf_handle h, int mode, int B) { return ens_grad_capacity(h, mode, B, true); }
 
 // ---- What cnf_loss_grad_many and ens_eval (cnf_inference_many, cnf_generate_many: further down) share, each step once: the
 // checks, the growth of the stores, the launch preamble and the read-back.  EnsCall is one call's arguments and, from ens_begin
@@ -2653,6 +2656,7 @@ struct EnsCall {
     std::unique_lock<std::mutex> lock;     // g_persist_mu
     bool hairer = false;
     Solve3Args sv{};
+    bool vjp = false;              // grad: cnf_inference_vjp_many (per-sample cotangents) rather than cnf_loss_grad_many
 };
 constexpr size_t ENS_ST_F = (sizeof(StepState) + 3) / 4;     // floats of one member's final state in ens_fin / ens_hfin ...
 static size_t ens_fin_floats(int M) { return (size_t)M * (ENS_ST_F + 5); }      // ... and of all M, their five loss sums behind them
@@ -2674,7 +2678,7 @@ static cnf_status ens_check(cnf_handle h, const EnsCall& c, bool null_ptr, const
     while (!h->collecting && !h->submitted.empty())       // (as any other call: the inferences submitted on the handle end first)
         if ((s = collect_one(h, nullptr)) != CNF_OK) return s;
     if (c.opts->kernel == CNF_KERNEL_GENERIC) return fail(h, CNF_ERR_UNSUPPORTED, "the ensemble form exists on the wave kernels only");
-    const int capacity = c.grad ? cnf_ensemble_capacity(h, c.mode, c.B) : cnf_ensemble_eval_capacity(h, c.mode, c.B);
+    const int capacity = c.grad ? ens_grad_capacity(h, c.mode, c.B, c.vjp) : cnf_ensemble_eval_capacity(h, c.mode, c.B);
     if (capacity < 1) return fail(h, CNF_ERR_UNSUPPORTED, "no ensemble form for this model, mode or batch");
     if (c.M > capacity)
         return fail(h, CNF_ERR_UNSUPPORTED, (std::string("more members than one launch takes (") + capacity_fn + ")").c_str());
@@ -2772,13 +2776,19 @@ static cnf_status ens_finish(cnf_handle h, EnsCall& c, int launches, bool sums, 
     return CNF_OK;
 }
 
-extern "C" cnf_status cnf_loss_grad_many(cnf_handle h, int mode, int M, const float* params_dev, const float* xs, const float* eps,
-                                         int B, const cnf_solve_opts* opts, const float* t1_host, float* loss_out, float* grad_dev,
-                                         int* status_out, cnf_solve_stats* stats_out, void* stream) {
+// What the two ensemble gradient calls share: cnf_loss_grad_many (cot_dev null: the built-in loss's cotangent, losses in loss_out;
+// logpx, regs and d / d z(t0) stay in the ensemble's own column store) and cnf_inference_vjp_many (cot_dev [M][4][B]: the CW
+// form of the kernel; logpx_dev, regs_dev and -- may be null -- grad_x_dev are the caller's, loss_out is null).
+static cnf_status ens_grad(cnf_handle h, bool vjp, int mode, int M, const float* params_dev, const float* xs, const float* eps, int B,
+                           const cnf_solve_opts* opts, const float* t1_host, const float* cot_dev, float* loss_out, float* logpx_dev,
+                           float* regs_dev, float* grad_dev, float* grad_x_dev, int* status_out, cnf_solve_stats* stats_out, void* stream) {
     const bool train = mode == CNF_MODE_TRAIN;
     EnsCall c{true, false, mode, M, B, 0, opts, t1_host, (hipStream_t)stream};
-    cnf_status s = ens_check(h, c, !params_dev || !xs || !opts || !loss_out || !grad_dev || !status_out || (train && !eps),
-                             "the loss is a mean over the batch: B must be >= 1", "cnf_ensemble_capacity");
+    c.vjp = vjp;
+    cnf_status s = ens_check(h, c, !params_dev || !xs || !opts || !grad_dev || !status_out || (train && !eps) ||
+                                       (vjp ? !cot_dev || !logpx_dev || !regs_dev : !loss_out),
+                             vjp ? "B must be >= 1" : "the loss is a mean over the batch: B must be >= 1",
+                             vjp ? "cnf_ensemble_vjp_capacity" : "cnf_ensemble_capacity");
     if (s != CNF_OK) return s;
     const NetDesc& nd = h->nd_wave;
     const size_t Mz = (size_t)M, Bz = (size_t)B, n_in = (size_t)nd.n_in, D = n_in + (train ? 3 : 1), np = h->n_params;
@@ -2792,13 +2802,14 @@ extern "C" cnf_status cnf_loss_grad_many(cnf_handle h, int mode, int M, const fl
     StepState* fin_dev = reinterpret_cast<StepState*>(h->ens_fin.data());
     float* cols = h->ens_cols;
     Solve3Args& sv = c.sv;
-    sv.xs = xs; sv.logpx = cols + Mz * Bz * D; sv.regs = sv.logpx + Mz * Bz; sv.sums5 = h->ens_fin + Mz * ENS_ST_F;
+    sv.xs = xs; sv.logpx = vjp ? logpx_dev : cols + Mz * Bz * D; sv.regs = vjp ? regs_dev : cols + Mz * Bz * (D + 1);
+    sv.sums5 = h->ens_fin + Mz * ENS_ST_F;
     WaveGradArgs wg;
     wg.traj = h->ens_traj; wg.traj_cap = cap; wg.hs_out = h->ens_hs; wg.gpart = h->ens_gpart;
-    wg.lam_out = cols + Mz * Bz * (D + 4); wg.n_params = (int)np;
+    wg.lam_out = grad_x_dev ? grad_x_dev : cols + Mz * Bz * (D + 4); wg.n_params = (int)np;
     wg.lam1 = h->lam[0]; wg.lam2 = h->lam[1]; wg.lam3 = h->lam[2];
     WaveEnsLaunch ens;
-    ens.M = M; ens.t1 = t1_host ? h->ens_t1.data() : nullptr;
+    ens.M = M; ens.t1 = t1_host ? h->ens_t1.data() : nullptr; ens.cw = vjp ? cot_dev : nullptr;
     ens.p_stride = np; ens.traj_stride = per_step * cap; ens.part_stride = WV_ENS_PART_FLOATS;
     int launches = 0;                                      // kernel launches of this call, counted where they are made
     s = wave_solve_launch(nd, train, params_dev, nullptr, 0, fin_dev, cols, eps, B, c.st, nullptr, 0, sv, &wg, &ens);
@@ -2809,10 +2820,41 @@ extern "C" cnf_status cnf_loss_grad_many(cnf_handle h, int mode, int M, const fl
     ++launches;
     if ((s = ens_finish(h, c, launches, true, loss_out, status_out, stats_out, h->ens_nacc, false)) != CNF_OK) return s;
     h->ens_M = M; h->ens_cap = cap;
+    if (vjp) {                                             // nothing of a member that is not CNF_OK is valid: NaN outputs, zero gradients
+        bool any_bad = false;
+        for (int m = 0; m < M; ++m)
+            if (status_out[m] != CNF_OK) {
+                any_bad = true;
+                const size_t mz = (size_t)m;
+                HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(logpx_dev + mz * Bz), 0x7fc00000, Bz, c.st));
+                HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(regs_dev + mz * 3 * Bz), 0x7fc00000, 3 * Bz, c.st));
+                HIPCHK(h, hipMemsetAsync(grad_dev + mz * np, 0, np * sizeof(float), c.st));
+                if (grad_x_dev) HIPCHK(h, hipMemsetAsync(grad_x_dev + mz * Bz * n_in, 0, Bz * n_in * sizeof(float), c.st));
+            }
+        if (any_bad) HIPCHK(h, hipStreamSynchronize(c.st));
+    }
     return CNF_OK;
 }
 
-// the signed accepted step sizes of member `member` of the last cnf_loss_grad_many call (read from the device when asked for)
+extern "C" cnf_status cnf_loss_grad_many(cnf_handle h, int mode, int M, const float* params_dev, const float* xs, const float* eps,
+                                         int B, const cnf_solve_opts* opts, const float* t1_host, float* loss_out, float* grad_dev,
+                                         int* status_out, cnf_solve_stats* stats_out, void* stream) {
+    return ens_grad(h, false, mode, M, params_dev, xs, eps, B, opts, t1_host, nullptr, loss_out, nullptr, nullptr, grad_dev, nullptr, status_out,
+                    stats_out, stream);
+}
+
+// Differentiable ensembles (include/cnfhip_ensemble_vjp.h): the vector-Jacobian product of the M members' inference for a
+// per-sample cotangent of its four outputs, by the CW form of the same launch.
+extern "C" cnf_status cnf_inference_vjp_many(cnf_handle h, int mode, int M, const float* params_dev, const float* xs, const float* eps,
+                                             int B, const cnf_solve_opts* opts, const float* t1_host, const float* cot_dev,
+                                             float* logpx_dev, float* regs_dev, float* grad_dev, float* grad_x_dev, int* status_out,
+                                             cnf_solve_stats* stats_out, void* stream) {
+    return ens_grad(h, true, mode, M, params_dev, xs, eps, B, opts, t1_host, cot_dev, nullptr, logpx_dev, regs_dev, grad_dev, grad_x_dev,
+                    status_out, stats_out, stream);
+}
+
+// the signed accepted step sizes of member `member` of the last ensemble gradient call -- cnf_loss_grad_many or
+// cnf_inference_vjp_many -- (read from the device when asked for)
 extern "C" int cnf_ensemble_steps(cnf_handle h, int member, float* hs, int cap) {
     if (!h || member < 0 || member >= h->ens_M) return -1;
     const int n = h->ens_nacc[member];

@@ -43,11 +43,14 @@ struct WaveEnsLaunch {
     size_t p_stride = 0;           // floats between two members' parameters
     size_t traj_stride = 0;        // ... trajectory stores (traj_cap x wave_grad_traj_floats)
     size_t part_stride = 0;        // ... meeting words, in floats (WV_ENS_PART_FLOATS)
+    const float* cw = nullptr;     // device, [M][4][B]: per-sample cotangents of (logpx, E, n, A) -- with `grad`, the CW form
+                                   // (cnf_inference_vjp_many) in place of the built-in loss's cotangent; null: the loss
 };
 #define WV_ENS_PART_FLOATS 8192    // a member's meeting words: 2 x 1024 of the meetings + 2048 of the loss-sum partials, 8 bytes each
 // the largest M a launch takes at batch B: workgroups the device holds at once / tiles (0: no ensemble form of this network
 // or mode, or the one-launch solves are switched off)
-int wave_ens_capacity(const NetDesc& nd, bool train, int B);
+// (cw: of the CW form, which has its own register budget)
+int wave_ens_capacity(const NetDesc& nd, bool train, int B, bool cw = false);
 // Without `grad`, `ens` launches the PLAIN ensemble form (cnf_inference_many / cnf_generate_many): either an inference (sv.xs,
 // sv.logpx [M][B], sv.regs [M][3][B], sv.sums5 [5 M]) or a bare solve (sv.u0 -> sv.u_out, [M][B][D] each); sv.trace, when
 // set, is [M][sv.trace_cap][4].  Its capacity: workgroups of one wave the device holds at once / tiles, at most 512 tiles.

@@ -74,6 +74,7 @@ struct WaveEnsArgs {
     size_t part_stride;    // ... their meeting words (as floats)
     const float* t0;       // plain forms: null, or the members' own start times [M] (sampling runs over reverse(steer_tspan));
                            // (last: the fields the gradient forms read keep their places among the kernel arguments)
+    const float* cw;       // CW forms: the members' per-sample cotangents [M][4][B], rows (logpx, E, n, A) (behind t0, for the same reason)
 };
 
 __device__ __forceinline__ f32x4 mm4(const float (&A)[4], const f32x4& b, f32x4 acc) {
@@ -158,11 +159,20 @@ __device__ __forceinline__ float wv_quad_sum(float v) {
 // serves -- t_n < tau <= t_n + h along the direction, the last step everything left -- from Tsit5's interpolant over the k_1 .. k_7
 // in its registers (tsit5_dense_b: wave-uniform fp32 Horner forms), each lane its own rows, before u <- u_new.  A cursor into the
 // save times is kept across attempts; the step sequence is the plain form's, bit for bit.
-template <int NI, int NH, int MODE, bool TANH, bool GRAD = false, bool ID2 = false, int WGW = 1, bool RICH = false, bool ENS = false, bool PATH = false>
+//
+// CW (the GRAD, ENS forms: cnf_inference_vjp_many): the backward pass pulls back a PER-SAMPLE cotangent of inference's four
+// outputs instead of the built-in loss's (-1/B, lam1/B, lam2/B, lam3/B).  A lane owns one column of its tile: it reads that
+// column's four cotangents (columns past the batch: 0) before the backward sweep; the three stage constants c_l, c_E, c_n become
+// per-lane values and the terminal cotangent is -g_logpx z + g_A unit(z_aug) (the N(0, I) case of k_vjp_cotangent; the rows a
+// handle does not integrate -- lam1, lam2, lam3 = 0, all three in TestMode -- carry nothing).  The forward half of the launch,
+// the helper wave, the contraction, the stores and the meetings are the GRAD, ENS form's.
+template <int NI, int NH, int MODE, bool TANH, bool GRAD = false, bool ID2 = false, int WGW = 1, bool RICH = false, bool ENS = false, bool PATH = false,
+          bool CW = false>
 __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wave(WaveArgs a, Solve3Args sv, const WvTab tab, const WaveEnsArgs en, const WavePathArgs pa) {
     constexpr bool HELP = GRAD && WGW == 1;
     static_assert(!PATH || (!GRAD && !ENS && WGW == 1), "PATH is a form of the plain solve with one tile per workgroup");
     static_assert(!ENS || (WGW == 1 && !RICH), "ENS forms have one tile per workgroup and no rich store");
+    static_assert(!CW || (GRAD && ENS), "CW is a form of the ensemble gradient");
     static_assert(!RICH || (GRAD && MODE == WV_VJP), "RICH is a form of the TrainMode / VJP gradient");
     constexpr int RR = 3 * NH + 3 * NI;                     // f32x4 per lane and stage evaluation in the rich store
     f32x4* rich_ptr = nullptr;                             // where the next evaluation files them (null: nowhere)
@@ -177,6 +187,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
     const int wloc = WGW > 1 ? (int)(threadIdx.x >> 6) : 0, nwg = WGW > 1 ? (int)(blockDim.x >> 6) : 1;
     const bool xwg = WGW > 1 && gridDim.x > 1;
     int wid_ = WGW > 1 ? (int)blockIdx.x * nwg + wloc : (int)blockIdx.x;
+    const float* cwp = nullptr;                            // CW: this member's cotangents [4][B]
     if constexpr (ENS) {
         const int member = (int)blockIdx.x / en.tiles;
         wid_ = (int)blockIdx.x - member * en.tiles;
@@ -192,6 +203,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
         if constexpr (GRAD) {
             a.g.traj += mb * en.traj_stride; a.g.hs_out += mb * (size_t)a.g.traj_cap;
             a.g.gpart += mb * (size_t)en.tiles * (size_t)a.g.n_params; a.g.lam_out += mb * Bz * nz;
+            if constexpr (CW) cwp = en.cw + mb * 4 * Bz;
         }
         sv.part += mb * en.part_stride; sv.base_dev += mb; sv.abort_flag += mb;
         if constexpr (GRAD) {
@@ -877,8 +889,19 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
         if (run_bwd) {
             // ================= backward: discrete adjoint of the accepted steps (oracle/cnf_grad_oracle.py) =================
             const float invB = 1.0f / (float)a.B;
-            const float cl0 = invB, cE0 = a.g.lam1 * invB, cn0 = a.g.lam2 * invB;   // cotangents of the scalar rows: constants
+            // CW: this lane's column of the member's cotangents, rows (logpx, E, n, A); columns past the batch carry none
+            float cwv[4] = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (CW) {
+                if (live) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) cwv[r] = cwp[(size_t)r * (size_t)a.B + (size_t)smp];
+                }
+            }
+            // cotangents of the scalar rows: constants of the loss -- CW: of this lane's column (the dlogp row carries -g_logpx;
+            // g_E and g_n are the cotangents themselves, not multiplied by lam1, lam2)
+            const float cl0 = CW ? -cwv[0] : invB, cE0 = CW ? cwv[1] : a.g.lam1 * invB, cn0 = CW ? cwv[2] : a.g.lam2 * invB;
             // d loss / d z(t1) = (z + lam3 unit(z_aug) on the augmented rows) / B      (k_final_cotangent)
+            // CW: -g_logpx z + g_A unit(z_aug) on the augmented rows                   (k_vjp_cotangent, N(0, I))
             f32x4 lam[NI];
             {
                 float sa = 0.f;
@@ -895,8 +918,14 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
                     for (int j = 0; j < 4; ++j) {
                         const int r = 16 * m + 4 * q + j;
                         float v = uz[m][j];
+                        if constexpr (CW) {
+                            v *= cl0;
+                            if (aug && r >= nd.nvars && nrm > 0.f) v = fmaf(cwv[3], uz[m][j] / nrm, v);
+                            lam[m][j] = live ? v : 0.f;
+                        } else {
                         if (aug && r >= nd.nvars && nrm > 0.f) v = fmaf(a.g.lam3, uz[m][j] / nrm, v);
                         lam[m][j] = live ? v * invB : 0.f;
+                        }
                     }
             }
             f32x4 gW2[NI][NH], gW1[NH][NI], gb1[NH], gb2[NI];
@@ -1360,17 +1389,17 @@ typedef void (*wave_fn)(WaveArgs, Solve3Args, const WvTab, const WaveEnsArgs, co
 constexpr int WV_M_VJP = 1, WV_M_TEST = 4, WV_M_ALL = 7;     // the modes a row of wave_instance is instantiated for: bit 1 << MODE
 
 // the mode, among those of MODES
-template <int MODES, int NI, int NH, bool TANH, bool GRAD, bool ID2, int WGW, bool RICH, bool ENS, bool PATH>
+template <int MODES, int NI, int NH, bool TANH, bool GRAD, bool ID2, int WGW, bool RICH, bool ENS, bool PATH, bool CW>
 wave_fn wave_instance_mode(int mode) {
-    if constexpr ((MODES & (1 << WV_VJP)) != 0) if (mode == WV_VJP) return (wave_fn)k_solve_wave<NI, NH, WV_VJP, TANH, GRAD, ID2, WGW, RICH, ENS, PATH>;
-    if constexpr ((MODES & (1 << WV_JVP)) != 0) if (mode == WV_JVP) return (wave_fn)k_solve_wave<NI, NH, WV_JVP, TANH, GRAD, ID2, WGW, RICH, ENS, PATH>;
-    if constexpr ((MODES & (1 << WV_TEST)) != 0) if (mode == WV_TEST) return (wave_fn)k_solve_wave<NI, NH, WV_TEST, TANH, GRAD, ID2, WGW, RICH, ENS, PATH>;
+    if constexpr ((MODES & (1 << WV_VJP)) != 0) if (mode == WV_VJP) return (wave_fn)k_solve_wave<NI, NH, WV_VJP, TANH, GRAD, ID2, WGW, RICH, ENS, PATH, CW>;
+    if constexpr ((MODES & (1 << WV_JVP)) != 0) if (mode == WV_JVP) return (wave_fn)k_solve_wave<NI, NH, WV_JVP, TANH, GRAD, ID2, WGW, RICH, ENS, PATH, CW>;
+    if constexpr ((MODES & (1 << WV_TEST)) != 0) if (mode == WV_TEST) return (wave_fn)k_solve_wave<NI, NH, WV_TEST, TANH, GRAD, ID2, WGW, RICH, ENS, PATH, CW>;
     return nullptr;
 }
 // the tiles: (1, 1..4) -- (1, 1) alone with the identity compiled out -- and, on the plain form, (2, 6)
-template <int MODES, bool TANH, bool GRAD, bool ID2, int WGW, bool RICH, bool ENS, bool PATH>
+template <int MODES, bool TANH, bool GRAD, bool ID2, int WGW, bool RICH, bool ENS, bool PATH, bool CW>
 wave_fn wave_instance_tiles(int ni, int nh, int mode) {
-#define WV_TILES(NIV, NHV) if (ni == NIV && nh == NHV) return wave_instance_mode<MODES, NIV, NHV, TANH, GRAD, ID2, WGW, RICH, ENS, PATH>(mode)
+#define WV_TILES(NIV, NHV) if (ni == NIV && nh == NHV) return wave_instance_mode<MODES, NIV, NHV, TANH, GRAD, ID2, WGW, RICH, ENS, PATH, CW>(mode)
     WV_TILES(1, 1);
     if constexpr (!ID2) {
         WV_TILES(1, 2);
@@ -1382,27 +1411,32 @@ wave_fn wave_instance_tiles(int ni, int nh, int mode) {
     return nullptr;
 }
 // One row per set of flags that is instantiated, each for the tiles above and the modes it names: these rows ARE the library's
-// k_solve_wave kernels (112 of them).  nullptr: no such kernel -- wave_variant does not return such a tuple.
-wave_fn wave_instance(const WaveVariant& v) {
-#define WV_ROW(MODES, TANH, GRAD, ID2, WGW, RICH, ENS, PATH)                                                                         \
-    if (v.tanh == TANH && v.grad == GRAD && v.id2 == ID2 && v.wgw == WGW && v.rich == RICH && v.ens == ENS && v.path == PATH) \
-        return wave_instance_tiles<MODES, TANH, GRAD, ID2, WGW, RICH, ENS, PATH>(v.ni, v.nh, v.mode)
-    //     modes      TANH   GRAD   ID2    WGW RICH   ENS    PATH
-    WV_ROW(WV_M_ALL,  true,  false, false, 1, false, false, false);     // WF_PLAIN
-    WV_ROW(WV_M_ALL,  false, false, false, 1, false, false, false);
-    WV_ROW(WV_M_ALL,  true,  false, true,  1, false, false, false);
-    WV_ROW(WV_M_ALL,  true,  false, false, 4, false, false, false);     // WF_WG4
-    WV_ROW(WV_M_VJP | WV_M_TEST, true, false, true, 4, false, false, false);
-    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, false, false);     // WF_GRAD
-    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, false, false);
-    WV_ROW(WV_M_VJP,  true,  true,  false, 1, true,  false, false);     // WF_GRAD_RICH
-    WV_ROW(WV_M_VJP,  true,  true,  true,  1, true,  false, false);
-    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, true,  false);     // WF_ENS_GRAD
-    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, true,  false);
-    WV_ROW(WV_M_ALL,  true,  false, false, 1, false, true,  false);     // WF_ENS_PLAIN
-    WV_ROW(WV_M_ALL,  true,  false, true,  1, false, true,  false);
-    WV_ROW(WV_M_ALL,  true,  false, false, 1, false, false, true);      // WF_PATH
-    WV_ROW(WV_M_ALL,  true,  false, true,  1, false, false, true);
+// k_solve_wave kernels (127 of them).  nullptr: no such kernel -- wave_variant does not return such a tuple.
+// cw: the CW form (per-sample cotangents, cnf_inference_vjp_many).  It is no WaveForm of its own: a caller selects it as "the
+// WF_ENS_GRAD answer of wave_variant, with CW" -- the same fifteen tuples, instantiated once more; with any other answer
+// there is no such kernel.
+wave_fn wave_instance(const WaveVariant& v, bool cw = false) {
+#define WV_ROW(MODES, TANH, GRAD, ID2, WGW, RICH, ENS, PATH, CW)                                                                         \
+    if (v.tanh == TANH && v.grad == GRAD && v.id2 == ID2 && v.wgw == WGW && v.rich == RICH && v.ens == ENS && v.path == PATH && cw == CW) \
+        return wave_instance_tiles<MODES, TANH, GRAD, ID2, WGW, RICH, ENS, PATH, CW>(v.ni, v.nh, v.mode)
+    //     modes      TANH   GRAD   ID2    WGW RICH   ENS    PATH   CW
+    WV_ROW(WV_M_ALL,  true,  false, false, 1, false, false, false, false);     // WF_PLAIN
+    WV_ROW(WV_M_ALL,  false, false, false, 1, false, false, false, false);
+    WV_ROW(WV_M_ALL,  true,  false, true,  1, false, false, false, false);
+    WV_ROW(WV_M_ALL,  true,  false, false, 4, false, false, false, false);     // WF_WG4
+    WV_ROW(WV_M_VJP | WV_M_TEST, true, false, true, 4, false, false, false, false);
+    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, false, false, false);     // WF_GRAD
+    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, false, false, false);
+    WV_ROW(WV_M_VJP,  true,  true,  false, 1, true,  false, false, false);     // WF_GRAD_RICH
+    WV_ROW(WV_M_VJP,  true,  true,  true,  1, true,  false, false, false);
+    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, true,  false, false);     // WF_ENS_GRAD
+    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, true,  false, false);
+    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, true,  false, true);      // WF_ENS_GRAD with CW
+    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, true,  false, true);
+    WV_ROW(WV_M_ALL,  true,  false, false, 1, false, true,  false, false);     // WF_ENS_PLAIN
+    WV_ROW(WV_M_ALL,  true,  false, true,  1, false, true,  false, false);
+    WV_ROW(WV_M_ALL,  true,  false, false, 1, false, false, true, false);      // WF_PATH
+    WV_ROW(WV_M_ALL,  true,  false, true,  1, false, false, true, false);
 #undef WV_ROW
     return nullptr;
 }
@@ -1412,9 +1446,9 @@ wave_fn wave_instance(const WaveVariant& v) {
 bool is_id2(const NetDesc& nd) { return nd.n_layers == 2 && nd.acts[0] == 1 && nd.acts[1] == 0; }
 int wave_mode(const NetDesc& nd, bool train) { return !train ? WV_TEST : (nd.jvp ? WV_JVP : WV_VJP); }
 // the kernel of `form` for this two-layer network and mode (nullptr: there is none)
-wave_fn wave_kernel(WaveForm form, const NetDesc& nd, bool train) {
+wave_fn wave_kernel(WaveForm form, const NetDesc& nd, bool train, bool cw = false) {
     const auto v = wave_variant(form, (nd.n_in + 15) / 16, (nd.dims[1] + 15) / 16, wave_mode(nd, train), nd.acts[0] == 1 && nd.acts[1] == 1, is_id2(nd));
-    return v ? wave_instance(*v) : nullptr;
+    return v ? wave_instance(*v, cw) : nullptr;
 }
 // CNF_PERSISTENT=0 / CNF_WAVE=0: no one-launch solve / none of this file's
 bool wave_off() {
@@ -1476,13 +1510,13 @@ bool wave_grad_supported(const NetDesc& nd, int B, bool train) {
 // ---- the ensemble form (cnf_loss_grad_many): M x tiles workgroups, each member's tiles meeting among themselves ----
 // (the envelope below -- two layers, tanh then tanh or identity, one input tile, up to four hidden tiles, one with the identity --
 // is restated in continuousnf.jl_amd/ensemble.py `_refusal`, which has to refuse before a handle exists: change both together)
-static wave_fn ens_fn(WaveForm form, const NetDesc& nd, bool train) {
+static wave_fn ens_fn(WaveForm form, const NetDesc& nd, bool train, bool cw = false) {
     if (nd.n_layers != 2 || nd.n_cond > 0 || nd.id2) return nullptr;      // (an APPENDED identity layer lives behind the handle's own parameters)
     if (nd.acts[0] != 1 || !(nd.acts[1] == 1 || is_id2(nd))) return nullptr;
-    return wave_kernel(form, nd, train);
+    return wave_kernel(form, nd, train, cw);
 }
-int wave_ens_capacity(const NetDesc& nd, bool train, int B) {
-    wave_fn fn = ens_fn(WF_ENS_GRAD, nd, train);
+int wave_ens_capacity(const NetDesc& nd, bool train, int B, bool cw) {
+    wave_fn fn = ens_fn(WF_ENS_GRAD, nd, train, cw);
     if (wave_off() || !fn || B < 1 || !wave_grad_supported(nd, B, train)) return 0;
     return wave_resident_workgroups(fn, 128) / wave_grad_waves(B);     // (main wave + helper)
 }
@@ -1498,7 +1532,9 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
                              const WaveGradArgs* grad, const WaveEnsLaunch* ens, const WavePathArgs* path) {
     if (!wave_solve_supported(nd, train, B)) return CNF_ERR_UNSUPPORTED;
     if (path && (grad || ens || !path->times || !path->out || path->K < 1 || (path->steps_cap > 0 && !path->steps))) return CNF_ERR_BAD_ARG;
-    if (ens && (cond || mirror || ens->M < 1 || ens->M > (grad ? wave_ens_capacity(nd, train, B) : wave_ens_eval_capacity(nd, train, B))))
+    const bool cw = ens && ens->cw;                        // the CW form of the ensemble gradient
+    if (cw && !grad) return CNF_ERR_BAD_ARG;
+    if (ens && (cond || mirror || ens->M < 1 || ens->M > (grad ? wave_ens_capacity(nd, train, B, cw) : wave_ens_eval_capacity(nd, train, B))))
         return CNF_ERR_UNSUPPORTED;
     if (grad && nd.n_cond > 0 && !grad->ys) return CNF_ERR_BAD_ARG;
     if (grad && (!wave_grad_supported(nd, B, train) || !grad->traj || !grad->gpart || !grad->lam_out || !grad->hs_out || grad->traj_cap < 1))
@@ -1526,7 +1562,7 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
     }
     if (tiles > 512 && !xwg) return CNF_ERR_UNSUPPORTED;     // (a meeting has at most 512 parties)
     // ---- the kernel ----
-    wave_fn fn = wave_kernel(form, nd, train);
+    wave_fn fn = wave_kernel(form, nd, train, cw);
     if (!fn) return form == WF_GRAD_RICH ? CNF_ERR_BAD_ARG : CNF_ERR_UNSUPPORTED;       // (wave_grad_rich_floats said it exists)
     // ---- grid and block: a gradient's tile has its main wave and its helper ----
     int grid = form == WF_WG4 ? (xwg ? (tiles + 3) / 4 : 1) : tiles;
@@ -1550,7 +1586,7 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
         en.t0 = ens->t0;
     } else if (ens) {
         if (grad->rich || sv.trace || sv.t_out || !sv.xs || !sv.logpx || !sv.regs || !sv.sums5 || sv.u_out) return CNF_ERR_BAD_ARG;
-        en.traj_stride = ens->traj_stride;
+        en.traj_stride = ens->traj_stride; en.cw = ens->cw;
     }
     if (ens) {                                             // M x tiles workgroups
         en.tiles = tiles; en.t1 = ens->t1; en.p_stride = ens->p_stride; en.part_stride = ens->part_stride;

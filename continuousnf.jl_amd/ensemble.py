@@ -491,6 +491,168 @@ def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, 
     return (xs, lq) if with_logp else xs
 
 
+# ---------------------------------------------------------------------------------------
+# differentiable ensembles (include/cnfhip_ensemble_vjp.h)
+# ---------------------------------------------------------------------------------------
+def ensemble_vjp_capacity(icnf: ICNF, mode, B: int) -> int:
+    """The largest M one ``inference_vjp_many`` launch takes for this model, mode and batch size (cnf_ensemble_vjp_capacity);
+    0: no ensemble form."""
+    m = _mode_id(mode)
+    if _refusal(icnf) is not None:
+        return 0
+    return int(_lib.lib().cnf_ensemble_vjp_capacity(icnf.handle(), m, int(B)))
+
+
+def _cot_many(cot, M, B):
+    """``(g_logpx, (g_E, g_n, g_A))``, each an (M, B) tensor or None (the convention of ``inference_pullback``; a bare None for
+    the triple: no cotangent on the regularisers) -> the four rows; ``ValueError`` for anything else.  Host logic only."""
+    if not isinstance(cot, (tuple, list)) or len(cot) != 2 or not (cot[1] is None or isinstance(cot[1], (tuple, list))):
+        raise ValueError("cot must be (g_logpx, (g_E, g_n, g_A))")
+    rows = [cot[0]] + list(cot[1] if cot[1] is not None else (None, None, None))
+    if len(rows) != 4:
+        raise ValueError("cot must be (g_logpx, (g_E, g_n, g_A))")
+    for name, r in zip(("g_logpx", "g_E", "g_n", "g_A"), rows):
+        if r is None:
+            continue
+        if not _is_torch(r):
+            raise ValueError(f"cot: {name} must be a device tensor or None")
+        if tuple(r.shape) != (M, B):
+            raise ValueError(f"cot: {name} must be (M = {M}, B = {B}), got {tuple(r.shape)}")
+    return rows
+
+
+def inference_vjp_many(icnf: ICNF, mode, xs, ps, st, cot, eps=None, t1=None, with_x=False, with_steps=False):
+    """``inference`` of M members and its vector-Jacobian product for a per-sample cotangent, in ONE launch and one of the
+    partial sums (cnf_inference_vjp_many): what ``inference_record`` + ``inference_pullback`` give for one model.  ``xs``
+    (M, nvars, B) or (nvars, B): one data set shared by all members, as ``inference_many`` takes it; ``ps`` (M, n_params);
+    ``cot = (g_logpx, (g_E, g_n, g_A))``, each (M, B) or None (zeros) -- the cotangents themselves, not multiplied by the
+    regularisers' weights; a row the model does not integrate (``lambda1``, ``lambda2``, ``lambda3`` = 0; all three in
+    TestMode) is ignored.  ``eps`` and ``t1`` as ``loss_and_grad_many`` takes and draws them, in its order.  Returns
+    ``(logpx (M, B), (E, n, A), grads (M, n_params), [grad_x (M, nvars, B) with with_x,] info)``:
+    ``grads[m] = sum_b sum_r cot[r][m, b] d out_r[m, b] / d ps[m]`` through the steps member m's own solve accepted.  ``info``
+    as ``loss_and_grad_many``'s, with ``eps`` (M, n_in, B; None in TestMode): the probes used; a member whose part of the launch
+    gave up is run again with ``inference_record`` + ``inference_pullback`` (``info["rerun"]``).  Failures and refusals as
+    ``loss_and_grad_many``."""
+    import torch
+    who = "inference_vjp_many"
+    if _is_torch(xs) and _is_torch(ps) and xs.dim() == 2 and ps.dim() == 2 and _refusal(icnf) is None:
+        xs = xs.unsqueeze(0).expand(ps.shape[0], *xs.shape)                # shared data: every member reads its own copy
+    m, M, B, n_in, t1 = _check_inputs(icnf, mode, xs, ps, eps, t1, who, "inference_record and inference_pullback")
+    rows = _cot_many(cot, M, B)
+    l, h = _lib.lib(), icnf.handle()
+    if not (xs.is_cuda and ps.is_cuda and (eps is None or eps.is_cuda) and all(r is None or r.is_cuda for r in rows)):
+        raise ValueError(f"{who}: torch tensors must live on the GPU")
+    cap = _device_capacity(who, "cnf_ensemble_vjp_capacity", h, m, B)
+    train = m == _lib.MODE_TRAIN
+    dev = xs.device
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    xr = _rows(xs)
+    pr = ps.detach().to(torch.float32).contiguous()
+    er, t1 = _probes_and_ends(icnf, mode, train, M, B, n_in, xr, eps, t1)
+    cm = torch.zeros((M, 4, B), dtype=torch.float32, device=dev)
+    for i, r in enumerate(rows):
+        if r is not None:
+            cm[:, i].copy_(r.detach())
+    opts = _solve_opts(icnf, icnf.tspan)
+    n_params = pr.shape[1]
+    logpx, regs = torch.empty((M, B), dtype=torch.float32, device=dev), torch.empty((M, 3, B), dtype=torch.float32, device=dev)
+    grads = torch.empty((M, n_params), dtype=torch.float32, device=dev)
+    gz = torch.empty((M, B, n_in), dtype=torch.float32, device=dev) if with_x else None
+    stats, status, calls, steps = _chunked_calls(icnf, M, cap, lambda lo, n, status, stats: l.cnf_inference_vjp_many(
+        h, m, n, pr[lo].data_ptr(), xr[lo].data_ptr(), er[lo].data_ptr() if er is not None else None, B, C.byref(opts),
+        t1[lo:].ctypes.data if t1 is not None else None, cm[lo].data_ptr(), logpx[lo].data_ptr(), regs[lo].data_ptr(),
+        grads[lo].data_ptr(), gz[lo].data_ptr() if with_x else None, status, stats, stream),
+        ensemble_steps if with_steps else None)
+    icnf._record = None                                    # (the call ended whatever was recorded on the handle)
+    info = _info(icnf, stats, status, calls, "t1", t1, eps=er.permute(0, 2, 1) if er is not None else None)
+    _raise_failed(status)
+    gx = gz[:, :, :icnf.nvars].permute(0, 2, 1).contiguous() if with_x else None
+    gave_up = [i for i in range(M) if status[i] != _lib.OK]
+    if gave_up:
+        from .vjp import inference_pullback, inference_record
+        with _one_member_at_a_time(icnf, t1) as member:
+            for i in gave_up:
+                member(i)
+                lp, rg = inference_record(icnf, mode, xr[i].t(), pr[i], st, eps=er[i].t() if train else None, tspan=icnf.tspan)
+                res = inference_pullback(icnf, cm[i], with_x=with_x)
+                logpx[i].copy_(lp)
+                regs[i].copy_(torch.stack(list(rg)))
+                grads[i].copy_(res[0] if with_x else res)
+                if with_x:
+                    gx[i].copy_(res[1])
+                status[i] = _lib.OK
+                info["stats"][i] = dict(icnf.last_stats)
+                if with_steps:
+                    steps[i] = np.array(icnf.last_steps, dtype=np.float32)
+        icnf._record = None                                # (the members' records are not the caller's)
+        info["rerun"] = gave_up
+    if with_steps:
+        info["steps"] = steps
+    icnf.last_stats = info["stats"][0]
+    out = (logpx, (regs[:, 0], regs[:, 1], regs[:, 2]), grads)
+    return out + ((gx, info) if with_x else (info,))
+
+
+_FUNCTION_MANY = None
+
+
+def _autograd_function_many():
+    import torch
+
+    class _InferenceMany(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, icnf, mode, xs, ps, eps, t1):
+            logpx, (E, n, A), _ = inference_many(icnf, mode, xs.detach(), ps.detach(), None, eps=eps, t1=t1)
+            ctx.icnf, ctx.mode = icnf, mode
+            # what the backward launch solves again: the same data, parameters, probes and end times
+            ctx.xs, ctx.ps, ctx.eps, ctx.t1 = xs.detach(), ps.detach().clone(), eps, t1
+            ctx.set_materialize_grads(False)
+            return logpx, E.clone(), n.clone(), A.clone()
+
+        @staticmethod
+        def backward(ctx, g_logpx, g_E, g_n, g_A):
+            icnf = ctx.icnf
+            need_x, need_ps = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+            if not (need_x or need_ps):
+                return None, None, None, None, None, None
+            res = inference_vjp_many(icnf, ctx.mode, ctx.xs, ctx.ps, None, (g_logpx, (g_E, g_n, g_A)), eps=ctx.eps, t1=ctx.t1,
+                                     with_x=bool(need_x))
+            icnf.last_backward_logpx = res[0]              # (the backward launch's own logpx: compared with the forward's in the tests)
+            gx = None
+            if need_x:
+                gx = res[3] if ctx.xs.dim() == 3 else res[3].sum(dim=0)    # (a shared data set collects every member's)
+            return None, None, gx, res[2] if need_ps else None, None, None
+
+    return _InferenceMany
+
+
+def differentiable_inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None):
+    """``inference_many`` as a differentiable function of ``ps`` (M, n_params) and, when it requires grad, ``xs`` ((M, nvars, B),
+    or (nvars, B) shared by all members): the forward is ``inference_many``, keeping the probes and end times it used; the
+    backward is ONE ``inference_vjp_many`` with those same draws.  Returns ``(logpx (M, B), (E, n, A))`` attached to the autograd
+    graph.  The backward launch solves again: its gradient is the exact discrete adjoint of the steps IT accepts (the solve is
+    deterministic, so they are the forward's for the same inputs; DESIGN 4.4 says how its ``logpx`` compares with the
+    forward's -- ``icnf.last_backward_logpx`` keeps it)."""
+    global _FUNCTION_MANY
+    import torch
+    if not (_is_torch(xs) and _is_torch(ps)):
+        raise NotImplementedError("differentiable_inference_many takes device tensors")
+    # the probes and the steered end times are settled here, once (inference_many's order: the probes, then the end times), so
+    # that forward and backward are given the very same ones
+    xe = xs.detach()
+    if xe.dim() == 2 and ps.dim() == 2 and _refusal(icnf) is None:
+        xe = xe.unsqueeze(0).expand(ps.shape[0], *xe.shape)
+    m, M, B, n_in, t1 = _check_inputs(icnf, mode, xe, ps, eps, t1, "differentiable_inference_many", "differentiable_inference")
+    if not (xs.is_cuda and ps.is_cuda and (eps is None or eps.is_cuda)):
+        raise ValueError("differentiable_inference_many: torch tensors must live on the GPU")
+    er, t1 = _probes_and_ends(icnf, mode, m == _lib.MODE_TRAIN, M, B, n_in, _rows(xe), eps, t1)
+    eps = er.permute(0, 2, 1) if er is not None else None
+    if _FUNCTION_MANY is None:
+        _FUNCTION_MANY = _autograd_function_many()
+    logpx, E, n, A = _FUNCTION_MANY.apply(icnf, mode, xs, ps, eps, t1)
+    return logpx, (E, n, A)
+
+
 # ---- the bagged density: a mixture of the members ----
 def mixture_logpdf(logp, weights):
     """``logsumexp_m(log w_m + logp[m, :])`` of an (M, n) matrix of the members' log-densities (numpy array or torch tensor;
@@ -544,7 +706,10 @@ class EnsembleDist:
         if not _is_torch(ps) or ps.dim() != 2:
             raise ValueError("ps must be an (M, n_params) tensor")
         self.m, self.mode, self.ps, self.st = icnf, mode, ps, st
-        self.weights = check_weights(weights, int(ps.shape[0]))
+        # (a tensor of weights -- e.g. the softmax of logits that stacking trains -- is kept for log_prob; its values are checked
+        # like any others)
+        self.weights_t = weights if _is_torch(weights) else None
+        self.weights = check_weights(weights.detach().cpu().numpy() if _is_torch(weights) else weights, int(ps.shape[0]))
 
     def __len__(self):
         return self.m.nvars
@@ -558,6 +723,17 @@ class EnsembleDist:
 
     def pdf(self, A, *, eps=None):
         return self.logpdf(A, eps=eps).exp()
+
+    def log_prob(self, xs):
+        """The mixture's exact log-density ``logsumexp_m(log w_m + logpdf_m(xs))`` of the columns of ``xs`` (nvars, n) as a
+        differentiable function of the members' parameters ``ps``, of ``xs`` and of ``weights`` when that is a tensor requiring
+        grad (stacking: the mixture weights trained together with the members; ``log_softmax`` of logits is the caller's
+        business): ``differentiable_inference_many`` in TestMode -- one launch forward, one ``inference_vjp_many`` backward."""
+        import torch
+        from .types import TestMode
+        logp = differentiable_inference_many(self.m, TestMode(), xs, self.ps, self.st)[0]
+        w = self.weights_t if self.weights_t is not None else torch.as_tensor(self.weights)
+        return torch.logsumexp(logp + torch.log(w.to(device=logp.device, dtype=logp.dtype))[:, None], dim=0)
 
     def rand(self, n: int, *, with_members=False):
         """``n`` draws of the mixture, (nvars, n) on the device: the members' counts from one multinomial draw on the model's

@@ -370,6 +370,10 @@ cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int B, float* 
  * cnf_ensemble_eval_steps (declared in cnfhip_ensemble_eval.h, part of this header) ---- */
 #include "cnfhip_ensemble_eval.h"
 
+/* ---- differentiable ensembles: cnf_ensemble_vjp_capacity / cnf_inference_vjp_many (declared in cnfhip_ensemble_vjp.h, part of
+ * this header) ---- */
+#include "cnfhip_ensemble_vjp.h"
+
 /* ---- flow paths: the solve's columns at caller-given times, from Tsit5's interpolant (declared in cnfhip_path.h, part of this
  * header) ---- */
 #include "cnfhip_path.h"

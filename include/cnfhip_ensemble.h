@@ -34,8 +34,9 @@ cnf_status cnf_loss_grad_many(cnf_handle h, int mode, int M, const float* params
                               const cnf_solve_opts* opts, const float* t1_host, float* loss_out, float* grad_dev,
                               int* status_out, cnf_solve_stats* stats_out, void* stream);
 
-/* The signed sizes of the steps member `member` accepted in the last cnf_loss_grad_many call, in the manner of cnf_grad_steps:
- * returns their number and copies min(number, cap) of them into hs (HOST; may be NULL).  -1: no such member, or it gave up. */
+/* The signed sizes of the steps member `member` accepted in the last ensemble gradient call -- cnf_loss_grad_many or
+ * cnf_inference_vjp_many (cnfhip_ensemble_vjp.h), whichever came last --, in the manner of cnf_grad_steps: returns their number
+ * and copies min(number, cap) of them into hs (HOST; may be NULL).  -1: no such member, or it gave up. */
 int cnf_ensemble_steps(cnf_handle h, int member, float* hs, int cap);
 
 #endif /* CNFHIP_ENSEMBLE_H */
