@@ -63,6 +63,7 @@ from .ensemble import ensemble_capacity, ensemble_steps, fit_many, loss_and_grad
 from .ensemble import EnsembleDist, ensemble_eval_capacity, ensemble_eval_steps, generate_many, inference_many, logpdf_members, \
     loss_many
 from .ensemble import differentiable_inference_many, ensemble_vjp_capacity, inference_vjp_many
+from .ensemble import differentiable_generate_many, ensemble_generate_vjp_capacity, generate_vjp_many, reverse_kl_many
 from . import path
 from .path import generate_path, inference_path, solve_path
 from .mlj import (Adam, CondICNFModel, ICNFModel, Lion, Machine, fit, fit_, fitted_params, load_params, machine, save_params,

@@ -160,6 +160,13 @@ _ENSEMBLE_VJP_SIGNATURES = {
                                          _fp, _fp, _fp, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 ENSEMBLE_VJP_EXPORTS = tuple(_ENSEMBLE_VJP_SIGNATURES)
+# differentiable ensemble sampling (include/cnfhip_ensemble_generate_vjp.h): likewise
+_ENSEMBLE_GENERATE_VJP_SIGNATURES = {
+    "cnf_ensemble_generate_vjp_capacity": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "cnf_generate_vjp_many": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), _fp, _fp, _fp,
+                                        _fp, _fp, _fp, _fp, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+ENSEMBLE_GENERATE_VJP_EXPORTS = tuple(_ENSEMBLE_GENERATE_VJP_SIGNATURES)
 # flow paths (include/cnfhip_path.h): likewise
 _PATH_SIGNATURES = {
     "cnf_solve_path": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), _fp, C.c_int, _fp,
@@ -206,7 +213,7 @@ def lib():
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in list(_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) + list(_BASEGRAD_SIGNATURES.items()) + \
                 list(_ENSEMBLE_SIGNATURES.items()) + list(_ENSEMBLE_EVAL_SIGNATURES.items()) + list(_ENSEMBLE_VJP_SIGNATURES.items()) + \
-                list(_PATH_SIGNATURES.items()):
+                list(_ENSEMBLE_GENERATE_VJP_SIGNATURES.items()) + list(_PATH_SIGNATURES.items()):
             f = getattr(l, name)
             f.restype, f.argtypes = res, args
         _lib = l

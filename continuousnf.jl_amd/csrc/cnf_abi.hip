@@ -2630,8 +2630,8 @@ static bool ens_handle_ok(cnf_handle h, int mode) {
     if (!h || (mode != CNF_MODE_TEST && mode != CNF_MODE_TRAIN)) return false;
     return !(h->nd.n_cond > 0 || h->bd.kind || h->grad_ys || h->shard_reduce || h->shard_comm || h->no_persist);
 }
-// cw: of the per-sample-cotangent form (cnf_inference_vjp_many), whose kernels have their own register budget
-static int ens_grad_capacity(cnf_handle h, int mode, int B, bool cw) {
+// cw: of that per-sample-cotangent form (cnf_inference_vjp_many, cnf_generate_vjp_many), whose kernels have their own register budget
+static int ens_grad_capacity(cnf_handle h, int mode, int B, WaveCot cw) {
     if (B < 1 || !ens_handle_ok(h, mode)) return 0;
     if (hipSetDevice(h->device) != hipSuccess) { (void)hipGetLastError(); return 0; }
     int cap = wave_ens_capacity(h->nd_wave, mode == CNF_MODE_TRAIN, B, cw);
@@ -2641,14 +2641,15 @@ static int ens_grad_capacity(cnf_handle h, int mode, int B, bool cw) {
     if ((size_t)cap > fit) cap = (int)fit;
     return cap;
 }
-extern "C" int cnf_ensemble_capacity(cnf_handle h, int mode, int B) { return ens_grad_capacity(h, mode, B, false); }
-extern "C" int cnf_ensemble_vjp_capacity(cnf_handle h, int mode, int B) { return ens_grad_capacity(h, mode, B, true); }
+extern "C" int cnf_ensemble_capacity(cnf_handle h, int mode, int B) { return ens_grad_capacity(h, mode, B, WC_LOSS); }
+extern "C" int cnf_ensemble_vjp_capacity(cnf_handle h, int mode, int B) { return ens_grad_capacity(h, mode, B, WC_INFERENCE); }
+extern "C" int cnf_ensemble_generate_vjp_capacity(cnf_handle h, int mode, int B) { return ens_grad_capacity(h, mode, B, WC_SAMPLING); }
 
 // ---- What cnf_loss_grad_many and ens_eval (cnf_inference_many, cnf_generate_many: further down) share, each step once: the
 // checks, the growth of the stores, the launch preamble and the read-back.  EnsCall is one call's arguments and, from ens_begin
 // to ens_finish, its lock and the common part of its Solve3Args. ----
 struct EnsCall {
-    bool grad, gen;                // cnf_loss_grad_many | ens_eval: sampling (times are the members' START times) or inference
+    bool grad, gen;                // an ensemble gradient call | sampling (times are the members' START times) or inference
     int mode, M, B, trace_cap;
     const cnf_solve_opts* opts;
     const float* times;            // the members' own end (gen: start) times on the host, or null: opts' for all
@@ -2656,7 +2657,7 @@ struct EnsCall {
     std::unique_lock<std::mutex> lock;     // g_persist_mu
     bool hairer = false;
     Solve3Args sv{};
-    bool vjp = false;              // grad: cnf_inference_vjp_many (per-sample cotangents) rather than cnf_loss_grad_many
+    WaveCot cot = WC_LOSS;         // grad: the built-in loss (cnf_loss_grad_many) or per-sample cotangents (the two vjp calls)
 };
 constexpr size_t ENS_ST_F = (sizeof(StepState) + 3) / 4;     // floats of one member's final state in ens_fin / ens_hfin ...
 static size_t ens_fin_floats(int M) { return (size_t)M * (ENS_ST_F + 5); }      // ... and of all M, their five loss sums behind them
@@ -2678,7 +2679,7 @@ static cnf_status ens_check(cnf_handle h, const EnsCall& c, bool null_ptr, const
     while (!h->collecting && !h->submitted.empty())       // (as any other call: the inferences submitted on the handle end first)
         if ((s = collect_one(h, nullptr)) != CNF_OK) return s;
     if (c.opts->kernel == CNF_KERNEL_GENERIC) return fail(h, CNF_ERR_UNSUPPORTED, "the ensemble form exists on the wave kernels only");
-    const int capacity = c.grad ? ens_grad_capacity(h, c.mode, c.B, c.vjp) : cnf_ensemble_eval_capacity(h, c.mode, c.B);
+    const int capacity = c.grad ? ens_grad_capacity(h, c.mode, c.B, c.cot) : cnf_ensemble_eval_capacity(h, c.mode, c.B);
     if (capacity < 1) return fail(h, CNF_ERR_UNSUPPORTED, "no ensemble form for this model, mode or batch");
     if (c.M > capacity)
         return fail(h, CNF_ERR_UNSUPPORTED, (std::string("more members than one launch takes (") + capacity_fn + ")").c_str());
@@ -2776,60 +2777,95 @@ static cnf_status ens_finish(cnf_handle h, EnsCall& c, int launches, bool sums, 
     return CNF_OK;
 }
 
-// What the two ensemble gradient calls share: cnf_loss_grad_many (cot_dev null: the built-in loss's cotangent, losses in loss_out;
-// logpx, regs and d / d z(t0) stay in the ensemble's own column store) and cnf_inference_vjp_many (cot_dev [M][4][B]: the CW
-// form of the kernel; logpx_dev, regs_dev and -- may be null -- grad_x_dev are the caller's, loss_out is null).
-static cnf_status ens_grad(cnf_handle h, bool vjp, int mode, int M, const float* params_dev, const float* xs, const float* eps, int B,
-                           const cnf_solve_opts* opts, const float* t1_host, const float* cot_dev, float* loss_out, float* logpx_dev,
-                           float* regs_dev, float* grad_dev, float* grad_x_dev, int* status_out, cnf_solve_stats* stats_out, void* stream) {
-    const bool train = mode == CNF_MODE_TRAIN;
-    EnsCall c{true, false, mode, M, B, 0, opts, t1_host, (hipStream_t)stream};
-    c.vjp = vjp;
-    cnf_status s = ens_check(h, c, !params_dev || !xs || !opts || !grad_dev || !status_out || (train && !eps) ||
-                                       (vjp ? !cot_dev || !logpx_dev || !regs_dev : !loss_out),
+// u0 = [z0; 0] of all `cols_n` = M B columns of a sampling call (the members' columns are contiguous), D floats per column
+static cnf_status ens_sampling_u0(cnf_handle h, float* u0, const float* z0, size_t cols_n, size_t n_in, size_t D, hipStream_t st) {
+    HIPCHK(h, hipMemsetAsync(u0, 0, cols_n * D * sizeof(float), st));
+    HIPCHK(h, hipMemcpy2DAsync(u0, D * sizeof(float), z0, n_in * sizeof(float), n_in * sizeof(float), cols_n, hipMemcpyDeviceToDevice, st));
+    return CNF_OK;
+}
+
+// What the three ensemble gradient calls share.
+//   cnf_loss_grad_many (WC_LOSS): src = xs; the built-in loss's cotangent, losses in loss_out; logpx, regs and d / d z(t0) stay in
+//     the ensemble's own column store.
+//   cnf_inference_vjp_many (WC_INFERENCE): src = xs, cot0 = [M][4][B]: the CW form of the kernel; out0 = logpx, out1 = regs and --
+//     may be null -- grad_in = d / d z(t0) are the caller's.
+//   cnf_generate_vjp_many (WC_SAMPLING): src = z0, times = the START times, cot0 = cot_z, cot1 = cot_logq (either may be null); the
+//     sampling CW form integrates u0 = [z0; 0] (built in the column store, the final columns behind it); out0 = x, out1 = logq
+//     and grad_in = d / d z0 (may be null) come from the column kernels of cnf_dist.hip over the M B columns as one batch.
+static cnf_status ens_grad(cnf_handle h, WaveCot cot, int mode, int M, const float* params_dev, const float* src, const float* eps, int B,
+                           const cnf_solve_opts* opts, const float* times_host, const float* cot0, const float* cot1, float* loss_out,
+                           float* out0, float* out1, float* grad_dev, float* grad_in, int* status_out, cnf_solve_stats* stats_out,
+                           void* stream) {
+    const bool train = mode == CNF_MODE_TRAIN, vjp = cot != WC_LOSS, gen = cot == WC_SAMPLING;
+    EnsCall c{true, gen, mode, M, B, 0, opts, times_host, (hipStream_t)stream};
+    c.cot = cot;
+    cnf_status s = ens_check(h, c, !params_dev || !src || !opts || !grad_dev || !status_out || (train && !eps) ||
+                                       (gen ? (!cot0 && !cot1) || !out0 || !out1 : vjp ? !cot0 || !out0 || !out1 : !loss_out),
                              vjp ? "B must be >= 1" : "the loss is a mean over the batch: B must be >= 1",
-                             vjp ? "cnf_ensemble_vjp_capacity" : "cnf_ensemble_capacity");
+                             gen ? "cnf_ensemble_generate_vjp_capacity" : vjp ? "cnf_ensemble_vjp_capacity" : "cnf_ensemble_capacity");
     if (s != CNF_OK) return s;
     const NetDesc& nd = h->nd_wave;
-    const size_t Mz = (size_t)M, Bz = (size_t)B, n_in = (size_t)nd.n_in, D = n_in + (train ? 3 : 1), np = h->n_params;
+    const size_t Mz = (size_t)M, Bz = (size_t)B, n_in = (size_t)nd.n_in, nv = (size_t)nd.nvars, D = n_in + (train ? 3 : 1), np = h->n_params;
     const size_t per_step = wave_grad_traj_floats(nd, B);
     // step slots per member: the single model's, for the M trajectory stores together
     const int tiles = wave_grad_waves(B), cap = traj_step_slots(per_step * Mz);
-    if ((s = ens_grow(h, c, Mz * Bz * (D + 4 + n_in), per_step * cap * Mz, Mz * cap, Mz * tiles * np, 0)) != CNF_OK) return s;
+    // the column store: final columns | logpx | regs | d / d z(t0);  sampling: u0 | final columns | d / d u(t_start)
+    if ((s = ens_grow(h, c, Mz * Bz * (gen ? 2 * D + n_in : D + 4 + n_in), per_step * cap * Mz, Mz * cap, Mz * tiles * np, 0)) != CNF_OK) return s;
     h->rec.clear();                                        // (as every gradient call; the handle's own model is not touched)
     h->ens_M = 0;
     if ((s = ens_begin(h, c)) != CNF_OK) return s;
     StepState* fin_dev = reinterpret_cast<StepState*>(h->ens_fin.data());
     float* cols = h->ens_cols;
+    float* fsol = gen ? cols + Mz * Bz * D : cols;         // the final columns
     Solve3Args& sv = c.sv;
-    sv.xs = xs; sv.logpx = vjp ? logpx_dev : cols + Mz * Bz * D; sv.regs = vjp ? regs_dev : cols + Mz * Bz * (D + 1);
-    sv.sums5 = h->ens_fin + Mz * ENS_ST_F;
     WaveGradArgs wg;
-    wg.traj = h->ens_traj; wg.traj_cap = cap; wg.hs_out = h->ens_hs; wg.gpart = h->ens_gpart;
-    wg.lam_out = grad_x_dev ? grad_x_dev : cols + Mz * Bz * (D + 4); wg.n_params = (int)np;
+    if (gen) {
+        if ((s = ens_sampling_u0(h, cols, src, Mz * Bz, n_in, D, c.st)) != CNF_OK) return s;
+        sv.u0 = cols;
+        wg.lam_out = cols + Mz * Bz * 2 * D;               // (k_generate_z0_grad must not write where it reads)
+    } else {
+        sv.xs = src; sv.logpx = vjp ? out0 : cols + Mz * Bz * D; sv.regs = vjp ? out1 : cols + Mz * Bz * (D + 1);
+        sv.sums5 = h->ens_fin + Mz * ENS_ST_F;
+        wg.lam_out = grad_in ? grad_in : cols + Mz * Bz * (D + 4);
+    }
+    wg.traj = h->ens_traj; wg.traj_cap = cap; wg.hs_out = h->ens_hs; wg.gpart = h->ens_gpart; wg.n_params = (int)np;
     wg.lam1 = h->lam[0]; wg.lam2 = h->lam[1]; wg.lam3 = h->lam[2];
     WaveEnsLaunch ens;
-    ens.M = M; ens.t1 = t1_host ? h->ens_t1.data() : nullptr; ens.cw = vjp ? cot_dev : nullptr;
+    ens.M = M;
+    (gen ? ens.t0 : ens.t1) = times_host ? h->ens_t1.data() : nullptr;
+    if (gen) { ens.sampling = true; ens.cot_z = cot0; ens.cot_logq = cot1; }
+    else ens.cw = vjp ? cot0 : nullptr;
     ens.p_stride = np; ens.traj_stride = per_step * cap; ens.part_stride = WV_ENS_PART_FLOATS;
     int launches = 0;                                      // kernel launches of this call, counted where they are made
-    s = wave_solve_launch(nd, train, params_dev, nullptr, 0, fin_dev, cols, eps, B, c.st, nullptr, 0, sv, &wg, &ens);
+    s = wave_solve_launch(nd, train, params_dev, nullptr, 0, fin_dev, fsol, eps, B, c.st, nullptr, 0, sv, &wg, &ens);
     if (s != CNF_OK) return fail(h, s, "the ensemble launch failed to start");
     ++launches;
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, launch_grad_reduce_many(wg.gpart, grad_dev, (int)np, tiles, fin_dev, M, c.st));
     ++launches;
-    if ((s = ens_finish(h, c, launches, true, loss_out, status_out, stats_out, h->ens_nacc, false)) != CNF_OK) return s;
+    if (gen) {                                             // the column kernels: x and logq off the final state, then the z0 tail
+        launch_generate_post_rows((int)n_in, (int)nv, (int)D, fsol, src, out0, out1, Mz * Bz, c.st);
+        HIPCHK(h, hipGetLastError());
+        ++launches;
+        if (grad_in) {
+            launch_generate_z0_grad((int)n_in, BaseDist{}, wg.lam_out, cot1, src, grad_in, Mz * Bz, c.st);
+            HIPCHK(h, hipGetLastError());
+            ++launches;
+        }
+    }
+    if ((s = ens_finish(h, c, launches, !gen, loss_out, status_out, stats_out, h->ens_nacc, false)) != CNF_OK) return s;
     h->ens_M = M; h->ens_cap = cap;
     if (vjp) {                                             // nothing of a member that is not CNF_OK is valid: NaN outputs, zero gradients
         bool any_bad = false;
+        const size_t n0 = gen ? Bz * nv : Bz, n1 = gen ? Bz : 3 * Bz;
         for (int m = 0; m < M; ++m)
             if (status_out[m] != CNF_OK) {
                 any_bad = true;
                 const size_t mz = (size_t)m;
-                HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(logpx_dev + mz * Bz), 0x7fc00000, Bz, c.st));
-                HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(regs_dev + mz * 3 * Bz), 0x7fc00000, 3 * Bz, c.st));
+                HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(out0 + mz * n0), 0x7fc00000, n0, c.st));
+                HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(out1 + mz * n1), 0x7fc00000, n1, c.st));
                 HIPCHK(h, hipMemsetAsync(grad_dev + mz * np, 0, np * sizeof(float), c.st));
-                if (grad_x_dev) HIPCHK(h, hipMemsetAsync(grad_x_dev + mz * Bz * n_in, 0, Bz * n_in * sizeof(float), c.st));
+                if (grad_in) HIPCHK(h, hipMemsetAsync(grad_in + mz * Bz * n_in, 0, Bz * n_in * sizeof(float), c.st));
             }
         if (any_bad) HIPCHK(h, hipStreamSynchronize(c.st));
     }
@@ -2839,8 +2875,8 @@ static cnf_status ens_grad(cnf_handle h, bool vjp, int mode, int M, const float*
 extern "C" cnf_status cnf_loss_grad_many(cnf_handle h, int mode, int M, const float* params_dev, const float* xs, const float* eps,
                                          int B, const cnf_solve_opts* opts, const float* t1_host, float* loss_out, float* grad_dev,
                                          int* status_out, cnf_solve_stats* stats_out, void* stream) {
-    return ens_grad(h, false, mode, M, params_dev, xs, eps, B, opts, t1_host, nullptr, loss_out, nullptr, nullptr, grad_dev, nullptr, status_out,
-                    stats_out, stream);
+    return ens_grad(h, WC_LOSS, mode, M, params_dev, xs, eps, B, opts, t1_host, nullptr, nullptr, loss_out, nullptr, nullptr, grad_dev, nullptr,
+                    status_out, stats_out, stream);
 }
 
 // Differentiable ensembles (include/cnfhip_ensemble_vjp.h): the vector-Jacobian product of the M members' inference for a
@@ -2849,12 +2885,23 @@ extern "C" cnf_status cnf_inference_vjp_many(cnf_handle h, int mode, int M, cons
                                              int B, const cnf_solve_opts* opts, const float* t1_host, const float* cot_dev,
                                              float* logpx_dev, float* regs_dev, float* grad_dev, float* grad_x_dev, int* status_out,
                                              cnf_solve_stats* stats_out, void* stream) {
-    return ens_grad(h, true, mode, M, params_dev, xs, eps, B, opts, t1_host, cot_dev, nullptr, logpx_dev, regs_dev, grad_dev, grad_x_dev,
-                    status_out, stats_out, stream);
+    return ens_grad(h, WC_INFERENCE, mode, M, params_dev, xs, eps, B, opts, t1_host, cot_dev, nullptr, nullptr, logpx_dev, regs_dev, grad_dev,
+                    grad_x_dev, status_out, stats_out, stream);
 }
 
-// the signed accepted step sizes of member `member` of the last ensemble gradient call -- cnf_loss_grad_many or
-// cnf_inference_vjp_many -- (read from the device when asked for)
+// Differentiable ensemble sampling (include/cnfhip_ensemble_generate_vjp.h): the M members' samples with their log-densities and
+// the vector-Jacobian product of (x, logq) for a per-sample cotangent, by the sampling CW form of the same launch -- what
+// cnf_generate_record + cnf_generate_pullback give for one model.
+extern "C" cnf_status cnf_generate_vjp_many(cnf_handle h, int mode, int M, const float* params_dev, const float* z0, const float* eps,
+                                            int B, const cnf_solve_opts* opts, const float* t0_host, const float* cot_z_dev,
+                                            const float* cot_logq_dev, float* x_out, float* logq_out, float* grad_dev,
+                                            float* grad_z0_dev, int* status_out, cnf_solve_stats* stats_out, void* stream) {
+    return ens_grad(h, WC_SAMPLING, mode, M, params_dev, z0, eps, B, opts, t0_host, cot_z_dev, cot_logq_dev, nullptr, x_out, logq_out,
+                    grad_dev, grad_z0_dev, status_out, stats_out, stream);
+}
+
+// the signed accepted step sizes of member `member` of the last ensemble gradient call -- cnf_loss_grad_many,
+// cnf_inference_vjp_many or cnf_generate_vjp_many -- (read from the device when asked for)
 extern "C" int cnf_ensemble_steps(cnf_handle h, int member, float* hs, int cap) {
     if (!h || member < 0 || member >= h->ens_M) return -1;
     const int n = h->ens_nacc[member];
@@ -2903,9 +2950,7 @@ static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float*
     float* cols = h->ens_cols;
     float* fsol = cols + Mz * Bz * D;                      // sampling: the final columns behind u0
     if (gen) {
-        // u0 = [z0; 0] of all M B columns (the members' columns are contiguous)
-        HIPCHK(h, hipMemsetAsync(cols, 0, Mz * Bz * D * sizeof(float), st));
-        HIPCHK(h, hipMemcpy2DAsync(cols, D * sizeof(float), src, n_in * sizeof(float), n_in * sizeof(float), Mz * Bz, hipMemcpyDeviceToDevice, st));
+        if ((s = ens_sampling_u0(h, cols, src, Mz * Bz, n_in, D, st)) != CNF_OK) return s;
         sv.u0 = cols; sv.u_out = fsol;
     } else {
         sv.xs = src; sv.logpx = out0; sv.regs = out1; sv.sums5 = h->ens_fin + Mz * ENS_ST_F;

@@ -43,6 +43,7 @@ void launch_generate_post_rows(int n_in, int n_out, int D, const float* fsol, co
                                hipStream_t s);
 // The terminal cotangent: lam = cot_z, cw = [3][B]: w_l = +cot_logq, w_E = w_n = 0 (null cotangents: zeros).  n_in >= 1.
 void launch_generate_cotangent(int n_in, const float* cot_z, const float* cot_logq, float* lam, float* cw, int B, hipStream_t s);
-// gz0 = lam0 + cot_logq d logpdf(base, z0) / d z0   (cot_logq null: a copy; gz0 must not alias lam0)
+// gz0 = lam0 + cot_logq d logpdf(base, z0) / d z0   (cot_logq null: a copy; gz0 must not alias lam0).  B: the columns -- of an
+// ensemble (cnf_generate_vjp_many) all M B of them as one batch
 void launch_generate_z0_grad(int n_in, const BaseDist& bd, const float* lam0, const float* cot_logq, const float* z0, float* gz0,
-                             int B, hipStream_t s);
+                             size_t B, hipStream_t s);

@@ -236,10 +236,11 @@ k_generate_cotangent(int n_in, const float* __restrict__ cot_z, const float* __r
 }
 
 // grad_z0[b] = lam0[b] + cot_logq[b] d logpdf(base, z0_b) / d z0 = lam0[b] - cot_logq[b] prec (z0_b - mean)   (kind 0: z0_b;
-// the expression of k_vjp_cotangent).  One lane per entry; must not alias lam0.
+// the expression of k_vjp_cotangent).  One lane per entry; must not alias lam0.  (B: a batch, or the M B columns of an ensemble --
+// cnf_generate_vjp_many, N(0, I) base -- as one batch.)
 __global__ void __launch_bounds__(256)
 k_generate_z0_grad(int n_in, BaseDist bd, const float* __restrict__ lam0, const float* __restrict__ cot_logq,
-                   const float* __restrict__ z0, float* __restrict__ gz0, int B) {
+                   const float* __restrict__ z0, float* __restrict__ gz0, size_t B) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (size_t)n_in * B) return;
     const size_t b = e / (size_t)n_in;
@@ -301,7 +302,7 @@ void launch_generate_cotangent(int n_in, const float* cot_z, const float* cot_lo
 }
 
 void launch_generate_z0_grad(int n_in, const BaseDist& bd, const float* lam0, const float* cot_logq, const float* z0, float* gz0,
-                             int B, hipStream_t s) {
+                             size_t B, hipStream_t s) {
     const size_t n = (size_t)n_in * B;
     hipLaunchKernelGGL(k_generate_z0_grad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_in, bd, lam0, cot_logq, z0, gz0, B);
 }

@@ -36,21 +36,29 @@ bool wave_solve_supported(const NetDesc& nd, bool train, int B);
 // first member's, with the members' copies behind it: [M][n_params] parameters (p_stride), [M][B][..] data, probes, logpx,
 // regs and final columns, [M] final states, 5 M sums, [M][traj_cap] step sizes, [M][tiles][n_params] partials, and
 // sv.base_dev / sv.abort_flag one word per member; no mirror, no trace, no clock, no rich store.
+// what the backward pass of an ensemble gradient pulls back: the built-in loss's cotangent, or a per-sample one (the CW forms of
+// the kernel) of inference's four outputs, or of sampling's (z, logq)
+enum WaveCot { WC_LOSS = 0, WC_INFERENCE = 1, WC_SAMPLING = 2 };
 struct WaveEnsLaunch {
     int M = 0;
     const float* t1 = nullptr;     // device, [M]: the members' own end times (null: sv.init.t1 for all)
-    const float* t0 = nullptr;     // device, [M]: the members' own start times (plain forms only; null: sv.init.t0 for all)
+    const float* t0 = nullptr;     // device, [M]: the members' own start times (plain forms and `sampling`; null: sv.init.t0 for all)
     size_t p_stride = 0;           // floats between two members' parameters
     size_t traj_stride = 0;        // ... trajectory stores (traj_cap x wave_grad_traj_floats)
     size_t part_stride = 0;        // ... meeting words, in floats (WV_ENS_PART_FLOATS)
     const float* cw = nullptr;     // device, [M][4][B]: per-sample cotangents of (logpx, E, n, A) -- with `grad`, the CW form
                                    // (cnf_inference_vjp_many) in place of the built-in loss's cotangent; null: the loss
+    // with `grad`, the sampling CW form (cnf_generate_vjp_many): a bare solve sv.u0 -> U0 from t0 (no t1, no cw) whose backward
+    // pass is seeded with cot_z [M][B][n_in] on the state rows and +cot_logq [M][B] on the dlogp row (either may be null, not both)
+    bool sampling = false;
+    const float* cot_z = nullptr;
+    const float* cot_logq = nullptr;
 };
 #define WV_ENS_PART_FLOATS 8192    // a member's meeting words: 2 x 1024 of the meetings + 2048 of the loss-sum partials, 8 bytes each
 // the largest M a launch takes at batch B: workgroups the device holds at once / tiles (0: no ensemble form of this network
 // or mode, or the one-launch solves are switched off)
-// (cw: of the CW form, which has its own register budget)
-int wave_ens_capacity(const NetDesc& nd, bool train, int B, bool cw = false);
+// (cw: of that CW form -- each has its own kernels, hence its own register budget)
+int wave_ens_capacity(const NetDesc& nd, bool train, int B, WaveCot cw = WC_LOSS);
 // Without `grad`, `ens` launches the PLAIN ensemble form (cnf_inference_many / cnf_generate_many): either an inference (sv.xs,
 // sv.logpx [M][B], sv.regs [M][3][B], sv.sums5 [5 M]) or a bare solve (sv.u0 -> sv.u_out, [M][B][D] each); sv.trace, when
 // set, is [M][sv.trace_cap][4].  Its capacity: workgroups of one wave the device holds at once / tiles, at most 512 tiles.

@@ -75,6 +75,8 @@ struct WaveEnsArgs {
     const float* t0;       // plain forms: null, or the members' own start times [M] (sampling runs over reverse(steer_tspan));
                            // (last: the fields the gradient forms read keep their places among the kernel arguments)
     const float* cw;       // CW forms: the members' per-sample cotangents [M][4][B], rows (logpx, E, n, A) (behind t0, for the same reason)
+    const float* gz;       // sampling CW forms: null, or the members' cotangents of the final state rows [M][B][n_in] ...
+    const float* gl;       // ... and null, or those of logq [M][B]
 };
 
 __device__ __forceinline__ f32x4 mm4(const float (&A)[4], const f32x4& b, f32x4 acc) {
@@ -166,13 +168,23 @@ __device__ __forceinline__ float wv_quad_sum(float v) {
 // per-lane values and the terminal cotangent is -g_logpx z + g_A unit(z_aug) (the N(0, I) case of k_vjp_cotangent; the rows a
 // handle does not integrate -- lam1, lam2, lam3 = 0, all three in TestMode -- carry nothing).  The forward half of the launch,
 // the helper wave, the contraction, the stores and the meetings are the GRAD, ENS form's.
+//
+// CW = WC_SAMPLING (cnf_generate_vjp_many): the same launch for the SAMPLING direction.  The forward half is a bare solve of the
+// member's columns u0 = [z0; 0] (read through sv.u0; sv.xs is null) from the member's own start time en.t0 to opts' end time,
+// as the plain ENS form samples; it has no loss sums and no inference_sol, and the final state goes to the member's columns in
+// a.U0.  The terminal cotangent is the one of k_generate_cotangent: a lane reads its column's cot_z[0 .. n_in) into lam on the
+// state rows, c_l = +cot_logq, c_E = c_n = 0 (the E and n rows are integrated but are not outputs of sampling); either array
+// may be null, columns past the batch carry zeros.  Everything behind that -- the stage sweeps, the helper wave, the
+// contraction, the stores, the meetings, lam_out = d / d u(t_start) -- is the CW form's.  logq and d / d z0 are column kernels
+// over the M B columns behind the launch (cnf_dist.hip).
 template <int NI, int NH, int MODE, bool TANH, bool GRAD = false, bool ID2 = false, int WGW = 1, bool RICH = false, bool ENS = false, bool PATH = false,
-          bool CW = false>
+          int CW = WC_LOSS>
 __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wave(WaveArgs a, Solve3Args sv, const WvTab tab, const WaveEnsArgs en, const WavePathArgs pa) {
     constexpr bool HELP = GRAD && WGW == 1;
     static_assert(!PATH || (!GRAD && !ENS && WGW == 1), "PATH is a form of the plain solve with one tile per workgroup");
     static_assert(!ENS || (WGW == 1 && !RICH), "ENS forms have one tile per workgroup and no rich store");
-    static_assert(!CW || (GRAD && ENS), "CW is a form of the ensemble gradient");
+    static_assert(CW == WC_LOSS || (GRAD && ENS), "CW is a form of the ensemble gradient");
+    constexpr bool CWI = CW == WC_INFERENCE, CWS = CW == WC_SAMPLING;   // per-sample cotangents of inference | of sampling
     static_assert(!RICH || (GRAD && MODE == WV_VJP), "RICH is a form of the TrainMode / VJP gradient");
     constexpr int RR = 3 * NH + 3 * NI;                     // f32x4 per lane and stage evaluation in the rich store
     f32x4* rich_ptr = nullptr;                             // where the next evaluation files them (null: nowhere)
@@ -188,12 +200,13 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
     const bool xwg = WGW > 1 && gridDim.x > 1;
     int wid_ = WGW > 1 ? (int)blockIdx.x * nwg + wloc : (int)blockIdx.x;
     const float* cwp = nullptr;                            // CW: this member's cotangents [4][B]
+    const float *gzp = nullptr, *glp = nullptr;            // sampling CW: this member's cot_z [B][n_in] and cot_logq [B] (null: zeros)
     if constexpr (ENS) {
         const int member = (int)blockIdx.x / en.tiles;
         wid_ = (int)blockIdx.x - member * en.tiles;
         const size_t mb = (size_t)member, Bz = (size_t)a.B, nz = (size_t)a.nd.n_in;
         a.P += mb * en.p_stride;
-        if (GRAD || sv.xs) {                               // (a bare solve of the plain forms has none of these: null stays null)
+        if ((GRAD && !CWS) || sv.xs) {                     // (a bare solve -- plain forms, sampling CW -- has none of these: null stays null)
             sv.xs += mb * Bz * (size_t)sv.nvars;
             sv.logpx += mb * Bz; sv.regs += mb * 3 * Bz; sv.sums5 += mb * 5;
         }
@@ -203,10 +216,17 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
         if constexpr (GRAD) {
             a.g.traj += mb * en.traj_stride; a.g.hs_out += mb * (size_t)a.g.traj_cap;
             a.g.gpart += mb * (size_t)en.tiles * (size_t)a.g.n_params; a.g.lam_out += mb * Bz * nz;
-            if constexpr (CW) cwp = en.cw + mb * 4 * Bz;
+            if constexpr (CWI) cwp = en.cw + mb * 4 * Bz;
+            if constexpr (CWS) {
+                if (en.gz) gzp = en.gz + mb * Bz * nz;
+                if (en.gl) glp = en.gl + mb * Bz;
+            }
         }
         sv.part += mb * en.part_stride; sv.base_dev += mb; sv.abort_flag += mb;
-        if constexpr (GRAD) {
+        if constexpr (CWS) {                               // a bare solve from the member's own start time (sampling), to opts' end
+            sv.u0 += mb * Bz * (nz + (MODE != WV_TEST ? 3 : 1));
+            if (en.t0) { sv.init.t = sv.init.t0 = en.t0[mb]; step_state_set_t1(&sv.init, sv.init.t1); }
+        } else if constexpr (GRAD) {
             if (en.t1) step_state_set_t1(&sv.init, en.t1[mb]);
         } else {
             const size_t Dz = nz + (MODE != WV_TEST ? 3 : 1);
@@ -891,7 +911,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
             const float invB = 1.0f / (float)a.B;
             // CW: this lane's column of the member's cotangents, rows (logpx, E, n, A); columns past the batch carry none
             float cwv[4] = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (CW) {
+            if constexpr (CWI) {
                 if (live) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) cwv[r] = cwp[(size_t)r * (size_t)a.B + (size_t)smp];
@@ -899,11 +919,22 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
             }
             // cotangents of the scalar rows: constants of the loss -- CW: of this lane's column (the dlogp row carries -g_logpx;
             // g_E and g_n are the cotangents themselves, not multiplied by lam1, lam2)
-            const float cl0 = CW ? -cwv[0] : invB, cE0 = CW ? cwv[1] : a.g.lam1 * invB, cn0 = CW ? cwv[2] : a.g.lam2 * invB;
+            // sampling CW: logq = logpdf(z0) + dlogp, so the dlogp row carries +g_logq; E and n are no outputs of sampling
+            const float cl0 = CWS ? ((glp && live) ? glp[smp] : 0.f) : CWI ? -cwv[0] : invB;
+            const float cE0 = CWS ? 0.f : CWI ? cwv[1] : a.g.lam1 * invB, cn0 = CWS ? 0.f : CWI ? cwv[2] : a.g.lam2 * invB;
             // d loss / d z(t1) = (z + lam3 unit(z_aug) on the augmented rows) / B      (k_final_cotangent)
             // CW: -g_logpx z + g_A unit(z_aug) on the augmented rows                   (k_vjp_cotangent, N(0, I))
+            // sampling CW: g_z, the cotangent of the final state's rows themselves       (k_generate_cotangent)
             f32x4 lam[NI];
-            {
+            if constexpr (CWS) {
+#pragma unroll
+                for (int m = 0; m < NI; ++m)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int r = 16 * m + 4 * q + j;
+                        lam[m][j] = (gzp && live && r < n_in) ? gzp[sb * n_in + r] : 0.f;
+                    }
+            } else {
                 float sa = 0.f;
                 const bool aug = TRAIN && nd.norm_z_aug && nd.naugs > 0;      // (TestMode: loss = -mean(logpx), src/base_icnf.jl:489-497)
 #pragma unroll
@@ -918,7 +949,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
                     for (int j = 0; j < 4; ++j) {
                         const int r = 16 * m + 4 * q + j;
                         float v = uz[m][j];
-                        if constexpr (CW) {
+                        if constexpr (CWI) {
                             v *= cl0;
                             if (aug && r >= nd.nvars && nrm > 0.f) v = fmaf(cwv[3], uz[m][j] / nrm, v);
                             lam[m][j] = live ? v : 0.f;
@@ -1389,7 +1420,7 @@ typedef void (*wave_fn)(WaveArgs, Solve3Args, const WvTab, const WaveEnsArgs, co
 constexpr int WV_M_VJP = 1, WV_M_TEST = 4, WV_M_ALL = 7;     // the modes a row of wave_instance is instantiated for: bit 1 << MODE
 
 // the mode, among those of MODES
-template <int MODES, int NI, int NH, bool TANH, bool GRAD, bool ID2, int WGW, bool RICH, bool ENS, bool PATH, bool CW>
+template <int MODES, int NI, int NH, bool TANH, bool GRAD, bool ID2, int WGW, bool RICH, bool ENS, bool PATH, int CW>
 wave_fn wave_instance_mode(int mode) {
     if constexpr ((MODES & (1 << WV_VJP)) != 0) if (mode == WV_VJP) return (wave_fn)k_solve_wave<NI, NH, WV_VJP, TANH, GRAD, ID2, WGW, RICH, ENS, PATH, CW>;
     if constexpr ((MODES & (1 << WV_JVP)) != 0) if (mode == WV_JVP) return (wave_fn)k_solve_wave<NI, NH, WV_JVP, TANH, GRAD, ID2, WGW, RICH, ENS, PATH, CW>;
@@ -1397,7 +1428,7 @@ wave_fn wave_instance_mode(int mode) {
     return nullptr;
 }
 // the tiles: (1, 1..4) -- (1, 1) alone with the identity compiled out -- and, on the plain form, (2, 6)
-template <int MODES, bool TANH, bool GRAD, bool ID2, int WGW, bool RICH, bool ENS, bool PATH, bool CW>
+template <int MODES, bool TANH, bool GRAD, bool ID2, int WGW, bool RICH, bool ENS, bool PATH, int CW>
 wave_fn wave_instance_tiles(int ni, int nh, int mode) {
 #define WV_TILES(NIV, NHV) if (ni == NIV && nh == NHV) return wave_instance_mode<MODES, NIV, NHV, TANH, GRAD, ID2, WGW, RICH, ENS, PATH, CW>(mode)
     WV_TILES(1, 1);
@@ -1411,32 +1442,34 @@ wave_fn wave_instance_tiles(int ni, int nh, int mode) {
     return nullptr;
 }
 // One row per set of flags that is instantiated, each for the tiles above and the modes it names: these rows ARE the library's
-// k_solve_wave kernels (127 of them).  nullptr: no such kernel -- wave_variant does not return such a tuple.
-// cw: the CW form (per-sample cotangents, cnf_inference_vjp_many).  It is no WaveForm of its own: a caller selects it as "the
-// WF_ENS_GRAD answer of wave_variant, with CW" -- the same fifteen tuples, instantiated once more; with any other answer
-// there is no such kernel.
-wave_fn wave_instance(const WaveVariant& v, bool cw = false) {
+// k_solve_wave kernels (142 of them).  nullptr: no such kernel -- wave_variant does not return such a tuple.
+// cw: the CW forms (per-sample cotangents: WC_INFERENCE of cnf_inference_vjp_many, WC_SAMPLING of cnf_generate_vjp_many).  They
+// are no WaveForm of their own: a caller selects one as "the WF_ENS_GRAD answer of wave_variant, with CW" -- the same fifteen
+// tuples, instantiated once more for each; with any other answer there is no such kernel.
+wave_fn wave_instance(const WaveVariant& v, WaveCot cw = WC_LOSS) {
 #define WV_ROW(MODES, TANH, GRAD, ID2, WGW, RICH, ENS, PATH, CW)                                                                         \
     if (v.tanh == TANH && v.grad == GRAD && v.id2 == ID2 && v.wgw == WGW && v.rich == RICH && v.ens == ENS && v.path == PATH && cw == CW) \
         return wave_instance_tiles<MODES, TANH, GRAD, ID2, WGW, RICH, ENS, PATH, CW>(v.ni, v.nh, v.mode)
     //     modes      TANH   GRAD   ID2    WGW RICH   ENS    PATH   CW
-    WV_ROW(WV_M_ALL,  true,  false, false, 1, false, false, false, false);     // WF_PLAIN
-    WV_ROW(WV_M_ALL,  false, false, false, 1, false, false, false, false);
-    WV_ROW(WV_M_ALL,  true,  false, true,  1, false, false, false, false);
-    WV_ROW(WV_M_ALL,  true,  false, false, 4, false, false, false, false);     // WF_WG4
-    WV_ROW(WV_M_VJP | WV_M_TEST, true, false, true, 4, false, false, false, false);
-    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, false, false, false);     // WF_GRAD
-    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, false, false, false);
-    WV_ROW(WV_M_VJP,  true,  true,  false, 1, true,  false, false, false);     // WF_GRAD_RICH
-    WV_ROW(WV_M_VJP,  true,  true,  true,  1, true,  false, false, false);
-    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, true,  false, false);     // WF_ENS_GRAD
-    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, true,  false, false);
-    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, true,  false, true);      // WF_ENS_GRAD with CW
-    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, true,  false, true);
-    WV_ROW(WV_M_ALL,  true,  false, false, 1, false, true,  false, false);     // WF_ENS_PLAIN
-    WV_ROW(WV_M_ALL,  true,  false, true,  1, false, true,  false, false);
-    WV_ROW(WV_M_ALL,  true,  false, false, 1, false, false, true, false);      // WF_PATH
-    WV_ROW(WV_M_ALL,  true,  false, true,  1, false, false, true, false);
+    WV_ROW(WV_M_ALL,  true,  false, false, 1, false, false, false, WC_LOSS);     // WF_PLAIN
+    WV_ROW(WV_M_ALL,  false, false, false, 1, false, false, false, WC_LOSS);
+    WV_ROW(WV_M_ALL,  true,  false, true,  1, false, false, false, WC_LOSS);
+    WV_ROW(WV_M_ALL,  true,  false, false, 4, false, false, false, WC_LOSS);     // WF_WG4
+    WV_ROW(WV_M_VJP | WV_M_TEST, true, false, true, 4, false, false, false, WC_LOSS);
+    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, false, false, WC_LOSS);     // WF_GRAD
+    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, false, false, WC_LOSS);
+    WV_ROW(WV_M_VJP,  true,  true,  false, 1, true,  false, false, WC_LOSS);     // WF_GRAD_RICH
+    WV_ROW(WV_M_VJP,  true,  true,  true,  1, true,  false, false, WC_LOSS);
+    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, true,  false, WC_LOSS);     // WF_ENS_GRAD
+    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, true,  false, WC_LOSS);
+    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, true,  false, WC_INFERENCE);     // WF_ENS_GRAD, CW: inference's cotangents
+    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, true,  false, WC_INFERENCE);
+    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, true,  false, WC_SAMPLING);      // WF_ENS_GRAD, CW: sampling's cotangents
+    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, true,  false, WC_SAMPLING);
+    WV_ROW(WV_M_ALL,  true,  false, false, 1, false, true,  false, WC_LOSS);     // WF_ENS_PLAIN
+    WV_ROW(WV_M_ALL,  true,  false, true,  1, false, true,  false, WC_LOSS);
+    WV_ROW(WV_M_ALL,  true,  false, false, 1, false, false, true, WC_LOSS);      // WF_PATH
+    WV_ROW(WV_M_ALL,  true,  false, true,  1, false, false, true, WC_LOSS);
 #undef WV_ROW
     return nullptr;
 }
@@ -1446,7 +1479,7 @@ wave_fn wave_instance(const WaveVariant& v, bool cw = false) {
 bool is_id2(const NetDesc& nd) { return nd.n_layers == 2 && nd.acts[0] == 1 && nd.acts[1] == 0; }
 int wave_mode(const NetDesc& nd, bool train) { return !train ? WV_TEST : (nd.jvp ? WV_JVP : WV_VJP); }
 // the kernel of `form` for this two-layer network and mode (nullptr: there is none)
-wave_fn wave_kernel(WaveForm form, const NetDesc& nd, bool train, bool cw = false) {
+wave_fn wave_kernel(WaveForm form, const NetDesc& nd, bool train, WaveCot cw = WC_LOSS) {
     const auto v = wave_variant(form, (nd.n_in + 15) / 16, (nd.dims[1] + 15) / 16, wave_mode(nd, train), nd.acts[0] == 1 && nd.acts[1] == 1, is_id2(nd));
     return v ? wave_instance(*v, cw) : nullptr;
 }
@@ -1510,12 +1543,12 @@ bool wave_grad_supported(const NetDesc& nd, int B, bool train) {
 // ---- the ensemble form (cnf_loss_grad_many): M x tiles workgroups, each member's tiles meeting among themselves ----
 // (the envelope below -- two layers, tanh then tanh or identity, one input tile, up to four hidden tiles, one with the identity --
 // is restated in continuousnf.jl_amd/ensemble.py `_refusal`, which has to refuse before a handle exists: change both together)
-static wave_fn ens_fn(WaveForm form, const NetDesc& nd, bool train, bool cw = false) {
+static wave_fn ens_fn(WaveForm form, const NetDesc& nd, bool train, WaveCot cw = WC_LOSS) {
     if (nd.n_layers != 2 || nd.n_cond > 0 || nd.id2) return nullptr;      // (an APPENDED identity layer lives behind the handle's own parameters)
     if (nd.acts[0] != 1 || !(nd.acts[1] == 1 || is_id2(nd))) return nullptr;
     return wave_kernel(form, nd, train, cw);
 }
-int wave_ens_capacity(const NetDesc& nd, bool train, int B, bool cw) {
+int wave_ens_capacity(const NetDesc& nd, bool train, int B, WaveCot cw) {
     wave_fn fn = ens_fn(WF_ENS_GRAD, nd, train, cw);
     if (wave_off() || !fn || B < 1 || !wave_grad_supported(nd, B, train)) return 0;
     return wave_resident_workgroups(fn, 128) / wave_grad_waves(B);     // (main wave + helper)
@@ -1532,8 +1565,13 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
                              const WaveGradArgs* grad, const WaveEnsLaunch* ens, const WavePathArgs* path) {
     if (!wave_solve_supported(nd, train, B)) return CNF_ERR_UNSUPPORTED;
     if (path && (grad || ens || !path->times || !path->out || path->K < 1 || (path->steps_cap > 0 && !path->steps))) return CNF_ERR_BAD_ARG;
-    const bool cw = ens && ens->cw;                        // the CW form of the ensemble gradient
-    if (cw && !grad) return CNF_ERR_BAD_ARG;
+    // the CW form of the ensemble gradient: per-sample cotangents of inference, or of sampling
+    const WaveCot cw = !ens ? WC_LOSS : ens->sampling ? WC_SAMPLING : ens->cw ? WC_INFERENCE : WC_LOSS;
+    if (cw != WC_LOSS && !grad) return CNF_ERR_BAD_ARG;
+    if (ens) {
+        const bool gcot = ens->cot_z || ens->cot_logq;     // (sampling: its own cotangents, at least one, and start times only)
+        if (ens->sampling ? (ens->cw || ens->t1 || !gcot) : gcot) return CNF_ERR_BAD_ARG;
+    }
     if (ens && (cond || mirror || ens->M < 1 || ens->M > (grad ? wave_ens_capacity(nd, train, B, cw) : wave_ens_eval_capacity(nd, train, B))))
         return CNF_ERR_UNSUPPORTED;
     if (grad && nd.n_cond > 0 && !grad->ys) return CNF_ERR_BAD_ARG;
@@ -1585,8 +1623,11 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
         if (!(inf || bare) || sv.t_out || (sv.trace && sv.trace_cap < 1)) return CNF_ERR_BAD_ARG;
         en.t0 = ens->t0;
     } else if (ens) {
-        if (grad->rich || sv.trace || sv.t_out || !sv.xs || !sv.logpx || !sv.regs || !sv.sums5 || sv.u_out) return CNF_ERR_BAD_ARG;
+        // an inference with all of its outputs, or (sampling) a bare solve from the caller's columns, whose final state goes to U0
+        const bool inf = sv.xs && sv.logpx && sv.regs && sv.sums5 && !sv.u0, bare = !sv.xs && !sv.logpx && !sv.regs && !sv.sums5 && sv.u0;
+        if (grad->rich || sv.trace || sv.t_out || sv.u_out || !(cw == WC_SAMPLING ? bare : inf)) return CNF_ERR_BAD_ARG;
         en.traj_stride = ens->traj_stride; en.cw = ens->cw;
+        if (cw == WC_SAMPLING) { en.t0 = ens->t0; en.gz = ens->cot_z; en.gl = ens->cot_logq; }
     }
     if (ens) {                                             // M x tiles workgroups
         en.tiles = tiles; en.t1 = ens->t1; en.p_stride = ens->p_stride; en.part_stride = ens->part_stride;

@@ -394,25 +394,15 @@ def _host_gen(icnf: ICNF):
     return icnf.rng._host if isinstance(icnf.rng, HIPRNG) else icnf.rng
 
 
-def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, t0=None, with_logp=False, with_steps=False):
-    """``generate`` of M members in one launch (cnf_generate_many): ``ps`` (M, n_params) on the device, ``z0`` and ``eps``
-    (M, n_in, n) device tensors or drawn as ``generate_prob`` draws them -- on a host generator member by member: the member's
-    base sample, its probes (drawn in TestMode too, and not used there), then its steered time; with a ``HIPRNG`` ONE draw of
-    M n columns for the base samples, one for the probes, then the M steered times from the generator's host side.  ``t0``:
-    the members' start times of the reversed span (what ``steer_tspan`` would return as the end time); every member ends at
-    ``tspan[0]``.  Returns ``xs (M, nvars, n)``, with ``with_logp`` ``(xs, logq (M, n))``: the log-density of each sample under
-    its member (``generate(..., with_logp=True)``).  ``icnf.last_ensemble_info`` holds ``stats``, ``status``, ``launches`` (2:
-    the solve and the column kernel), ``calls``, ``rerun``, ``t0`` and the inputs used (``z0``, ``eps``); after ``with_steps``
-    the members' step attempts are read with ``ensemble_eval_steps`` (``info["steps"]``).  Failures and refusals as
-    ``inference_many``."""
-    import torch
-    who = "generate_many"
+def _check_sampling_inputs(icnf: ICNF, mode, ps, n, z0, eps, t0, who, single):
+    """The argument checks of the sampling calls (``generate_many``, ``generate_vjp_many``).  Host logic only: nothing is drawn,
+    no handle is made.  Returns ``(mode id, M, n, n_in, t0 as a float32 vector or None)``."""
     m = _mode_id(mode)
     why = _refusal(icnf)
     if why is not None:
         raise NotImplementedError(f"{who}: " + why)
     if not _is_torch(ps):
-        raise NotImplementedError(f"{who} takes device tensors (host arrays: generate, one member at a time)")
+        raise NotImplementedError(f"{who} takes device tensors (host arrays: {single}, one member at a time)")
     n_params = icnf.nn.n_params_internal
     if ps.dim() != 2 or ps.shape[0] < 1 or ps.shape[1] != n_params:
         raise ValueError(f"ps must be (M, n_params = {n_params}), got {tuple(ps.shape)}")
@@ -420,7 +410,6 @@ def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, 
     if n < 1:
         raise ValueError("n must be >= 1")
     n_in = icnf.nvars + n_augment_input(icnf)
-    train = m == _lib.MODE_TRAIN
     for name, a in (("z0", z0), ("eps", eps)):
         if a is not None and (not _is_torch(a) or tuple(a.shape) != (M, n_in, n)):
             raise ValueError(f"{name} must be a device tensor (M = {M}, n_in = {n_in}, n = {n})")
@@ -430,13 +419,13 @@ def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, 
             raise ValueError(f"t0 must have one start time per member (M = {M}), got {t0.shape[0]}")
         if not np.isfinite(t0).all() or (t0 == np.float32(icnf.tspan[0])).any():
             raise ValueError("t0: every member needs a finite start time different from tspan[0]")
-    l, h = _lib.lib(), icnf.handle()
-    if not (ps.is_cuda and (z0 is None or z0.is_cuda) and (eps is None or eps.is_cuda)):
-        raise ValueError(f"{who}: torch tensors must live on the GPU")
-    cap = _device_capacity(who, "cnf_ensemble_eval_capacity", h, m, n)
-    dev = ps.device
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    pr = ps.detach().to(torch.float32).contiguous()
+    return m, M, n, n_in, t0
+
+
+def _sampling_draws(icnf: ICNF, mode, train, M, n, n_in, dev, z0, eps, t0):
+    """The members' base samples and probes ([M][n][n_in] on ``dev``) and start times (None: ``tspan[1]`` for all), given or
+    drawn in the order ``generate_many`` documents."""
+    import torch
     zr = _rows(z0) if z0 is not None else None
     er = _rows(eps) if eps is not None else None
     steer = t0 is None and icnf.STEER and train
@@ -462,6 +451,32 @@ def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, 
             er = torch.from_numpy(np.stack(es)).to(dev)
         if steer:
             t0 = np.asarray(starts, dtype=np.float32)
+    return zr, er, t0
+
+
+def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, t0=None, with_logp=False, with_steps=False):
+    """``generate`` of M members in one launch (cnf_generate_many): ``ps`` (M, n_params) on the device, ``z0`` and ``eps``
+    (M, n_in, n) device tensors or drawn as ``generate_prob`` draws them -- on a host generator member by member: the member's
+    base sample, its probes (drawn in TestMode too, and not used there), then its steered time; with a ``HIPRNG`` ONE draw of
+    M n columns for the base samples, one for the probes, then the M steered times from the generator's host side.  ``t0``:
+    the members' start times of the reversed span (what ``steer_tspan`` would return as the end time); every member ends at
+    ``tspan[0]``.  Returns ``xs (M, nvars, n)``, with ``with_logp`` ``(xs, logq (M, n))``: the log-density of each sample under
+    its member (``generate(..., with_logp=True)``).  ``icnf.last_ensemble_info`` holds ``stats``, ``status``, ``launches`` (2:
+    the solve and the column kernel), ``calls``, ``rerun``, ``t0`` and the inputs used (``z0``, ``eps``); after ``with_steps``
+    the members' step attempts are read with ``ensemble_eval_steps`` (``info["steps"]``).  Failures and refusals as
+    ``inference_many``."""
+    import torch
+    who = "generate_many"
+    m, M, n, n_in, t0 = _check_sampling_inputs(icnf, mode, ps, n, z0, eps, t0, who, "generate")
+    l, h = _lib.lib(), icnf.handle()
+    if not (ps.is_cuda and (z0 is None or z0.is_cuda) and (eps is None or eps.is_cuda)):
+        raise ValueError(f"{who}: torch tensors must live on the GPU")
+    cap = _device_capacity(who, "cnf_ensemble_eval_capacity", h, m, n)
+    train = m == _lib.MODE_TRAIN
+    dev = ps.device
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    pr = ps.detach().to(torch.float32).contiguous()
+    zr, er, t0 = _sampling_draws(icnf, mode, train, M, n, n_in, dev, z0, eps, t0)
     opts = _solve_opts(icnf, (icnf.tspan[1], icnf.tspan[0]))              # reverse(tspan)
     xo = torch.empty((M, n, icnf.nvars), dtype=torch.float32, device=dev)
     lq = torch.empty((M, n), dtype=torch.float32, device=dev) if with_logp else None
@@ -651,6 +666,182 @@ def differentiable_inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t
         _FUNCTION_MANY = _autograd_function_many()
     logpx, E, n, A = _FUNCTION_MANY.apply(icnf, mode, xs, ps, eps, t1)
     return logpx, (E, n, A)
+
+
+# ---------------------------------------------------------------------------------------
+# differentiable ensemble sampling (include/cnfhip_ensemble_generate_vjp.h)
+# ---------------------------------------------------------------------------------------
+def ensemble_generate_vjp_capacity(icnf: ICNF, mode, n: int) -> int:
+    """The largest M one ``generate_vjp_many`` launch takes for this model, mode and number of samples per member
+    (cnf_ensemble_generate_vjp_capacity); 0: no ensemble form."""
+    m = _mode_id(mode)
+    if _refusal(icnf) is not None:
+        return 0
+    return int(_lib.lib().cnf_ensemble_generate_vjp_capacity(icnf.handle(), m, int(n)))
+
+
+def _cot_pair_many(icnf: ICNF, cot, M, n):
+    """``(g_x, g_logq)`` -> ``(g_x, g_logq)`` checked: ``g_x`` an (M, nvars, n) or (M, n_in, n) tensor or None, ``g_logq`` an
+    (M, n) tensor or None, not both None; ``ValueError`` for anything else.  Host logic only."""
+    if not isinstance(cot, (tuple, list)) or len(cot) != 2:
+        raise ValueError("cot must be (g_x, g_logq)")
+    gx, gl = cot
+    n_in = icnf.nvars + n_augment_input(icnf)
+    if gx is None and gl is None:
+        raise ValueError("cot: g_x and g_logq are both None")
+    if gx is not None:
+        if not _is_torch(gx):
+            raise ValueError("cot: g_x must be a device tensor or None")
+        if tuple(gx.shape) not in ((M, icnf.nvars, n), (M, n_in, n)):
+            raise ValueError(f"cot: g_x must be (M = {M}, nvars = {icnf.nvars} or n_in = {n_in}, n = {n}), got {tuple(gx.shape)}")
+    if gl is not None:
+        if not _is_torch(gl):
+            raise ValueError("cot: g_logq must be a device tensor or None")
+        if tuple(gl.shape) != (M, n):
+            raise ValueError(f"cot: g_logq must be (M = {M}, n = {n}), got {tuple(gl.shape)}")
+    return gx, gl
+
+
+def generate_vjp_many(icnf: ICNF, mode, ps, st, n, cot, z0=None, eps=None, t0=None, with_z0=False, with_steps=False):
+    """``generate`` of M members with the log-density of every sample, and the vector-Jacobian product of both for a per-sample
+    cotangent, in ONE launch and one of the partial sums plus the column kernels (cnf_generate_vjp_many): what
+    ``generate_record`` + ``generate_pullback`` give for one model.  ``ps`` (M, n_params) on the device; ``cot = (g_x, g_logq)``:
+    ``g_x`` is (M, nvars, n) or (M, n_in, n) -- rows beyond those given are zero --, ``g_logq`` is (M, n); either may be None
+    (zeros), not both.  ``z0``, ``eps`` (M, n_in, n) and ``t0`` (the members' start times of the reversed span) as
+    ``generate_many`` takes and draws them, in its order, on a host generator and on a ``HIPRNG``.  Returns
+    ``(xs (M, nvars, n), logq (M, n), grads (M, n_params), [grad_z0 (M, n_in, n) with with_z0,] info)``:
+    ``grads[m] = sum_b (<g_x[m, :, b], d xs[m, :, b] / d ps[m]> + g_logq[m, b] d logq[m, b] / d ps[m])`` through the steps member
+    m's own solve accepted; ``logq`` is the density of the whole n_in-row final state, as ``generate_record``'s.  ``info`` as
+    ``generate_many``'s (``t0``, ``z0``, ``eps``: the inputs used), ``launches`` counting the column kernels too; with
+    ``with_steps`` also ``steps``: every member's signed accepted step sizes (cnf_ensemble_steps).  A member whose part of the
+    launch gave up is run again with ``generate_record`` + ``generate_pullback`` (``info["rerun"]``).  Failures and refusals as
+    ``generate_many``: ``NotImplementedError`` before anything is drawn."""
+    import torch
+    who = "generate_vjp_many"
+    m, M, n, n_in, t0 = _check_sampling_inputs(icnf, mode, ps, n, z0, eps, t0, who, "generate_record and generate_pullback")
+    gx, gl = _cot_pair_many(icnf, cot, M, n)
+    l, h = _lib.lib(), icnf.handle()
+    if not (ps.is_cuda and all(a is None or a.is_cuda for a in (z0, eps, gx, gl))):
+        raise ValueError(f"{who}: torch tensors must live on the GPU")
+    cap = _device_capacity(who, "cnf_ensemble_generate_vjp_capacity", h, m, n)
+    train = m == _lib.MODE_TRAIN
+    dev = ps.device
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    pr = ps.detach().to(torch.float32).contiguous()
+    zr, er, t0 = _sampling_draws(icnf, mode, train, M, n, n_in, dev, z0, eps, t0)
+    cz = cl = None
+    if gx is not None:                                     # [M][n][n_in], zeros on the rows that were not given
+        cz = torch.zeros((M, n, n_in), dtype=torch.float32, device=dev)
+        cz[:, :, :gx.shape[1]] = gx.detach().permute(0, 2, 1)
+    if gl is not None:
+        cl = gl.detach().to(torch.float32).contiguous()
+    opts = _solve_opts(icnf, (icnf.tspan[1], icnf.tspan[0]))              # reverse(tspan)
+    n_params = pr.shape[1]
+    xo = torch.empty((M, n, icnf.nvars), dtype=torch.float32, device=dev)
+    lq = torch.empty((M, n), dtype=torch.float32, device=dev)
+    grads = torch.empty((M, n_params), dtype=torch.float32, device=dev)
+    gz = torch.empty((M, n, n_in), dtype=torch.float32, device=dev) if with_z0 else None
+    stats, status, calls, steps = _chunked_calls(icnf, M, cap, lambda lo, k, status, stats: l.cnf_generate_vjp_many(
+        h, m, k, pr[lo].data_ptr(), zr[lo].data_ptr(), er[lo].data_ptr() if train else None, n, C.byref(opts),
+        t0[lo:].ctypes.data if t0 is not None else None, cz[lo].data_ptr() if cz is not None else None,
+        cl[lo].data_ptr() if cl is not None else None, xo[lo].data_ptr(), lq[lo].data_ptr(), grads[lo].data_ptr(),
+        gz[lo].data_ptr() if with_z0 else None, status, stats, stream), ensemble_steps if with_steps else None)
+    icnf._record = None                                    # (the call ended whatever was recorded on the handle)
+    info = _info(icnf, stats, status, calls, "t0", t0, z0=zr.permute(0, 2, 1), eps=er.permute(0, 2, 1))
+    icnf.last_ensemble_info = info
+    _raise_failed(status)
+    gave_up = [i for i in range(M) if status[i] != _lib.OK]
+    if gave_up:
+        from .gen_vjp import generate_pullback, generate_record
+        with _one_member_at_a_time(icnf, t0) as member:
+            for i in gave_up:
+                member(i)
+                x_i, lq_i = generate_record(icnf, mode, pr[i], st, n, z0=zr[i].t(), eps=er[i].t(), tspan=icnf.tspan)
+                res = generate_pullback(icnf, (cz[i].t() if cz is not None else None, cl[i] if cl is not None else None),
+                                        with_z0=with_z0)
+                xo[i].copy_(x_i.t())
+                lq[i].copy_(lq_i)
+                grads[i].copy_(res[0] if with_z0 else res)
+                if with_z0:
+                    gz[i].copy_(res[1].t())
+                status[i] = _lib.OK
+                info["stats"][i] = dict(icnf.last_stats)
+                if with_steps:
+                    steps[i] = np.array(icnf.last_steps, dtype=np.float32)
+        icnf._record = None                                # (the members' records are not the caller's)
+        info["rerun"] = gave_up
+    if with_steps:
+        info["steps"] = steps
+    icnf.last_stats = info["stats"][0]
+    out = (xo.permute(0, 2, 1), lq, grads)
+    return out + ((gz.permute(0, 2, 1), info) if with_z0 else (info,))
+
+
+_FUNCTION_GENERATE_MANY = None
+
+
+def _autograd_function_generate_many():
+    import torch
+
+    class _GenerateMany(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, icnf, mode, ps, z0, eps, t0):
+            n = z0.shape[2]
+            xs, logq = generate_many(icnf, mode, ps.detach(), None, n, z0=z0.detach(), eps=eps, t0=t0, with_logp=True)
+            ctx.icnf, ctx.mode = icnf, mode
+            # what the backward launch solves again: the same parameters, base draws, probes and start times
+            ctx.ps, ctx.z0, ctx.eps, ctx.t0 = ps.detach().clone(), z0.detach(), eps, t0
+            ctx.set_materialize_grads(False)
+            return xs.clone(), logq
+
+        @staticmethod
+        def backward(ctx, g_x, g_logq):
+            icnf = ctx.icnf
+            need_ps, need_z0 = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+            if (g_x is None and g_logq is None) or not (need_ps or need_z0):
+                return None, None, None, None, None, None
+            res = generate_vjp_many(icnf, ctx.mode, ctx.ps, None, ctx.z0.shape[2], (g_x, g_logq), z0=ctx.z0, eps=ctx.eps, t0=ctx.t0,
+                                    with_z0=bool(need_z0))
+            # (the backward launch's own outputs: compared with the forward's in the tests)
+            icnf.last_backward_xs, icnf.last_backward_logq = res[0], res[1]
+            return None, None, res[2] if need_ps else None, res[3].contiguous() if need_z0 else None, None, None
+
+    return _GenerateMany
+
+
+def differentiable_generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, t0=None):
+    """``generate_many(with_logp=True)`` as a differentiable function of ``ps`` (M, n_params) and, when it requires grad, ``z0``
+    (M, n_in, n): the forward is ``generate_many`` with the base draws, probes and steered start times settled once (its order);
+    the backward is ONE ``generate_vjp_many`` with those same draws.  Returns ``(xs (M, nvars, n), logq (M, n))`` attached to the
+    autograd graph.  The backward launch solves again: its gradient is the exact discrete adjoint of the steps IT accepts (the
+    solve is deterministic, so they are the forward's for the same inputs; DESIGN 4.4 says how its ``xs`` / ``logq`` compare with
+    the forward's -- ``icnf.last_backward_logq`` and ``icnf.last_backward_xs`` keep them)."""
+    global _FUNCTION_GENERATE_MANY
+    who = "differentiable_generate_many"
+    m, M, n, n_in, t0 = _check_sampling_inputs(icnf, mode, ps, n, z0, eps, t0, who, "differentiable_generate")
+    if not (ps.is_cuda and (z0 is None or z0.is_cuda) and (eps is None or eps.is_cuda)):
+        raise ValueError(f"{who}: torch tensors must live on the GPU")
+    zr, er, t0 = _sampling_draws(icnf, mode, m == _lib.MODE_TRAIN, M, n, n_in, ps.device,
+                                 z0.detach() if z0 is not None else None, eps, t0)
+    if not (z0 is not None and z0.requires_grad):          # (a z0 that asks for a gradient stays the caller's tensor)
+        z0 = zr.permute(0, 2, 1)
+    if _FUNCTION_GENERATE_MANY is None:
+        _FUNCTION_GENERATE_MANY = _autograd_function_generate_many()
+    return _FUNCTION_GENERATE_MANY.apply(icnf, mode, ps, z0, er.permute(0, 2, 1), t0)
+
+
+def reverse_kl_many(icnf: ICNF, mode, ps, st, n, target_logpdf, **kw):
+    """The M members' reverse Kullback-Leibler divergences to unnormalised targets, each estimated on ``n`` samples of its
+    member: ``(logq - target_logpdf(xs)).mean(dim=1)``, an (M,) tensor, with ``(xs, logq) = differentiable_generate_many(icnf,
+    mode, ps, st, n, **kw)`` -- M variational fits (restarts, targets of one family, a temperature ladder) differentiated by one
+    launch; sum or weight the losses as the problem asks.  ``target_logpdf`` is ONE torch callable for all members: it takes
+    the samples (M, nvars, n) and returns (M, n) log-densities, so that members with different targets index their own
+    parameters by the leading axis (a per-member list would be M calls on slices of one tensor)."""
+    xs, logq = differentiable_generate_many(icnf, mode, ps, st, n, **kw)
+    t = target_logpdf(xs)
+    if tuple(t.shape) != tuple(logq.shape):
+        raise ValueError(f"target_logpdf must return (M = {logq.shape[0]}, n = {logq.shape[1]}), got {tuple(t.shape)}")
+    return (logq - t).mean(dim=1)
 
 
 # ---- the bagged density: a mixture of the members ----

@@ -374,6 +374,10 @@ cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int B, float* 
  * this header) ---- */
 #include "cnfhip_ensemble_vjp.h"
 
+/* ---- differentiable ensemble sampling: cnf_ensemble_generate_vjp_capacity / cnf_generate_vjp_many (declared in
+ * cnfhip_ensemble_generate_vjp.h, part of this header) ---- */
+#include "cnfhip_ensemble_generate_vjp.h"
+
 /* ---- flow paths: the solve's columns at caller-given times, from Tsit5's interpolant (declared in cnfhip_path.h, part of this
  * header) ---- */
 #include "cnfhip_path.h"
