@@ -66,6 +66,9 @@ from .ensemble import differentiable_inference_many, ensemble_vjp_capacity, infe
 from .ensemble import differentiable_generate_many, ensemble_generate_vjp_capacity, generate_vjp_many, reverse_kl_many
 from . import path
 from .path import generate_path, inference_path, solve_path
+from . import path_vjp
+from .path_vjp import differentiable_generate_path, differentiable_inference_path, generate_path_vjp, inference_path_vjp, \
+    path_vjp_max_batch, path_vjp_steps
 from .mlj import (Adam, CondICNFModel, ICNFModel, Lion, Machine, fit, fit_, fitted_params, load_params, machine, save_params,
                   transform)
 

@@ -174,6 +174,16 @@ _PATH_SIGNATURES = {
     "cnf_path_steps": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int]),
 }
 PATH_EXPORTS = tuple(_PATH_SIGNATURES)
+# differentiable flow paths (include/cnfhip_path_vjp.h): likewise
+_PATH_VJP_SIGNATURES = {
+    "cnf_path_vjp_max_batch": (C.c_int, [C.c_void_p, C.c_int]),
+    "cnf_inference_path_vjp": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), _fp, C.c_int, _fp, _fp,
+                                         _fp, _fp, _fp, _fp, _fp, C.POINTER(cnf_solve_stats), C.c_void_p]),
+    "cnf_generate_path_vjp": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), _fp, C.c_int, _fp, _fp,
+                                        _fp, _fp, _fp, _fp, _fp, _fp, C.POINTER(cnf_solve_stats), C.c_void_p]),
+    "cnf_path_vjp_steps": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int]),
+}
+PATH_VJP_EXPORTS = tuple(_PATH_VJP_SIGNATURES)
 
 _lib = None
 
@@ -213,7 +223,7 @@ def lib():
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in list(_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) + list(_BASEGRAD_SIGNATURES.items()) + \
                 list(_ENSEMBLE_SIGNATURES.items()) + list(_ENSEMBLE_EVAL_SIGNATURES.items()) + list(_ENSEMBLE_VJP_SIGNATURES.items()) + \
-                list(_ENSEMBLE_GENERATE_VJP_SIGNATURES.items()) + list(_PATH_SIGNATURES.items()):
+                list(_ENSEMBLE_GENERATE_VJP_SIGNATURES.items()) + list(_PATH_SIGNATURES.items()) + list(_PATH_VJP_SIGNATURES.items()):
             f = getattr(l, name)
             f.restype, f.argtypes = res, args
         _lib = l

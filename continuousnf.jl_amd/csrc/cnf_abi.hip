@@ -185,6 +185,10 @@ struct cnf_ctx {
     DevBuf<float> d_path_steps;   // [PATH_STEPS_CAP][2]
     std::vector<float> path_t, path_h;
     bool path_valid = false;
+    // cnf_inference_path_vjp / cnf_generate_path_vjp (include/cnfhip_path_vjp.h) share the two device buffers above; the accepted
+    // steps of the last such call (cnf_path_vjp_steps)
+    std::vector<float> pvjp_t, pvjp_h;
+    bool pvjp_valid = false;
     std::string err;
 };
 static const int PATH_STEPS_CAP = 16384;
@@ -1540,23 +1544,26 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
 }
 
 // ---- flow paths (include/cnfhip_path.h) ----
+// What is wrong with the save times of a path call (cnf_solve_path and the two calls of include/cnfhip_path_vjp.h), or null: K >= 1
+// finite times, monotone along opts->t0 -> opts->t1 and inside that closed span.  Looks at no handle.
+static const char* saveat_error(const cnf_solve_opts* opts, const float* saveat_host, int K) {
+    if (!opts || !saveat_host) return "null pointer";
+    if (K < 1) return "saveat is empty";
+    if (!std::isfinite(opts->t0) || !std::isfinite(opts->t1) || opts->t0 == opts->t1) return "empty or non-finite time span";
+    const float dir = opts->t1 >= opts->t0 ? 1.f : -1.f;
+    for (int i = 0; i < K; ++i) {
+        const float tau = saveat_host[i];
+        if (!std::isfinite(tau)) return "saveat must be finite";
+        if (dir * (tau - opts->t0) < 0.f || dir * (opts->t1 - tau) < 0.f) return "saveat must lie inside the time span";
+        if (i > 0 && dir * (tau - saveat_host[i - 1]) < 0.f) return "saveat must be monotone along the direction of integration";
+    }
+    return nullptr;
+}
 extern "C" cnf_status cnf_solve_path(cnf_handle h, int mode, const float* u0, const float* eps, float* u_out, int B,
                                      const cnf_solve_opts* opts, const float* saveat_host, int K, float* path_out_dev,
                                      cnf_solve_stats* stats, void* stream) {
     // the save times against the span, before the handle is looked at
-    const char* bad = nullptr;
-    if (!opts || !saveat_host || !path_out_dev) bad = "null pointer";
-    else if (K < 1) bad = "saveat is empty";
-    else if (!std::isfinite(opts->t0) || !std::isfinite(opts->t1) || opts->t0 == opts->t1) bad = "empty or non-finite time span";
-    else {
-        const float dir = opts->t1 >= opts->t0 ? 1.f : -1.f;
-        for (int i = 0; i < K && !bad; ++i) {
-            const float tau = saveat_host[i];
-            if (!std::isfinite(tau)) bad = "saveat must be finite";
-            else if (dir * (tau - opts->t0) < 0.f || dir * (opts->t1 - tau) < 0.f) bad = "saveat must lie inside the time span";
-            else if (i > 0 && dir * (tau - saveat_host[i - 1]) < 0.f) bad = "saveat must be monotone along the direction of integration";
-        }
-    }
+    const char* bad = !path_out_dev ? "null pointer" : saveat_error(opts, saveat_host, K);
     if (bad) return h ? fail(h, CNF_ERR_BAD_ARG, bad) : CNF_ERR_BAD_ARG;
     if (!h) return CNF_ERR_BAD_ARG;
     if (!u_out) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
@@ -2792,18 +2799,31 @@ static cnf_status ens_sampling_u0(cnf_handle h, float* u0, const float* z0, size
 //   cnf_generate_vjp_many (WC_SAMPLING): src = z0, times = the START times, cot0 = cot_z, cot1 = cot_logq (either may be null); the
 //     sampling CW form integrates u0 = [z0; 0] (built in the column store, the final columns behind it); out0 = x, out1 = logq
 //     and grad_in = d / d z0 (may be null) come from the column kernels of cnf_dist.hip over the M B columns as one batch.
+//   cnf_inference_path_vjp / cnf_generate_path_vjp (WC_INFERENCE_PATH, WC_SAMPLING_PATH; M = 1): the two above plus `ep` -- the
+//     save times, the cotangent of the slices and where the slices go (either may be null, and so may cot0 / cot1 then).
+struct EnsPath {
+    const float* saveat;           // host, [K]: checked by the caller (saveat_error)
+    int K;
+    const float* cot;              // device, [K][B][D] or null
+    float* out;                    // device, [K][B][D] or null
+};
 static cnf_status ens_grad(cnf_handle h, WaveCot cot, int mode, int M, const float* params_dev, const float* src, const float* eps, int B,
                            const cnf_solve_opts* opts, const float* times_host, const float* cot0, const float* cot1, float* loss_out,
                            float* out0, float* out1, float* grad_dev, float* grad_in, int* status_out, cnf_solve_stats* stats_out,
-                           void* stream) {
-    const bool train = mode == CNF_MODE_TRAIN, vjp = cot != WC_LOSS, gen = cot == WC_SAMPLING;
+                           void* stream, const EnsPath* ep = nullptr) {
+    const bool train = mode == CNF_MODE_TRAIN, vjp = cot != WC_LOSS, gen = wave_cot_sampling(cot);
+    if (h && ep) h->pvjp_valid = false;
     EnsCall c{true, gen, mode, M, B, 0, opts, times_host, (hipStream_t)stream};
     c.cot = cot;
     cnf_status s = ens_check(h, c, !params_dev || !src || !opts || !grad_dev || !status_out || (train && !eps) ||
-                                       (gen ? (!cot0 && !cot1) || !out0 || !out1 : vjp ? !cot0 || !out0 || !out1 : !loss_out),
+                                       (gen ? (!ep && !cot0 && !cot1) || !out0 || !out1 : vjp ? (!ep && !cot0) || !out0 || !out1 : !loss_out),
                              vjp ? "B must be >= 1" : "the loss is a mean over the batch: B must be >= 1",
-                             gen ? "cnf_ensemble_generate_vjp_capacity" : vjp ? "cnf_ensemble_vjp_capacity" : "cnf_ensemble_capacity");
+                             ep ? "cnf_path_vjp_max_batch" : gen ? "cnf_ensemble_generate_vjp_capacity" : vjp ? "cnf_ensemble_vjp_capacity" : "cnf_ensemble_capacity");
     if (s != CNF_OK) return s;
+    if (ep) {                                              // the save times' and the accepted steps' device buffers (cnf_solve_path's)
+        RESERVE(h, h->d_saveat, (size_t)ep->K);
+        RESERVE(h, h->d_path_steps, (size_t)2 * PATH_STEPS_CAP);
+    }
     const NetDesc& nd = h->nd_wave;
     const size_t Mz = (size_t)M, Bz = (size_t)B, n_in = (size_t)nd.n_in, nv = (size_t)nd.nvars, D = n_in + (train ? 3 : 1), np = h->n_params;
     const size_t per_step = wave_grad_traj_floats(nd, B);
@@ -2836,8 +2856,13 @@ static cnf_status ens_grad(cnf_handle h, WaveCot cot, int mode, int M, const flo
     if (gen) { ens.sampling = true; ens.cot_z = cot0; ens.cot_logq = cot1; }
     else ens.cw = vjp ? cot0 : nullptr;
     ens.p_stride = np; ens.traj_stride = per_step * cap; ens.part_stride = WV_ENS_PART_FLOATS;
+    WavePathArgs wp{};
+    if (ep) {
+        HIPCHK(h, hipMemcpyAsync(h->d_saveat, ep->saveat, (size_t)ep->K * sizeof(float), hipMemcpyHostToDevice, c.st));
+        wp.times = h->d_saveat; wp.K = ep->K; wp.out = ep->out; wp.cot = ep->cot; wp.steps = h->d_path_steps; wp.steps_cap = PATH_STEPS_CAP;
+    }
     int launches = 0;                                      // kernel launches of this call, counted where they are made
-    s = wave_solve_launch(nd, train, params_dev, nullptr, 0, fin_dev, fsol, eps, B, c.st, nullptr, 0, sv, &wg, &ens);
+    s = wave_solve_launch(nd, train, params_dev, nullptr, 0, fin_dev, fsol, eps, B, c.st, nullptr, 0, sv, &wg, &ens, ep ? &wp : nullptr);
     if (s != CNF_OK) return fail(h, s, "the ensemble launch failed to start");
     ++launches;
     HIPCHK(h, hipGetLastError());
@@ -2866,8 +2891,17 @@ static cnf_status ens_grad(cnf_handle h, WaveCot cot, int mode, int M, const flo
                 HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(out1 + mz * n1), 0x7fc00000, n1, c.st));
                 HIPCHK(h, hipMemsetAsync(grad_dev + mz * np, 0, np * sizeof(float), c.st));
                 if (grad_in) HIPCHK(h, hipMemsetAsync(grad_in + mz * Bz * n_in, 0, Bz * n_in * sizeof(float), c.st));
+                if (ep && ep->out) HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)ep->out, 0x7fc00000, (size_t)ep->K * Bz * D, c.st));
             }
         if (any_bad) HIPCHK(h, hipStreamSynchronize(c.st));
+    }
+    if (ep && status_out[0] == CNF_OK) {                   // the accepted steps back from the device (cnf_path_vjp_steps)
+        const int n = h->ens_nacc[0];
+        std::vector<float> pairs((size_t)2 * (n > 0 ? n : 0));
+        if (n > 0) HIPCHK(h, hipMemcpy(pairs.data(), h->d_path_steps, pairs.size() * sizeof(float), hipMemcpyDeviceToHost));
+        h->pvjp_t.resize((size_t)(n > 0 ? n : 0)); h->pvjp_h.resize(h->pvjp_t.size());
+        for (size_t i = 0; i < h->pvjp_t.size(); ++i) { h->pvjp_t[i] = pairs[2 * i]; h->pvjp_h[i] = pairs[2 * i + 1]; }
+        h->pvjp_valid = n >= 0;
     }
     return CNF_OK;
 }
@@ -2898,6 +2932,54 @@ extern "C" cnf_status cnf_generate_vjp_many(cnf_handle h, int mode, int M, const
                                             float* grad_z0_dev, int* status_out, cnf_solve_stats* stats_out, void* stream) {
     return ens_grad(h, WC_SAMPLING, mode, M, params_dev, z0, eps, B, opts, t0_host, cot_z_dev, cot_logq_dev, nullptr, x_out, logq_out,
                     grad_dev, grad_z0_dev, status_out, stats_out, stream);
+}
+
+// Differentiable flow paths (include/cnfhip_path_vjp.h): one model's inference (sampling) with the flow at the caller's save times,
+// and the vector-Jacobian product of the outputs AND of those slices, by the PATH forms of the per-sample-cotangent launch (M = 1).
+extern "C" int cnf_path_vjp_max_batch(cnf_handle h, int mode) {
+    if (!ens_handle_ok(h, mode)) return 0;
+    // both directions' kernels hold it; a batch is tiles of 16 columns, at most 512 of them
+    for (int B = 16 * 512; B >= 16; B -= 16)
+        if (ens_grad_capacity(h, mode, B, WC_INFERENCE_PATH) >= 1 && ens_grad_capacity(h, mode, B, WC_SAMPLING_PATH) >= 1) return B;
+    return 0;
+}
+// the member's status is the call's: there is one member and no streamed route behind this call
+static cnf_status path_vjp_status(cnf_handle h, cnf_status s, int status) {
+    if (s != CNF_OK || status == CNF_OK) return s;
+    return fail(h, (cnf_status)status, status == CNF_ERR_UNSUPPORTED
+                ? "the launch gave up: more accepted steps than it can differentiate, or a wait ran out (there is no streamed route for this call)"
+                : status == CNF_ERR_MAXITERS ? "maxiters reached" : "solver state became NaN/Inf");
+}
+extern "C" cnf_status cnf_inference_path_vjp(cnf_handle h, int mode, const float* params_dev, const float* xs, const float* eps, int B,
+                                             const cnf_solve_opts* opts, const float* saveat_host, int K, const float* cot_dev,
+                                             const float* path_cot_dev, float* logpx_dev, float* regs_dev, float* path_out_dev,
+                                             float* grad_dev, float* grad_x_dev, cnf_solve_stats* stats, void* stream) {
+    if (const char* bad = saveat_error(opts, saveat_host, K)) return h ? fail(h, CNF_ERR_BAD_ARG, bad) : CNF_ERR_BAD_ARG;
+    const EnsPath ep{saveat_host, K, path_cot_dev, path_out_dev};
+    int status = CNF_OK;
+    const cnf_status s = ens_grad(h, WC_INFERENCE_PATH, mode, 1, params_dev, xs, eps, B, opts, nullptr, cot_dev, nullptr, nullptr, logpx_dev,
+                                  regs_dev, grad_dev, grad_x_dev, &status, stats, stream, &ep);
+    return path_vjp_status(h, s, status);
+}
+extern "C" cnf_status cnf_generate_path_vjp(cnf_handle h, int mode, const float* params_dev, const float* z0, const float* eps, int B,
+                                            const cnf_solve_opts* opts, const float* saveat_host, int K, const float* cot_z_dev,
+                                            const float* cot_logq_dev, const float* path_cot_dev, float* x_out, float* logq_out,
+                                            float* path_out_dev, float* grad_dev, float* grad_z0_dev, cnf_solve_stats* stats, void* stream) {
+    if (const char* bad = saveat_error(opts, saveat_host, K)) return h ? fail(h, CNF_ERR_BAD_ARG, bad) : CNF_ERR_BAD_ARG;
+    const EnsPath ep{saveat_host, K, path_cot_dev, path_out_dev};
+    int status = CNF_OK;
+    const cnf_status s = ens_grad(h, WC_SAMPLING_PATH, mode, 1, params_dev, z0, eps, B, opts, nullptr, cot_z_dev, cot_logq_dev, nullptr, x_out,
+                                  logq_out, grad_dev, grad_z0_dev, &status, stats, stream, &ep);
+    return path_vjp_status(h, s, status);
+}
+extern "C" int cnf_path_vjp_steps(cnf_handle h, float* t_host, float* h_host, int cap) {
+    if (!h || !h->pvjp_valid) return -1;
+    const int n = (int)h->pvjp_t.size();
+    for (int i = 0; i < n && i < cap; ++i) {
+        if (t_host) t_host[i] = h->pvjp_t[i];
+        if (h_host) h_host[i] = h->pvjp_h[i];
+    }
+    return n;
 }
 
 // the signed accepted step sizes of member `member` of the last ensemble gradient call -- cnf_loss_grad_many,

@@ -38,7 +38,11 @@ bool wave_solve_supported(const NetDesc& nd, bool train, int B);
 // sv.base_dev / sv.abort_flag one word per member; no mirror, no trace, no clock, no rich store.
 // what the backward pass of an ensemble gradient pulls back: the built-in loss's cotangent, or a per-sample one (the CW forms of
 // the kernel) of inference's four outputs, or of sampling's (z, logq)
-enum WaveCot { WC_LOSS = 0, WC_INFERENCE = 1, WC_SAMPLING = 2 };
+// ... and the two PATH forms of those (cnf_inference_path_vjp, cnf_generate_path_vjp): the same launch also stores the flow at the
+// caller's save times and injects a cotangent of those slices into the backward sweep (the adjoint of Tsit5's interpolant)
+enum WaveCot { WC_LOSS = 0, WC_INFERENCE = 1, WC_SAMPLING = 2, WC_INFERENCE_PATH = 3, WC_SAMPLING_PATH = 4 };
+inline bool wave_cot_sampling(WaveCot c) { return c == WC_SAMPLING || c == WC_SAMPLING_PATH; }
+inline bool wave_cot_path(WaveCot c) { return c == WC_INFERENCE_PATH || c == WC_SAMPLING_PATH; }
 struct WaveEnsLaunch {
     int M = 0;
     const float* t1 = nullptr;     // device, [M]: the members' own end times (null: sv.init.t1 for all)
@@ -71,9 +75,14 @@ struct WavePathArgs {
     float* out = nullptr;              // [K][B][D]: slice k in the layout of u_out
     float* steps = nullptr;            // [steps_cap][2]: (t_n, signed h_n) of accepted step n (steps beyond the capacity are not filed)
     int steps_cap = 0;
+    // the PATH forms of the ensemble gradient (WC_INFERENCE_PATH, WC_SAMPLING_PATH) only: the cotangent of the slices, in the
+    // layout of `out` (null: nothing is injected); there `out` and `steps` may be null too (nothing is stored)
+    const float* cot = nullptr;
 };
 // `path`: the PATH form -- a plain solve (no grad, no ens) of one tile per workgroup, whatever the batch (B <= 8192), on the
 // tanh networks with one input tile; CNF_ERR_UNSUPPORTED for everything else (the caller takes the streamed path).
+// `path` with `grad` and `ens` (M = 1): the PATH form of the per-sample-cotangent gradient -- ens->cw / ens->cot_z / ens->cot_logq
+// may then all be null (no terminal cotangent).
 cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_params, const float* cond, int cbs, StepState* st_out,
                              float* U0, const float* eps, int B, hipStream_t s, void* mirror, unsigned seq, const Solve3Args& sv,
                              const WaveGradArgs* grad = nullptr, const WaveEnsLaunch* ens = nullptr, const WavePathArgs* path = nullptr);

@@ -177,6 +177,21 @@ __device__ __forceinline__ float wv_quad_sum(float v) {
 // may be null, columns past the batch carry zeros.  Everything behind that -- the stage sweeps, the helper wave, the
 // contraction, the stores, the meetings, lam_out = d / d u(t_start) -- is the CW form's.  logq and d / d z0 are column kernels
 // over the M B columns behind the launch (cnf_dist.hip).
+//
+// CW = WC_INFERENCE_PATH / WC_SAMPLING_PATH (CWP; cnf_inference_path_vjp, cnf_generate_path_vjp; one member): the two CW forms
+// plus the path in both halves.  Forward: the PATH block above on the CW form's solve (pa.out may be null), and t_att filed
+// beside h_att per accepted step (tsL beside hsL).  Backward: the adjoint of the interpolant -- with pbar_j = pa.cot[j] the
+// cotangent of slice j, theta_j = (tau_j - t_n) / h_n a constant of the frozen step sequence and the forward's bracketing found
+// again by walking the cursor backwards over tsL (path_lo / path_theta):
+//   tau_j == t_start:    lam += pbar_j behind the sweep (it reaches lam_out alone);
+//   end of its step:     lam += pbar_j on all rows before step n is pulled back;
+//   interior:            kbar_i = h_n (b_i lam + s_i + sum_{m > i} a_{m,i} w_m), s_i = sum_j b_i(theta_j) pbar_j formed inside the
+//                        rolled stage loop; lam += sum_j pbar_j after the step; the scalar rows' part goes through c_l, c_E, c_n,
+//                        which are running per-lane values here; k_7 of step n is k_1 of step n + 1 (FSAL): h_n s_7[n] joins that
+//                        stage's kbar_1 -- only a LAST step with interior saves costs one more stage pullback, run as stage 1 of a
+//                        step of size 0 at the final state (`virt`), and one more evaluation in the helper's count.
+// Each lane reads its own column of pbar_j (its z rows, the column's scalar rows); columns past the batch carry zeros, a null
+// pa.cot injects nothing.
 template <int NI, int NH, int MODE, bool TANH, bool GRAD = false, bool ID2 = false, int WGW = 1, bool RICH = false, bool ENS = false, bool PATH = false,
           int CW = WC_LOSS>
 __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wave(WaveArgs a, Solve3Args sv, const WvTab tab, const WaveEnsArgs en, const WavePathArgs pa) {
@@ -184,7 +199,9 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
     static_assert(!PATH || (!GRAD && !ENS && WGW == 1), "PATH is a form of the plain solve with one tile per workgroup");
     static_assert(!ENS || (WGW == 1 && !RICH), "ENS forms have one tile per workgroup and no rich store");
     static_assert(CW == WC_LOSS || (GRAD && ENS), "CW is a form of the ensemble gradient");
-    constexpr bool CWI = CW == WC_INFERENCE, CWS = CW == WC_SAMPLING;   // per-sample cotangents of inference | of sampling
+    // per-sample cotangents of inference | of sampling;  CWP: ... and of the path (the launch also stores it)
+    constexpr bool CWI = CW == WC_INFERENCE || CW == WC_INFERENCE_PATH, CWS = CW == WC_SAMPLING || CW == WC_SAMPLING_PATH;
+    constexpr bool CWP = CW == WC_INFERENCE_PATH || CW == WC_SAMPLING_PATH;
     static_assert(!RICH || (GRAD && MODE == WV_VJP), "RICH is a form of the TrainMode / VJP gradient");
     constexpr int RR = 3 * NH + 3 * NI;                     // f32x4 per lane and stage evaluation in the rich store
     f32x4* rich_ptr = nullptr;                             // where the next evaluation files them (null: nowhere)
@@ -216,7 +233,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
         if constexpr (GRAD) {
             a.g.traj += mb * en.traj_stride; a.g.hs_out += mb * (size_t)a.g.traj_cap;
             a.g.gpart += mb * (size_t)en.tiles * (size_t)a.g.n_params; a.g.lam_out += mb * Bz * nz;
-            if constexpr (CWI) cwp = en.cw + mb * 4 * Bz;
+            if constexpr (CWI) cwp = (CWP && !en.cw) ? nullptr : en.cw + mb * 4 * Bz;     // (a path form may have no terminal cotangent)
             if constexpr (CWS) {
                 if (en.gz) gzp = en.gz + mb * Bz * nz;
                 if (en.gl) glp = en.gl + mb * Bz;
@@ -430,6 +447,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
     };
 
     __shared__ float hsL[GRAD ? WV_GCAP : 1];                                           // step sizes of the accepted steps
+    __shared__ float tsL[CWP ? WV_GCAP : 1];               // CWP: ... and their start times (theta of a save time is the forward's)
     constexpr int TBW = 4 * (NI + NH) * 256;                // floats of one set of factor tiles
     // factor tiles, [sample][row]: one set per wave -- HELP: two sets, filed by the main wave and contracted by the helper in turn
     __shared__ __attribute__((aligned(16))) float tbuf_all[GRAD ? (HELP ? 2 : WGW) * TBW : 4];
@@ -669,9 +687,10 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
             for (int j = 0; j < 4; ++j) { const int r = 16 * m + 4 * q + j; if (r < n_in) o[r] = z[m][j]; }
         if (sown) o[n_in + q] = s;
     };
-    if constexpr (PATH) {                                  // save times at the start of the span: u0 itself
+    const bool pstore = PATH || (CWP && pa.out != nullptr);   // (a CWP launch may be asked for the gradient alone)
+    if constexpr (PATH || CWP) {                           // save times at the start of the span: u0 itself
         const float t_start = uni(ns.t0);
-        while (pcur < pa.K && uni(pa.times[pcur]) == t_start) { path_store(pcur, uz, us); ++pcur; }
+        while (pstore && pcur < pa.K && uni(pa.times[pcur]) == t_start) { path_store(pcur, uz, us); ++pcur; }
     }
     // ---- step attempts ----
     constexpr float BT[7] = {TS_BT1, TS_BT2, TS_BT3, TS_BT4, TS_BT5, TS_BT6, TS_BT7};
@@ -777,12 +796,13 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
         if (GRAD && accepted) {                            // h_n of this step (its stage states were filed by the attempt)
             if (acc0 < a.g.traj_cap && acc0 < WV_GCAP) {
                 hsL[acc0] = h_att;
+                if constexpr (CWP) tsL[acc0] = t_att;
                 if (wid == 0 && lane == 0) a.g.hs_out[acc0] = h_att;
             } else gover = true;
         }
-        if constexpr (PATH) {
-            if (accepted) {
-                if (wid == 0 && lane == 0 && acc0 < pa.steps_cap) { pa.steps[2 * acc0] = t_att; pa.steps[2 * acc0 + 1] = h_att; }
+        if constexpr (PATH || CWP) {
+            if (accepted && wid == 0 && lane == 0 && acc0 < pa.steps_cap) { pa.steps[2 * acc0] = t_att; pa.steps[2 * acc0 + 1] = h_att; }
+            if (accepted && pstore) {
                 const float t_end = uni(ns.t), tdir = uni(ns.tdir);       // (the last step's end is t1 itself)
                 const bool last = __builtin_amdgcn_readfirstlane(ns.done) != 0;
                 while (pcur < pa.K) {
@@ -902,8 +922,35 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
     }
     if constexpr (GRAD) {
         const bool run_bwd = alive && !gover && __builtin_amdgcn_readfirstlane(ns.done) && !__builtin_amdgcn_readfirstlane(ns.nonfinite);
+        // ---- CWP: which accepted step served which save times, found again from the filed (t_n, h_n) -- the forward's cursor walked
+        // backwards.  Step n took the indices [path_lo(n, hi), hi): what lies strictly behind its start along the direction and
+        // was not taken by a later step (hi: the later step's lo; K for the last one, which takes everything left); the indices
+        // below path_lo(0, .) are the save times at t_start.  path_theta: the forward's theta of save time j in step n, and
+        // whether the slice is the interpolant (true) or the accepted state u_{n+1} itself (false), by the forward's own rule. ----
+        const float p_tdir = uni(ns.tdir), p_tfin = uni(ns.t);
+        const int p_nacc = __builtin_amdgcn_readfirstlane(ns.naccept);
+        auto path_lo = [&](int n, int hi) __attribute__((always_inline)) {
+            const float tn = uni(tsL[n]);
+            int lo = hi;
+            while (lo > 0 && p_tdir * (uni(pa.times[lo - 1]) - tn) > 0.f) --lo;
+            return lo;
+        };
+        auto path_theta = [&](int j, int n, float& th) __attribute__((always_inline)) {
+            const float tau = uni(pa.times[j]), t_end = n == p_nacc - 1 ? p_tfin : uni(tsL[n + 1]);
+            th = (tau - uni(tsL[n])) / uni(hsL[n]);
+            return !(tau == t_end || !(th < 1.f));
+        };
+        const bool inject = CWP && pa.cot != nullptr;      // (null: the path is stored, nothing is injected)
+        // k_7 = f(u_{n+1}) of a step with interior save times is, bit for bit, k_1 of the next step (FSAL): its cotangent joins that
+        // stage's.  Only the LAST step's k_7 has no such stage: one more stage pullback at the final state, if it has interior saves.
+        bool extra = false;
+        if constexpr (CWP) {
+            if (inject && run_bwd && p_nacc > 0) {
+                for (int j = path_lo(p_nacc - 1, pa.K); j < pa.K; ++j) { float th; if (path_theta(j, p_nacc - 1, th)) extra = true; }
+            }
+        }
         if constexpr (HELP) {                              // the helper learns how many stage evaluations it will be handed
-            if (lane == 0) hcnt = run_bwd ? 6 * __builtin_amdgcn_readfirstlane(ns.naccept) : 0;
+            if (lane == 0) hcnt = run_bwd ? 6 * p_nacc + (extra ? 1 : 0) : 0;
             __syncthreads();
         }
         if (run_bwd) {
@@ -912,7 +959,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
             // CW: this lane's column of the member's cotangents, rows (logpx, E, n, A); columns past the batch carry none
             float cwv[4] = {0.f, 0.f, 0.f, 0.f};
             if constexpr (CWI) {
-                if (live) {
+                if (live && (!CWP || cwp)) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) cwv[r] = cwp[(size_t)r * (size_t)a.B + (size_t)smp];
                 }
@@ -1047,9 +1094,39 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
 #pragma unroll
                 for (int r = 0; r < RR; ++r) Rnx[r] = nx ? nx[r] : zero4;
             }
-            for (int n = nacc - 1; n >= 0; --n) {
-                const float hn = hsL[n];
+            // CWP: the cotangents of the scalar rows are running values (the path's cotangents join them on the way back), and this
+            // lane's part of the cotangent of slice j: its z rows of its column, and the column's scalar rows
+            float cl = cl0, cE = cE0, cn = cn0;
+            int pend = CWP ? pa.K : 0;                     // the save indices below pend are still to be injected
+            auto pc_load = [&](int j, f32x4 (&pz)[NI], float (&psc)[3]) __attribute__((always_inline)) {
+                const float* pc = pa.cot + ((size_t)j * (size_t)a.B + sb) * D;
+#pragma unroll
+                for (int m = 0; m < NI; ++m)
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) { const int r = 16 * m + 4 * q + jj; pz[m][jj] = (live && r < n_in) ? pc[r] : 0.f; }
+#pragma unroll
+                for (int r = 0; r < 3; ++r) psc[r] = (live && r < NS) ? pc[n_in + r] : 0.f;
+            };
+            // pbar_j joins the cotangent of the whole state (the slice is u_{n+1} itself, or the u_n term of the interpolant)
+            auto pc_add = [&](int j) __attribute__((always_inline)) {
+                f32x4 pz[NI];
+                float psc[3];
+                pc_load(j, pz, psc);
+#pragma unroll
+                for (int m = 0; m < NI; ++m) lam[m] += pz[m];
+                cl += psc[0]; cE += psc[1]; cn += psc[2];
+            };
+            // (extra: the pullback of the last step's k_7 runs as stage 1 of a step of size 0 at the final state, n = nacc)
+            for (int n = extra ? nacc : nacc - 1; n >= 0; --n) {
+                const bool virt = CWP && n == nacc;
+                const float hn = virt ? 0.f : hsL[n];
                 f32x4 U[6][NI];                            // the stage states the forward pass filed; the next step's are requested a step ahead
+                if (virt) {
+#pragma unroll
+                    for (int i = 0; i < 6; ++i)
+#pragma unroll
+                        for (int m = 0; m < NI; ++m) U[i][m] = i == 0 ? uz[m] : zero4;
+                } else {
 #pragma unroll
                 for (int i = 0; i < 6; ++i)
 #pragma unroll
@@ -1060,13 +1137,66 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
 #pragma unroll
                         for (int m = 0; m < NI; ++m) U_next[i][m] = tj0[(size_t)(n - 1) * tstep + i * tstage + m];
                 }
+                }
+                // CWP: the save times of this step whose slice is the accepted state u_{n+1}: lambda += pbar_j before the step
+                int plo = pend;
+                if constexpr (CWP) {
+                    if (inject && !virt) {
+                        plo = path_lo(n, pend);
+                        for (int j = plo; j < pend; ++j) { float th; if (!path_theta(j, n, th)) pc_add(j); }
+                    }
+                }
                 f32x4 ws[6][NI];
 #pragma unroll
                 for (int i = 0; i < 6; ++i)
 #pragma unroll
                     for (int m = 0; m < NI; ++m) ws[i][m] = zero4;
 #pragma unroll 1
-                for (int i = 5; i >= 0; --i) {
+                for (int i = virt ? 0 : 5; i >= 0; --i) {
+                    // CWP: the seeds of this stage, s_i = sum_j b_i(theta_j) pbar_j over the interior save times of the step, formed here
+                    // (not held for all seven stages); fz: h_{n-1} s_7 of the step BEFORE this one, whose k_7 is this step's k_1
+                    f32x4 sz[CWP ? NI : 1], fz[CWP ? NI : 1];
+                    float ssc[3] = {0.f, 0.f, 0.f}, fsc[3] = {0.f, 0.f, 0.f};
+                    if constexpr (CWP) {
+#pragma unroll
+                        for (int m = 0; m < NI; ++m) { sz[m] = zero4; fz[m] = zero4; }
+                        if (inject && !virt) {
+                            for (int j = plo; j < pend; ++j) {
+                                float th;
+                                if (!path_theta(j, n, th)) continue;
+                                float bth[7];
+                                tsit5_dense_b(th, bth);
+                                float bt = bth[0];
+#pragma unroll
+                                for (int k = 1; k < 6; ++k) bt = i == k ? bth[k] : bt;
+                                f32x4 pz[NI];
+                                float psc[3];
+                                pc_load(j, pz, psc);
+#pragma unroll
+                                for (int m = 0; m < NI; ++m) sz[m] += bt * pz[m];
+#pragma unroll
+                                for (int r = 0; r < 3; ++r) ssc[r] = fmaf(bt, psc[r], ssc[r]);
+                            }
+                        }
+                        if (inject && i == 0 && n > 0) {
+                            const int n1 = n - 1;
+                            const float h1 = uni(hsL[n1]);
+                            for (int j = path_lo(n1, plo); j < plo; ++j) {
+                                float th;
+                                if (!path_theta(j, n1, th)) continue;
+                                float bth[7];
+                                tsit5_dense_b(th, bth);
+                                const float bt = h1 * bth[6];
+                                f32x4 pz[NI];
+                                float psc[3];
+                                pc_load(j, pz, psc);
+#pragma unroll
+                                for (int m = 0; m < NI; ++m) fz[m] += bt * pz[m];
+#pragma unroll
+                                for (int r = 0; r < 3; ++r) fsc[r] = fmaf(bt, psc[r], fsc[r]);
+                            }
+                        }
+                    }
                     // ---- this stage's point and the cotangent of its k:  kbar = h (b_i lam + sum_{m > i} a_{m,i} w_m) ----
                     f32x4 z[NI], kb[NI];
                     const float bi = tab.a[6][i];
@@ -1078,9 +1208,13 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
                         f32x4 acc = bi * lam[m];
 #pragma unroll
                         for (int k = 1; k < 6; ++k) acc += tab.a[k][i] * ws[k][m];     // (a_{k,i} = 0 for k <= i)
-                        kb[m] = hn * acc;
+                        if constexpr (CWP) kb[m] = hn * (acc + sz[m]) + fz[m];
+                        else kb[m] = hn * acc;
                     }
-                    const float c_l = hn * bi * cl0, c_E = hn * bi * cE0, c_n = hn * bi * cn0;
+                    // (CWP: the scalar rows take their part of lambda, of s_i and of the step before's s_7 the same way)
+                    const float c_l = CWP ? fmaf(hn * bi, cl, fmaf(hn, ssc[0], fsc[0])) : hn * bi * cl0;
+                    const float c_E = CWP ? fmaf(hn * bi, cE, fmaf(hn, ssc[1], fsc[1])) : hn * bi * cE0;
+                    const float c_n = CWP ? fmaf(hn * bi, cn, fmaf(hn, ssc[2], fsc[2])) : hn * bi * cn0;
                     (void)c_E; (void)c_n;
                     // ---- forward: h_1, sigma', sigma'' ; zdot ; ahat = kbar + c_E zdot / |zdot| ----
                     f32x4 h1[NH], d1[NH], zd[NI], d2[NI];
@@ -1325,7 +1459,21 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
                 // lambda <- lambda + sum_i w_i
 #pragma unroll
                 for (int m = 0; m < NI; ++m) lam[m] += ((ws[0][m] + ws[1][m]) + (ws[2][m] + ws[3][m])) + (ws[4][m] + ws[5][m]);
+                // CWP: ... + e, the sum of the cotangents of the step's interior save times (the u_n term of the interpolant)
+                if constexpr (CWP) {
+                    if (inject && !virt) {
+                        for (int j = plo; j < pend; ++j) { float th; if (path_theta(j, n, th)) pc_add(j); }
+                    }
+                    pend = plo;
+                }
             }
+            // CWP: the save times at t_start (the slice is u0): their cotangent reaches d / d u(t_start) alone
+            if constexpr (CWP) {
+                if (inject) {
+                    for (int j = 0; j < pend; ++j) pc_add(j);
+                }
+            }
+            (void)cl; (void)cE; (void)cn; (void)pend;
             // ---- outputs: d loss / d z(t0), this wave's partial of the flat gradient (Lux order: W out x in column-major, then b) ----
             if (live) {
 #pragma unroll
@@ -1442,10 +1590,11 @@ wave_fn wave_instance_tiles(int ni, int nh, int mode) {
     return nullptr;
 }
 // One row per set of flags that is instantiated, each for the tiles above and the modes it names: these rows ARE the library's
-// k_solve_wave kernels (142 of them).  nullptr: no such kernel -- wave_variant does not return such a tuple.
+// k_solve_wave kernels (172 of them).  nullptr: no such kernel -- wave_variant does not return such a tuple.
 // cw: the CW forms (per-sample cotangents: WC_INFERENCE of cnf_inference_vjp_many, WC_SAMPLING of cnf_generate_vjp_many).  They
 // are no WaveForm of their own: a caller selects one as "the WF_ENS_GRAD answer of wave_variant, with CW" -- the same fifteen
-// tuples, instantiated once more for each; with any other answer there is no such kernel.
+// tuples, instantiated once more for each, and once more for the PATH form of each (WC_INFERENCE_PATH, WC_SAMPLING_PATH:
+// cnf_inference_path_vjp, cnf_generate_path_vjp); with any other answer there is no such kernel.
 wave_fn wave_instance(const WaveVariant& v, WaveCot cw = WC_LOSS) {
 #define WV_ROW(MODES, TANH, GRAD, ID2, WGW, RICH, ENS, PATH, CW)                                                                         \
     if (v.tanh == TANH && v.grad == GRAD && v.id2 == ID2 && v.wgw == WGW && v.rich == RICH && v.ens == ENS && v.path == PATH && cw == CW) \
@@ -1466,6 +1615,10 @@ wave_fn wave_instance(const WaveVariant& v, WaveCot cw = WC_LOSS) {
     WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, true,  false, WC_INFERENCE);
     WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, true,  false, WC_SAMPLING);      // WF_ENS_GRAD, CW: sampling's cotangents
     WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, true,  false, WC_SAMPLING);
+    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, true,  false, WC_INFERENCE_PATH);     // WF_ENS_GRAD, CW: ... and the path's
+    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, true,  false, WC_INFERENCE_PATH);
+    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, true,  false, WC_SAMPLING_PATH);
+    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, true,  false, WC_SAMPLING_PATH);
     WV_ROW(WV_M_ALL,  true,  false, false, 1, false, true,  false, WC_LOSS);     // WF_ENS_PLAIN
     WV_ROW(WV_M_ALL,  true,  false, true,  1, false, true,  false, WC_LOSS);
     WV_ROW(WV_M_ALL,  true,  false, false, 1, false, false, true, WC_LOSS);      // WF_PATH
@@ -1564,13 +1717,17 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
                              float* U0, const float* eps, int B, hipStream_t s, void* mirror, unsigned seq, const Solve3Args& sv_,
                              const WaveGradArgs* grad, const WaveEnsLaunch* ens, const WavePathArgs* path) {
     if (!wave_solve_supported(nd, train, B)) return CNF_ERR_UNSUPPORTED;
-    if (path && (grad || ens || !path->times || !path->out || path->K < 1 || (path->steps_cap > 0 && !path->steps))) return CNF_ERR_BAD_ARG;
-    // the CW form of the ensemble gradient: per-sample cotangents of inference, or of sampling
-    const WaveCot cw = !ens ? WC_LOSS : ens->sampling ? WC_SAMPLING : ens->cw ? WC_INFERENCE : WC_LOSS;
+    // the PATH form of the per-sample-cotangent gradient: one member, with its gradient; it may store nothing and inject nothing
+    const bool gpath = path && grad && ens;
+    if (path && !gpath && (grad || ens || !path->out || path->cot)) return CNF_ERR_BAD_ARG;
+    if (path && (!path->times || path->K < 1 || (path->steps_cap > 0 && !path->steps) || (gpath && ens->M != 1))) return CNF_ERR_BAD_ARG;
+    // the CW form of the ensemble gradient: per-sample cotangents of inference, or of sampling -- and of the path
+    const WaveCot cw = !ens ? WC_LOSS : ens->sampling ? (gpath ? WC_SAMPLING_PATH : WC_SAMPLING)
+                                      : gpath ? WC_INFERENCE_PATH : ens->cw ? WC_INFERENCE : WC_LOSS;
     if (cw != WC_LOSS && !grad) return CNF_ERR_BAD_ARG;
     if (ens) {
         const bool gcot = ens->cot_z || ens->cot_logq;     // (sampling: its own cotangents, at least one, and start times only)
-        if (ens->sampling ? (ens->cw || ens->t1 || !gcot) : gcot) return CNF_ERR_BAD_ARG;
+        if (ens->sampling ? (ens->cw || ens->t1 || (!gcot && !gpath)) : gcot) return CNF_ERR_BAD_ARG;
     }
     if (ens && (cond || mirror || ens->M < 1 || ens->M > (grad ? wave_ens_capacity(nd, train, B, cw) : wave_ens_eval_capacity(nd, train, B))))
         return CNF_ERR_UNSUPPORTED;
@@ -1582,7 +1739,7 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
     const int tiles = (B + 15) / 16;
     bool xwg = false;                                      // WF_WG4: workgroups of four tiles (false: one workgroup of `tiles` waves)
     WaveForm form = WF_PLAIN;
-    if (path) form = WF_PATH;                              // one tile per workgroup, whatever the batch
+    if (path && !gpath) form = WF_PATH;                    // one tile per workgroup, whatever the batch
     else if (ens) form = grad ? WF_ENS_GRAD : WF_ENS_PLAIN;       // (one tile per workgroup -- and its helper, as every gradient)
     else if (grad)                                         // the forward pass files its intermediates: the RICH instantiations
         form = grad->rich && wave_mode(nd, train) == WV_VJP && nd.n_in <= 16 ? WF_GRAD_RICH : WF_GRAD;
@@ -1625,9 +1782,9 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
     } else if (ens) {
         // an inference with all of its outputs, or (sampling) a bare solve from the caller's columns, whose final state goes to U0
         const bool inf = sv.xs && sv.logpx && sv.regs && sv.sums5 && !sv.u0, bare = !sv.xs && !sv.logpx && !sv.regs && !sv.sums5 && sv.u0;
-        if (grad->rich || sv.trace || sv.t_out || sv.u_out || !(cw == WC_SAMPLING ? bare : inf)) return CNF_ERR_BAD_ARG;
+        if (grad->rich || sv.trace || sv.t_out || sv.u_out || !(wave_cot_sampling(cw) ? bare : inf)) return CNF_ERR_BAD_ARG;
         en.traj_stride = ens->traj_stride; en.cw = ens->cw;
-        if (cw == WC_SAMPLING) { en.t0 = ens->t0; en.gz = ens->cot_z; en.gl = ens->cot_logq; }
+        if (wave_cot_sampling(cw)) { en.t0 = ens->t0; en.gz = ens->cot_z; en.gl = ens->cot_logq; }
     }
     if (ens) {                                             // M x tiles workgroups
         en.tiles = tiles; en.t1 = ens->t1; en.p_stride = ens->p_stride; en.part_stride = ens->part_stride;
@@ -1635,7 +1792,7 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
     }
     WavePathArgs pa{};
     if (path) {
-        if (sv.xs || !sv.u0) return CNF_ERR_BAD_ARG;       // (a bare solve: the path starts from the caller's columns)
+        if (!gpath && (sv.xs || !sv.u0)) return CNF_ERR_BAD_ARG;       // (a bare solve: the path starts from the caller's columns)
         pa = *path;
     }
     void* args[] = {&a, &sv, &tab, &en, &pa};

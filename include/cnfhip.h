@@ -382,6 +382,10 @@ cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int B, float* 
  * header) ---- */
 #include "cnfhip_path.h"
 
+/* ---- differentiable flow paths: cnf_path_vjp_max_batch / cnf_inference_path_vjp / cnf_generate_path_vjp / cnf_path_vjp_steps
+ * (declared in cnfhip_path_vjp.h, part of this header) ---- */
+#include "cnfhip_path_vjp.h"
+
 /* ---- device random numbers ------------------------------------------
  *
  * The library's own counter-based generator, the counterpart of the device RNG the reference draws eps and
