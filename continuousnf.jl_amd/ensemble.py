@@ -13,17 +13,21 @@ ensemble form of the same kernel; ``EnsembleDist`` is the bagged density: a weig
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import time
 from contextlib import contextmanager
+from types import SimpleNamespace
 
 import numpy as np
 
 from . import _lib
-from .base_icnf import ICNF, _Buf, _is_torch, _mode_id, _solve_opts, draw_eps, generate, inference, loss_and_grad, n_augment_input, \
-    steer_tspan
+from .base_icnf import ICNF, _Buf, _is_torch, _mode_id, _solve_opts, _stream, draw_eps, generate, inference, loss_and_grad, \
+    n_augment_input, steer_tspan
+from .gen_vjp import _cot_two
 from .layers import setup
 from .rng import HIPRNG
 from .types import TrainMode
+from .vjp import _cot_rows
 
 
 def _refusal(icnf: ICNF):
@@ -47,12 +51,18 @@ def _refusal(icnf: ICNF):
     return None
 
 
-def ensemble_capacity(icnf: ICNF, mode, B: int) -> int:
-    """The largest M one launch takes for this model, mode and batch size (cnf_ensemble_capacity); 0: no ensemble form."""
+def _capacity(icnf: ICNF, mode, capacity_fn, *size) -> int:
+    """What ``capacity_fn`` of the C ABI answers for this model, mode and size; 0, without making a handle, for a model
+    ``_refusal`` turns away."""
     m = _mode_id(mode)
     if _refusal(icnf) is not None:
         return 0
-    return int(_lib.lib().cnf_ensemble_capacity(icnf.handle(), m, int(B)))
+    return int(getattr(_lib.lib(), capacity_fn)(icnf.handle(), m, *(int(s) for s in size)))
+
+
+def ensemble_capacity(icnf: ICNF, mode, B: int) -> int:
+    """The largest M one launch takes for this model, mode and batch size (cnf_ensemble_capacity); 0: no ensemble form."""
+    return _capacity(icnf, mode, "cnf_ensemble_capacity", B)
 
 
 def _check_inputs(icnf: ICNF, mode, xs, ps, eps, t1, who="loss_and_grad_many", single="loss_and_grad"):
@@ -83,10 +93,12 @@ def _check_inputs(icnf: ICNF, mode, xs, ps, eps, t1, who="loss_and_grad_many", s
     return m, M, B, n_in, t1
 
 
-def _probes_and_ends(icnf: ICNF, mode, train, M, B, n_in, xr, eps, t1):
+def _probes_and_ends(icnf: ICNF, mode, train, M, B, n_in, xr, eps, t1, steer=True):
     """The members' probes ([M][B][n_in] on the device of ``xr``; None in TestMode) and end times (None: ``tspan[1]`` for all),
-    given or drawn in the order ``loss_and_grad_many`` documents."""
+    given or drawn in the order ``loss_and_grad_many`` documents.  ``steer=False``: no steer variate is drawn (the path calls,
+    which are this draw with one member)."""
     import torch
+    steer = steer and train and t1 is None and icnf.STEER      # (given end times and TestMode never steer)
     if not train:
         er = None
     elif eps is not None:
@@ -96,9 +108,7 @@ def _probes_and_ends(icnf: ICNF, mode, train, M, B, n_in, xr, eps, t1):
     else:
         # the host generator, member by member in the order a loop of ``loss_and_grad`` consumes it (the member's probes, then
         # its end time: base_icnf.loss_and_grad), so that one seed gives the members the draws that loop would; one upload
-        host, draws = _Buf(None, icnf.nvars, B, None), []
-        steer = t1 is None and icnf.STEER
-        ends = []
+        host, draws, ends = _Buf(None, icnf.nvars, B, None), [], []
         for _ in range(M):
             draws.append(draw_eps(icnf, host, B).arr.reshape(B, n_in))
             if steer:
@@ -106,7 +116,7 @@ def _probes_and_ends(icnf: ICNF, mode, train, M, B, n_in, xr, eps, t1):
         er = torch.from_numpy(np.stack(draws)).to(xr.device)
         if steer:
             t1 = np.asarray(ends, dtype=np.float32)
-    if t1 is None and icnf.STEER and train:                # (given probes, TestMode never steers, or a device generator: M draws)
+    if steer and t1 is None:                               # (given probes, or a device generator: M draws)
         t1 = np.asarray([steer_tspan(icnf, mode)[1] for _ in range(M)], dtype=np.float32)
     return er, t1
 
@@ -125,30 +135,75 @@ def _device_capacity(who, capacity_fn, h, m, B):
     return cap
 
 
-def _chunked_calls(icnf: ICNF, M, cap, call, steps_of=None):
-    """The ensemble call in launches of at most ``cap`` members (M above the capacity: consecutive launches).
-    ``call(lo, n, status, stats)`` makes the ABI call for the members ``lo .. lo + n - 1`` with the two pointers as its
-    ``status_out`` and ``stats_out``; ``steps_of(icnf, i)`` reads the steps of member i of the call just made (asked for the
-    members that succeeded; None: no steps).  Returns ``(stats, status, calls, steps)``."""
-    h = icnf.handle()
+def _settle_density(icnf: ICNF, mode, xs, ps, eps, t1, who, single, capacity_fn=None, cot_rows=None, shared=True):
+    """The inputs of a density-direction ensemble call, checked, placed and drawn, in the one order the callers promise: the
+    host-side refusals and shape checks (``_check_inputs``, then ``cot_rows(M, B)``: the call's cotangent tensors) -- nothing is
+    drawn, no handle is made --; the handle (no device: cnf_create's error, as everywhere); the device check; the capacity
+    (``capacity_fn`` of the C ABI; None: not asked, for the ``differentiable_*`` entries, whose forward asks); the probes and
+    end times (``_probes_and_ends``).  ``shared``: ``xs`` may be one (nvars, B) data set for all members.  Returns a namespace:
+    ``m, M, B, n_in, train, cot, cap, dev, stream, xr, pr, er, t1``."""
+    import torch
+    if shared and _is_torch(xs) and _is_torch(ps) and xs.dim() == 2 and ps.dim() == 2 and _refusal(icnf) is None:
+        xs = xs.unsqueeze(0).expand(ps.shape[0], *xs.shape)                # shared data: every member reads its own copy
+    m, M, B, n_in, t1 = _check_inputs(icnf, mode, xs, ps, eps, t1, who, single)
+    cot = cot_rows(M, B) if cot_rows is not None else ()
+    h = icnf.handle() if capacity_fn is not None else None
+    if not (xs.is_cuda and ps.is_cuda and all(a is None or a.is_cuda for a in (eps, *cot))):
+        raise ValueError(f"{who}: torch tensors must live on the GPU")
+    cap = _device_capacity(who, capacity_fn, h, m, B) if capacity_fn is not None else None
+    train, dev = m == _lib.MODE_TRAIN, xs.device
+    xr = _rows(xs)
+    pr = ps.detach().to(torch.float32).contiguous()
+    er, t1 = _probes_and_ends(icnf, mode, train, M, B, n_in, xr, eps, t1)
+    return SimpleNamespace(m=m, M=M, B=B, n_in=n_in, train=train, cot=cot, cap=cap, dev=dev, xr=xr, pr=pr, er=er, t1=t1,
+                           stream=_stream(_Buf(xr, icnf.nvars, M * B, torch)))
+
+
+def _launch(icnf: ICNF, s, call, steps_of, times_key, times, **more):
+    """The first half of every ensemble call: the ABI call in launches of at most ``s.cap`` members (``s.M`` above the
+    capacity: consecutive launches), and what every ensemble call reports.  ``call(lo, n, status, stats)`` makes the ABI call
+    for the members ``lo .. lo + n - 1`` with the two pointers as its ``status_out`` and ``stats_out``; ``steps_of(icnf, i)``
+    reads the steps of member i of the call just made (asked for the members that succeeded; None: no steps); ``times``: the
+    members' own times (None: ``tspan[1]`` for all), reported as ``info[times_key]``.  Returns ``(info, steps)``; failures are
+    ``_finish``'s, so that a caller may publish ``info`` before they are raised."""
+    h, M = icnf.handle(), s.M
     status = np.empty(M, dtype=np.int32)
     stats = (_lib.cnf_solve_stats * M)()
-    calls, steps = 0, []
-    for lo in range(0, M, cap):
-        n = min(cap, M - lo)
+    calls, steps = 0, [] if steps_of is not None else None
+    for lo in range(0, M, s.cap):
+        n = min(s.cap, M - lo)
         _lib.check(call(lo, n, status[lo:].ctypes.data, C.byref(stats, lo * C.sizeof(_lib.cnf_solve_stats))), h)
         calls += 1
         if steps_of is not None:
             steps += [steps_of(icnf, i) if status[lo + i] == _lib.OK else None for i in range(n)]
-    return stats, status, calls, steps
-
-
-def _info(icnf: ICNF, stats, status, calls, times_key, times, **more):
-    """What every ensemble call reports; ``times``: the members' own times (None: ``tspan[1]`` for all)."""
     if times is None:
-        times = np.full(len(status), icnf.tspan[1], dtype=np.float32)
-    return {"stats": [s.as_dict() for s in stats], "status": status, "launches": max(s.launches for s in stats), "calls": calls,
-            "rerun": [], times_key: times, **more}
+        times = np.full(M, icnf.tspan[1], dtype=np.float32)
+    info = {"stats": [st.as_dict() for st in stats], "status": status, "launches": max(st.launches for st in stats),
+            "calls": calls, "rerun": [], times_key: times, **more}
+    return info, steps
+
+
+def _finish(icnf: ICNF, info, steps, times, rerun):
+    """The second half: a member that failed raises; the members whose part of the launch gave up are run again one at a
+    time.  ``rerun(i)`` runs member i on the single-model route, writes its outputs and returns ``(stats, steps)`` as that
+    route reports them (None for what it does not report).  Fills ``info["rerun"]`` and, when steps were asked for,
+    ``info["steps"]``."""
+    status = info["status"]
+    _raise_failed(status)
+    gave_up = [i for i in range(len(status)) if status[i] != _lib.OK]
+    if gave_up:
+        with _one_member_at_a_time(icnf, times) as member:
+            for i in gave_up:
+                member(i)
+                stats_i, steps_i = rerun(i)
+                status[i] = _lib.OK
+                if stats_i is not None:
+                    info["stats"][i] = stats_i
+                if steps is not None:
+                    steps[i] = steps_i
+        info["rerun"] = gave_up
+    if steps is not None:
+        info["steps"] = steps
 
 
 def _raise_failed(status):
@@ -188,45 +243,32 @@ def loss_and_grad_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, wit
     for what has no ensemble form: conditional models, a non-default ``basedist``, host arrays, PlanarLayer chains, networks
     outside the in-launch gradient's envelope, ``kernel="generic"``."""
     import torch
-    m, M, B, n_in, t1 = _check_inputs(icnf, mode, xs, ps, eps, t1)
-    l, h = _lib.lib(), icnf.handle()                       # (no device: cnf_create's error, as everywhere)
-    if not (xs.is_cuda and ps.is_cuda and (eps is None or eps.is_cuda)):
-        raise ValueError("loss_and_grad_many: torch tensors must live on the GPU")
-    cap = _device_capacity("loss_and_grad_many", "cnf_ensemble_capacity", h, m, B)
-    train = m == _lib.MODE_TRAIN
-    dev = xs.device
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    xr = _rows(xs)
-    pr = ps.detach().to(torch.float32).contiguous()
-    er, t1 = _probes_and_ends(icnf, mode, train, M, B, n_in, xr, eps, t1)
+    s = _settle_density(icnf, mode, xs, ps, eps, t1, "loss_and_grad_many", "loss_and_grad", "cnf_ensemble_capacity", shared=False)
+    l, h = _lib.lib(), icnf.handle()
+    m, M, B, xr, pr, er, t1 = s.m, s.M, s.B, s.xr, s.pr, s.er, s.t1
     opts = _solve_opts(icnf, icnf.tspan)
-    n_params = pr.shape[1]
-    grads = torch.empty((M, n_params), dtype=torch.float32, device=dev)
+    grads = torch.empty((M, pr.shape[1]), dtype=torch.float32, device=s.dev)
     losses = np.empty(M, dtype=np.float32)
-    stats, status, calls, steps = _chunked_calls(icnf, M, cap, lambda lo, n, status, stats: l.cnf_loss_grad_many(
+    info, steps = _launch(icnf, s, lambda lo, n, status, stats: l.cnf_loss_grad_many(
         h, m, n, pr[lo].data_ptr(), xr[lo].data_ptr(), er[lo].data_ptr() if er is not None else None, B, C.byref(opts),
-        t1[lo:].ctypes.data if t1 is not None else None, losses[lo:].ctypes.data, grads[lo].data_ptr(), status, stats, stream),
-        ensemble_steps if with_steps else None)
-    info = _info(icnf, stats, status, calls, "t1", t1)
-    _raise_failed(status)
-    gave_up = [i for i in range(M) if status[i] != _lib.OK]
-    if gave_up:
-        with _one_member_at_a_time(icnf, t1) as member:
-            for i in gave_up:
-                member(i)
-                args = dict(eps=er[i].t()) if train else {}
-                val, g = loss_and_grad(icnf, mode, xr[i].t(), pr[i], st, **args)
-                losses[i] = val
-                grads[i].copy_(g)
-                status[i] = _lib.OK
-                info["stats"][i] = dict(icnf.last_stats)
-                if with_steps:
-                    steps[i] = np.array(icnf.last_steps, dtype=np.float32)
-        info["rerun"] = gave_up
-    if with_steps:
-        info["steps"] = steps
+        t1[lo:].ctypes.data if t1 is not None else None, losses[lo:].ctypes.data, grads[lo].data_ptr(), status, stats, s.stream),
+        ensemble_steps if with_steps else None, "t1", t1)
+
+    def rerun(i):
+        args = dict(eps=er[i].t()) if s.train else {}
+        val, g = loss_and_grad(icnf, mode, xr[i].t(), pr[i], st, **args)
+        losses[i] = val
+        grads[i].copy_(g)
+        return _stats_and_steps(icnf)
+
+    _finish(icnf, info, steps, t1, rerun)
     icnf.last_stats = info["stats"][0]
     return losses, grads, info
+
+
+def _stats_and_steps(icnf: ICNF):
+    """What a single-model gradient route reports of the solve it just made: its statistics and signed accepted step sizes."""
+    return dict(icnf.last_stats), np.array(icnf.last_steps, dtype=np.float32)
 
 
 def ensemble_steps(icnf: ICNF, member: int):
@@ -301,10 +343,7 @@ def fit_many(model, verbosity: int, Xs, *, seeds=None):
 def ensemble_eval_capacity(icnf: ICNF, mode, B: int) -> int:
     """The largest M one ``inference_many`` / ``generate_many`` launch takes for this model, mode and batch size
     (cnf_ensemble_eval_capacity); 0: no ensemble form."""
-    m = _mode_id(mode)
-    if _refusal(icnf) is not None:
-        return 0
-    return int(_lib.lib().cnf_ensemble_eval_capacity(icnf.handle(), m, int(B)))
+    return _capacity(icnf, mode, "cnf_ensemble_eval_capacity", B)
 
 
 def ensemble_eval_steps(icnf: ICNF, member: int):
@@ -340,46 +379,28 @@ def inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, with_st
     accepted)`` of its step attempts (None for a member that was run again).  A member whose solve went non-finite or hit maxiters raises ``CNFError`` naming it;
     ``NotImplementedError`` -- before anything is drawn -- for what ``loss_and_grad_many`` refuses."""
     import torch
-    who = "inference_many"
-    if _is_torch(xs) and _is_torch(ps) and xs.dim() == 2 and ps.dim() == 2 and _refusal(icnf) is None:
-        xs = xs.unsqueeze(0).expand(ps.shape[0], *xs.shape)                # shared data: every member reads its own copy
-    m, M, B, n_in, t1 = _check_inputs(icnf, mode, xs, ps, eps, t1, who, "inference")
+    s = _settle_density(icnf, mode, xs, ps, eps, t1, "inference_many", "inference", "cnf_ensemble_eval_capacity")
     l, h = _lib.lib(), icnf.handle()
-    if not (xs.is_cuda and ps.is_cuda and (eps is None or eps.is_cuda)):
-        raise ValueError(f"{who}: torch tensors must live on the GPU")
-    cap = _device_capacity(who, "cnf_ensemble_eval_capacity", h, m, B)
-    train = m == _lib.MODE_TRAIN
-    dev = xs.device
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    xr = _rows(xs)
-    pr = ps.detach().to(torch.float32).contiguous()
-    er, t1 = _probes_and_ends(icnf, mode, train, M, B, n_in, xr, eps, t1)
+    m, M, B, dev, xr, pr, er, t1 = s.m, s.M, s.B, s.dev, s.xr, s.pr, s.er, s.t1
     opts = _solve_opts(icnf, icnf.tspan)
     logpx, regs = torch.empty((M, B), dtype=torch.float32, device=dev), torch.empty((M, 3, B), dtype=torch.float32, device=dev)
     losses = np.empty(M, dtype=np.float32)
     tc = _trace_cap(opts, with_steps)
-    stats, status, calls, steps = _chunked_calls(icnf, M, cap, lambda lo, n, status, stats: l.cnf_inference_many(
+    info, steps = _launch(icnf, s, lambda lo, n, status, stats: l.cnf_inference_many(
         h, m, n, pr[lo].data_ptr(), xr[lo].data_ptr(), er[lo].data_ptr() if er is not None else None, B, C.byref(opts),
         t1[lo:].ctypes.data if t1 is not None else None, logpx[lo].data_ptr(), regs[lo].data_ptr(), losses[lo:].ctypes.data,
-        status, stats, tc, stream), ensemble_eval_steps if with_steps else None)
-    info = _info(icnf, stats, status, calls, "t1", t1, losses=losses)
-    _raise_failed(status)
-    gave_up = [i for i in range(M) if status[i] != _lib.OK]
-    if gave_up:
+        status, stats, tc, s.stream), ensemble_eval_steps if with_steps else None, "t1", t1, losses=losses)
+
+    def rerun(i):
         from .base_icnf import loss_from_sums
-        with _one_member_at_a_time(icnf, t1) as member:
-            for i in gave_up:
-                member(i)
-                args = dict(eps=er[i].t()) if train else {}
-                lp, rg, sums = inference(icnf, mode, xr[i].t(), pr[i], st, with_sums=True, **args)
-                logpx[i].copy_(lp)
-                regs[i].copy_(torch.stack(list(rg)))
-                losses[i] = loss_from_sums(icnf, mode, sums)
-                status[i] = _lib.OK
-                info["stats"][i] = dict(icnf.last_stats)
-        info["rerun"] = gave_up
-    if with_steps:
-        info["steps"] = steps
+        args = dict(eps=er[i].t()) if s.train else {}
+        lp, rg, sums = inference(icnf, mode, xr[i].t(), pr[i], st, with_sums=True, **args)
+        logpx[i].copy_(lp)
+        regs[i].copy_(torch.stack(list(rg)))
+        losses[i] = loss_from_sums(icnf, mode, sums)
+        return dict(icnf.last_stats), None             # (inference keeps no step trace: None for a member that was run again)
+
+    _finish(icnf, info, steps, t1, rerun)
     icnf.last_stats = info["stats"][0]
     return logpx, (regs[:, 0], regs[:, 1], regs[:, 2]), info
 
@@ -422,13 +443,14 @@ def _check_sampling_inputs(icnf: ICNF, mode, ps, n, z0, eps, t0, who, single):
     return m, M, n, n_in, t0
 
 
-def _sampling_draws(icnf: ICNF, mode, train, M, n, n_in, dev, z0, eps, t0):
+def _sampling_draws(icnf: ICNF, mode, train, M, n, n_in, dev, z0, eps, t0, steer=True):
     """The members' base samples and probes ([M][n][n_in] on ``dev``) and start times (None: ``tspan[1]`` for all), given or
-    drawn in the order ``generate_many`` documents."""
+    drawn in the order ``generate_many`` documents.  ``steer=False``: no steer variate is drawn (the path calls, which are
+    this draw with one member)."""
     import torch
     zr = _rows(z0) if z0 is not None else None
     er = _rows(eps) if eps is not None else None
-    steer = t0 is None and icnf.STEER and train
+    steer = steer and train and t0 is None and icnf.STEER      # (given start times and TestMode never steer)
     if isinstance(icnf.rng, HIPRNG):
         if zr is None:
             zr = icnf.rng.normal(n_in * M * n, dev.index if dev.index is not None else icnf.device).view(M, n, n_in)
@@ -454,6 +476,24 @@ def _sampling_draws(icnf: ICNF, mode, train, M, n, n_in, dev, z0, eps, t0):
     return zr, er, t0
 
 
+def _settle_sampling(icnf: ICNF, mode, ps, n, z0, eps, t0, who, single, capacity_fn=None, cot_pair=None):
+    """``_settle_density`` for the sampling direction, in the same order: ``_check_sampling_inputs`` and ``cot_pair(M, n)``
+    (the call's cotangent tensors); the handle; the device check; the capacity (None: not asked); ``_sampling_draws``.
+    Returns a namespace: ``m, M, n, n_in, train, cot, cap, dev, stream, pr, zr, er, t0``."""
+    import torch
+    m, M, n, n_in, t0 = _check_sampling_inputs(icnf, mode, ps, n, z0, eps, t0, who, single)
+    cot = cot_pair(M, n) if cot_pair is not None else ()
+    h = icnf.handle() if capacity_fn is not None else None
+    if not (ps.is_cuda and all(a is None or a.is_cuda for a in (z0, eps, *cot))):
+        raise ValueError(f"{who}: torch tensors must live on the GPU")
+    cap = _device_capacity(who, capacity_fn, h, m, n) if capacity_fn is not None else None
+    train, dev = m == _lib.MODE_TRAIN, ps.device
+    pr = ps.detach().to(torch.float32).contiguous()
+    zr, er, t0 = _sampling_draws(icnf, mode, train, M, n, n_in, dev, z0, eps, t0)
+    return SimpleNamespace(m=m, M=M, n=n, n_in=n_in, train=train, cot=cot, cap=cap, dev=dev, pr=pr, zr=zr, er=er, t0=t0,
+                           stream=_stream(_Buf(pr, pr.shape[1], M, torch)))
+
+
 def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, t0=None, with_logp=False, with_steps=False):
     """``generate`` of M members in one launch (cnf_generate_many): ``ps`` (M, n_params) on the device, ``z0`` and ``eps``
     (M, n_in, n) device tensors or drawn as ``generate_prob`` draws them -- on a host generator member by member: the member's
@@ -466,43 +506,30 @@ def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, 
     the members' step attempts are read with ``ensemble_eval_steps`` (``info["steps"]``).  Failures and refusals as
     ``inference_many``."""
     import torch
-    who = "generate_many"
-    m, M, n, n_in, t0 = _check_sampling_inputs(icnf, mode, ps, n, z0, eps, t0, who, "generate")
+    s = _settle_sampling(icnf, mode, ps, n, z0, eps, t0, "generate_many", "generate", "cnf_ensemble_eval_capacity")
     l, h = _lib.lib(), icnf.handle()
-    if not (ps.is_cuda and (z0 is None or z0.is_cuda) and (eps is None or eps.is_cuda)):
-        raise ValueError(f"{who}: torch tensors must live on the GPU")
-    cap = _device_capacity(who, "cnf_ensemble_eval_capacity", h, m, n)
-    train = m == _lib.MODE_TRAIN
-    dev = ps.device
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    pr = ps.detach().to(torch.float32).contiguous()
-    zr, er, t0 = _sampling_draws(icnf, mode, train, M, n, n_in, dev, z0, eps, t0)
+    m, M, n, dev, pr, zr, er, t0 = s.m, s.M, s.n, s.dev, s.pr, s.zr, s.er, s.t0
     opts = _solve_opts(icnf, (icnf.tspan[1], icnf.tspan[0]))              # reverse(tspan)
     xo = torch.empty((M, n, icnf.nvars), dtype=torch.float32, device=dev)
     lq = torch.empty((M, n), dtype=torch.float32, device=dev) if with_logp else None
     tc = _trace_cap(opts, with_steps)
-    stats, status, calls, steps = _chunked_calls(icnf, M, cap, lambda lo, k, status, stats: l.cnf_generate_many(
-        h, m, k, pr[lo].data_ptr(), zr[lo].data_ptr(), er[lo].data_ptr() if train else None, n, C.byref(opts),
+    info, steps = _launch(icnf, s, lambda lo, k, status, stats: l.cnf_generate_many(
+        h, m, k, pr[lo].data_ptr(), zr[lo].data_ptr(), er[lo].data_ptr() if s.train else None, n, C.byref(opts),
         t0[lo:].ctypes.data if t0 is not None else None, xo[lo].data_ptr(), lq[lo].data_ptr() if with_logp else None,
-        status, stats, tc, stream), ensemble_eval_steps if with_steps else None)
-    info = _info(icnf, stats, status, calls, "t0", t0, z0=zr.permute(0, 2, 1), eps=er.permute(0, 2, 1))
-    icnf.last_ensemble_info = info
-    _raise_failed(status)
-    gave_up = [i for i in range(M) if status[i] != _lib.OK]
-    if gave_up:
-        with _one_member_at_a_time(icnf, t0) as member:
-            for i in gave_up:
-                member(i)
-                r = generate(icnf, mode, pr[i], st, n, z0=zr[i].t(), eps=er[i].t(), with_logp=with_logp)
-                xs_i = r[0] if with_logp else r
-                xo[i].copy_(torch.as_tensor(xs_i, device=dev)[: icnf.nvars].t())
-                if with_logp:
-                    lq[i].copy_(torch.as_tensor(r[1], device=dev))
-                status[i] = _lib.OK
-        info["rerun"] = gave_up
-    if with_steps:
-        info["steps"] = steps
-    xs = xo.permute(0, 2, 1)
+        status, stats, tc, s.stream), ensemble_eval_steps if with_steps else None, "t0", t0,
+        z0=zr.permute(0, 2, 1), eps=er.permute(0, 2, 1))
+    icnf.last_ensemble_info = info                         # (published before a failed member raises: it says which)
+
+    def rerun(i):
+        r = generate(icnf, mode, pr[i], st, n, z0=zr[i].t(), eps=er[i].t(), with_logp=with_logp)
+        xs_i = r[0] if with_logp else r
+        xo[i].copy_(torch.as_tensor(xs_i, device=dev)[: icnf.nvars].t())
+        if with_logp:
+            lq[i].copy_(torch.as_tensor(r[1], device=dev))
+        return None, None                              # (generate reports no statistics: the launch's stay)
+
+    _finish(icnf, info, steps, t0, rerun)
+    xs = xo.permute(0, 2, 1)                               # (generate does not set icnf.last_stats; nor does this)
     return (xs, lq) if with_logp else xs
 
 
@@ -512,19 +539,14 @@ def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, 
 def ensemble_vjp_capacity(icnf: ICNF, mode, B: int) -> int:
     """The largest M one ``inference_vjp_many`` launch takes for this model, mode and batch size (cnf_ensemble_vjp_capacity);
     0: no ensemble form."""
-    m = _mode_id(mode)
-    if _refusal(icnf) is not None:
-        return 0
-    return int(_lib.lib().cnf_ensemble_vjp_capacity(icnf.handle(), m, int(B)))
+    return _capacity(icnf, mode, "cnf_ensemble_vjp_capacity", B)
 
 
 def _cot_many(cot, M, B):
     """``(g_logpx, (g_E, g_n, g_A))``, each an (M, B) tensor or None (the convention of ``inference_pullback``; a bare None for
     the triple: no cotangent on the regularisers) -> the four rows; ``ValueError`` for anything else.  Host logic only."""
-    if not isinstance(cot, (tuple, list)) or len(cot) != 2 or not (cot[1] is None or isinstance(cot[1], (tuple, list))):
-        raise ValueError("cot must be (g_logpx, (g_E, g_n, g_A))")
-    rows = [cot[0]] + list(cot[1] if cot[1] is not None else (None, None, None))
-    if len(rows) != 4:
+    rows = _cot_rows(cot)
+    if rows is None:                                       # (a bare tensor: the single-model calls' other form)
         raise ValueError("cot must be (g_logpx, (g_E, g_n, g_A))")
     for name, r in zip(("g_logpx", "g_E", "g_n", "g_A"), rows):
         if r is None:
@@ -549,68 +571,45 @@ def inference_vjp_many(icnf: ICNF, mode, xs, ps, st, cot, eps=None, t1=None, wit
     gave up is run again with ``inference_record`` + ``inference_pullback`` (``info["rerun"]``).  Failures and refusals as
     ``loss_and_grad_many``."""
     import torch
-    who = "inference_vjp_many"
-    if _is_torch(xs) and _is_torch(ps) and xs.dim() == 2 and ps.dim() == 2 and _refusal(icnf) is None:
-        xs = xs.unsqueeze(0).expand(ps.shape[0], *xs.shape)                # shared data: every member reads its own copy
-    m, M, B, n_in, t1 = _check_inputs(icnf, mode, xs, ps, eps, t1, who, "inference_record and inference_pullback")
-    rows = _cot_many(cot, M, B)
+    s = _settle_density(icnf, mode, xs, ps, eps, t1, "inference_vjp_many", "inference_record and inference_pullback",
+                        "cnf_ensemble_vjp_capacity", cot_rows=lambda M, B: _cot_many(cot, M, B))
     l, h = _lib.lib(), icnf.handle()
-    if not (xs.is_cuda and ps.is_cuda and (eps is None or eps.is_cuda) and all(r is None or r.is_cuda for r in rows)):
-        raise ValueError(f"{who}: torch tensors must live on the GPU")
-    cap = _device_capacity(who, "cnf_ensemble_vjp_capacity", h, m, B)
-    train = m == _lib.MODE_TRAIN
-    dev = xs.device
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    xr = _rows(xs)
-    pr = ps.detach().to(torch.float32).contiguous()
-    er, t1 = _probes_and_ends(icnf, mode, train, M, B, n_in, xr, eps, t1)
+    m, M, B, dev, xr, pr, er, t1 = s.m, s.M, s.B, s.dev, s.xr, s.pr, s.er, s.t1
     cm = torch.zeros((M, 4, B), dtype=torch.float32, device=dev)
-    for i, r in enumerate(rows):
+    for i, r in enumerate(s.cot):
         if r is not None:
             cm[:, i].copy_(r.detach())
     opts = _solve_opts(icnf, icnf.tspan)
-    n_params = pr.shape[1]
     logpx, regs = torch.empty((M, B), dtype=torch.float32, device=dev), torch.empty((M, 3, B), dtype=torch.float32, device=dev)
-    grads = torch.empty((M, n_params), dtype=torch.float32, device=dev)
-    gz = torch.empty((M, B, n_in), dtype=torch.float32, device=dev) if with_x else None
-    stats, status, calls, steps = _chunked_calls(icnf, M, cap, lambda lo, n, status, stats: l.cnf_inference_vjp_many(
+    grads = torch.empty((M, pr.shape[1]), dtype=torch.float32, device=dev)
+    gz = torch.empty((M, B, s.n_in), dtype=torch.float32, device=dev) if with_x else None
+    info, steps = _launch(icnf, s, lambda lo, n, status, stats: l.cnf_inference_vjp_many(
         h, m, n, pr[lo].data_ptr(), xr[lo].data_ptr(), er[lo].data_ptr() if er is not None else None, B, C.byref(opts),
         t1[lo:].ctypes.data if t1 is not None else None, cm[lo].data_ptr(), logpx[lo].data_ptr(), regs[lo].data_ptr(),
-        grads[lo].data_ptr(), gz[lo].data_ptr() if with_x else None, status, stats, stream),
-        ensemble_steps if with_steps else None)
+        grads[lo].data_ptr(), gz[lo].data_ptr() if with_x else None, status, stats, s.stream),
+        ensemble_steps if with_steps else None, "t1", t1, eps=er.permute(0, 2, 1) if er is not None else None)
     icnf._record = None                                    # (the call ended whatever was recorded on the handle)
-    info = _info(icnf, stats, status, calls, "t1", t1, eps=er.permute(0, 2, 1) if er is not None else None)
-    _raise_failed(status)
     gx = gz[:, :, :icnf.nvars].permute(0, 2, 1).contiguous() if with_x else None
-    gave_up = [i for i in range(M) if status[i] != _lib.OK]
-    if gave_up:
+
+    def rerun(i):
         from .vjp import inference_pullback, inference_record
-        with _one_member_at_a_time(icnf, t1) as member:
-            for i in gave_up:
-                member(i)
-                lp, rg = inference_record(icnf, mode, xr[i].t(), pr[i], st, eps=er[i].t() if train else None, tspan=icnf.tspan)
-                res = inference_pullback(icnf, cm[i], with_x=with_x)
-                logpx[i].copy_(lp)
-                regs[i].copy_(torch.stack(list(rg)))
-                grads[i].copy_(res[0] if with_x else res)
-                if with_x:
-                    gx[i].copy_(res[1])
-                status[i] = _lib.OK
-                info["stats"][i] = dict(icnf.last_stats)
-                if with_steps:
-                    steps[i] = np.array(icnf.last_steps, dtype=np.float32)
-        icnf._record = None                                # (the members' records are not the caller's)
-        info["rerun"] = gave_up
-    if with_steps:
-        info["steps"] = steps
+        lp, rg = inference_record(icnf, mode, xr[i].t(), pr[i], st, eps=er[i].t() if s.train else None, tspan=icnf.tspan)
+        res = inference_pullback(icnf, cm[i], with_x=with_x)
+        logpx[i].copy_(lp)
+        regs[i].copy_(torch.stack(list(rg)))
+        grads[i].copy_(res[0] if with_x else res)
+        if with_x:
+            gx[i].copy_(res[1])
+        return _stats_and_steps(icnf)
+
+    _finish(icnf, info, steps, t1, rerun)
+    icnf._record = None                                    # (the members' records are not the caller's)
     icnf.last_stats = info["stats"][0]
     out = (logpx, (regs[:, 0], regs[:, 1], regs[:, 2]), grads)
     return out + ((gx, info) if with_x else (info,))
 
 
-_FUNCTION_MANY = None
-
-
+@functools.lru_cache(maxsize=None)
 def _autograd_function_many():
     import torch
 
@@ -648,23 +647,13 @@ def differentiable_inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t
     graph.  The backward launch solves again: its gradient is the exact discrete adjoint of the steps IT accepts (the solve is
     deterministic, so they are the forward's for the same inputs; DESIGN 4.4 says how its ``logpx`` compares with the
     forward's -- ``icnf.last_backward_logpx`` keeps it)."""
-    global _FUNCTION_MANY
-    import torch
     if not (_is_torch(xs) and _is_torch(ps)):
         raise NotImplementedError("differentiable_inference_many takes device tensors")
     # the probes and the steered end times are settled here, once (inference_many's order: the probes, then the end times), so
     # that forward and backward are given the very same ones
-    xe = xs.detach()
-    if xe.dim() == 2 and ps.dim() == 2 and _refusal(icnf) is None:
-        xe = xe.unsqueeze(0).expand(ps.shape[0], *xe.shape)
-    m, M, B, n_in, t1 = _check_inputs(icnf, mode, xe, ps, eps, t1, "differentiable_inference_many", "differentiable_inference")
-    if not (xs.is_cuda and ps.is_cuda and (eps is None or eps.is_cuda)):
-        raise ValueError("differentiable_inference_many: torch tensors must live on the GPU")
-    er, t1 = _probes_and_ends(icnf, mode, m == _lib.MODE_TRAIN, M, B, n_in, _rows(xe), eps, t1)
-    eps = er.permute(0, 2, 1) if er is not None else None
-    if _FUNCTION_MANY is None:
-        _FUNCTION_MANY = _autograd_function_many()
-    logpx, E, n, A = _FUNCTION_MANY.apply(icnf, mode, xs, ps, eps, t1)
+    s = _settle_density(icnf, mode, xs.detach(), ps, eps, t1, "differentiable_inference_many", "differentiable_inference")
+    eps = s.er.permute(0, 2, 1) if s.er is not None else None
+    logpx, E, n, A = _autograd_function_many().apply(icnf, mode, xs, ps, eps, s.t1)
     return logpx, (E, n, A)
 
 
@@ -674,18 +663,13 @@ def differentiable_inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t
 def ensemble_generate_vjp_capacity(icnf: ICNF, mode, n: int) -> int:
     """The largest M one ``generate_vjp_many`` launch takes for this model, mode and number of samples per member
     (cnf_ensemble_generate_vjp_capacity); 0: no ensemble form."""
-    m = _mode_id(mode)
-    if _refusal(icnf) is not None:
-        return 0
-    return int(_lib.lib().cnf_ensemble_generate_vjp_capacity(icnf.handle(), m, int(n)))
+    return _capacity(icnf, mode, "cnf_ensemble_generate_vjp_capacity", n)
 
 
 def _cot_pair_many(icnf: ICNF, cot, M, n):
     """``(g_x, g_logq)`` -> ``(g_x, g_logq)`` checked: ``g_x`` an (M, nvars, n) or (M, n_in, n) tensor or None, ``g_logq`` an
     (M, n) tensor or None, not both None; ``ValueError`` for anything else.  Host logic only."""
-    if not isinstance(cot, (tuple, list)) or len(cot) != 2:
-        raise ValueError("cot must be (g_x, g_logq)")
-    gx, gl = cot
+    gx, gl = _cot_two(cot)
     n_in = icnf.nvars + n_augment_input(icnf)
     if gx is None and gl is None:
         raise ValueError("cot: g_x and g_logq are both None")
@@ -717,18 +701,11 @@ def generate_vjp_many(icnf: ICNF, mode, ps, st, n, cot, z0=None, eps=None, t0=No
     launch gave up is run again with ``generate_record`` + ``generate_pullback`` (``info["rerun"]``).  Failures and refusals as
     ``generate_many``: ``NotImplementedError`` before anything is drawn."""
     import torch
-    who = "generate_vjp_many"
-    m, M, n, n_in, t0 = _check_sampling_inputs(icnf, mode, ps, n, z0, eps, t0, who, "generate_record and generate_pullback")
-    gx, gl = _cot_pair_many(icnf, cot, M, n)
+    s = _settle_sampling(icnf, mode, ps, n, z0, eps, t0, "generate_vjp_many", "generate_record and generate_pullback",
+                         "cnf_ensemble_generate_vjp_capacity", cot_pair=lambda M, n: _cot_pair_many(icnf, cot, M, n))
     l, h = _lib.lib(), icnf.handle()
-    if not (ps.is_cuda and all(a is None or a.is_cuda for a in (z0, eps, gx, gl))):
-        raise ValueError(f"{who}: torch tensors must live on the GPU")
-    cap = _device_capacity(who, "cnf_ensemble_generate_vjp_capacity", h, m, n)
-    train = m == _lib.MODE_TRAIN
-    dev = ps.device
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    pr = ps.detach().to(torch.float32).contiguous()
-    zr, er, t0 = _sampling_draws(icnf, mode, train, M, n, n_in, dev, z0, eps, t0)
+    m, M, n, n_in, dev, pr, zr, er, t0 = s.m, s.M, s.n, s.n_in, s.dev, s.pr, s.zr, s.er, s.t0
+    gx, gl = s.cot
     cz = cl = None
     if gx is not None:                                     # [M][n][n_in], zeros on the rows that were not given
         cz = torch.zeros((M, n, n_in), dtype=torch.float32, device=dev)
@@ -736,50 +713,38 @@ def generate_vjp_many(icnf: ICNF, mode, ps, st, n, cot, z0=None, eps=None, t0=No
     if gl is not None:
         cl = gl.detach().to(torch.float32).contiguous()
     opts = _solve_opts(icnf, (icnf.tspan[1], icnf.tspan[0]))              # reverse(tspan)
-    n_params = pr.shape[1]
     xo = torch.empty((M, n, icnf.nvars), dtype=torch.float32, device=dev)
     lq = torch.empty((M, n), dtype=torch.float32, device=dev)
-    grads = torch.empty((M, n_params), dtype=torch.float32, device=dev)
+    grads = torch.empty((M, pr.shape[1]), dtype=torch.float32, device=dev)
     gz = torch.empty((M, n, n_in), dtype=torch.float32, device=dev) if with_z0 else None
-    stats, status, calls, steps = _chunked_calls(icnf, M, cap, lambda lo, k, status, stats: l.cnf_generate_vjp_many(
-        h, m, k, pr[lo].data_ptr(), zr[lo].data_ptr(), er[lo].data_ptr() if train else None, n, C.byref(opts),
+    info, steps = _launch(icnf, s, lambda lo, k, status, stats: l.cnf_generate_vjp_many(
+        h, m, k, pr[lo].data_ptr(), zr[lo].data_ptr(), er[lo].data_ptr() if s.train else None, n, C.byref(opts),
         t0[lo:].ctypes.data if t0 is not None else None, cz[lo].data_ptr() if cz is not None else None,
         cl[lo].data_ptr() if cl is not None else None, xo[lo].data_ptr(), lq[lo].data_ptr(), grads[lo].data_ptr(),
-        gz[lo].data_ptr() if with_z0 else None, status, stats, stream), ensemble_steps if with_steps else None)
+        gz[lo].data_ptr() if with_z0 else None, status, stats, s.stream), ensemble_steps if with_steps else None, "t0", t0,
+        z0=zr.permute(0, 2, 1), eps=er.permute(0, 2, 1))
     icnf._record = None                                    # (the call ended whatever was recorded on the handle)
-    info = _info(icnf, stats, status, calls, "t0", t0, z0=zr.permute(0, 2, 1), eps=er.permute(0, 2, 1))
     icnf.last_ensemble_info = info
-    _raise_failed(status)
-    gave_up = [i for i in range(M) if status[i] != _lib.OK]
-    if gave_up:
+
+    def rerun(i):
         from .gen_vjp import generate_pullback, generate_record
-        with _one_member_at_a_time(icnf, t0) as member:
-            for i in gave_up:
-                member(i)
-                x_i, lq_i = generate_record(icnf, mode, pr[i], st, n, z0=zr[i].t(), eps=er[i].t(), tspan=icnf.tspan)
-                res = generate_pullback(icnf, (cz[i].t() if cz is not None else None, cl[i] if cl is not None else None),
-                                        with_z0=with_z0)
-                xo[i].copy_(x_i.t())
-                lq[i].copy_(lq_i)
-                grads[i].copy_(res[0] if with_z0 else res)
-                if with_z0:
-                    gz[i].copy_(res[1].t())
-                status[i] = _lib.OK
-                info["stats"][i] = dict(icnf.last_stats)
-                if with_steps:
-                    steps[i] = np.array(icnf.last_steps, dtype=np.float32)
-        icnf._record = None                                # (the members' records are not the caller's)
-        info["rerun"] = gave_up
-    if with_steps:
-        info["steps"] = steps
+        x_i, lq_i = generate_record(icnf, mode, pr[i], st, n, z0=zr[i].t(), eps=er[i].t(), tspan=icnf.tspan)
+        res = generate_pullback(icnf, (cz[i].t() if cz is not None else None, cl[i] if cl is not None else None), with_z0=with_z0)
+        xo[i].copy_(x_i.t())
+        lq[i].copy_(lq_i)
+        grads[i].copy_(res[0] if with_z0 else res)
+        if with_z0:
+            gz[i].copy_(res[1].t())
+        return _stats_and_steps(icnf)
+
+    _finish(icnf, info, steps, t0, rerun)
+    icnf._record = None                                    # (the members' records are not the caller's)
     icnf.last_stats = info["stats"][0]
     out = (xo.permute(0, 2, 1), lq, grads)
     return out + ((gz.permute(0, 2, 1), info) if with_z0 else (info,))
 
 
-_FUNCTION_GENERATE_MANY = None
-
-
+@functools.lru_cache(maxsize=None)
 def _autograd_function_generate_many():
     import torch
 
@@ -816,18 +781,11 @@ def differentiable_generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=N
     autograd graph.  The backward launch solves again: its gradient is the exact discrete adjoint of the steps IT accepts (the
     solve is deterministic, so they are the forward's for the same inputs; DESIGN 4.4 says how its ``xs`` / ``logq`` compare with
     the forward's -- ``icnf.last_backward_logq`` and ``icnf.last_backward_xs`` keep them)."""
-    global _FUNCTION_GENERATE_MANY
-    who = "differentiable_generate_many"
-    m, M, n, n_in, t0 = _check_sampling_inputs(icnf, mode, ps, n, z0, eps, t0, who, "differentiable_generate")
-    if not (ps.is_cuda and (z0 is None or z0.is_cuda) and (eps is None or eps.is_cuda)):
-        raise ValueError(f"{who}: torch tensors must live on the GPU")
-    zr, er, t0 = _sampling_draws(icnf, mode, m == _lib.MODE_TRAIN, M, n, n_in, ps.device,
-                                 z0.detach() if z0 is not None else None, eps, t0)
+    s = _settle_sampling(icnf, mode, ps, n, z0.detach() if _is_torch(z0) else z0, eps, t0, "differentiable_generate_many",
+                         "differentiable_generate")
     if not (z0 is not None and z0.requires_grad):          # (a z0 that asks for a gradient stays the caller's tensor)
-        z0 = zr.permute(0, 2, 1)
-    if _FUNCTION_GENERATE_MANY is None:
-        _FUNCTION_GENERATE_MANY = _autograd_function_generate_many()
-    return _FUNCTION_GENERATE_MANY.apply(icnf, mode, ps, z0, er.permute(0, 2, 1), t0)
+        z0 = s.zr.permute(0, 2, 1)
+    return _autograd_function_generate_many().apply(icnf, mode, ps, z0, s.er.permute(0, 2, 1), s.t0)
 
 
 def reverse_kl_many(icnf: ICNF, mode, ps, st, n, target_logpdf, **kw):

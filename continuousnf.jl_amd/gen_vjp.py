@@ -23,12 +23,14 @@ the fixed-``z0`` partial only.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
 from . import _lib
-from .base_icnf import (ICNF, _generate_inputs, _is_torch, _mode_id, _solve_opts, base_logpdf_pullback, base_sample_pullback,
-                        grad_result, grad_steps, grad_ys, n_augment_input, raise_if_no_gpu, set_grad_ys, steer_tspan, to_device)
+from .base_icnf import (ICNF, _generate_inputs, _is_torch, _mode_id, _solve_opts, _stream, base_logpdf_pullback,
+                        base_sample_pullback, grad_result, grad_steps, grad_ys, n_augment_input, raise_if_no_gpu, set_grad_ys,
+                        steer_tspan, to_device)
 from .distributions import learnable
 from .vjp import _base_grads, _base_key, _base_tensors, _pull_recorded
 
@@ -63,10 +65,9 @@ def generate_record(icnf: ICNF, mode, ps, st=None, n: int = 1, *, ys=None, z0=No
     opts = _solve_opts(icnf, (t1, t0))                     # reverse(tspan)
     stats = _lib.cnf_solve_stats()
     l, h = _lib.lib(), icnf.handle()
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     icnf._record = None
     _lib.check(l.cnf_generate_record(h, m, zb.ptr, eb.ptr if m == _lib.MODE_TRAIN else None, n, C.byref(opts), z.data_ptr(),
-                                     logq.data_ptr(), C.byref(stats), stream), h)
+                                     logq.data_ptr(), C.byref(stats), _stream(zb)), h)
     icnf.last_stats = stats.as_dict()
     grad_steps(icnf)
     zfull = z.view(n, n_in).t()
@@ -79,14 +80,21 @@ def generate_record(icnf: ICNF, mode, ps, st=None, n: int = 1, *, ys=None, z0=No
     return xs, logq
 
 
+def _cot_two(cot):
+    """``(g_x, g_logq)`` -> the two entries as given (either may be None); ``ValueError`` for anything that is not such a pair.
+    The one check of this convention: what the entries may be is the caller's (host arrays here, device tensors only in
+    ``ensemble._cot_pair_many``)."""
+    if not isinstance(cot, (tuple, list)) or len(cot) != 2:
+        raise ValueError("cot must be (g_x, g_logq)")
+    return cot[0], cot[1]
+
+
 def _cot_pair(icnf: ICNF, cot, dev):
     """(g_x, g_logq) -> (cot_z [B][n_in] or None, cot_logq [B] or None, B); rows of g_x beyond those given are zero."""
     import torch
-    if not isinstance(cot, (tuple, list)) or len(cot) != 2:
-        raise ValueError("cot must be (g_x, g_logq)")
+    gx, gl = _cot_two(cot)
     n_in = icnf.nvars + n_augment_input(icnf)
     t = lambda a: (a if _is_torch(a) else torch.from_numpy(np.asarray(a, dtype=np.float32))).detach().to(device=dev, dtype=torch.float32)
-    gx, gl = cot
     cz = cl = None
     sizes = set()
     if gx is not None:
@@ -141,6 +149,7 @@ def generate_pullback(icnf: ICNF, cot, with_z0=False, with_ys=False, with_base=F
     return grad_result((grad,), host, (with_z0, gz0), (with_ys, gy), (with_base, gb))
 
 
+@functools.lru_cache(maxsize=None)
 def _autograd_function():
     import torch
 
@@ -192,9 +201,6 @@ def _autograd_function():
     return _Generate
 
 
-_FUNCTION = None
-
-
 def differentiable_generate(icnf: ICNF, mode, ps, st=None, n: int = 1, *, ys=None, z0=None, eps=None):
     """``generate`` with ``logq`` as a differentiable function of ``ps``, of ``z0`` when it requires grad (``z0 = g(context)``:
     amortised inference), for a conditional model of ``ys`` when it requires grad, and of the ``mean`` / scale tensors of a
@@ -203,7 +209,6 @@ def differentiable_generate(icnf: ICNF, mode, ps, st=None, n: int = 1, *, ys=Non
     autograd graph (device tensors).  ``z0`` and ``eps`` are drawn as ``generate`` draws them when not given.  If another call on the model displaced the record before
     ``backward``, the solve is recorded again from the saved inputs (same outputs bit for bit) and then pulled back; the values
     of a ``LearnableNormal`` base are not saved, so ``RuntimeError`` if they changed in between."""
-    global _FUNCTION
     import torch
     m = _mode_id(mode)
     dev = _device(icnf)
@@ -222,9 +227,7 @@ def differentiable_generate(icnf: ICNF, mode, ps, st=None, n: int = 1, *, ys=Non
     if not (_is_torch(z0) and z0.requires_grad):
         z0 = to_device(icnf, zb).view()
     eps = to_device(icnf, eb).view() if m == _lib.MODE_TRAIN else None
-    if _FUNCTION is None:
-        _FUNCTION = _autograd_function()
-    return _FUNCTION.apply(icnf, mode, ps, ys, z0, eps, tspan, normals, bmean, bscale)
+    return _autograd_function().apply(icnf, mode, ps, ys, z0, eps, tspan, normals, bmean, bscale)
 
 
 def reverse_kl(icnf: ICNF, mode, ps, st, n, target_logpdf, **kw):

@@ -17,8 +17,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .base_icnf import (ICNF, ODEProblem, _Buf, _mode_id, _post, _solve_opts, generate_prob, inference_prob, n_augment_input,
-                        to_device)
+from .base_icnf import (ICNF, ODEProblem, _Buf, _mode_id, _post, _solve_opts, device_and_stream, generate_prob, inference_prob,
+                        n_augment_input, to_device)
 
 
 def check_saveat(saveat, tspan):
@@ -43,16 +43,22 @@ def check_saveat(saveat, tspan):
     return np.ascontiguousarray(sv)
 
 
-def path_steps(icnf: ICNF):
-    """``(t_n, h_n)`` of the accepted steps of the last ``solve_path`` on this model (cnf_path_steps): two float32 vectors, or
-    ``None`` when there is none."""
-    l, h = _lib.lib(), icnf.handle()
-    n = l.cnf_path_steps(h, None, None, 0)
+def _accepted_steps(icnf: ICNF, steps_fn):
+    """``(t_n, h_n)`` of the accepted steps ``steps_fn`` of the C ABI keeps for this model: two float32 vectors, or ``None``
+    when there is none."""
+    read, h = getattr(_lib.lib(), steps_fn), icnf.handle()
+    n = read(h, None, None, 0)
     if n < 0:
         return None
     t, hs = np.empty(max(n, 1), dtype=np.float32), np.empty(max(n, 1), dtype=np.float32)
-    l.cnf_path_steps(h, t.ctypes.data, hs.ctypes.data, n)
+    read(h, t.ctypes.data, hs.ctypes.data, n)
     return t[:n], hs[:n]
+
+
+def path_steps(icnf: ICNF):
+    """``(t_n, h_n)`` of the accepted steps of the last ``solve_path`` on this model (cnf_path_steps): two float32 vectors, or
+    ``None`` when there is none."""
+    return _accepted_steps(icnf, "cnf_path_steps")
 
 
 def solve_path(icnf: ICNF, prob: ODEProblem, saveat):
@@ -67,12 +73,11 @@ def solve_path(icnf: ICNF, prob: ODEProblem, saveat):
     host = prob.u0.torch is None
     u0, eb = to_device(icnf, prob.u0), to_device(icnf, prob.eps)
     D, B, K = u0.rows, u0.B, int(sv.size)
-    dev = u0.arr.device
+    dev, stream = device_and_stream(icnf, u0)
     out = torch.empty(D * B, dtype=torch.float32, device=dev)
     pth = torch.empty(K * B * D, dtype=torch.float32, device=dev)
     opts = _solve_opts(icnf, prob.tspan)
     stats = _lib.cnf_solve_stats()
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(l.cnf_solve_path(h, m, u0.ptr, eb.ptr if eb is not None else None, out.data_ptr(), B, C.byref(opts),
                                 sv.ctypes.data, K, pth.data_ptr(), C.byref(stats), stream), h)
     prob.stats = stats.as_dict()

@@ -12,35 +12,26 @@ do not.  There is no streamed route behind it: a solve of more accepted steps th
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
 from . import _lib
-from .base_icnf import ICNF, _Buf, _is_torch, _mode_id, _solve_opts, draw_eps, n_augment_input
-from .ensemble import _refusal
-from .path import check_saveat, generate_path, inference_path
-from .rng import HIPRNG
+from .base_icnf import ICNF, _Buf, _is_torch, _mode_id, _solve_opts, _stream, n_augment_input
+from .ensemble import _capacity, _probes_and_ends, _refusal, _sampling_draws
+from .path import _accepted_steps, _path_rows, check_saveat, generate_path, inference_path
 
 
 def path_vjp_max_batch(icnf: ICNF, mode) -> int:
     """The largest batch one ``inference_path_vjp`` / ``generate_path_vjp`` launch takes for this model and mode
     (cnf_path_vjp_max_batch); 0: no such form."""
-    m = _mode_id(mode)
-    if _refusal(icnf) is not None:
-        return 0
-    return int(_lib.lib().cnf_path_vjp_max_batch(icnf.handle(), m))
+    return _capacity(icnf, mode, "cnf_path_vjp_max_batch")
 
 
 def path_vjp_steps(icnf: ICNF):
     """``(t_n, h_n)`` of the accepted steps of the last ``*_path_vjp`` call on this model (cnf_path_vjp_steps): two float32
     vectors, or ``None`` when there is none."""
-    l, h = _lib.lib(), icnf.handle()
-    n = l.cnf_path_vjp_steps(h, None, None, 0)
-    if n < 0:
-        return None
-    t, hs = np.empty(max(n, 1), dtype=np.float32), np.empty(max(n, 1), dtype=np.float32)
-    l.cnf_path_vjp_steps(h, t.ctypes.data, hs.ctypes.data, n)
-    return t[:n], hs[:n]
+    return _accepted_steps(icnf, "cnf_path_vjp_steps")
 
 
 def _refuse(icnf: ICNF, who, single, *tensors):
@@ -92,11 +83,12 @@ def _path_cot(icnf: ICNF, who, path_cot, names, K, B, train, dev):
     return pc
 
 
-def _rows_of(pv, n_in, train, sv, steps):
-    rows = {"t": sv, "z": pv[:, :n_in, :], "dlogp": pv[:, n_in, :], "steps": steps}
-    if train:
-        rows["E"], rows["n"] = pv[:, n_in + 1, :], pv[:, n_in + 2, :]
-    return rows
+def _probes(icnf: ICNF, mode, train, xr, eps):
+    """The probes of a single-model call on the data ``xr`` ([B][nvars]), as [B][n_in] (None in TestMode): ``eps`` (n_in, B), or
+    the ensemble calls' draw with one member -- and no steer variate: the path calls integrate ``icnf.tspan``."""
+    B, n_in = xr.shape[0], icnf.nvars + n_augment_input(icnf)
+    er, _ = _probes_and_ends(icnf, mode, train, 1, B, n_in, xr[None], eps[None] if eps is not None else None, None, steer=False)
+    return er[0] if er is not None else None
 
 
 def inference_path_vjp(icnf: ICNF, mode, xs, ps, st=None, *, saveat, cot=None, path_cot=None, eps=None, with_x=False):
@@ -141,13 +133,9 @@ def inference_path_vjp(icnf: ICNF, mode, xs, ps, st=None, *, saveat, cot=None, p
     _check_batch(icnf, who, m, B)
     xr = xs.detach().to(torch.float32).t().contiguous()
     pr = ps.detach().to(torch.float32).contiguous().reshape(-1)
-    er = None
-    if train:
-        er = eps.detach().to(torch.float32).t().contiguous() if eps is not None else \
-            draw_eps(icnf, _Buf(xr.view(-1), icnf.nvars, B, torch), B).arr.view(B, n_in) if isinstance(icnf.rng, HIPRNG) else \
-            torch.from_numpy(draw_eps(icnf, _Buf(None, icnf.nvars, B, None), B).arr.reshape(B, n_in)).to(dev)
+    er = _probes(icnf, mode, train, xr, eps)
     opts = _solve_opts(icnf, icnf.tspan)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = _stream(_Buf(xr.view(-1), icnf.nvars, B, torch))
     logpx, regs = torch.empty(B, dtype=torch.float32, device=dev), torch.empty((3, B), dtype=torch.float32, device=dev)
     pth = torch.empty((K, B, D), dtype=torch.float32, device=dev)
     grads = torch.empty(n_params, dtype=torch.float32, device=dev)
@@ -160,7 +148,7 @@ def inference_path_vjp(icnf: ICNF, mode, xs, ps, st=None, *, saveat, cot=None, p
                                         grads.data_ptr(), gz.data_ptr() if with_x else None, C.byref(stats), stream), h)
     icnf.last_stats = stats.as_dict()
     info = {"stats": icnf.last_stats, "steps": path_vjp_steps(icnf), "eps": er.t() if er is not None else None}
-    path = _rows_of(pth.permute(0, 2, 1), n_in, train, sv, info["steps"])
+    path = _path_rows(icnf, m, pth.permute(0, 2, 1), {"t": sv, "steps": info["steps"]})
     out = (logpx, (regs[0], regs[1], regs[2]), path, grads)
     return out + ((gz[:, :icnf.nvars].t().contiguous(), info) if with_x else (info,))
 
@@ -204,13 +192,12 @@ def generate_path_vjp(icnf: ICNF, mode, ps, st=None, n: int = 1, *, saveat, cot=
     pc = _path_cot(icnf, who, path_cot, {"z": 0, "logq": n_in}, K, n, train, dev)
     l, h = _lib.lib(), icnf.handle()
     _check_batch(icnf, who, m, n)
-    from .ensemble import _sampling_draws
-    zr, er, _ = _sampling_draws(icnf, mode, False, 1, n, n_in, dev, z0.unsqueeze(0) if z0 is not None else None,
-                                eps.unsqueeze(0) if eps is not None else None, None)       # (train=False: no steer variate)
+    zr, er, _ = _sampling_draws(icnf, mode, train, 1, n, n_in, dev, z0.unsqueeze(0) if z0 is not None else None,
+                                eps.unsqueeze(0) if eps is not None else None, None, steer=False)
     zr, er = zr[0].contiguous(), er[0].contiguous()
     pr = ps.detach().to(torch.float32).contiguous().reshape(-1)
     opts = _solve_opts(icnf, (t1, t0))                     # reverse(tspan)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = _stream(_Buf(pr, n_params, 1, torch))
     xo, lq = torch.empty((n, icnf.nvars), dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
     pth = torch.empty((K, n, D), dtype=torch.float32, device=dev)
     grads = torch.empty(n_params, dtype=torch.float32, device=dev)
@@ -224,7 +211,7 @@ def generate_path_vjp(icnf: ICNF, mode, ps, st=None, n: int = 1, *, saveat, cot=
                                        gz.data_ptr() if with_z0 else None, C.byref(stats), stream), h)
     icnf.last_stats = stats.as_dict()
     info = {"stats": icnf.last_stats, "steps": path_vjp_steps(icnf), "z0": zr.t(), "eps": er.t()}
-    path = _rows_of(pth.permute(0, 2, 1), n_in, train, sv, info["steps"])
+    path = _path_rows(icnf, m, pth.permute(0, 2, 1), {"t": sv, "steps": info["steps"]})
     log2pi = np.float32(1.8378770664093453)
     path["logq"] = (-0.5 * ((zr * zr).sum(1) + n_in * log2pi))[None, :] + path["dlogp"]
     if with_z0 and pc is not None and path_cot.get("logq") is not None:
@@ -237,9 +224,7 @@ def generate_path_vjp(icnf: ICNF, mode, ps, st=None, n: int = 1, *, saveat, cot=
 # ---------------------------------------------------------------------------------------
 # autograd
 # ---------------------------------------------------------------------------------------
-_FN_INFERENCE = _FN_GENERATE = None
-
-
+@functools.lru_cache(maxsize=None)
 def _autograd_inference():
     import torch
 
@@ -282,7 +267,6 @@ def differentiable_inference_path(icnf: ICNF, mode, xs, ps, st=None, *, saveat, 
     ``inference_path_vjp`` launch with the same draws.  The backward launch solves again with the gradient form's tanh: its
     gradient is the exact discrete adjoint of the steps IT accepts, and DESIGN 4.4 says how its path compares with the forward's
     (``icnf.last_backward_path`` keeps it).  Refusals as ``inference_path_vjp``."""
-    global _FN_INFERENCE
     import torch
     who = "differentiable_inference_path"
     m = _mode_id(mode)
@@ -293,19 +277,15 @@ def differentiable_inference_path(icnf: ICNF, mode, xs, ps, st=None, *, saveat, 
     B = int(xs.shape[1])
     _check_batch(icnf, who, m, B)
     if m == _lib.MODE_TRAIN and eps is None:               # settled here, once, so that forward and backward are given the same
-        n_in = icnf.nvars + n_augment_input(icnf)
-        xr = xs.detach().to(torch.float32).t().contiguous()
-        eps = draw_eps(icnf, _Buf(xr.view(-1), icnf.nvars, B, torch), B).arr.view(B, n_in).t() if isinstance(icnf.rng, HIPRNG) else \
-            torch.from_numpy(draw_eps(icnf, _Buf(None, icnf.nvars, B, None), B).arr.reshape(B, n_in)).to(xs.device).t()
-    if _FN_INFERENCE is None:
-        _FN_INFERENCE = _autograd_inference()
-    outs = _FN_INFERENCE.apply(icnf, mode, xs, ps, eps, sv)
+        eps = _probes(icnf, mode, True, xs.detach().to(torch.float32).t().contiguous(), None).t()
+    outs = _autograd_inference().apply(icnf, mode, xs, ps, eps, sv)
     path = {"t": sv, "z": outs[4], "dlogp": outs[5]}
     if len(outs) > 6:
         path["E"], path["n"] = outs[6], outs[7]
     return outs[0], (outs[1], outs[2], outs[3]), path
 
 
+@functools.lru_cache(maxsize=None)
 def _autograd_generate():
     import torch
 
@@ -346,7 +326,6 @@ def differentiable_generate_path(icnf: ICNF, mode, ps, st=None, n: int = 1, *, s
     (running integrals: they are not outputs of sampling and take no cotangent).  The forward is the one-launch
     ``generate_path`` with the draws kept; the backward is ONE ``generate_path_vjp`` launch.  As for
     ``differentiable_inference_path``, the backward launch solves again (``icnf.last_backward_path``)."""
-    global _FN_GENERATE
     import torch
     who = "differentiable_generate_path"
     m = _mode_id(mode)
@@ -361,14 +340,12 @@ def differentiable_generate_path(icnf: ICNF, mode, ps, st=None, n: int = 1, *, s
     if not (ps.is_cuda and (z0 is None or z0.is_cuda) and (eps is None or eps.is_cuda)):
         raise ValueError(f"{who}: torch tensors must live on the GPU")
     _check_batch(icnf, who, m, n)
-    from .ensemble import _sampling_draws
-    zr, er, _ = _sampling_draws(icnf, mode, False, 1, n, n_in, ps.device, z0.detach().unsqueeze(0) if z0 is not None else None,
-                                eps.unsqueeze(0) if eps is not None else None, None)
+    zr, er, _ = _sampling_draws(icnf, mode, m == _lib.MODE_TRAIN, 1, n, n_in, ps.device,
+                                z0.detach().unsqueeze(0) if z0 is not None else None,
+                                eps.unsqueeze(0) if eps is not None else None, None, steer=False)
     if not (z0 is not None and z0.requires_grad):          # (a z0 that asks for a gradient stays the caller's tensor)
         z0 = zr[0].t()
-    if _FN_GENERATE is None:
-        _FN_GENERATE = _autograd_generate()
-    outs = _FN_GENERATE.apply(icnf, mode, ps, z0, er[0].t(), sv)
+    outs = _autograd_generate().apply(icnf, mode, ps, z0, er[0].t(), sv)
     path = {"t": sv, "z": outs[2], "logq": outs[3]}
     if len(outs) > 4:
         path["E"], path["n"] = outs[4], outs[5]

@@ -16,6 +16,7 @@ does not depend on the base, so the cotangent of ``logpx`` is all it takes); ``e
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -62,15 +63,22 @@ def inference_record(icnf: ICNF, mode, xs, *args, eps=None, tspan=None):
     return logpx, (r[0], r[1], r[2])
 
 
+def _cot_rows(cot):
+    """``(g_logpx, (g_E, g_n, g_A))`` -- a bare None for the triple: no cotangent on the regularisers -- -> the four rows, as
+    given (entries may be None); ``ValueError`` for a triple that is not three; None for anything that is not such a pair (the
+    callers that take a bare ``4 x B`` array go on with it, the others refuse).  The one parse of this convention."""
+    if not (isinstance(cot, (tuple, list)) and len(cot) == 2 and (cot[1] is None or isinstance(cot[1], (tuple, list)))):
+        return None
+    rows = [cot[0]] + list(cot[1] if cot[1] is not None else (None, None, None))
+    if len(rows) != 4:
+        raise ValueError("cot must be (g_logpx, (g_E, g_n, g_A))")
+    return rows
+
+
 def _cot_matrix(cot, B, device):
     """(g_logpx, (g_E, g_n, g_A)) or a 4 x B array -> one contiguous 4 x B float32 device tensor; None entries are zeros."""
     import torch
-    if isinstance(cot, (tuple, list)) and len(cot) == 2 and (cot[1] is None or isinstance(cot[1], (tuple, list))):
-        rows = [cot[0]] + list(cot[1] if cot[1] is not None else (None, None, None))
-        if len(rows) != 4:
-            raise ValueError("cot must be (g_logpx, (g_E, g_n, g_A))")
-    else:
-        rows = None
+    rows = _cot_rows(cot)
     out = torch.zeros(4, B, dtype=torch.float32, device=device)
     if rows is None:
         c = cot if _is_torch(cot) else torch.from_numpy(np.asarray(cot, dtype=np.float32))
@@ -102,8 +110,8 @@ def inference_pullback(icnf: ICNF, cot, with_x=False, with_ys=False, with_base=F
     dev = rec["xb"].arr.device if rec is not None else torch.device("cuda", icnf.device)
     host = rec["host"] if rec is not None else False
     # (B is the cotangent's: the library refuses one that does not match the record)
-    if isinstance(cot, (tuple, list)) and len(cot) == 2 and (cot[1] is None or isinstance(cot[1], (tuple, list))):
-        rows = [cot[0]] + list(cot[1] or ())
+    rows = _cot_rows(cot)
+    if rows is not None:
         sizes = {int(r.numel()) if _is_torch(r) else int(np.size(r)) for r in rows if r is not None}
         if len(sizes) > 1:
             raise ValueError("every cotangent row needs one entry per sample")
@@ -124,6 +132,7 @@ def inference_pullback(icnf: ICNF, cot, with_x=False, with_ys=False, with_base=F
                        (with_base, base_logpdf_pullback(icnf, cm[0]) if with_base else None))      # (row 0: the cotangent of logpx)
 
 
+@functools.lru_cache(maxsize=None)
 def _autograd_function():
     import torch
 
@@ -225,9 +234,6 @@ def _base_tensors(icnf: ICNF):
     return None, None
 
 
-_FUNCTION = None
-
-
 def differentiable_inference(icnf: ICNF, mode, xs, *args, eps=None):
     """``inference`` as a differentiable function of ``ps``, ``xs``, (conditional models) ``ys`` and the ``mean`` / scale tensors
     of a ``LearnableNormal`` base when either requires grad (device tensors): forward
@@ -235,20 +241,17 @@ def differentiable_inference(icnf: ICNF, mode, xs, *args, eps=None):
     model displaced the record before ``backward``, the solve is recorded again from the saved inputs (same outputs bit for
     bit: the solve is deterministic) and then pulled back; the values of a ``LearnableNormal`` base are not saved, so
     ``RuntimeError`` if they changed in between."""
-    global _FUNCTION
     import torch
     if not _is_torch(xs):
         raise ValueError("differentiable_inference needs device tensors")
     ys, ps, st = _split_cond_args(icnf, args)
     ps = ps if _is_torch(ps) else to_device(icnf, ps, xs.device)
-    if _FUNCTION is None:
-        _FUNCTION = _autograd_function()
     # eps first and then the steered t1: the order in which loss_and_grad draws, so that one seed gives one problem
     m = _mode_id(mode)
     if m == _lib.MODE_TRAIN and eps is None:
         eps = draw_eps(icnf, _xs_colmajor(icnf, xs.detach()), xs.shape[1]).view()
     tspan = steer_tspan(icnf, mode)
-    logpx, E, n, A = _FUNCTION.apply(icnf, mode, xs, ys, ps, eps, tspan, *_base_tensors(icnf))
+    logpx, E, n, A = _autograd_function().apply(icnf, mode, xs, ys, ps, eps, tspan, *_base_tensors(icnf))
     return logpx, (E, n, A)
 
 
