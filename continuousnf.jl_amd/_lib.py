@@ -184,6 +184,12 @@ _PATH_VJP_SIGNATURES = {
     "cnf_path_vjp_steps": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int]),
 }
 PATH_VJP_EXPORTS = tuple(_PATH_VJP_SIGNATURES)
+# heterogeneous ensembles (include/cnfhip_ensemble_hetero.h): likewise
+_ENSEMBLE_HETERO_SIGNATURES = {
+    "cnf_ensemble_set_members": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), _fp, _fp]),
+    "cnf_ensemble_clear_members": (C.c_int, [C.c_void_p]),
+}
+ENSEMBLE_HETERO_EXPORTS = tuple(_ENSEMBLE_HETERO_SIGNATURES)
 
 _lib = None
 
@@ -223,7 +229,8 @@ def lib():
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in list(_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) + list(_BASEGRAD_SIGNATURES.items()) + \
                 list(_ENSEMBLE_SIGNATURES.items()) + list(_ENSEMBLE_EVAL_SIGNATURES.items()) + list(_ENSEMBLE_VJP_SIGNATURES.items()) + \
-                list(_ENSEMBLE_GENERATE_VJP_SIGNATURES.items()) + list(_PATH_SIGNATURES.items()) + list(_PATH_VJP_SIGNATURES.items()):
+                list(_ENSEMBLE_GENERATE_VJP_SIGNATURES.items()) + list(_PATH_SIGNATURES.items()) + list(_PATH_VJP_SIGNATURES.items()) + \
+                list(_ENSEMBLE_HETERO_SIGNATURES.items()):
             f = getattr(l, name)
             f.restype, f.argtypes = res, args
         _lib = l

@@ -179,6 +179,14 @@ struct cnf_ctx {
     DevBuf<float> ens_trace;      // [M][trace_cap][4] the members' step attempts (cnf_ensemble_eval_steps)
     int ensv_M = 0, ensv_tcap = 0;   // the last call that kept a trace: members, rows per member
     std::vector<int> ensv_att;    //   attempts per member (-1: the member gave up)
+    // heterogeneous members (include/cnfhip_ensemble_hetero.h): what cnf_ensemble_set_members left for the NEXT ensemble call, which
+    // takes it away at its entry (EnsHet) whatever becomes of that call; and that call's device copy with its pinned staging
+    int het_M = 0;                //   0: nothing pending
+    std::vector<int> het_counts;  //   [M], or empty: every member at the call's B
+    std::vector<float> het_lams;  //   [M][3], or empty: the handle's
+    std::vector<float> het_tols;  //   [M][2] (abstol, reltol), or empty: the options'
+    DevBuf<float> ens_het;        // [M] counts (ints) | [M][3] lambdas | [M][2] tolerances
+    PinnedBuf<float> ens_hhet;
     // cnf_solve_path (include/cnfhip_path.h): the save times on the device and the step pairs the in-launch route files (both
     // allocated on first use), and the accepted steps of the last call on either route (cnf_path_steps)
     DevBuf<float> d_saveat;
@@ -1823,16 +1831,20 @@ extern "C" cnf_status cnf_set_shard_comm(cnf_handle h, cnf_comm comm) {
     return CNF_OK;
 }
 
-extern "C" cnf_status cnf_loss_from_sums(cnf_handle h, int mode, const float* sums5, float* loss) {
+// (lam: the handle's regularisers, or a heterogeneous ensemble member's own)
+static cnf_status loss_from_sums_lam(cnf_handle h, int mode, const float* sums5, const float* lam, float* loss) {
     if (!h || !sums5 || !loss) return CNF_ERR_BAD_ARG;
     const double cnt = sums5[4];
     if (!(cnt > 0)) return fail(h, CNF_ERR_BAD_SHAPE, "empty batch");
     if (mode == CNF_MODE_TRAIN)      // src/icnf.jl:489
-        *loss = (float)((-(double)sums5[0] + (double)h->lam[0] * sums5[1] + (double)h->lam[1] * sums5[2] +
-                         (double)h->lam[2] * sums5[3]) / cnt);
+        *loss = (float)((-(double)sums5[0] + (double)lam[0] * sums5[1] + (double)lam[1] * sums5[2] +
+                         (double)lam[2] * sums5[3]) / cnt);
     else                             // src/base_icnf.jl:496
         *loss = (float)(-(double)sums5[0] / cnt);
     return CNF_OK;
+}
+extern "C" cnf_status cnf_loss_from_sums(cnf_handle h, int mode, const float* sums5, float* loss) {
+    return loss_from_sums_lam(h, mode, sums5, h ? h->lam : nullptr, loss);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2665,7 +2677,20 @@ struct EnsCall {
     bool hairer = false;
     Solve3Args sv{};
     WaveCot cot = WC_LOSS;         // grad: the built-in loss (cnf_loss_grad_many) or per-sample cotangents (the two vjp calls)
+    // heterogeneous members: what cnf_ensemble_set_members left for this call (ens_take_members); M = 0: nothing
+    int het_M = 0;
+    std::vector<int> counts;
+    std::vector<float> lams, tols;
+    const int* d_counts = nullptr;         // ... on the device, from ens_begin on (null: not given)
+    const float *d_lams = nullptr, *d_tols = nullptr;
 };
+// The one-shot state changes hands: whatever becomes of the call, no later call is steered by these arrays.
+static void ens_take_members(cnf_handle h, EnsCall& c) {
+    if (!h) return;
+    c.het_M = h->het_M; h->het_M = 0;
+    c.counts.swap(h->het_counts); c.lams.swap(h->het_lams); c.tols.swap(h->het_tols);
+    h->het_counts.clear(); h->het_lams.clear(); h->het_tols.clear();
+}
 constexpr size_t ENS_ST_F = (sizeof(StepState) + 3) / 4;     // floats of one member's final state in ens_fin / ens_hfin ...
 static size_t ens_fin_floats(int M) { return (size_t)M * (ENS_ST_F + 5); }      // ... and of all M, their five loss sums behind them
 
@@ -2679,6 +2704,16 @@ static cnf_status ens_check(cnf_handle h, const EnsCall& c, bool null_ptr, const
     if (!h) return CNF_ERR_BAD_ARG;
     cnf_status s = check_solve_opts(h, c.opts);
     if (s != CNF_OK) return s;
+    if (c.het_M > 0) {                                     // (cnf_ensemble_set_members: host arrays, checked before any device is asked for)
+        if (c.het_M != c.M) return fail(h, CNF_ERR_BAD_ARG, "cnf_ensemble_set_members was called for another number of members");
+        for (int v : c.counts)
+            if (v < 1 || v > c.B) return fail(h, CNF_ERR_BAD_ARG, "a member's count must be within [1, B]");
+        for (float v : c.tols)
+            if (!std::isfinite(v) || !(v > 0.f)) return fail(h, CNF_ERR_BAD_ARG, "a member's tolerances must be finite and positive");
+        for (size_t i = 0; i < c.lams.size(); ++i)         // (which of the lambdas are zero decides the state rows: the handle's)
+            if (!std::isfinite(c.lams[i]) || (c.lams[i] == 0.f) != (h->lam[i % 3] == 0.f))
+                return fail(h, CNF_ERR_BAD_ARG, "a member's lambda must be finite, and zero exactly where the handle's is");
+    }
     if (c.times)
         for (int m = 0; m < c.M; ++m)
             if (!std::isfinite(c.times[m]) || c.times[m] == (c.gen ? c.opts->t1 : c.opts->t0))
@@ -2701,7 +2736,7 @@ static cnf_status ens_grow(cnf_handle h, const EnsCall& c, size_t cols_f, size_t
     if (traj_f <= h->ens_traj.capacity() && hs_f <= h->ens_hs.capacity() && gpart_f <= h->ens_gpart.capacity() &&
         trace_f <= h->ens_trace.capacity() && cols_f <= h->ens_cols.capacity() && part_f <= h->ens_part.capacity() &&
         2 * Mz <= h->ens_words.capacity() && fin_f <= h->ens_fin.capacity() && fin_f + Mz <= h->ens_hfin.capacity() &&
-        Mz <= h->ens_t1.capacity())
+        Mz <= h->ens_t1.capacity() && (c.het_M == 0 || (6 * Mz <= h->ens_het.capacity() && 6 * Mz <= h->ens_hhet.capacity())))
         return CNF_OK;
     HIPCHK(h, hipDeviceSynchronize());
     if (c.grad) h->ens_M = 0;
@@ -2715,6 +2750,10 @@ static cnf_status ens_grow(cnf_handle h, const EnsCall& c, size_t cols_f, size_t
     RESERVE(h, h->ens_hfin, fin_f + Mz);
     RESERVE(h, h->ens_t1, Mz);
     RESERVE(h, h->ens_trace, trace_f);
+    if (c.het_M > 0) {
+        RESERVE(h, h->ens_het, 6 * Mz);
+        RESERVE(h, h->ens_hhet, 6 * Mz);
+    }
     if (part_f > h->ens_part.capacity()) {
         RESERVE(h, h->ens_part, part_f);
         HIPCHK(h, hipMemset(h->ens_part, 0, part_f * sizeof(float)));
@@ -2746,6 +2785,13 @@ static cnf_status ens_begin(cnf_handle h, EnsCall& c) {
         memcpy(pin, c.times, Mz * sizeof(float));
         HIPCHK(h, hipMemcpyAsync(h->ens_t1, pin, Mz * sizeof(float), hipMemcpyHostToDevice, c.st));
     }
+    if (c.het_M > 0) {                                     // the members' own counts | lambdas | tolerances: one copy through pinned memory
+        float* pin = h->ens_hhet;
+        if (!c.counts.empty()) { memcpy(pin, c.counts.data(), Mz * sizeof(int)); c.d_counts = reinterpret_cast<const int*>(h->ens_het.data()); }
+        if (!c.lams.empty()) { memcpy(pin + Mz, c.lams.data(), 3 * Mz * sizeof(float)); c.d_lams = h->ens_het + Mz; }
+        if (!c.tols.empty()) { memcpy(pin + 4 * Mz, c.tols.data(), 2 * Mz * sizeof(float)); c.d_tols = h->ens_het + 4 * Mz; }
+        HIPCHK(h, hipMemcpyAsync(h->ens_het, pin, 6 * Mz * sizeof(float), hipMemcpyHostToDevice, c.st));
+    }
     c.hairer = opts->adaptive && opts->dt == 0.f;
     Solve3Args& sv = c.sv;
     sv.part = h->ens_part; sv.base_dev = h->ens_words; sv.abort_flag = reinterpret_cast<int*>(h->ens_words.data() + Mz);
@@ -2775,7 +2821,9 @@ static cnf_status ens_finish(cnf_handle h, EnsCall& c, int launches, bool sums, 
         else if (!fin.done) status_out[m] = CNF_ERR_MAXITERS;
         else {
             // (a failure here is that member's status: the launch ran, so the call goes on and returns CNF_OK)
-            status_out[m] = sums ? cnf_loss_from_sums(h, c.mode, h->ens_hfin + Mz * ENS_ST_F + 5 * (size_t)m, &loss) : CNF_OK;
+            // (the fifth sum is the member's own count, as its part of the launch wrote it; the lambdas are its own too)
+            const float* lam = c.lams.empty() ? h->lam : c.lams.data() + 3 * (size_t)m;
+            status_out[m] = sums ? loss_from_sums_lam(h, c.mode, h->ens_hfin + Mz * ENS_ST_F + 5 * (size_t)m, lam, &loss) : CNF_OK;
             if (status_out[m] == CNF_OK) steps[m] = attempts ? natt : fin.naccept;
             else loss = NAN;
         }
@@ -2784,8 +2832,29 @@ static cnf_status ens_finish(cnf_handle h, EnsCall& c, int launches, bool sums, 
     return CNF_OK;
 }
 
+// Nothing of a member that is not CNF_OK is valid: NaN in its own columns of the two outputs (out1 may be null) -- out0 [B][nv]
+// and out1 [B] of sampling, out0 [B] and out1 [3][B] of an inference; a heterogeneous member's columns behind its count stay
+// as the caller left them.
+static size_t ens_member_count(const EnsCall& c, int m) { return (size_t)(c.counts.empty() ? c.B : c.counts[(size_t)m]); }
+static cnf_status ens_fill_member(cnf_handle h, const EnsCall& c, int m, bool gen, size_t nv, float* out0, float* out1) {
+    const size_t Bz = (size_t)c.B, cnt = ens_member_count(c, m);
+    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)out0, 0x7fc00000, gen ? cnt * nv : cnt, c.st));
+    if (!out1) return CNF_OK;
+    for (size_t r = 0; r < (gen ? 1u : 3u); ++r) {
+        if (cnt == Bz && !gen) { HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)out1, 0x7fc00000, 3 * Bz, c.st)); break; }
+        HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(out1 + r * Bz), 0x7fc00000, cnt, c.st));
+    }
+    return CNF_OK;
+}
+
 // u0 = [z0; 0] of all `cols_n` = M B columns of a sampling call (the members' columns are contiguous), D floats per column
-static cnf_status ens_sampling_u0(cnf_handle h, float* u0, const float* z0, size_t cols_n, size_t n_in, size_t D, hipStream_t st) {
+static cnf_status ens_sampling_u0(cnf_handle h, float* u0, const float* z0, size_t cols_n, size_t n_in, size_t D, hipStream_t st,
+                                  const int* counts, int B) {
+    if (counts) {                                          // (heterogeneous members: a column kernel that skips what lies behind a count)
+        launch_ens_u0_counts((int)n_in, (int)D, z0, u0, cols_n, counts, B, st);
+        HIPCHK(h, hipGetLastError());
+        return CNF_OK;
+    }
     HIPCHK(h, hipMemsetAsync(u0, 0, cols_n * D * sizeof(float), st));
     HIPCHK(h, hipMemcpy2DAsync(u0, D * sizeof(float), z0, n_in * sizeof(float), n_in * sizeof(float), cols_n, hipMemcpyDeviceToDevice, st));
     return CNF_OK;
@@ -2815,6 +2884,8 @@ static cnf_status ens_grad(cnf_handle h, WaveCot cot, int mode, int M, const flo
     if (h && ep) h->pvjp_valid = false;
     EnsCall c{true, gen, mode, M, B, 0, opts, times_host, (hipStream_t)stream};
     c.cot = cot;
+    ens_take_members(h, c);
+    if (ep) { c.het_M = 0; c.counts.clear(); c.lams.clear(); c.tols.clear(); }      // (the path calls run one member: taken and dropped)
     cnf_status s = ens_check(h, c, !params_dev || !src || !opts || !grad_dev || !status_out || (train && !eps) ||
                                        (gen ? (!ep && !cot0 && !cot1) || !out0 || !out1 : vjp ? (!ep && !cot0) || !out0 || !out1 : !loss_out),
                              vjp ? "B must be >= 1" : "the loss is a mean over the batch: B must be >= 1",
@@ -2840,7 +2911,7 @@ static cnf_status ens_grad(cnf_handle h, WaveCot cot, int mode, int M, const flo
     Solve3Args& sv = c.sv;
     WaveGradArgs wg;
     if (gen) {
-        if ((s = ens_sampling_u0(h, cols, src, Mz * Bz, n_in, D, c.st)) != CNF_OK) return s;
+        if ((s = ens_sampling_u0(h, cols, src, Mz * Bz, n_in, D, c.st, c.d_counts, B)) != CNF_OK) return s;
         sv.u0 = cols;
         wg.lam_out = cols + Mz * Bz * 2 * D;               // (k_generate_z0_grad must not write where it reads)
     } else {
@@ -2852,6 +2923,7 @@ static cnf_status ens_grad(cnf_handle h, WaveCot cot, int mode, int M, const flo
     wg.lam1 = h->lam[0]; wg.lam2 = h->lam[1]; wg.lam3 = h->lam[2];
     WaveEnsLaunch ens;
     ens.M = M;
+    ens.counts = c.d_counts; ens.lams = c.d_lams; ens.tols = c.d_tols;
     (gen ? ens.t0 : ens.t1) = times_host ? h->ens_t1.data() : nullptr;
     if (gen) { ens.sampling = true; ens.cot_z = cot0; ens.cot_logq = cot1; }
     else ens.cw = vjp ? cot0 : nullptr;
@@ -2866,14 +2938,14 @@ static cnf_status ens_grad(cnf_handle h, WaveCot cot, int mode, int M, const flo
     if (s != CNF_OK) return fail(h, s, "the ensemble launch failed to start");
     ++launches;
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, launch_grad_reduce_many(wg.gpart, grad_dev, (int)np, tiles, fin_dev, M, c.st));
+    HIPCHK(h, launch_grad_reduce_many(wg.gpart, grad_dev, (int)np, tiles, fin_dev, M, c.st, c.d_counts));
     ++launches;
     if (gen) {                                             // the column kernels: x and logq off the final state, then the z0 tail
-        launch_generate_post_rows((int)n_in, (int)nv, (int)D, fsol, src, out0, out1, Mz * Bz, c.st);
+        launch_generate_post_rows((int)n_in, (int)nv, (int)D, fsol, src, out0, out1, Mz * Bz, c.st, c.d_counts, B);
         HIPCHK(h, hipGetLastError());
         ++launches;
         if (grad_in) {
-            launch_generate_z0_grad((int)n_in, BaseDist{}, wg.lam_out, cot1, src, grad_in, Mz * Bz, c.st);
+            launch_generate_z0_grad((int)n_in, BaseDist{}, wg.lam_out, cot1, src, grad_in, Mz * Bz, c.st, c.d_counts, B);
             HIPCHK(h, hipGetLastError());
             ++launches;
         }
@@ -2887,10 +2959,9 @@ static cnf_status ens_grad(cnf_handle h, WaveCot cot, int mode, int M, const flo
             if (status_out[m] != CNF_OK) {
                 any_bad = true;
                 const size_t mz = (size_t)m;
-                HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(out0 + mz * n0), 0x7fc00000, n0, c.st));
-                HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(out1 + mz * n1), 0x7fc00000, n1, c.st));
+                if ((s = ens_fill_member(h, c, m, gen, nv, out0 + mz * n0, out1 + mz * n1)) != CNF_OK) return s;
                 HIPCHK(h, hipMemsetAsync(grad_dev + mz * np, 0, np * sizeof(float), c.st));
-                if (grad_in) HIPCHK(h, hipMemsetAsync(grad_in + mz * Bz * n_in, 0, Bz * n_in * sizeof(float), c.st));
+                if (grad_in) HIPCHK(h, hipMemsetAsync(grad_in + mz * Bz * n_in, 0, ens_member_count(c, m) * n_in * sizeof(float), c.st));
                 if (ep && ep->out) HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)ep->out, 0x7fc00000, (size_t)ep->K * Bz * D, c.st));
             }
         if (any_bad) HIPCHK(h, hipStreamSynchronize(c.st));
@@ -2982,6 +3053,26 @@ extern "C" int cnf_path_vjp_steps(cnf_handle h, float* t_host, float* h_host, in
     return n;
 }
 
+// Heterogeneous ensembles (include/cnfhip_ensemble_hetero.h): the members' own batch sizes, regularisers and tolerances for the
+// NEXT ensemble call on the handle.  Host state only: the arrays are checked by that call (it knows M, B and the handle's
+// lambdas), copied to the device in front of its launch, and gone when it returns.
+extern "C" cnf_status cnf_ensemble_set_members(cnf_handle h, int M, const int* counts, const float* lams, const float* tols) {
+    if (!h) return CNF_ERR_BAD_ARG;
+    h->het_M = 0; h->het_counts.clear(); h->het_lams.clear(); h->het_tols.clear();
+    if (M < 1) return fail(h, CNF_ERR_BAD_ARG, "cnf_ensemble_set_members: an ensemble has at least one member");
+    const size_t Mz = (size_t)M;
+    if (counts) h->het_counts.assign(counts, counts + Mz);
+    if (lams) h->het_lams.assign(lams, lams + 3 * Mz);
+    if (tols) h->het_tols.assign(tols, tols + 2 * Mz);
+    h->het_M = (counts || lams || tols) ? M : 0;
+    return CNF_OK;
+}
+extern "C" cnf_status cnf_ensemble_clear_members(cnf_handle h) {
+    if (!h) return CNF_ERR_BAD_ARG;
+    h->het_M = 0; h->het_counts.clear(); h->het_lams.clear(); h->het_tols.clear();
+    return CNF_OK;
+}
+
 // the signed accepted step sizes of member `member` of the last ensemble gradient call -- cnf_loss_grad_many,
 // cnf_inference_vjp_many or cnf_generate_vjp_many -- (read from the device when asked for)
 extern "C" int cnf_ensemble_steps(cnf_handle h, int member, float* hs, int cap) {
@@ -3017,6 +3108,7 @@ static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float*
                            int* status_out, cnf_solve_stats* stats_out, int trace_cap, void* stream) {
     const bool train = mode == CNF_MODE_TRAIN;
     EnsCall c{false, gen, mode, M, B, trace_cap, opts, times_host, (hipStream_t)stream};
+    ens_take_members(h, c);
     cnf_status s = ens_check(h, c, !params_dev || !src || !opts || !out0 || (!gen && !out1) || !status_out || (train && !eps),
                              "B must be >= 1", "cnf_ensemble_eval_capacity");
     if (s != CNF_OK) return s;
@@ -3032,7 +3124,7 @@ static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float*
     float* cols = h->ens_cols;
     float* fsol = cols + Mz * Bz * D;                      // sampling: the final columns behind u0
     if (gen) {
-        if ((s = ens_sampling_u0(h, cols, src, Mz * Bz, n_in, D, st)) != CNF_OK) return s;
+        if ((s = ens_sampling_u0(h, cols, src, Mz * Bz, n_in, D, st, c.d_counts, B)) != CNF_OK) return s;
         sv.u0 = cols; sv.u_out = fsol;
     } else {
         sv.xs = src; sv.logpx = out0; sv.regs = out1; sv.sums5 = h->ens_fin + Mz * ENS_ST_F;
@@ -3041,6 +3133,7 @@ static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float*
     ens.M = M;
     (gen ? ens.t0 : ens.t1) = times_host ? h->ens_t1.data() : nullptr;
     ens.p_stride = h->n_params; ens.part_stride = WV_ENS_PART_FLOATS;
+    ens.counts = c.d_counts; ens.tols = c.d_tols;          // (the plain forms read no lambda; the members' losses take theirs: ens_finish)
     int launches = 0;
     s = wave_solve_launch(nd, train, params_dev, nullptr, 0, reinterpret_cast<StepState*>(h->ens_fin.data()), cols, eps, B, st, nullptr, 0,
                           sv, nullptr, &ens);
@@ -3048,7 +3141,7 @@ static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float*
     ++launches;
     HIPCHK(h, hipGetLastError());
     if (gen) {
-        launch_generate_post_rows((int)n_in, (int)nv, (int)D, fsol, src, out0, out1, Mz * Bz, st);
+        launch_generate_post_rows((int)n_in, (int)nv, (int)D, fsol, src, out0, out1, Mz * Bz, st, c.d_counts, B);
         HIPCHK(h, hipGetLastError());
         ++launches;
     }
@@ -3059,8 +3152,7 @@ static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float*
         if (status_out[m] != CNF_OK) {                     // nothing of such a member is valid: NaN, whatever the kernel left
             any_bad = true;
             const size_t n0 = gen ? Bz * nv : Bz, n1 = gen ? Bz : 3 * Bz;
-            HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(out0 + (size_t)m * n0), 0x7fc00000, n0, st));
-            if (out1) HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(out1 + (size_t)m * n1), 0x7fc00000, n1, st));
+            if ((s = ens_fill_member(h, c, m, gen, nv, out0 + (size_t)m * n0, out1 ? out1 + (size_t)m * n1 : nullptr)) != CNF_OK) return s;
         }
     if (any_bad) HIPCHK(h, hipStreamSynchronize(st));
     if (trace_cap > 0) { h->ensv_att.swap(att); h->ensv_M = M; h->ensv_tcap = trace_cap; }

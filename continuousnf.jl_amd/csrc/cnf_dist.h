@@ -39,11 +39,14 @@ void launch_vjp_cotangent(const NetDesc& nd, int D, const BaseDist& bd, int with
 void launch_generate_post(int n_in, int D, const BaseDist& bd, const float* fsol, const float* z0, float* z_out, float* logq, int B,
                           hipStream_t s);
 // cnf_generate_many: the M B columns of an ensemble as one batch, N(0, I) base: x_out[b] = the first n_out rows, logq may be null
+// (counts, device [M] with Bm columns per member: heterogeneous members -- columns at or behind their member's count are skipped)
 void launch_generate_post_rows(int n_in, int n_out, int D, const float* fsol, const float* z0, float* x_out, float* logq, size_t B,
-                               hipStream_t s);
+                               hipStream_t s, const int* counts = nullptr, int Bm = 0);
+// ... and u0 = [z0; 0] of those members' own columns ([cols][D] from [cols][n_in])
+void launch_ens_u0_counts(int n_in, int D, const float* z0, float* u0, size_t cols, const int* counts, int Bm, hipStream_t s);
 // The terminal cotangent: lam = cot_z, cw = [3][B]: w_l = +cot_logq, w_E = w_n = 0 (null cotangents: zeros).  n_in >= 1.
 void launch_generate_cotangent(int n_in, const float* cot_z, const float* cot_logq, float* lam, float* cw, int B, hipStream_t s);
 // gz0 = lam0 + cot_logq d logpdf(base, z0) / d z0   (cot_logq null: a copy; gz0 must not alias lam0).  B: the columns -- of an
 // ensemble (cnf_generate_vjp_many) all M B of them as one batch
 void launch_generate_z0_grad(int n_in, const BaseDist& bd, const float* lam0, const float* cot_logq, const float* z0, float* gz0,
-                             size_t B, hipStream_t s);
+                             size_t B, hipStream_t s, const int* counts = nullptr, int Bm = 0);

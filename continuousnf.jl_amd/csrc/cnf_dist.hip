@@ -203,17 +203,25 @@ k_generate_post(int n_in, int D, BaseDist bd, const float* __restrict__ fsol, co
 // only the first n_out = nvars rows of the sample are written, logq (may be null) with k_generate_post's arithmetic.
 __global__ void __launch_bounds__(256)
 k_generate_post_rows(int n_in, int n_out, int D, const float* __restrict__ fsol, const float* __restrict__ z0,
-                     float* __restrict__ x_out, float* __restrict__ logq, size_t B) {
+                     float* __restrict__ x_out, float* __restrict__ logq, size_t B, const int* __restrict__ counts, int Bm) {
     const int tid = threadIdx.x, p = tid & 3;
     const size_t b = (size_t)blockIdx.x * 64 + (tid >> 2);
-    const size_t bb = b < B ? b : B - 1;
+    size_t bb = b < B ? b : B - 1;
+    // heterogeneous members (counts: [M], Bm columns per member): a column at or behind its member's count is neither read nor
+    // written -- its lanes read the member's first column for the shuffles and leave
+    bool pad = false;
+    if (counts) {
+        const size_t m = bb / (size_t)Bm;
+        pad = bb - m * (size_t)Bm >= (size_t)counts[m];
+        if (pad) bb = m * (size_t)Bm;
+    }
     const float* c = fsol + bb * D;
     const float* z = z0 + bb * n_in;
     float ss = 0.f;
     for (int i = p; i < n_in; i += 4) ss = fmaf(z[i], z[i], ss);
     ss += __shfl_xor(ss, 1, 64);
     ss += __shfl_xor(ss, 2, 64);
-    if (b >= B) return;
+    if (b >= B || pad) return;
     for (int i = p; i < n_out; i += 4) x_out[bb * n_out + i] = c[i];
     if (p == 0 && logq) {
         const float log2pi = 1.8378770664093453f;
@@ -240,10 +248,14 @@ k_generate_cotangent(int n_in, const float* __restrict__ cot_z, const float* __r
 // cnf_generate_vjp_many, N(0, I) base -- as one batch.)
 __global__ void __launch_bounds__(256)
 k_generate_z0_grad(int n_in, BaseDist bd, const float* __restrict__ lam0, const float* __restrict__ cot_logq,
-                   const float* __restrict__ z0, float* __restrict__ gz0, size_t B) {
+                   const float* __restrict__ z0, float* __restrict__ gz0, size_t B, const int* __restrict__ counts, int Bm) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (size_t)n_in * B) return;
     const size_t b = e / (size_t)n_in;
+    if (counts) {                                    // heterogeneous members: nothing of a column at or behind its member's count
+        const size_t m = b / (size_t)Bm;
+        if (b - m * (size_t)Bm >= (size_t)counts[m]) return;
+    }
     const int i = (int)(e - b * (size_t)n_in);
     float g = lam0[e];
     if (cot_logq) {
@@ -263,7 +275,24 @@ k_generate_z0_grad(int n_in, BaseDist bd, const float* __restrict__ lam0, const 
     gz0[e] = g;
 }
 
+// cnf_generate_many / cnf_generate_vjp_many with heterogeneous members: u0 = [z0; 0] of the columns below their member's count
+// (one lane per entry of u0; the homogeneous calls do this with a memset and a strided copy of all M B columns)
+__global__ void __launch_bounds__(256)
+k_ens_u0_counts(int n_in, int D, const float* __restrict__ z0, float* __restrict__ u0, size_t cols, const int* __restrict__ counts, int Bm) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= cols * (size_t)D) return;
+    const size_t b = e / (size_t)D, m = b / (size_t)Bm;
+    const int i = (int)(e - b * (size_t)D);
+    if (b - m * (size_t)Bm >= (size_t)counts[m]) return;
+    u0[e] = i < n_in ? z0[b * n_in + i] : 0.f;
+}
+
 }  // namespace
+
+void launch_ens_u0_counts(int n_in, int D, const float* z0, float* u0, size_t cols, const int* counts, int Bm, hipStream_t s) {
+    const size_t n = cols * (size_t)D;
+    hipLaunchKernelGGL(k_ens_u0_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_in, D, z0, u0, cols, counts, Bm);
+}
 
 void launch_base_post(int n_in, int D, const BaseDist& bd, const StepState* st, const float* U0, const float* U1, float* logpx,
                       const float* regs, int B, float* sums5, float* part, unsigned* ticket, hipStream_t s) {
@@ -292,8 +321,9 @@ void launch_generate_post(int n_in, int D, const BaseDist& bd, const float* fsol
 }
 
 void launch_generate_post_rows(int n_in, int n_out, int D, const float* fsol, const float* z0, float* x_out, float* logq, size_t B,
-                               hipStream_t s) {
-    hipLaunchKernelGGL(k_generate_post_rows, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, s, n_in, n_out, D, fsol, z0, x_out, logq, B);
+                               hipStream_t s, const int* counts, int Bm) {
+    hipLaunchKernelGGL(k_generate_post_rows, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, s, n_in, n_out, D, fsol, z0, x_out, logq, B,
+                       counts, Bm);
 }
 
 void launch_generate_cotangent(int n_in, const float* cot_z, const float* cot_logq, float* lam, float* cw, int B, hipStream_t s) {
@@ -302,7 +332,8 @@ void launch_generate_cotangent(int n_in, const float* cot_z, const float* cot_lo
 }
 
 void launch_generate_z0_grad(int n_in, const BaseDist& bd, const float* lam0, const float* cot_logq, const float* z0, float* gz0,
-                             size_t B, hipStream_t s) {
+                             size_t B, hipStream_t s, const int* counts, int Bm) {
     const size_t n = (size_t)n_in * B;
-    hipLaunchKernelGGL(k_generate_z0_grad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_in, bd, lam0, cot_logq, z0, gz0, B);
+    hipLaunchKernelGGL(k_generate_z0_grad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_in, bd, lam0, cot_logq, z0, gz0, B,
+                       counts, Bm);
 }

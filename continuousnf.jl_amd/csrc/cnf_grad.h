@@ -69,7 +69,8 @@ hipError_t launch_wgrad(const NetDesc& nd, const GradLayout& g, const float* AB,
 hipError_t launch_grad_reduce(const float* gpart, float* grad, int n_params, int ksplit, hipStream_t s);
 // M models' partials [M][ksplit][n_params] -> grad [M][n_params], each member's in k_grad_reduce's order; zeros for a member
 // whose final state (states[m]) is not that of a completed launch
-hipError_t launch_grad_reduce_many(const float* gpart, float* grad, int n_params, int ksplit, const StepState* states, int M, hipStream_t s);
+hipError_t launch_grad_reduce_many(const float* gpart, float* grad, int n_params, int ksplit, const StepState* states, int M, hipStream_t s,
+                                   const int* counts = nullptr);   // counts: device [M], a member's own first ceil(counts[m] / 16) partials
 // the same sum guarded by the final state of the launch that wrote the partials (zeros if it gave up) + the loss, in device memory
 hipError_t launch_grad_finish(const float* gpart, float* grad, int n_params, int ksplit, const StepState* state, const float* sums5,
                               float l1, float l2, float l3, int train, float* loss_dev, hipStream_t s);

@@ -1039,23 +1039,28 @@ hipError_t launch_grad_reduce(const float* gpart, float* grad, int n_params, int
 // cnf_loss_grad_many: k_grad_reduce's sum (the same order: bit for bit what one model's call forms) for member blockIdx.y of an
 // ensemble -- or zeros where the member's final state says that its launch gave up or did not end in a usable state.
 __global__ void __launch_bounds__(256)
-k_grad_reduce_many(const float* __restrict__ gpart, float* __restrict__ grad, int n_params, int ksplit, const StepState* __restrict__ states) {
+k_grad_reduce_many(const float* __restrict__ gpart, float* __restrict__ grad, int n_params, int ksplit, const StepState* __restrict__ states,
+                   const int* __restrict__ counts) {
     __shared__ float part[4][64];
     const StepState* state = states + blockIdx.y;
     const bool ok = state->n_partials >= 0 && state->done && !state->nonfinite;
     gpart += (size_t)blockIdx.y * ksplit * n_params;
     grad += (size_t)blockIdx.y * n_params;
+    // heterogeneous members: the member's own waves wrote partials -- its first ceil(counts[m] / 16) -- and k_grad_reduce at that
+    // batch size adds just those, in this order
+    const int kown = counts ? (counts[blockIdx.y] + 15) >> 4 : ksplit;
     const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
     const int p = blockIdx.x * 64 + c;
     float s = 0.f;
     if (ok && p < n_params)
-        for (int k = q; k < ksplit; k += 4) s += gpart[(size_t)k * n_params + p];
+        for (int k = q; k < kown; k += 4) s += gpart[(size_t)k * n_params + p];
     part[q][c] = s;
     __syncthreads();
     if (q == 0 && p < n_params) grad[p] = (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]);
 }
-hipError_t launch_grad_reduce_many(const float* gpart, float* grad, int n_params, int ksplit, const StepState* states, int M, hipStream_t s) {
-    hipLaunchKernelGGL(k_grad_reduce_many, dim3((n_params + 63) / 64, M), dim3(256), 0, s, gpart, grad, n_params, ksplit, states);
+hipError_t launch_grad_reduce_many(const float* gpart, float* grad, int n_params, int ksplit, const StepState* states, int M, hipStream_t s,
+                                   const int* counts) {
+    hipLaunchKernelGGL(k_grad_reduce_many, dim3((n_params + 63) / 64, M), dim3(256), 0, s, gpart, grad, n_params, ksplit, states, counts);
     return hipGetLastError();
 }
 

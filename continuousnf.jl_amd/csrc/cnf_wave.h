@@ -57,6 +57,12 @@ struct WaveEnsLaunch {
     bool sampling = false;
     const float* cot_z = nullptr;
     const float* cot_logq = nullptr;
+    // heterogeneous members (cnf_ensemble_set_members), device, each null or: counts [M] batch sizes within [1, B] -- every array
+    // stays [M][B]..; a member's columns behind its count are neither read nor written --, lams [M][3] (the loss form of the
+    // gradient), tols [M][2] (abstol, reltol)
+    const int* counts = nullptr;
+    const float* lams = nullptr;
+    const float* tols = nullptr;
 };
 #define WV_ENS_PART_FLOATS 8192    // a member's meeting words: 2 x 1024 of the meetings + 2048 of the loss-sum partials, 8 bytes each
 // the largest M a launch takes at batch B: workgroups the device holds at once / tiles (0: no ensemble form of this network

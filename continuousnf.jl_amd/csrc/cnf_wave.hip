@@ -77,6 +77,10 @@ struct WaveEnsArgs {
     const float* cw;       // CW forms: the members' per-sample cotangents [M][4][B], rows (logpx, E, n, A) (behind t0, for the same reason)
     const float* gz;       // sampling CW forms: null, or the members' cotangents of the final state rows [M][B][n_in] ...
     const float* gl;       // ... and null, or those of logq [M][B]
+    // heterogeneous members (cnf_ensemble_set_members; behind gl, for the same reason; null: the launch's own for every member)
+    const int* counts;     // the members' own batch sizes [M], 1 <= counts[m] <= B: the strides stay the launch's B, [M][B]..
+    const float* lams;     // the members' own lambda_1..3 [M][3] (the loss forms of the gradient)
+    const float* tols;     // the members' own (abstol, reltol) [M][2]
 };
 
 __device__ __forceinline__ f32x4 mm4(const float (&A)[4], const f32x4& b, f32x4 acc) {
@@ -218,10 +222,14 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
     int wid_ = WGW > 1 ? (int)blockIdx.x * nwg + wloc : (int)blockIdx.x;
     const float* cwp = nullptr;                            // CW: this member's cotangents [4][B]
     const float *gzp = nullptr, *glp = nullptr;            // sampling CW: this member's cot_z [B][n_in] and cot_logq [B] (null: zeros)
+    // ENS: the launch's B -- the row stride of the [3][B] / [4][B] arrays, whatever a member's own a.B -- and the member's tiles
+    // (both dead in the other forms, whose code is what it was)
+    int ens_B = 0, ens_tiles = 0;
     if constexpr (ENS) {
         const int member = (int)blockIdx.x / en.tiles;
         wid_ = (int)blockIdx.x - member * en.tiles;
         const size_t mb = (size_t)member, Bz = (size_t)a.B, nz = (size_t)a.nd.n_in;
+        ens_B = a.B; ens_tiles = en.tiles;
         a.P += mb * en.p_stride;
         if ((GRAD && !CWS) || sv.xs) {                     // (a bare solve -- plain forms, sampling CW -- has none of these: null stays null)
             sv.xs += mb * Bz * (size_t)sv.nvars;
@@ -240,6 +248,22 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
             }
         }
         sv.part += mb * en.part_stride; sv.base_dev += mb; sv.abort_flag += mb;
+        // a member's own batch size, regularisers and tolerances: the body behind the prologue is the single model's at that batch
+        // (a workgroup beyond the member's tiles is no party of its meetings: it leaves before it touches a word of the member's)
+        // (compiled out of the PATH forms of the gradient, which run one member and are never given the arrays: two of them paid
+        // for the null tests with a scratch frame)
+        if constexpr (!CWP) {
+            if (en.counts) {
+                const int cnt = en.counts[mb];
+                ens_tiles = (cnt + 15) >> 4;
+                if (wid_ >= ens_tiles) return;
+                a.B = cnt; a.n_total = (float)((size_t)(a.nd.n_in + (MODE != WV_TEST ? 3 : 1)) * (size_t)cnt);
+            }
+            if constexpr (GRAD && CW == WC_LOSS) {
+                if (en.lams) { a.g.lam1 = en.lams[3 * mb]; a.g.lam2 = en.lams[3 * mb + 1]; a.g.lam3 = en.lams[3 * mb + 2]; }
+            }
+            if (en.tols) { sv.init.abstol = en.tols[2 * mb]; sv.init.reltol = en.tols[2 * mb + 1]; }
+        }
         if constexpr (CWS) {                               // a bare solve from the member's own start time (sampling), to opts' end
             sv.u0 += mb * Bz * (nz + (MODE != WV_TEST ? 3 : 1));
             if (en.t0) { sv.init.t = sv.init.t0 = en.t0[mb]; step_state_set_t1(&sv.init, sv.init.t1); }
@@ -255,7 +279,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
         }
     }
     const int wid = wid_;                                  // this wave's tile
-    const int tiles = ENS ? en.tiles : (int)gridDim.x;     // (WGW == 1) tiles of the batch = parties of a meeting
+    const int tiles = ENS ? ens_tiles : (int)gridDim.x;    // (WGW == 1) tiles of the batch (ENS: of the member's) = parties of a meeting
     const NetDesc& nd = a.nd;
     const int n_in = nd.n_in, nh = nd.dims[1], D = n_in + NS;
     const int act1 = nd.acts[0], act2 = nd.acts[1];
@@ -869,7 +893,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
             const float lp = -0.5f * fmaf((float)n_in, log2pi, ss) - us;
             const float aa = (sv.norm_z_aug && sv.naugs > 0) ? sqrtf(sa) : 0.f;
             const float Ev = TRAIN ? s1 : 0.f, Nv = TRAIN ? s2 : 0.f;
-            const size_t bb = (size_t)smp, Bz = (size_t)a.B;
+            const size_t bb = (size_t)smp, Bz = (size_t)(ENS ? ens_B : a.B);
             sv.logpx[bb] = lp; sv.regs[bb] = Ev; sv.regs[Bz + bb] = Nv; sv.regs[2 * Bz + bb] = aa;
             v4[0] = lp; v4[1] = Ev; v4[2] = Nv; v4[3] = aa;
         }
@@ -961,7 +985,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
             if constexpr (CWI) {
                 if (live && (!CWP || cwp)) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) cwv[r] = cwp[(size_t)r * (size_t)a.B + (size_t)smp];
+                    for (int r = 0; r < 4; ++r) cwv[r] = cwp[(size_t)r * (size_t)ens_B + (size_t)smp];
                 }
             }
             // cotangents of the scalar rows: constants of the loss -- CW: of this lane's column (the dlogp row carries -g_logpx;
@@ -1788,6 +1812,7 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
     }
     if (ens) {                                             // M x tiles workgroups
         en.tiles = tiles; en.t1 = ens->t1; en.p_stride = ens->p_stride; en.part_stride = ens->part_stride;
+        en.counts = ens->counts; en.lams = ens->lams; en.tols = ens->tols;
         grid *= ens->M;
     }
     WavePathArgs pa{};

@@ -93,10 +93,11 @@ def _check_inputs(icnf: ICNF, mode, xs, ps, eps, t1, who="loss_and_grad_many", s
     return m, M, B, n_in, t1
 
 
-def _probes_and_ends(icnf: ICNF, mode, train, M, B, n_in, xr, eps, t1, steer=True):
+def _probes_and_ends(icnf: ICNF, mode, train, M, B, n_in, xr, eps, t1, steer=True, counts=None):
     """The members' probes ([M][B][n_in] on the device of ``xr``; None in TestMode) and end times (None: ``tspan[1]`` for all),
     given or drawn in the order ``loss_and_grad_many`` documents.  ``steer=False``: no steer variate is drawn (the path calls,
-    which are this draw with one member)."""
+    which are this draw with one member).  ``counts``: on a host generator member m draws ``counts[m]`` columns -- what a loop of
+    the single-model call at that batch size draws -- and the columns behind them are zeros."""
     import torch
     steer = steer and train and t1 is None and icnf.STEER      # (given end times and TestMode never steer)
     if not train:
@@ -109,8 +110,13 @@ def _probes_and_ends(icnf: ICNF, mode, train, M, B, n_in, xr, eps, t1, steer=Tru
         # the host generator, member by member in the order a loop of ``loss_and_grad`` consumes it (the member's probes, then
         # its end time: base_icnf.loss_and_grad), so that one seed gives the members the draws that loop would; one upload
         host, draws, ends = _Buf(None, icnf.nvars, B, None), [], []
-        for _ in range(M):
-            draws.append(draw_eps(icnf, host, B).arr.reshape(B, n_in))
+        for i in range(M):
+            if counts is None:
+                draws.append(draw_eps(icnf, host, B).arr.reshape(B, n_in))
+            else:
+                k = int(counts[i])
+                draws.append(np.zeros((B, n_in), dtype=np.float32))
+                draws[-1][:k] = draw_eps(icnf, _Buf(None, icnf.nvars, k, None), k).arr.reshape(k, n_in)
             if steer:
                 ends.append(steer_tspan(icnf, mode)[1])
         er = torch.from_numpy(np.stack(draws)).to(xr.device)
@@ -127,6 +133,121 @@ def _rows(x):
     return x.detach().to(torch.float32).permute(0, 2, 1).contiguous()
 
 
+# ---- heterogeneous members (include/cnfhip_ensemble_hetero.h): per-member batch size, lambdas and tolerances ----
+def _default_tols(icnf: ICNF):
+    """(abstol, reltol) of the model's ``sol_kwargs`` (OrdinaryDiffEq's defaults where it has none: ``_solve_opts_build``)."""
+    return float(icnf.sol_kwargs.get("abstol", 1e-6)), float(icnf.sol_kwargs.get("reltol", 1e-3))
+
+
+def _members(icnf: ICNF, M, B, counts=None, lambdas=None, reltol=None, abstol=None, who="loss_and_grad_many"):
+    """The per-member arguments of an ensemble call, checked.  Host logic only: nothing is drawn, no handle is made.  ``counts``:
+    M batch sizes within [1, B]; ``lambdas``: (M, 3) finite values, zero exactly where the model's are (that decides the rows of
+    the state); ``reltol`` / ``abstol``: a positive finite scalar or M of them (one given: the other is the model's).  Returns
+    None when none is given (the call is then today's), else a namespace ``counts`` (int32 (M,) or None), ``lambdas`` (float32
+    (M, 3) or None), ``tols`` (float32 (M, 2): abstol, reltol; or None)."""
+    if counts is None and lambdas is None and reltol is None and abstol is None:
+        return None
+    c = lam = tols = None
+    if counts is not None:
+        c = np.asarray(counts)
+        if c.ndim != 1 or c.shape[0] != M or not np.issubdtype(c.dtype, np.integer):
+            raise ValueError(f"{who}: counts must be M = {M} integers, got {np.asarray(counts).shape}")
+        if (c < 1).any() or (c > B).any():
+            raise ValueError(f"{who}: every count must be within [1, B = {B}], got {c.tolist()}")
+        c = np.ascontiguousarray(c, dtype=np.int32)
+    if lambdas is not None:
+        lam = np.asarray(lambdas, dtype=np.float32)
+        if lam.shape != (M, 3):
+            raise ValueError(f"{who}: lambdas must be (M = {M}, 3), got {lam.shape}")
+        own = np.asarray([icnf.lambda1, icnf.lambda2, icnf.lambda3], dtype=np.float32)
+        if not np.isfinite(lam).all() or ((lam == 0) != (own == 0)[None, :]).any():
+            raise ValueError(f"{who}: every lambda must be finite, and zero exactly where the model's is (they decide the rows of "
+                             f"the state): the model has {own.tolist()}")
+        lam = np.ascontiguousarray(lam)
+    if reltol is not None or abstol is not None:
+        a0, r0 = _default_tols(icnf)
+        cols = []
+        for name, v, dflt in (("abstol", abstol, a0), ("reltol", reltol, r0)):
+            v = np.asarray(dflt if v is None else v, dtype=np.float32)
+            if v.ndim == 0:
+                v = np.full(M, v, dtype=np.float32)
+            if v.shape != (M,):
+                raise ValueError(f"{who}: {name} must be a scalar or M = {M} values, got {v.shape}")
+            if not np.isfinite(v).all() or (v <= 0).any():
+                raise ValueError(f"{who}: every {name} must be finite and positive")
+            cols.append(v)
+        tols = np.ascontiguousarray(np.stack(cols, axis=1), dtype=np.float32)
+    return SimpleNamespace(counts=c, lambdas=lam, tols=tols)
+
+
+@functools.lru_cache(maxsize=64)
+def _call_values(M, B, lams, tols):
+    """(counts, lambdas, tols) of a call whose members are all the call's own: read-only arrays, made once per shape."""
+    out = (np.full(M, B, dtype=np.int32), np.tile(np.asarray(lams, dtype=np.float32), (M, 1)), np.tile(np.asarray(tols, dtype=np.float32), (M, 1)))
+    for a in out:
+        a.flags.writeable = False
+    return out
+
+
+def _members_used(icnf: ICNF, het, M, B):
+    """What a call reports as ``info["counts"]``, ``info["lambdas"]`` and ``info["tols"]``: the members' own, or the call's."""
+    c, lam, tols = _call_values(int(M), int(B), (icnf.lambda1, icnf.lambda2, icnf.lambda3), _default_tols(icnf))
+    if het is None:
+        return dict(counts=c, lambdas=lam, tols=tols)
+    return dict(counts=het.counts.copy() if het.counts is not None else c, lambdas=het.lambdas.copy() if het.lambdas is not None else lam,
+                tols=het.tols.copy() if het.tols is not None else tols)
+
+
+def _set_members(h, het, lo, n):
+    """cnf_ensemble_set_members for the members ``lo .. lo + n - 1``: the next ensemble call on the handle takes them away."""
+    part = [a[lo:lo + n] if a is not None else None for a in (het.counts, het.lambdas, het.tols)]
+    _lib.check(_lib.lib().cnf_ensemble_set_members(
+        h, n, part[0].ctypes.data_as(C.POINTER(C.c_int)) if part[0] is not None else None,
+        part[1].ctypes.data if part[1] is not None else None, part[2].ctypes.data if part[2] is not None else None), h)
+
+
+def member_twin(icnf: ICNF, lambdas=None, tols=None):
+    """A model of its own handle that is ``icnf`` with one member's regularisers (``lambdas``: three values) and tolerances
+    (``tols``: abstol, reltol) -- what the member of a heterogeneous call is compared with and, when its part of a launch gave
+    up, run again on.  It shares ``icnf``'s generator and network; the caller closes it."""
+    import dataclasses
+    kw = dict(icnf.sol_kwargs)
+    if tols is not None:
+        kw["abstol"], kw["reltol"] = float(np.float32(tols[0])), float(np.float32(tols[1]))
+    lam = (icnf.lambda1, icnf.lambda2, icnf.lambda3) if lambdas is None else tuple(float(np.float32(v)) for v in lambdas)
+    return dataclasses.replace(icnf, sol_kwargs=kw, lambda1=lam[0], lambda2=lam[1], lambda3=lam[2], _handle=None, _cond_id=None,
+                               _params_id=None, _base_id=None)
+
+
+def pad_columns(parts, B, fill=0.0):
+    """Ragged members -> one rectangular array: ``parts[m]`` is (rows, counts[m]); the result is (M, rows, B) with ``fill`` in
+    the columns at and behind a member's count (numpy arrays or torch tensors; the result is of the same kind)."""
+    if _is_torch(parts[0]):
+        import torch
+        out = torch.full((len(parts), parts[0].shape[0], B), fill, dtype=parts[0].dtype, device=parts[0].device)
+    else:
+        out = np.full((len(parts), parts[0].shape[0], B), fill, dtype=parts[0].dtype)
+    for m, p in enumerate(parts):
+        if p.shape[1] > B:
+            raise ValueError(f"member {m} has {p.shape[1]} columns, more than B = {B}")
+        out[m, :, :p.shape[1]] = p
+    return out
+
+
+def member_loss_from_sums(mode, sums5, lambdas):
+    """A member's loss from its five sums (logpx, E, n, A, count) with its own regularisers: ``(-S_logpx + l1 S_E + l2 S_n + l3
+    S_A) / count`` in TrainMode (src/icnf.jl:489), ``-S_logpx / count`` in TestMode (src/base_icnf.jl:496), formed in float64 and
+    rounded once -- the arithmetic of the library's per-member loss; ``inference_many`` forms the loss of a member that was run
+    again with it."""
+    s = np.asarray(sums5.detach().cpu() if _is_torch(sums5) else sums5, dtype=np.float32).astype(np.float64)
+    lam = np.asarray(lambdas, dtype=np.float32).astype(np.float64)
+    if not s[4] > 0:
+        raise ValueError("empty batch")
+    if _mode_id(mode) == _lib.MODE_TRAIN:
+        return np.float32((-s[0] + lam[0] * s[1] + lam[1] * s[2] + lam[2] * s[3]) / s[4])
+    return np.float32(-s[0] / s[4])
+
+
 def _device_capacity(who, capacity_fn, h, m, B):
     """The members one launch takes on this device (``capacity_fn`` of the C ABI), or ``NotImplementedError``."""
     cap = int(getattr(_lib.lib(), capacity_fn)(h, m, B))
@@ -135,18 +256,20 @@ def _device_capacity(who, capacity_fn, h, m, B):
     return cap
 
 
-def _settle_density(icnf: ICNF, mode, xs, ps, eps, t1, who, single, capacity_fn=None, cot_rows=None, shared=True):
+def _settle_density(icnf: ICNF, mode, xs, ps, eps, t1, who, single, capacity_fn=None, cot_rows=None, shared=True, members=None):
     """The inputs of a density-direction ensemble call, checked, placed and drawn, in the one order the callers promise: the
     host-side refusals and shape checks (``_check_inputs``, then ``cot_rows(M, B)``: the call's cotangent tensors) -- nothing is
     drawn, no handle is made --; the handle (no device: cnf_create's error, as everywhere); the device check; the capacity
     (``capacity_fn`` of the C ABI; None: not asked, for the ``differentiable_*`` entries, whose forward asks); the probes and
-    end times (``_probes_and_ends``).  ``shared``: ``xs`` may be one (nvars, B) data set for all members.  Returns a namespace:
-    ``m, M, B, n_in, train, cot, cap, dev, stream, xr, pr, er, t1``."""
+    end times (``_probes_and_ends``).  ``shared``: ``xs`` may be one (nvars, B) data set for all members.  ``members``: the
+    keywords ``counts``, ``lambdas``, ``reltol``, ``abstol`` of the call (``_members`` checks them with the shapes).  Returns a
+    namespace: ``m, M, B, n_in, train, cot, cap, dev, stream, xr, pr, er, t1, het``."""
     import torch
     if shared and _is_torch(xs) and _is_torch(ps) and xs.dim() == 2 and ps.dim() == 2 and _refusal(icnf) is None:
         xs = xs.unsqueeze(0).expand(ps.shape[0], *xs.shape)                # shared data: every member reads its own copy
     m, M, B, n_in, t1 = _check_inputs(icnf, mode, xs, ps, eps, t1, who, single)
     cot = cot_rows(M, B) if cot_rows is not None else ()
+    het = _members(icnf, M, B, who=who, **members) if members else None
     h = icnf.handle() if capacity_fn is not None else None
     if not (xs.is_cuda and ps.is_cuda and all(a is None or a.is_cuda for a in (eps, *cot))):
         raise ValueError(f"{who}: torch tensors must live on the GPU")
@@ -154,24 +277,26 @@ def _settle_density(icnf: ICNF, mode, xs, ps, eps, t1, who, single, capacity_fn=
     train, dev = m == _lib.MODE_TRAIN, xs.device
     xr = _rows(xs)
     pr = ps.detach().to(torch.float32).contiguous()
-    er, t1 = _probes_and_ends(icnf, mode, train, M, B, n_in, xr, eps, t1)
-    return SimpleNamespace(m=m, M=M, B=B, n_in=n_in, train=train, cot=cot, cap=cap, dev=dev, xr=xr, pr=pr, er=er, t1=t1,
+    er, t1 = _probes_and_ends(icnf, mode, train, M, B, n_in, xr, eps, t1, counts=het.counts if het is not None else None)
+    return SimpleNamespace(m=m, M=M, B=B, n_in=n_in, train=train, cot=cot, cap=cap, dev=dev, xr=xr, pr=pr, er=er, t1=t1, het=het,
                            stream=_stream(_Buf(xr, icnf.nvars, M * B, torch)))
 
 
-def _launch(icnf: ICNF, s, call, steps_of, times_key, times, **more):
+def _launch(icnf: ICNF, s, width, call, steps_of, times_key, times, **more):
     """The first half of every ensemble call: the ABI call in launches of at most ``s.cap`` members (``s.M`` above the
     capacity: consecutive launches), and what every ensemble call reports.  ``call(lo, n, status, stats)`` makes the ABI call
     for the members ``lo .. lo + n - 1`` with the two pointers as its ``status_out`` and ``stats_out``; ``steps_of(icnf, i)``
     reads the steps of member i of the call just made (asked for the members that succeeded; None: no steps); ``times``: the
-    members' own times (None: ``tspan[1]`` for all), reported as ``info[times_key]``.  Returns ``(info, steps)``; failures are
+    members' own times (None: ``tspan[1]`` for all), reported as ``info[times_key]``; ``width``: the columns of the call's rectangle.  Returns ``(info, steps)``; failures are
     ``_finish``'s, so that a caller may publish ``info`` before they are raised."""
-    h, M = icnf.handle(), s.M
+    h, M, het = icnf.handle(), s.M, getattr(s, "het", None)
     status = np.empty(M, dtype=np.int32)
     stats = (_lib.cnf_solve_stats * M)()
     calls, steps = 0, [] if steps_of is not None else None
     for lo in range(0, M, s.cap):
         n = min(s.cap, M - lo)
+        if het is not None:                                # (a split slices the members' arrays with the members)
+            _set_members(h, het, lo, n)
         _lib.check(call(lo, n, status[lo:].ctypes.data, C.byref(stats, lo * C.sizeof(_lib.cnf_solve_stats))), h)
         calls += 1
         if steps_of is not None:
@@ -179,23 +304,23 @@ def _launch(icnf: ICNF, s, call, steps_of, times_key, times, **more):
     if times is None:
         times = np.full(M, icnf.tspan[1], dtype=np.float32)
     info = {"stats": [st.as_dict() for st in stats], "status": status, "launches": max(st.launches for st in stats),
-            "calls": calls, "rerun": [], times_key: times, **more}
+            "calls": calls, "rerun": [], times_key: times, **_members_used(icnf, het, M, width), **more}
     return info, steps
 
 
-def _finish(icnf: ICNF, info, steps, times, rerun):
+def _finish(icnf: ICNF, info, steps, times, rerun, het=None):
     """The second half: a member that failed raises; the members whose part of the launch gave up are run again one at a
-    time.  ``rerun(i)`` runs member i on the single-model route, writes its outputs and returns ``(stats, steps)`` as that
+    time.  ``rerun(i, model, k)`` runs member i on the single-model route of ``model`` -- ``icnf``, or the twin that carries the
+    member's own lambdas and tolerances -- at its ``k`` columns, writes its outputs and returns ``(stats, steps)`` as that
     route reports them (None for what it does not report).  Fills ``info["rerun"]`` and, when steps were asked for,
     ``info["steps"]``."""
     status = info["status"]
     _raise_failed(status)
     gave_up = [i for i in range(len(status)) if status[i] != _lib.OK]
     if gave_up:
-        with _one_member_at_a_time(icnf, times) as member:
+        with _one_member_at_a_time(icnf, times, het) as member:
             for i in gave_up:
-                member(i)
-                stats_i, steps_i = rerun(i)
+                stats_i, steps_i = rerun(i, member(i), int(info["counts"][i]))
                 status[i] = _lib.OK
                 if stats_i is not None:
                     info["stats"][i] = stats_i
@@ -214,22 +339,35 @@ def _raise_failed(status):
 
 
 @contextmanager
-def _one_member_at_a_time(icnf: ICNF, times):
+def _one_member_at_a_time(icnf: ICNF, times, het=None):
     """For the re-run of the members whose part of the launch gave up -- the existing route, its fallbacks included: ``tspan``
-    and ``steer_rate`` are set aside and restored; ``member(i)`` of the yielded function puts member i's own time in."""
+    and ``steer_rate`` are set aside and restored; ``member(i)`` of the yielded function puts member i's own time in and returns
+    the model to run it on: ``icnf`` itself, or -- members with their own lambdas or tolerances -- a ``member_twin`` that carries
+    them (closed when the next one is asked for, and at the end)."""
     span, steer = icnf.tspan, icnf.steer_rate
+    own = het is not None and (het.lambdas is not None or het.tols is not None)
+    twin = []
 
     def member(i):
         if times is not None:
             icnf.tspan = (span[0], float(times[i]))
+        if not own:
+            return icnf
+        while twin:
+            twin.pop().close()
+        twin.append(member_twin(icnf, het.lambdas[i] if het.lambdas is not None else None, het.tols[i] if het.tols is not None else None))
+        return twin[0]                                     # (made behind the assignments above: it has the member's span, no steering)
     try:
         icnf.steer_rate = 0.0
         yield member
     finally:
         icnf.tspan, icnf.steer_rate = span, steer
+        while twin:
+            twin.pop().close()
 
 
-def loss_and_grad_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, with_steps=False):
+def loss_and_grad_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, with_steps=False, counts=None, lambdas=None,
+                       reltol=None, abstol=None):
     """``loss_and_grad`` of M members at once: ``xs`` (M, nvars, B) and ``ps`` (M, n_params) device tensors, ``eps``
     (M, n_in, B; TrainMode, drawn with ``draw_eps`` when not given), ``t1`` one end time per member (with ``steer_rate > 0``
     and ``t1=None`` each member gets its own ``steer_tspan`` draw: on a host generator member by member, the member's probes and
@@ -241,27 +379,35 @@ def loss_and_grad_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, wit
     ``with_steps`` also ``steps``: every member's signed accepted step sizes (cnf_ensemble_steps).  A member whose
     solve went non-finite or hit maxiters raises ``CNFError`` naming it.  ``NotImplementedError`` -- before anything is drawn --
     for what has no ensemble form: conditional models, a non-default ``basedist``, host arrays, PlanarLayer chains, networks
-    outside the in-launch gradient's envelope, ``kernel="generic"``."""
+    outside the in-launch gradient's envelope, ``kernel="generic"``.
+
+    Heterogeneous members (cnf_ensemble_set_members): ``counts`` -- M batch sizes within [1, B]: member m uses its first
+    ``counts[m]`` columns, every tensor keeps its rectangular shape, the columns at and behind a count are never read or written
+    by the device (value outputs there are NaN, input gradients 0, cotangents there are ignored) and a loss is the mean over the
+    member's own count; ``reltol`` / ``abstol`` -- a scalar or one per member, in place of ``sol_kwargs``'.  Member m computes, bit
+    for bit, what the call with M = 1 at ``B = counts[m]`` computes on ``member_twin`` of it.  ``info["counts"]``,
+    ``info["lambdas"]`` and ``info["tols"]`` (abstol, reltol) report what was used.  ``lambdas`` -- (M, 3): the members' own lambda_1..3 (a sweep), zero exactly where the model's are."""
     import torch
-    s = _settle_density(icnf, mode, xs, ps, eps, t1, "loss_and_grad_many", "loss_and_grad", "cnf_ensemble_capacity", shared=False)
+    s = _settle_density(icnf, mode, xs, ps, eps, t1, "loss_and_grad_many", "loss_and_grad", "cnf_ensemble_capacity", shared=False,
+                        members=dict(counts=counts, lambdas=lambdas, reltol=reltol, abstol=abstol))
     l, h = _lib.lib(), icnf.handle()
     m, M, B, xr, pr, er, t1 = s.m, s.M, s.B, s.xr, s.pr, s.er, s.t1
     opts = _solve_opts(icnf, icnf.tspan)
     grads = torch.empty((M, pr.shape[1]), dtype=torch.float32, device=s.dev)
     losses = np.empty(M, dtype=np.float32)
-    info, steps = _launch(icnf, s, lambda lo, n, status, stats: l.cnf_loss_grad_many(
+    info, steps = _launch(icnf, s, B, lambda lo, n, status, stats: l.cnf_loss_grad_many(
         h, m, n, pr[lo].data_ptr(), xr[lo].data_ptr(), er[lo].data_ptr() if er is not None else None, B, C.byref(opts),
         t1[lo:].ctypes.data if t1 is not None else None, losses[lo:].ctypes.data, grads[lo].data_ptr(), status, stats, s.stream),
         ensemble_steps if with_steps else None, "t1", t1)
 
-    def rerun(i):
-        args = dict(eps=er[i].t()) if s.train else {}
-        val, g = loss_and_grad(icnf, mode, xr[i].t(), pr[i], st, **args)
+    def rerun(i, model, k):
+        args = dict(eps=er[i, :k].t()) if s.train else {}
+        val, g = loss_and_grad(model, mode, xr[i, :k].t(), pr[i], st, **args)
         losses[i] = val
         grads[i].copy_(g)
-        return _stats_and_steps(icnf)
+        return _stats_and_steps(model)
 
-    _finish(icnf, info, steps, t1, rerun)
+    _finish(icnf, info, steps, t1, rerun, s.het)
     icnf.last_stats = info["stats"][0]
     return losses, grads, info
 
@@ -283,12 +429,34 @@ def ensemble_steps(icnf: ICNF, member: int):
     return hs[:n]
 
 
-def fit_many(model, verbosity: int, Xs, *, seeds=None):
-    """``mlj.fit`` for M data sets of the same number of rows (folds, bootstrap replicas, or one set M times), trained side by
+def _fit_batches(ns, use_batch, batch_size):
+    """The batches of one epoch of ``fit_many`` for data sets of ``ns`` rows: a list of ``(lo, counts)`` -- member m's batch is
+    ``perm_m[lo : lo + counts[m]]``.  ``ValueError`` unless every member has the same number of batches per epoch
+    (``ceil(n_m / batch_size)``): no member sits out an iteration.  Host logic only."""
+    ns = np.asarray(ns, dtype=np.int64)
+    if (ns < 1).any():
+        raise ValueError("fit_many: every data set needs at least one row")
+    if not use_batch:
+        return [(0, ns.copy())]
+    bs = int(batch_size)
+    k = (ns + bs - 1) // bs
+    if (k != k[0]).any():
+        raise ValueError(f"fit_many: every member needs the same number of batches per epoch; batch_size = {bs} gives {k.tolist()} "
+                         f"for data sets of {ns.tolist()} rows")
+    return [(lo, np.minimum(bs, ns - lo)) for lo in range(0, int(ns.max()), bs)]
+
+
+def fit_many(model, verbosity: int, Xs, *, seeds=None, lambdas=None, reltol=None, abstol=None):
+    """``mlj.fit`` for M data sets (folds, bootstrap replicas, or one set M times), trained side by
     side: member m is initialised with ``setup(seeds[m], ...)``, shuffles with its own generator seeded by ``seeds[m]`` and has
     its own rows of the optimiser's state; an iteration is one ``loss_and_grad_many`` and one application of the optimiser to
     the (M, n_params) tensor.  The loop is synchronous; the last, partial batch of an epoch is an ensemble call of its own
-    size.  The built-in loss only.  Returns ``([(ps_m, st)], report)``; ``report["losses"]`` is (M, iterations)."""
+    size.  The built-in loss only.  Returns ``([(ps_m, st)], report)``; ``report["losses"]`` is (M, iterations).
+
+    The data sets may have unequal numbers of rows as long as every member has the same number of batches per epoch
+    (``ceil(n_m / batch_size)``; ``ValueError`` otherwise, before anything is drawn): the last batch of an epoch is then the one
+    ragged call (``counts``).  ``lambdas`` (M, 3), ``reltol`` / ``abstol`` (scalar or M values) make the M members a sweep: they are
+    passed to every ``loss_and_grad_many``."""
     import torch
     from .base_icnf import loss as _builtin_loss
     from .mlj import _device_matrix
@@ -304,12 +472,17 @@ def fit_many(model, verbosity: int, Xs, *, seeds=None):
     seeds = list(range(M)) if seeds is None else [int(s) for s in seeds]
     if len(seeds) != M:
         raise ValueError("one seed per data set")
-    x = torch.stack([_device_matrix(icnf, X) for X in Xs])             # (M, nvars, n): equal row counts or stack refuses
+    ns = [int(np.shape(X)[0]) for X in Xs]                             # rows of the (n, nvars) tables
+    batches = _fit_batches(ns, model.use_batch, model.batch_size)
+    sweep = dict(lambdas=lambdas, reltol=reltol, abstol=abstol)
+    _members(icnf, M, max(ns), who="fit_many", **sweep)                # (checked before anything is drawn or asks for a device)
+    mats = [_device_matrix(icnf, X) for X in Xs]
+    ragged = len(set(ns)) > 1
+    x = pad_columns(mats, max(ns)) if ragged else torch.stack(mats)   # (M, nvars, n)
     n = x.shape[2]
     gens = [np.random.default_rng(s) for s in seeds]
     st = {}
     ps = torch.from_numpy(np.stack([setup(g, icnf.nn, init=model.init)[0] for g in gens])).to(x.device)
-    bs = model.batch_size if model.use_batch else n
     losses = []
     t0 = time.perf_counter()
     it = 0
@@ -317,18 +490,21 @@ def fit_many(model, verbosity: int, Xs, *, seeds=None):
     for opt in model.optimizers:
         state = opt.init(ps)
         for _epoch in range(model.n_epochs):
-            perm = torch.from_numpy(np.stack([g.permutation(n) for g in gens])).to(x.device)
-            for lo in range(0, n, bs):
-                idx = perm[:, lo:lo + bs]
+            perm = np.zeros((M, n), dtype=np.int64)                    # (behind a member's own rows: index 0, which no call reads)
+            for i, g in enumerate(gens):
+                perm[i, :ns[i]] = g.permutation(ns[i])
+            perm = torch.from_numpy(perm).to(x.device)
+            for lo, cnt in batches:
+                idx = perm[:, lo:lo + int(cnt.max())]
                 xb = x[rows, :, idx].permute(0, 2, 1)                  # (M, nvars, b): member m's own columns
-                val, g, _ = loss_and_grad_many(icnf, TrainMode(), xb, ps, st)
+                val, g, _ = loss_and_grad_many(icnf, TrainMode(), xb, ps, st, counts=cnt if (cnt != cnt[0]).any() else None, **sweep)
                 opt.apply(state, ps, g)
                 losses.append(val)
                 it += 1
                 if model.callback is not None:
                     model.callback(it, val)
             if verbosity > 0:
-                k = max(1, (n + bs - 1) // bs)
+                k = len(batches)
                 print(f"epoch {_epoch + 1}/{model.n_epochs}: mean loss per member "
                       f"{np.array2string(np.mean(losses[-k:], axis=0), precision=5)}", flush=True)
     torch.cuda.synchronize(x.device)
@@ -368,7 +544,8 @@ def _trace_cap(opts, with_steps):
     return min(int(opts.maxiters), _TRACE_ROWS) if with_steps else 0
 
 
-def inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, with_steps=False):
+def inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, with_steps=False, counts=None, lambdas=None, reltol=None,
+                   abstol=None):
     """``inference`` of M members in one launch (cnf_inference_many).  ``xs`` (M, nvars, B): one data set per member (the
     held-out folds), or (nvars, B): one data set scored by every member (bagging; expanded here, the kernel reads M copies);
     ``ps`` (M, n_params); ``eps`` (M, n_in, B; TrainMode) and ``t1`` as ``loss_and_grad_many`` takes and draws them, in its
@@ -377,37 +554,63 @@ def inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, with_st
     (more than one when M exceeds ``ensemble_eval_capacity``), ``rerun`` (the members whose part of the launch gave up and
     that were run again with ``inference``) and, with ``with_steps``, ``steps``: per member the rows ``(t, signed h, EEst,
     accepted)`` of its step attempts (None for a member that was run again).  A member whose solve went non-finite or hit maxiters raises ``CNFError`` naming it;
-    ``NotImplementedError`` -- before anything is drawn -- for what ``loss_and_grad_many`` refuses."""
+    ``NotImplementedError`` -- before anything is drawn -- for what ``loss_and_grad_many`` refuses.
+
+    Heterogeneous members (cnf_ensemble_set_members): ``counts`` -- M batch sizes within [1, B]: member m uses its first
+    ``counts[m]`` columns, every tensor keeps its rectangular shape, the columns at and behind a count are never read or written
+    by the device (value outputs there are NaN, input gradients 0, cotangents there are ignored) and a loss is the mean over the
+    member's own count; ``reltol`` / ``abstol`` -- a scalar or one per member, in place of ``sol_kwargs``'.  Member m computes, bit
+    for bit, what the call with M = 1 at ``B = counts[m]`` computes on ``member_twin`` of it.  ``info["counts"]``,
+    ``info["lambdas"]`` and ``info["tols"]`` (abstol, reltol) report what was used.  ``lambdas`` -- (M, 3): they weigh ``info["losses"]`` (``loss_many``)."""
     import torch
-    s = _settle_density(icnf, mode, xs, ps, eps, t1, "inference_many", "inference", "cnf_ensemble_eval_capacity")
+    s = _settle_density(icnf, mode, xs, ps, eps, t1, "inference_many", "inference", "cnf_ensemble_eval_capacity",
+                        members=dict(counts=counts, lambdas=lambdas, reltol=reltol, abstol=abstol))
     l, h = _lib.lib(), icnf.handle()
     m, M, B, dev, xr, pr, er, t1 = s.m, s.M, s.B, s.dev, s.xr, s.pr, s.er, s.t1
     opts = _solve_opts(icnf, icnf.tspan)
-    logpx, regs = torch.empty((M, B), dtype=torch.float32, device=dev), torch.empty((M, 3, B), dtype=torch.float32, device=dev)
+    logpx, regs = _values(s.het, (M, B), dev), _values(s.het, (M, 3, B), dev)
     losses = np.empty(M, dtype=np.float32)
     tc = _trace_cap(opts, with_steps)
-    info, steps = _launch(icnf, s, lambda lo, n, status, stats: l.cnf_inference_many(
+    info, steps = _launch(icnf, s, B, lambda lo, n, status, stats: l.cnf_inference_many(
         h, m, n, pr[lo].data_ptr(), xr[lo].data_ptr(), er[lo].data_ptr() if er is not None else None, B, C.byref(opts),
         t1[lo:].ctypes.data if t1 is not None else None, logpx[lo].data_ptr(), regs[lo].data_ptr(), losses[lo:].ctypes.data,
         status, stats, tc, s.stream), ensemble_eval_steps if with_steps else None, "t1", t1, losses=losses)
 
-    def rerun(i):
-        from .base_icnf import loss_from_sums
-        args = dict(eps=er[i].t()) if s.train else {}
-        lp, rg, sums = inference(icnf, mode, xr[i].t(), pr[i], st, with_sums=True, **args)
-        logpx[i].copy_(lp)
-        regs[i].copy_(torch.stack(list(rg)))
-        losses[i] = loss_from_sums(icnf, mode, sums)
-        return dict(icnf.last_stats), None             # (inference keeps no step trace: None for a member that was run again)
+    def rerun(i, model, k):
+        args = dict(eps=er[i, :k].t()) if s.train else {}
+        lp, rg, sums = inference(model, mode, xr[i, :k].t(), pr[i], st, with_sums=True, **args)
+        logpx[i, :k].copy_(lp)
+        regs[i, :, :k].copy_(torch.stack(list(rg)))
+        losses[i] = member_loss_from_sums(mode, sums, info["lambdas"][i])
+        return dict(model.last_stats), None            # (inference keeps no step trace: None for a member that was run again)
 
-    _finish(icnf, info, steps, t1, rerun)
+    _finish(icnf, info, steps, t1, rerun, s.het)
     icnf.last_stats = info["stats"][0]
     return logpx, (regs[:, 0], regs[:, 1], regs[:, 2]), info
 
 
-def loss_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None):
-    """The M members' losses (``loss`` of each on its own data): ``inference_many(...)[2]["losses"]``, a numpy vector."""
-    return inference_many(icnf, mode, xs, ps, st, eps=eps, t1=t1)[2]["losses"]
+def loss_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, counts=None, lambdas=None, reltol=None, abstol=None):
+    """The M members' losses (``loss`` of each on its own data): ``inference_many(...)[2]["losses"]``, a numpy vector -- with
+    ``counts`` means over the members' own counts, with ``lambdas`` weighed by the members' own regularisers."""
+    return inference_many(icnf, mode, xs, ps, st, eps=eps, t1=t1, counts=counts, lambdas=lambdas, reltol=reltol,
+                          abstol=abstol)[2]["losses"]
+
+
+def _values(het, shape, dev):
+    """A value output of an ensemble call: uninitialised, or -- members with their own counts -- NaN, which is what stays in the
+    columns the device does not touch."""
+    import torch
+    if het is not None and het.counts is not None:
+        return torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
+    return torch.empty(shape, dtype=torch.float32, device=dev)
+
+
+def _input_grads(het, shape, dev):
+    """... and an input gradient: zeros there, so that autograd through padded inputs is clean."""
+    import torch
+    if het is not None and het.counts is not None:
+        return torch.zeros(shape, dtype=torch.float32, device=dev)
+    return torch.empty(shape, dtype=torch.float32, device=dev)
 
 
 def _host_gen(icnf: ICNF):
@@ -443,10 +646,11 @@ def _check_sampling_inputs(icnf: ICNF, mode, ps, n, z0, eps, t0, who, single):
     return m, M, n, n_in, t0
 
 
-def _sampling_draws(icnf: ICNF, mode, train, M, n, n_in, dev, z0, eps, t0, steer=True):
+def _sampling_draws(icnf: ICNF, mode, train, M, n, n_in, dev, z0, eps, t0, steer=True, counts=None):
     """The members' base samples and probes ([M][n][n_in] on ``dev``) and start times (None: ``tspan[1]`` for all), given or
     drawn in the order ``generate_many`` documents.  ``steer=False``: no steer variate is drawn (the path calls, which are
-    this draw with one member)."""
+    this draw with one member).  ``counts``: on a host generator member m draws ``counts[m]`` columns of each -- what a loop of
+    ``generate`` at that size draws --, zeros behind them."""
     import torch
     zr = _rows(z0) if z0 is not None else None
     er = _rows(eps) if eps is not None else None
@@ -460,11 +664,14 @@ def _sampling_draws(icnf: ICNF, mode, train, M, n, n_in, dev, z0, eps, t0, steer
             t0 = np.asarray([steer_tspan(icnf, mode)[1] for _ in range(M)], dtype=np.float32)
     else:
         host, zs, es, starts = _Buf(None, n_in, n, None), [], [], []
-        for _ in range(M):                                 # generate_prob's order, member by member
+        for i in range(M):                                 # generate_prob's order, member by member
+            k = n if counts is None else int(counts[i])
             if zr is None:
-                zs.append(icnf.rng.standard_normal((n, n_in)).astype(np.float32))
+                zs.append(np.zeros((n, n_in), dtype=np.float32))
+                zs[-1][:k] = icnf.rng.standard_normal((k, n_in)).astype(np.float32)
             if er is None:
-                es.append(draw_eps(icnf, host, n).arr.reshape(n, n_in))
+                es.append(np.zeros((n, n_in), dtype=np.float32))
+                es[-1][:k] = draw_eps(icnf, host if k == n else _Buf(None, n_in, k, None), k).arr.reshape(k, n_in)
             if steer:
                 starts.append(steer_tspan(icnf, mode)[1])
         if zr is None:
@@ -476,25 +683,28 @@ def _sampling_draws(icnf: ICNF, mode, train, M, n, n_in, dev, z0, eps, t0, steer
     return zr, er, t0
 
 
-def _settle_sampling(icnf: ICNF, mode, ps, n, z0, eps, t0, who, single, capacity_fn=None, cot_pair=None):
+def _settle_sampling(icnf: ICNF, mode, ps, n, z0, eps, t0, who, single, capacity_fn=None, cot_pair=None, members=None):
     """``_settle_density`` for the sampling direction, in the same order: ``_check_sampling_inputs`` and ``cot_pair(M, n)``
     (the call's cotangent tensors); the handle; the device check; the capacity (None: not asked); ``_sampling_draws``.
-    Returns a namespace: ``m, M, n, n_in, train, cot, cap, dev, stream, pr, zr, er, t0``."""
+    ``members``: the call's ``counts``, ``reltol``, ``abstol`` (``_members``).  Returns a namespace: ``m, M, n, n_in, train, cot,
+    cap, dev, stream, pr, zr, er, t0, het``."""
     import torch
     m, M, n, n_in, t0 = _check_sampling_inputs(icnf, mode, ps, n, z0, eps, t0, who, single)
     cot = cot_pair(M, n) if cot_pair is not None else ()
+    het = _members(icnf, M, n, who=who, **members) if members else None
     h = icnf.handle() if capacity_fn is not None else None
     if not (ps.is_cuda and all(a is None or a.is_cuda for a in (z0, eps, *cot))):
         raise ValueError(f"{who}: torch tensors must live on the GPU")
     cap = _device_capacity(who, capacity_fn, h, m, n) if capacity_fn is not None else None
     train, dev = m == _lib.MODE_TRAIN, ps.device
     pr = ps.detach().to(torch.float32).contiguous()
-    zr, er, t0 = _sampling_draws(icnf, mode, train, M, n, n_in, dev, z0, eps, t0)
-    return SimpleNamespace(m=m, M=M, n=n, n_in=n_in, train=train, cot=cot, cap=cap, dev=dev, pr=pr, zr=zr, er=er, t0=t0,
+    zr, er, t0 = _sampling_draws(icnf, mode, train, M, n, n_in, dev, z0, eps, t0, counts=het.counts if het is not None else None)
+    return SimpleNamespace(m=m, M=M, n=n, n_in=n_in, train=train, cot=cot, cap=cap, dev=dev, pr=pr, zr=zr, er=er, t0=t0, het=het,
                            stream=_stream(_Buf(pr, pr.shape[1], M, torch)))
 
 
-def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, t0=None, with_logp=False, with_steps=False):
+def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, t0=None, with_logp=False, with_steps=False,
+                  counts=None, reltol=None, abstol=None):
     """``generate`` of M members in one launch (cnf_generate_many): ``ps`` (M, n_params) on the device, ``z0`` and ``eps``
     (M, n_in, n) device tensors or drawn as ``generate_prob`` draws them -- on a host generator member by member: the member's
     base sample, its probes (drawn in TestMode too, and not used there), then its steered time; with a ``HIPRNG`` ONE draw of
@@ -504,31 +714,33 @@ def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, 
     its member (``generate(..., with_logp=True)``).  ``icnf.last_ensemble_info`` holds ``stats``, ``status``, ``launches`` (2:
     the solve and the column kernel), ``calls``, ``rerun``, ``t0`` and the inputs used (``z0``, ``eps``); after ``with_steps``
     the members' step attempts are read with ``ensemble_eval_steps`` (``info["steps"]``).  Failures and refusals as
-    ``inference_many``."""
+    ``inference_many``.  ``counts``, ``reltol``, ``abstol``: heterogeneous members, as ``loss_and_grad_many`` takes them (``n`` is then the rectangle's width: member m samples ``counts[m]``
+    columns, ``xs`` and ``logq`` behind them are NaN)."""
     import torch
-    s = _settle_sampling(icnf, mode, ps, n, z0, eps, t0, "generate_many", "generate", "cnf_ensemble_eval_capacity")
+    s = _settle_sampling(icnf, mode, ps, n, z0, eps, t0, "generate_many", "generate", "cnf_ensemble_eval_capacity",
+                         members=dict(counts=counts, reltol=reltol, abstol=abstol))
     l, h = _lib.lib(), icnf.handle()
     m, M, n, dev, pr, zr, er, t0 = s.m, s.M, s.n, s.dev, s.pr, s.zr, s.er, s.t0
     opts = _solve_opts(icnf, (icnf.tspan[1], icnf.tspan[0]))              # reverse(tspan)
-    xo = torch.empty((M, n, icnf.nvars), dtype=torch.float32, device=dev)
-    lq = torch.empty((M, n), dtype=torch.float32, device=dev) if with_logp else None
+    xo = _values(s.het, (M, n, icnf.nvars), dev)
+    lq = _values(s.het, (M, n), dev) if with_logp else None
     tc = _trace_cap(opts, with_steps)
-    info, steps = _launch(icnf, s, lambda lo, k, status, stats: l.cnf_generate_many(
+    info, steps = _launch(icnf, s, n, lambda lo, k, status, stats: l.cnf_generate_many(
         h, m, k, pr[lo].data_ptr(), zr[lo].data_ptr(), er[lo].data_ptr() if s.train else None, n, C.byref(opts),
         t0[lo:].ctypes.data if t0 is not None else None, xo[lo].data_ptr(), lq[lo].data_ptr() if with_logp else None,
         status, stats, tc, s.stream), ensemble_eval_steps if with_steps else None, "t0", t0,
         z0=zr.permute(0, 2, 1), eps=er.permute(0, 2, 1))
     icnf.last_ensemble_info = info                         # (published before a failed member raises: it says which)
 
-    def rerun(i):
-        r = generate(icnf, mode, pr[i], st, n, z0=zr[i].t(), eps=er[i].t(), with_logp=with_logp)
+    def rerun(i, model, k):
+        r = generate(model, mode, pr[i], st, k, z0=zr[i, :k].t(), eps=er[i, :k].t(), with_logp=with_logp)
         xs_i = r[0] if with_logp else r
-        xo[i].copy_(torch.as_tensor(xs_i, device=dev)[: icnf.nvars].t())
+        xo[i, :k].copy_(torch.as_tensor(xs_i, device=dev)[: icnf.nvars].t())
         if with_logp:
-            lq[i].copy_(torch.as_tensor(r[1], device=dev))
+            lq[i, :k].copy_(torch.as_tensor(r[1], device=dev))
         return None, None                              # (generate reports no statistics: the launch's stay)
 
-    _finish(icnf, info, steps, t0, rerun)
+    _finish(icnf, info, steps, t0, rerun, s.het)
     xs = xo.permute(0, 2, 1)                               # (generate does not set icnf.last_stats; nor does this)
     return (xs, lq) if with_logp else xs
 
@@ -558,7 +770,8 @@ def _cot_many(cot, M, B):
     return rows
 
 
-def inference_vjp_many(icnf: ICNF, mode, xs, ps, st, cot, eps=None, t1=None, with_x=False, with_steps=False):
+def inference_vjp_many(icnf: ICNF, mode, xs, ps, st, cot, eps=None, t1=None, with_x=False, with_steps=False, counts=None,
+                       reltol=None, abstol=None):
     """``inference`` of M members and its vector-Jacobian product for a per-sample cotangent, in ONE launch and one of the
     partial sums (cnf_inference_vjp_many): what ``inference_record`` + ``inference_pullback`` give for one model.  ``xs``
     (M, nvars, B) or (nvars, B): one data set shared by all members, as ``inference_many`` takes it; ``ps`` (M, n_params);
@@ -569,10 +782,12 @@ def inference_vjp_many(icnf: ICNF, mode, xs, ps, st, cot, eps=None, t1=None, wit
     ``grads[m] = sum_b sum_r cot[r][m, b] d out_r[m, b] / d ps[m]`` through the steps member m's own solve accepted.  ``info``
     as ``loss_and_grad_many``'s, with ``eps`` (M, n_in, B; None in TestMode): the probes used; a member whose part of the launch
     gave up is run again with ``inference_record`` + ``inference_pullback`` (``info["rerun"]``).  Failures and refusals as
-    ``loss_and_grad_many``."""
+    ``loss_and_grad_many``.  ``counts``, ``reltol``, ``abstol``: heterogeneous members, as ``loss_and_grad_many`` takes them (``grad_x`` is 0 behind a member's count, the cotangents there are
+    ignored)."""
     import torch
     s = _settle_density(icnf, mode, xs, ps, eps, t1, "inference_vjp_many", "inference_record and inference_pullback",
-                        "cnf_ensemble_vjp_capacity", cot_rows=lambda M, B: _cot_many(cot, M, B))
+                        "cnf_ensemble_vjp_capacity", cot_rows=lambda M, B: _cot_many(cot, M, B),
+                        members=dict(counts=counts, reltol=reltol, abstol=abstol))
     l, h = _lib.lib(), icnf.handle()
     m, M, B, dev, xr, pr, er, t1 = s.m, s.M, s.B, s.dev, s.xr, s.pr, s.er, s.t1
     cm = torch.zeros((M, 4, B), dtype=torch.float32, device=dev)
@@ -580,10 +795,10 @@ def inference_vjp_many(icnf: ICNF, mode, xs, ps, st, cot, eps=None, t1=None, wit
         if r is not None:
             cm[:, i].copy_(r.detach())
     opts = _solve_opts(icnf, icnf.tspan)
-    logpx, regs = torch.empty((M, B), dtype=torch.float32, device=dev), torch.empty((M, 3, B), dtype=torch.float32, device=dev)
+    logpx, regs = _values(s.het, (M, B), dev), _values(s.het, (M, 3, B), dev)
     grads = torch.empty((M, pr.shape[1]), dtype=torch.float32, device=dev)
-    gz = torch.empty((M, B, s.n_in), dtype=torch.float32, device=dev) if with_x else None
-    info, steps = _launch(icnf, s, lambda lo, n, status, stats: l.cnf_inference_vjp_many(
+    gz = _input_grads(s.het, (M, B, s.n_in), dev) if with_x else None
+    info, steps = _launch(icnf, s, B, lambda lo, n, status, stats: l.cnf_inference_vjp_many(
         h, m, n, pr[lo].data_ptr(), xr[lo].data_ptr(), er[lo].data_ptr() if er is not None else None, B, C.byref(opts),
         t1[lo:].ctypes.data if t1 is not None else None, cm[lo].data_ptr(), logpx[lo].data_ptr(), regs[lo].data_ptr(),
         grads[lo].data_ptr(), gz[lo].data_ptr() if with_x else None, status, stats, s.stream),
@@ -591,18 +806,18 @@ def inference_vjp_many(icnf: ICNF, mode, xs, ps, st, cot, eps=None, t1=None, wit
     icnf._record = None                                    # (the call ended whatever was recorded on the handle)
     gx = gz[:, :, :icnf.nvars].permute(0, 2, 1).contiguous() if with_x else None
 
-    def rerun(i):
+    def rerun(i, model, k):
         from .vjp import inference_pullback, inference_record
-        lp, rg = inference_record(icnf, mode, xr[i].t(), pr[i], st, eps=er[i].t() if s.train else None, tspan=icnf.tspan)
-        res = inference_pullback(icnf, cm[i], with_x=with_x)
-        logpx[i].copy_(lp)
-        regs[i].copy_(torch.stack(list(rg)))
+        lp, rg = inference_record(model, mode, xr[i, :k].t(), pr[i], st, eps=er[i, :k].t() if s.train else None, tspan=icnf.tspan)
+        res = inference_pullback(model, cm[i, :, :k].contiguous(), with_x=with_x)
+        logpx[i, :k].copy_(lp)
+        regs[i, :, :k].copy_(torch.stack(list(rg)))
         grads[i].copy_(res[0] if with_x else res)
         if with_x:
-            gx[i].copy_(res[1])
-        return _stats_and_steps(icnf)
+            gx[i, :, :k].copy_(res[1])
+        return _stats_and_steps(model)
 
-    _finish(icnf, info, steps, t1, rerun)
+    _finish(icnf, info, steps, t1, rerun, s.het)
     icnf._record = None                                    # (the members' records are not the caller's)
     icnf.last_stats = info["stats"][0]
     out = (logpx, (regs[:, 0], regs[:, 1], regs[:, 2]), grads)
@@ -615,9 +830,9 @@ def _autograd_function_many():
 
     class _InferenceMany(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, icnf, mode, xs, ps, eps, t1):
-            logpx, (E, n, A), _ = inference_many(icnf, mode, xs.detach(), ps.detach(), None, eps=eps, t1=t1)
-            ctx.icnf, ctx.mode = icnf, mode
+        def forward(ctx, icnf, mode, xs, ps, eps, t1, het):
+            logpx, (E, n, A), _ = inference_many(icnf, mode, xs.detach(), ps.detach(), None, eps=eps, t1=t1, **het)
+            ctx.icnf, ctx.mode, ctx.het = icnf, mode, het
             # what the backward launch solves again: the same data, parameters, probes and end times
             ctx.xs, ctx.ps, ctx.eps, ctx.t1 = xs.detach(), ps.detach().clone(), eps, t1
             ctx.set_materialize_grads(False)
@@ -628,32 +843,34 @@ def _autograd_function_many():
             icnf = ctx.icnf
             need_x, need_ps = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
             if not (need_x or need_ps):
-                return None, None, None, None, None, None
+                return None, None, None, None, None, None, None
             res = inference_vjp_many(icnf, ctx.mode, ctx.xs, ctx.ps, None, (g_logpx, (g_E, g_n, g_A)), eps=ctx.eps, t1=ctx.t1,
-                                     with_x=bool(need_x))
+                                     with_x=bool(need_x), **ctx.het)
             icnf.last_backward_logpx = res[0]              # (the backward launch's own logpx: compared with the forward's in the tests)
             gx = None
             if need_x:
                 gx = res[3] if ctx.xs.dim() == 3 else res[3].sum(dim=0)    # (a shared data set collects every member's)
-            return None, None, gx, res[2] if need_ps else None, None, None
+            return None, None, gx, res[2] if need_ps else None, None, None, None
 
     return _InferenceMany
 
 
-def differentiable_inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None):
+def differentiable_inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, counts=None, reltol=None, abstol=None):
     """``inference_many`` as a differentiable function of ``ps`` (M, n_params) and, when it requires grad, ``xs`` ((M, nvars, B),
     or (nvars, B) shared by all members): the forward is ``inference_many``, keeping the probes and end times it used; the
     backward is ONE ``inference_vjp_many`` with those same draws.  Returns ``(logpx (M, B), (E, n, A))`` attached to the autograd
     graph.  The backward launch solves again: its gradient is the exact discrete adjoint of the steps IT accepts (the solve is
     deterministic, so they are the forward's for the same inputs; DESIGN 4.4 says how its ``logpx`` compares with the
-    forward's -- ``icnf.last_backward_logpx`` keeps it)."""
+    forward's -- ``icnf.last_backward_logpx`` keeps it).  ``counts``, ``reltol``, ``abstol``: heterogeneous members, as ``loss_and_grad_many`` takes them: the outputs behind a member's count are NaN
+    (mask them out of a loss: their cotangents are ignored) and the gradient of ``xs`` there is 0."""
     if not (_is_torch(xs) and _is_torch(ps)):
         raise NotImplementedError("differentiable_inference_many takes device tensors")
     # the probes and the steered end times are settled here, once (inference_many's order: the probes, then the end times), so
     # that forward and backward are given the very same ones
-    s = _settle_density(icnf, mode, xs.detach(), ps, eps, t1, "differentiable_inference_many", "differentiable_inference")
+    het = dict(counts=counts, reltol=reltol, abstol=abstol)
+    s = _settle_density(icnf, mode, xs.detach(), ps, eps, t1, "differentiable_inference_many", "differentiable_inference", members=het)
     eps = s.er.permute(0, 2, 1) if s.er is not None else None
-    logpx, E, n, A = _autograd_function_many().apply(icnf, mode, xs, ps, eps, s.t1)
+    logpx, E, n, A = _autograd_function_many().apply(icnf, mode, xs, ps, eps, s.t1, het)
     return logpx, (E, n, A)
 
 
@@ -686,7 +903,8 @@ def _cot_pair_many(icnf: ICNF, cot, M, n):
     return gx, gl
 
 
-def generate_vjp_many(icnf: ICNF, mode, ps, st, n, cot, z0=None, eps=None, t0=None, with_z0=False, with_steps=False):
+def generate_vjp_many(icnf: ICNF, mode, ps, st, n, cot, z0=None, eps=None, t0=None, with_z0=False, with_steps=False, counts=None,
+                      reltol=None, abstol=None):
     """``generate`` of M members with the log-density of every sample, and the vector-Jacobian product of both for a per-sample
     cotangent, in ONE launch and one of the partial sums plus the column kernels (cnf_generate_vjp_many): what
     ``generate_record`` + ``generate_pullback`` give for one model.  ``ps`` (M, n_params) on the device; ``cot = (g_x, g_logq)``:
@@ -699,10 +917,12 @@ def generate_vjp_many(icnf: ICNF, mode, ps, st, n, cot, z0=None, eps=None, t0=No
     ``generate_many``'s (``t0``, ``z0``, ``eps``: the inputs used), ``launches`` counting the column kernels too; with
     ``with_steps`` also ``steps``: every member's signed accepted step sizes (cnf_ensemble_steps).  A member whose part of the
     launch gave up is run again with ``generate_record`` + ``generate_pullback`` (``info["rerun"]``).  Failures and refusals as
-    ``generate_many``: ``NotImplementedError`` before anything is drawn."""
+    ``generate_many``: ``NotImplementedError`` before anything is drawn.  ``counts``, ``reltol``, ``abstol``: heterogeneous members, as ``loss_and_grad_many`` takes them (``grad_z0`` is 0 behind a
+    member's count, the cotangents there are ignored)."""
     import torch
     s = _settle_sampling(icnf, mode, ps, n, z0, eps, t0, "generate_vjp_many", "generate_record and generate_pullback",
-                         "cnf_ensemble_generate_vjp_capacity", cot_pair=lambda M, n: _cot_pair_many(icnf, cot, M, n))
+                         "cnf_ensemble_generate_vjp_capacity", cot_pair=lambda M, n: _cot_pair_many(icnf, cot, M, n),
+                         members=dict(counts=counts, reltol=reltol, abstol=abstol))
     l, h = _lib.lib(), icnf.handle()
     m, M, n, n_in, dev, pr, zr, er, t0 = s.m, s.M, s.n, s.n_in, s.dev, s.pr, s.zr, s.er, s.t0
     gx, gl = s.cot
@@ -713,11 +933,11 @@ def generate_vjp_many(icnf: ICNF, mode, ps, st, n, cot, z0=None, eps=None, t0=No
     if gl is not None:
         cl = gl.detach().to(torch.float32).contiguous()
     opts = _solve_opts(icnf, (icnf.tspan[1], icnf.tspan[0]))              # reverse(tspan)
-    xo = torch.empty((M, n, icnf.nvars), dtype=torch.float32, device=dev)
-    lq = torch.empty((M, n), dtype=torch.float32, device=dev)
+    xo = _values(s.het, (M, n, icnf.nvars), dev)
+    lq = _values(s.het, (M, n), dev)
     grads = torch.empty((M, pr.shape[1]), dtype=torch.float32, device=dev)
-    gz = torch.empty((M, n, n_in), dtype=torch.float32, device=dev) if with_z0 else None
-    info, steps = _launch(icnf, s, lambda lo, k, status, stats: l.cnf_generate_vjp_many(
+    gz = _input_grads(s.het, (M, n, n_in), dev) if with_z0 else None
+    info, steps = _launch(icnf, s, n, lambda lo, k, status, stats: l.cnf_generate_vjp_many(
         h, m, k, pr[lo].data_ptr(), zr[lo].data_ptr(), er[lo].data_ptr() if s.train else None, n, C.byref(opts),
         t0[lo:].ctypes.data if t0 is not None else None, cz[lo].data_ptr() if cz is not None else None,
         cl[lo].data_ptr() if cl is not None else None, xo[lo].data_ptr(), lq[lo].data_ptr(), grads[lo].data_ptr(),
@@ -726,18 +946,19 @@ def generate_vjp_many(icnf: ICNF, mode, ps, st, n, cot, z0=None, eps=None, t0=No
     icnf._record = None                                    # (the call ended whatever was recorded on the handle)
     icnf.last_ensemble_info = info
 
-    def rerun(i):
+    def rerun(i, model, k):
         from .gen_vjp import generate_pullback, generate_record
-        x_i, lq_i = generate_record(icnf, mode, pr[i], st, n, z0=zr[i].t(), eps=er[i].t(), tspan=icnf.tspan)
-        res = generate_pullback(icnf, (cz[i].t() if cz is not None else None, cl[i] if cl is not None else None), with_z0=with_z0)
-        xo[i].copy_(x_i.t())
-        lq[i].copy_(lq_i)
+        x_i, lq_i = generate_record(model, mode, pr[i], st, k, z0=zr[i, :k].t(), eps=er[i, :k].t(), tspan=icnf.tspan)
+        res = generate_pullback(model, (cz[i, :k].t() if cz is not None else None, cl[i, :k] if cl is not None else None),
+                                with_z0=with_z0)
+        xo[i, :k].copy_(x_i.t())
+        lq[i, :k].copy_(lq_i)
         grads[i].copy_(res[0] if with_z0 else res)
         if with_z0:
-            gz[i].copy_(res[1].t())
-        return _stats_and_steps(icnf)
+            gz[i, :k].copy_(res[1].t())
+        return _stats_and_steps(model)
 
-    _finish(icnf, info, steps, t0, rerun)
+    _finish(icnf, info, steps, t0, rerun, s.het)
     icnf._record = None                                    # (the members' records are not the caller's)
     icnf.last_stats = info["stats"][0]
     out = (xo.permute(0, 2, 1), lq, grads)
@@ -750,10 +971,10 @@ def _autograd_function_generate_many():
 
     class _GenerateMany(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, icnf, mode, ps, z0, eps, t0):
+        def forward(ctx, icnf, mode, ps, z0, eps, t0, het):
             n = z0.shape[2]
-            xs, logq = generate_many(icnf, mode, ps.detach(), None, n, z0=z0.detach(), eps=eps, t0=t0, with_logp=True)
-            ctx.icnf, ctx.mode = icnf, mode
+            xs, logq = generate_many(icnf, mode, ps.detach(), None, n, z0=z0.detach(), eps=eps, t0=t0, with_logp=True, **het)
+            ctx.icnf, ctx.mode, ctx.het = icnf, mode, het
             # what the backward launch solves again: the same parameters, base draws, probes and start times
             ctx.ps, ctx.z0, ctx.eps, ctx.t0 = ps.detach().clone(), z0.detach(), eps, t0
             ctx.set_materialize_grads(False)
@@ -764,42 +985,55 @@ def _autograd_function_generate_many():
             icnf = ctx.icnf
             need_ps, need_z0 = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
             if (g_x is None and g_logq is None) or not (need_ps or need_z0):
-                return None, None, None, None, None, None
+                return None, None, None, None, None, None, None
             res = generate_vjp_many(icnf, ctx.mode, ctx.ps, None, ctx.z0.shape[2], (g_x, g_logq), z0=ctx.z0, eps=ctx.eps, t0=ctx.t0,
-                                    with_z0=bool(need_z0))
+                                    with_z0=bool(need_z0), **ctx.het)
             # (the backward launch's own outputs: compared with the forward's in the tests)
             icnf.last_backward_xs, icnf.last_backward_logq = res[0], res[1]
-            return None, None, res[2] if need_ps else None, res[3].contiguous() if need_z0 else None, None, None
+            return None, None, res[2] if need_ps else None, res[3].contiguous() if need_z0 else None, None, None, None
 
     return _GenerateMany
 
 
-def differentiable_generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, t0=None):
+def differentiable_generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, t0=None, counts=None, reltol=None,
+                                 abstol=None):
     """``generate_many(with_logp=True)`` as a differentiable function of ``ps`` (M, n_params) and, when it requires grad, ``z0``
     (M, n_in, n): the forward is ``generate_many`` with the base draws, probes and steered start times settled once (its order);
     the backward is ONE ``generate_vjp_many`` with those same draws.  Returns ``(xs (M, nvars, n), logq (M, n))`` attached to the
     autograd graph.  The backward launch solves again: its gradient is the exact discrete adjoint of the steps IT accepts (the
     solve is deterministic, so they are the forward's for the same inputs; DESIGN 4.4 says how its ``xs`` / ``logq`` compare with
-    the forward's -- ``icnf.last_backward_logq`` and ``icnf.last_backward_xs`` keep them)."""
+    the forward's -- ``icnf.last_backward_logq`` and ``icnf.last_backward_xs`` keep them).  ``counts``, ``reltol``, ``abstol``: heterogeneous members, as ``loss_and_grad_many`` takes them: ``xs`` and
+    ``logq`` behind a member's count are NaN (mask them out of a loss) and the gradient of ``z0`` there is 0."""
+    het = dict(counts=counts, reltol=reltol, abstol=abstol)
     s = _settle_sampling(icnf, mode, ps, n, z0.detach() if _is_torch(z0) else z0, eps, t0, "differentiable_generate_many",
-                         "differentiable_generate")
+                         "differentiable_generate", members=het)
     if not (z0 is not None and z0.requires_grad):          # (a z0 that asks for a gradient stays the caller's tensor)
         z0 = s.zr.permute(0, 2, 1)
-    return _autograd_function_generate_many().apply(icnf, mode, ps, z0, s.er.permute(0, 2, 1), s.t0)
+    return _autograd_function_generate_many().apply(icnf, mode, ps, z0, s.er.permute(0, 2, 1), s.t0, het)
 
 
-def reverse_kl_many(icnf: ICNF, mode, ps, st, n, target_logpdf, **kw):
+def reverse_kl_many(icnf: ICNF, mode, ps, st, n, target_logpdf, counts=None, reltol=None, abstol=None, **kw):
     """The M members' reverse Kullback-Leibler divergences to unnormalised targets, each estimated on ``n`` samples of its
     member: ``(logq - target_logpdf(xs)).mean(dim=1)``, an (M,) tensor, with ``(xs, logq) = differentiable_generate_many(icnf,
     mode, ps, st, n, **kw)`` -- M variational fits (restarts, targets of one family, a temperature ladder) differentiated by one
     launch; sum or weight the losses as the problem asks.  ``target_logpdf`` is ONE torch callable for all members: it takes
     the samples (M, nvars, n) and returns (M, n) log-densities, so that members with different targets index their own
-    parameters by the leading axis (a per-member list would be M calls on slices of one tensor)."""
-    xs, logq = differentiable_generate_many(icnf, mode, ps, st, n, **kw)
-    t = target_logpdf(xs)
+    parameters by the leading axis (a per-member list would be M calls on slices of one tensor).  ``counts``, ``reltol``, ``abstol``: heterogeneous members, as ``loss_and_grad_many`` takes them: member
+    m's divergence is the mean over its own ``counts[m]`` samples (``target_logpdf`` sees zeros in the columns behind them, and
+    what it returns there is not used)."""
+    import torch
+    xs, logq = differentiable_generate_many(icnf, mode, ps, st, n, counts=counts, reltol=reltol, abstol=abstol, **kw)
+    if counts is None:
+        t = target_logpdf(xs)
+        if tuple(t.shape) != tuple(logq.shape):
+            raise ValueError(f"target_logpdf must return (M = {logq.shape[0]}, n = {logq.shape[1]}), got {tuple(t.shape)}")
+        return (logq - t).mean(dim=1)
+    c = torch.as_tensor(np.asarray(counts), device=logq.device)
+    live = torch.arange(logq.shape[1], device=logq.device)[None, :] < c[:, None]
+    t = target_logpdf(torch.where(live[:, None, :], xs, torch.zeros_like(xs)))
     if tuple(t.shape) != tuple(logq.shape):
         raise ValueError(f"target_logpdf must return (M = {logq.shape[0]}, n = {logq.shape[1]}), got {tuple(t.shape)}")
-    return (logq - t).mean(dim=1)
+    return torch.where(live, logq - t, torch.zeros_like(logq)).sum(dim=1) / c.to(logq.dtype)
 
 
 # ---- the bagged density: a mixture of the members ----
@@ -884,12 +1118,15 @@ class EnsembleDist:
         w = self.weights_t if self.weights_t is not None else torch.as_tensor(self.weights)
         return torch.logsumexp(logp + torch.log(w.to(device=logp.device, dtype=logp.dtype))[:, None], dim=0)
 
-    def rand(self, n: int, *, with_members=False):
+    def rand(self, n: int, *, with_members=False, ragged=False):
         """``n`` draws of the mixture, (nvars, n) on the device: the members' counts from one multinomial draw on the model's
         host generator (``split_counts``), then ONE ``generate_many`` with ``B = max count`` columns per member, of which member
         m keeps its first ``count_m``; the draws are ordered by member.  The launch computes M max(count) columns for n kept
         ones: M max(count) - n are wasted (about (M - 1) / M of them for a one-hot mixture, few for uniform weights and
-        n >> M).  ``with_members``: also the member index of every column."""
+        n >> M).  ``with_members``: also the member index of every column.  ``ragged=True``: the same multinomial draw, then one
+        ``generate_many`` over the members with a non-zero count only, with ``counts`` = their counts: every member solves just
+        its own columns (a one-hot mixture launches one member); on a host generator the base draws are then the members' own
+        ``count_m`` columns, so the samples differ from the default's for the same seed."""
         import torch
         if int(n) < 1:                                     # (nothing is drawn, nothing is launched)
             if int(n) < 0:
@@ -897,6 +1134,12 @@ class EnsembleDist:
             out = torch.empty((self.m.nvars, 0), dtype=torch.float32, device=self.ps.device)
             return (out, np.zeros(0, dtype=np.int64)) if with_members else out
         counts = split_counts(_host_gen(self.m), n, self.weights)
+        if ragged:
+            live = np.flatnonzero(counts)
+            xs = generate_many(self.m, self.mode, self.ps[torch.as_tensor(live, device=self.ps.device)], self.st, int(counts.max()),
+                               counts=counts[live])
+            out = torch.cat([xs[j, :, :counts[i]] for j, i in enumerate(live)], dim=1)
+            return (out, np.repeat(np.arange(len(counts)), counts)) if with_members else out
         xs = generate_many(self.m, self.mode, self.ps, self.st, int(counts.max()))
         out = torch.cat([xs[i, :, :c] for i, c in enumerate(counts)], dim=1)
         if with_members:

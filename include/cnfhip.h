@@ -378,6 +378,10 @@ cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int B, float* 
  * cnfhip_ensemble_generate_vjp.h, part of this header) ---- */
 #include "cnfhip_ensemble_generate_vjp.h"
 
+/* ---- heterogeneous ensembles: cnf_ensemble_set_members / cnf_ensemble_clear_members -- per-member batch size, lambdas and
+ * tolerances for the next ensemble call (declared in cnfhip_ensemble_hetero.h, part of this header) ---- */
+#include "cnfhip_ensemble_hetero.h"
+
 /* ---- flow paths: the solve's columns at caller-given times, from Tsit5's interpolant (declared in cnfhip_path.h, part of this
  * header) ---- */
 #include "cnfhip_path.h"
