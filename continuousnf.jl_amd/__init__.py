@@ -70,6 +70,10 @@ from .path import generate_path, inference_path, solve_path
 from . import path_vjp
 from .path_vjp import differentiable_generate_path, differentiable_inference_path, generate_path_vjp, inference_path_vjp, \
     path_vjp_max_batch, path_vjp_steps
+from . import ensemble_path
+from .ensemble_path import differentiable_generate_path_many, differentiable_inference_path_many, ensemble_path_capacity, \
+    ensemble_path_steps, ensemble_path_vjp_capacity, generate_path_many, generate_path_vjp_many, inference_path_many, \
+    inference_path_vjp_many
 from .mlj import (Adam, CondICNFModel, ICNFModel, Lion, Machine, fit, fit_, fitted_params, load_params, machine, save_params,
                   transform)
 

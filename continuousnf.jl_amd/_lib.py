@@ -190,6 +190,21 @@ _ENSEMBLE_HETERO_SIGNATURES = {
     "cnf_ensemble_clear_members": (C.c_int, [C.c_void_p]),
 }
 ENSEMBLE_HETERO_EXPORTS = tuple(_ENSEMBLE_HETERO_SIGNATURES)
+# ensemble flow paths (include/cnfhip_ensemble_path.h): likewise
+_ENSEMBLE_PATH_SIGNATURES = {
+    "cnf_ensemble_path_capacity": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "cnf_ensemble_path_vjp_capacity": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "cnf_inference_path_many": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), _fp, _fp, _fp, _fp,
+                                          _fp, C.c_void_p, C.c_int, C.c_void_p, _fp, C.c_int, C.c_int, _fp]),
+    "cnf_generate_path_many": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), _fp, _fp, _fp,
+                                         _fp, C.c_void_p, C.c_int, C.c_void_p, _fp, C.c_int, C.c_int, _fp]),
+    "cnf_inference_path_vjp_many": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), _fp, C.c_int,
+                                              C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p, C.c_void_p]),
+    "cnf_generate_path_vjp_many": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), _fp, C.c_int,
+                                             C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p, C.c_void_p]),
+    "cnf_ensemble_path_steps": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.c_int]),
+}
+ENSEMBLE_PATH_EXPORTS = tuple(_ENSEMBLE_PATH_SIGNATURES)
 
 _lib = None
 
@@ -230,7 +245,7 @@ def lib():
         for name, (res, args) in list(_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) + list(_BASEGRAD_SIGNATURES.items()) + \
                 list(_ENSEMBLE_SIGNATURES.items()) + list(_ENSEMBLE_EVAL_SIGNATURES.items()) + list(_ENSEMBLE_VJP_SIGNATURES.items()) + \
                 list(_ENSEMBLE_GENERATE_VJP_SIGNATURES.items()) + list(_PATH_SIGNATURES.items()) + list(_PATH_VJP_SIGNATURES.items()) + \
-                list(_ENSEMBLE_HETERO_SIGNATURES.items()):
+                list(_ENSEMBLE_HETERO_SIGNATURES.items()) + list(_ENSEMBLE_PATH_SIGNATURES.items()):
             f = getattr(l, name)
             f.restype, f.argtypes = res, args
         _lib = l

@@ -197,9 +197,19 @@ struct cnf_ctx {
     // steps of the last such call (cnf_path_vjp_steps)
     std::vector<float> pvjp_t, pvjp_h;
     bool pvjp_valid = false;
+    // the four calls of include/cnfhip_ensemble_path.h: the members' step pairs, a buffer of their own (the single-model calls'
+    // steps above are not theirs to overwrite), read back on demand (cnf_ensemble_path_steps)
+    DevBuf<float> ens_psteps;     // [M][epath_cap][2]
+    int epath_M = 0, epath_cap = 0;  // the last such call: members, step pairs a member files
+    std::vector<int> epath_nacc;  //   accepted steps per member (-1: the member was not CNF_OK)
+    std::vector<float> epath_host;   // [M][epath_rows][2]: the pairs on the host, fetched by ONE strided copy when first asked for
+    int epath_rows = -1;          //   pairs per member in epath_host (-1: not fetched yet)
+    std::vector<float> saveat_rep;   // one set of save times laid out M times, on its way to the device
     std::string err;
 };
 static const int PATH_STEPS_CAP = 16384;
+// ... and per member of the ensemble path calls: the plain ones | the vjp ones (WV_GCAP: what a launch differentiates)
+static const int ENS_PATH_STEPS_CAP = 4096, ENS_PATH_VJP_STEPS_CAP = 1024;
 
 static const int MAX_PARTIALS = 1024;
 
@@ -2683,6 +2693,7 @@ struct EnsCall {
     std::vector<float> lams, tols;
     const int* d_counts = nullptr;         // ... on the device, from ens_begin on (null: not given)
     const float *d_lams = nullptr, *d_tols = nullptr;
+    bool path_many = false;        // one of the four calls of include/cnfhip_ensemble_path.h: their own capacities
 };
 // The one-shot state changes hands: whatever becomes of the call, no later call is steered by these arrays.
 static void ens_take_members(cnf_handle h, EnsCall& c) {
@@ -2721,7 +2732,8 @@ static cnf_status ens_check(cnf_handle h, const EnsCall& c, bool null_ptr, const
     while (!h->collecting && !h->submitted.empty())       // (as any other call: the inferences submitted on the handle end first)
         if ((s = collect_one(h, nullptr)) != CNF_OK) return s;
     if (c.opts->kernel == CNF_KERNEL_GENERIC) return fail(h, CNF_ERR_UNSUPPORTED, "the ensemble form exists on the wave kernels only");
-    const int capacity = c.grad ? ens_grad_capacity(h, c.mode, c.B, c.cot) : cnf_ensemble_eval_capacity(h, c.mode, c.B);
+    const int capacity = c.path_many ? (c.grad ? cnf_ensemble_path_vjp_capacity(h, c.mode, c.B) : cnf_ensemble_path_capacity(h, c.mode, c.B))
+                         : c.grad    ? ens_grad_capacity(h, c.mode, c.B, c.cot) : cnf_ensemble_eval_capacity(h, c.mode, c.B);
     if (capacity < 1) return fail(h, CNF_ERR_UNSUPPORTED, "no ensemble form for this model, mode or batch");
     if (c.M > capacity)
         return fail(h, CNF_ERR_UNSUPPORTED, (std::string("more members than one launch takes (") + capacity_fn + ")").c_str());
@@ -2804,12 +2816,13 @@ static cnf_status ens_begin(cnf_handle h, EnsCall& c) {
 // member its stats, its status and -- sums: the call has loss sums -- its loss.  steps[m]: the accepted steps (attempts: all
 // attempts) of a member that succeeded, -1 of the others.
 static cnf_status ens_finish(cnf_handle h, EnsCall& c, int launches, bool sums, float* loss_out, int* status_out,
-                             cnf_solve_stats* stats_out, std::vector<int>& steps, bool attempts) {
+                             cnf_solve_stats* stats_out, std::vector<int>& steps, bool attempts, std::vector<int>* nacc = nullptr) {
     const size_t Mz = (size_t)c.M;
     HIPCHK(h, hipMemcpyAsync(h->ens_hfin, h->ens_fin, ens_fin_floats(c.M) * sizeof(float), hipMemcpyDeviceToHost, c.st));
     HIPCHK(h, hipStreamSynchronize(c.st));
     c.lock.unlock();
     steps.assign(Mz, -1);
+    if (nacc) nacc->assign(Mz, -1);                        // (the accepted steps beside the attempts: the path calls file pairs of them)
     for (int m = 0; m < c.M; ++m) {
         StepState fin;
         memcpy(&fin, h->ens_hfin + (size_t)m * ENS_ST_F, sizeof fin);
@@ -2824,7 +2837,7 @@ static cnf_status ens_finish(cnf_handle h, EnsCall& c, int launches, bool sums, 
             // (the fifth sum is the member's own count, as its part of the launch wrote it; the lambdas are its own too)
             const float* lam = c.lams.empty() ? h->lam : c.lams.data() + 3 * (size_t)m;
             status_out[m] = sums ? loss_from_sums_lam(h, c.mode, h->ens_hfin + Mz * ENS_ST_F + 5 * (size_t)m, lam, &loss) : CNF_OK;
-            if (status_out[m] == CNF_OK) steps[m] = attempts ? natt : fin.naccept;
+            if (status_out[m] == CNF_OK) { steps[m] = attempts ? natt : fin.naccept; if (nacc) (*nacc)[(size_t)m] = fin.naccept; }
             else loss = NAN;
         }
         if (loss_out) loss_out[m] = loss;
@@ -2868,33 +2881,68 @@ static cnf_status ens_sampling_u0(cnf_handle h, float* u0, const float* z0, size
 //   cnf_generate_vjp_many (WC_SAMPLING): src = z0, times = the START times, cot0 = cot_z, cot1 = cot_logq (either may be null); the
 //     sampling CW form integrates u0 = [z0; 0] (built in the column store, the final columns behind it); out0 = x, out1 = logq
 //     and grad_in = d / d z0 (may be null) come from the column kernels of cnf_dist.hip over the M B columns as one batch.
-//   cnf_inference_path_vjp / cnf_generate_path_vjp (WC_INFERENCE_PATH, WC_SAMPLING_PATH; M = 1): the two above plus `ep` -- the
-//     save times, the cotangent of the slices and where the slices go (either may be null, and so may cot0 / cot1 then).
+//   cnf_inference_path_vjp / cnf_generate_path_vjp and their _many forms (WC_INFERENCE_PATH, WC_SAMPLING_PATH): the two above plus
+//     `ep` -- the save times, the cotangent of the slices and where the slices go (either may be null, and so may cot0 / cot1
+//     then).  The single-model calls are the M = 1 case; they keep their own step record (cnf_path_vjp_steps) and capacity.
 struct EnsPath {
-    const float* saveat;           // host, [K]: checked by the caller (saveat_error)
+    const float* saveat;           // host, [K] or (per_member) [M][K]: checked by the caller (saveat_error / saveat_error_many)
     int K;
-    const float* cot;              // device, [K][B][D] or null
-    float* out;                    // device, [K][B][D] or null
+    const float* cot;              // device, [M][K][B][D] or null
+    float* out;                    // device, [M][K][B][D] or null
+    bool per_member = false;       // every member has its own save times
+    bool many = false;             // a call of include/cnfhip_ensemble_path.h (false: of cnfhip_path_vjp.h, M = 1)
 };
+// the save times of M members, each set checked as cnf_solve_path checks its own; looks at no handle
+static const char* saveat_error_many(const cnf_solve_opts* opts, const float* saveat_host, int K, int M, int per_member) {
+    if (per_member != 0 && per_member != 1) return "saveat_per_member is 0 or 1";
+    const int sets = per_member && M > 1 ? M : 1;
+    for (int m = 0; m < sets; ++m)
+        if (const char* bad = saveat_error(opts, saveat_host ? saveat_host + (size_t)m * (size_t)(K > 0 ? K : 0) : nullptr, K)) return bad;
+    return nullptr;
+}
+// the save times to the device, the members' step pairs: the path arguments of a launch of M members
+static cnf_status ens_path_args(cnf_handle h, const EnsPath& ep, int M, bool grad, hipStream_t st, WavePathArgs& wp) {
+    // the kernel reads [M][K] save times: one set for all members is laid out M times here (the stride arithmetic is the host's)
+    const size_t Kz = (size_t)ep.K, Mz = (size_t)M;
+    RESERVE(h, h->d_saveat, Mz * Kz);
+    const float* src = ep.saveat;
+    if (!ep.per_member && M > 1) {
+        h->saveat_rep.resize(Mz * Kz);
+        for (size_t m = 0; m < Mz; ++m) memcpy(h->saveat_rep.data() + m * Kz, ep.saveat, Kz * sizeof(float));
+        src = h->saveat_rep.data();
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_saveat, src, Mz * Kz * sizeof(float), hipMemcpyHostToDevice, st));
+    wp.times = h->d_saveat; wp.K = ep.K; wp.out = ep.out; wp.cot = ep.cot;
+    if (ep.many) {
+        wp.steps_cap = grad ? ENS_PATH_VJP_STEPS_CAP : ENS_PATH_STEPS_CAP;
+        RESERVE(h, h->ens_psteps, (size_t)M * 2 * (size_t)wp.steps_cap);
+        wp.steps = h->ens_psteps;
+    } else {
+        RESERVE(h, h->d_path_steps, (size_t)2 * PATH_STEPS_CAP);
+        wp.steps = h->d_path_steps; wp.steps_cap = PATH_STEPS_CAP;
+    }
+    return CNF_OK;
+}
+// a member that is not CNF_OK: NaN in its own slab of the slices
+static cnf_status ens_path_fill(cnf_handle h, const EnsPath& ep, int m, size_t slab, hipStream_t st) {
+    if (ep.out) HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(ep.out + (size_t)m * slab), 0x7fc00000, slab, st));
+    return CNF_OK;
+}
 static cnf_status ens_grad(cnf_handle h, WaveCot cot, int mode, int M, const float* params_dev, const float* src, const float* eps, int B,
                            const cnf_solve_opts* opts, const float* times_host, const float* cot0, const float* cot1, float* loss_out,
                            float* out0, float* out1, float* grad_dev, float* grad_in, int* status_out, cnf_solve_stats* stats_out,
                            void* stream, const EnsPath* ep = nullptr) {
     const bool train = mode == CNF_MODE_TRAIN, vjp = cot != WC_LOSS, gen = wave_cot_sampling(cot);
-    if (h && ep) h->pvjp_valid = false;
+    if (h && ep) { if (ep->many) h->epath_M = 0; else h->pvjp_valid = false; }
     EnsCall c{true, gen, mode, M, B, 0, opts, times_host, (hipStream_t)stream};
-    c.cot = cot;
+    c.cot = cot; c.path_many = ep && ep->many;
     ens_take_members(h, c);
-    if (ep) { c.het_M = 0; c.counts.clear(); c.lams.clear(); c.tols.clear(); }      // (the path calls run one member: taken and dropped)
+    if (ep) { c.het_M = 0; c.counts.clear(); c.lams.clear(); c.tols.clear(); }      // (the path calls take no such arrays: taken and dropped)
     cnf_status s = ens_check(h, c, !params_dev || !src || !opts || !grad_dev || !status_out || (train && !eps) ||
                                        (gen ? (!ep && !cot0 && !cot1) || !out0 || !out1 : vjp ? (!ep && !cot0) || !out0 || !out1 : !loss_out),
                              vjp ? "B must be >= 1" : "the loss is a mean over the batch: B must be >= 1",
-                             ep ? "cnf_path_vjp_max_batch" : gen ? "cnf_ensemble_generate_vjp_capacity" : vjp ? "cnf_ensemble_vjp_capacity" : "cnf_ensemble_capacity");
+                             ep ? (ep->many ? "cnf_ensemble_path_vjp_capacity" : "cnf_path_vjp_max_batch") : gen ? "cnf_ensemble_generate_vjp_capacity" : vjp ? "cnf_ensemble_vjp_capacity" : "cnf_ensemble_capacity");
     if (s != CNF_OK) return s;
-    if (ep) {                                              // the save times' and the accepted steps' device buffers (cnf_solve_path's)
-        RESERVE(h, h->d_saveat, (size_t)ep->K);
-        RESERVE(h, h->d_path_steps, (size_t)2 * PATH_STEPS_CAP);
-    }
     const NetDesc& nd = h->nd_wave;
     const size_t Mz = (size_t)M, Bz = (size_t)B, n_in = (size_t)nd.n_in, nv = (size_t)nd.nvars, D = n_in + (train ? 3 : 1), np = h->n_params;
     const size_t per_step = wave_grad_traj_floats(nd, B);
@@ -2929,10 +2977,7 @@ static cnf_status ens_grad(cnf_handle h, WaveCot cot, int mode, int M, const flo
     else ens.cw = vjp ? cot0 : nullptr;
     ens.p_stride = np; ens.traj_stride = per_step * cap; ens.part_stride = WV_ENS_PART_FLOATS;
     WavePathArgs wp{};
-    if (ep) {
-        HIPCHK(h, hipMemcpyAsync(h->d_saveat, ep->saveat, (size_t)ep->K * sizeof(float), hipMemcpyHostToDevice, c.st));
-        wp.times = h->d_saveat; wp.K = ep->K; wp.out = ep->out; wp.cot = ep->cot; wp.steps = h->d_path_steps; wp.steps_cap = PATH_STEPS_CAP;
-    }
+    if (ep && (s = ens_path_args(h, *ep, M, true, c.st, wp)) != CNF_OK) return s;
     int launches = 0;                                      // kernel launches of this call, counted where they are made
     s = wave_solve_launch(nd, train, params_dev, nullptr, 0, fin_dev, fsol, eps, B, c.st, nullptr, 0, sv, &wg, &ens, ep ? &wp : nullptr);
     if (s != CNF_OK) return fail(h, s, "the ensemble launch failed to start");
@@ -2962,11 +3007,13 @@ static cnf_status ens_grad(cnf_handle h, WaveCot cot, int mode, int M, const flo
                 if ((s = ens_fill_member(h, c, m, gen, nv, out0 + mz * n0, out1 + mz * n1)) != CNF_OK) return s;
                 HIPCHK(h, hipMemsetAsync(grad_dev + mz * np, 0, np * sizeof(float), c.st));
                 if (grad_in) HIPCHK(h, hipMemsetAsync(grad_in + mz * Bz * n_in, 0, ens_member_count(c, m) * n_in * sizeof(float), c.st));
-                if (ep && ep->out) HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)ep->out, 0x7fc00000, (size_t)ep->K * Bz * D, c.st));
+                if (ep && (s = ens_path_fill(h, *ep, m, (size_t)ep->K * Bz * D, c.st)) != CNF_OK) return s;
             }
         if (any_bad) HIPCHK(h, hipStreamSynchronize(c.st));
     }
-    if (ep && status_out[0] == CNF_OK) {                   // the accepted steps back from the device (cnf_path_vjp_steps)
+    if (ep && ep->many) {                                  // (the members' step pairs stay on the device: cnf_ensemble_path_steps)
+        h->epath_nacc = h->ens_nacc; h->epath_M = M; h->epath_cap = wp.steps_cap; h->epath_rows = -1;
+    } else if (ep && status_out[0] == CNF_OK) {            // the accepted steps back from the device (cnf_path_vjp_steps)
         const int n = h->ens_nacc[0];
         std::vector<float> pairs((size_t)2 * (n > 0 ? n : 0));
         if (n > 0) HIPCHK(h, hipMemcpy(pairs.data(), h->d_path_steps, pairs.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -3105,12 +3152,15 @@ extern "C" int cnf_ensemble_eval_capacity(cnf_handle h, int mode, int B) {
 // times; gen = true: src = z0 [M][B][n_in], out0 = xs_out [M][B][nvars], out1 = logq [M][B] or null, times = the start times.
 static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float* params_dev, const float* src, const float* eps, int B,
                            const cnf_solve_opts* opts, const float* times_host, float* out0, float* out1, float* loss_out,
-                           int* status_out, cnf_solve_stats* stats_out, int trace_cap, void* stream) {
+                           int* status_out, cnf_solve_stats* stats_out, int trace_cap, void* stream, const EnsPath* ep = nullptr) {
     const bool train = mode == CNF_MODE_TRAIN;
+    if (h && ep) h->epath_M = 0;
     EnsCall c{false, gen, mode, M, B, trace_cap, opts, times_host, (hipStream_t)stream};
+    c.path_many = ep != nullptr;
     ens_take_members(h, c);
-    cnf_status s = ens_check(h, c, !params_dev || !src || !opts || !out0 || (!gen && !out1) || !status_out || (train && !eps),
-                             "B must be >= 1", "cnf_ensemble_eval_capacity");
+    if (ep) { c.het_M = 0; c.counts.clear(); c.lams.clear(); c.tols.clear(); }      // (the path calls take no such arrays: taken and dropped)
+    cnf_status s = ens_check(h, c, !params_dev || !src || !opts || !out0 || (!gen && !out1) || !status_out || (train && !eps) || (ep && !ep->out),
+                             "B must be >= 1", ep ? "cnf_ensemble_path_capacity" : "cnf_ensemble_eval_capacity");
     if (s != CNF_OK) return s;
     const NetDesc& nd = h->nd_wave;
     const size_t Mz = (size_t)M, Bz = (size_t)B, n_in = (size_t)nd.n_in, nv = (size_t)nd.nvars, D = n_in + (train ? 3 : 1);
@@ -3134,9 +3184,11 @@ static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float*
     (gen ? ens.t0 : ens.t1) = times_host ? h->ens_t1.data() : nullptr;
     ens.p_stride = h->n_params; ens.part_stride = WV_ENS_PART_FLOATS;
     ens.counts = c.d_counts; ens.tols = c.d_tols;          // (the plain forms read no lambda; the members' losses take theirs: ens_finish)
+    WavePathArgs wp{};
+    if (ep && (s = ens_path_args(h, *ep, M, false, st, wp)) != CNF_OK) return s;
     int launches = 0;
     s = wave_solve_launch(nd, train, params_dev, nullptr, 0, reinterpret_cast<StepState*>(h->ens_fin.data()), cols, eps, B, st, nullptr, 0,
-                          sv, nullptr, &ens);
+                          sv, nullptr, &ens, ep ? &wp : nullptr);
     if (s != CNF_OK) return fail(h, s, "the ensemble launch failed to start");
     ++launches;
     HIPCHK(h, hipGetLastError());
@@ -3145,16 +3197,21 @@ static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float*
         HIPCHK(h, hipGetLastError());
         ++launches;
     }
-    std::vector<int> att;
-    if ((s = ens_finish(h, c, launches, !gen, loss_out, status_out, stats_out, att, true)) != CNF_OK) return s;
+    std::vector<int> att, nacc;
+    if ((s = ens_finish(h, c, launches, !gen, loss_out, status_out, stats_out, att, true, ep ? &nacc : nullptr)) != CNF_OK) return s;
     bool any_bad = false;
     for (int m = 0; m < M; ++m)
         if (status_out[m] != CNF_OK) {                     // nothing of such a member is valid: NaN, whatever the kernel left
             any_bad = true;
             const size_t n0 = gen ? Bz * nv : Bz, n1 = gen ? Bz : 3 * Bz;
             if ((s = ens_fill_member(h, c, m, gen, nv, out0 + (size_t)m * n0, out1 ? out1 + (size_t)m * n1 : nullptr)) != CNF_OK) return s;
+            if (ep && (s = ens_path_fill(h, *ep, m, (size_t)ep->K * Bz * D, st)) != CNF_OK) return s;
         }
     if (any_bad) HIPCHK(h, hipStreamSynchronize(st));
+    if (ep) {                                              // (the members' step pairs stay on the device: cnf_ensemble_path_steps)
+        for (int& n : nacc) if (n > wp.steps_cap) n = -1;  // (more accepted steps than a member files)
+        h->epath_nacc.swap(nacc); h->epath_M = M; h->epath_cap = wp.steps_cap; h->epath_rows = -1;
+    }
     if (trace_cap > 0) { h->ensv_att.swap(att); h->ensv_M = M; h->ensv_tcap = trace_cap; }
     return CNF_OK;
 }
@@ -3184,6 +3241,98 @@ extern "C" int cnf_ensemble_eval_steps(cnf_handle h, int member, float* rows, in
             hipMemcpy(rows, h->ens_trace + (size_t)member * 4 * h->ensv_tcap, (size_t)take * 4 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
             (void)hipGetLastError();
             return -1;
+        }
+    }
+    return n;
+}
+
+// ---------------------------------------------------------------------------------------
+// Ensemble flow paths (include/cnfhip_ensemble_path.h): the paths of M members by the plain ensemble form with the path
+// (ens_eval), and their vector-Jacobian products by the PATH forms of the per-sample-cotangent launch (ens_grad), M members each.
+// ---------------------------------------------------------------------------------------
+extern "C" int cnf_ensemble_path_capacity(cnf_handle h, int mode, int B) {
+    if (B < 1 || !ens_handle_ok(h, mode)) return 0;
+    if (hipSetDevice(h->device) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    return wave_ens_eval_capacity(h->nd_wave, mode == CNF_MODE_TRAIN, B, true);
+}
+extern "C" int cnf_ensemble_path_vjp_capacity(cnf_handle h, int mode, int B) {
+    const int a = ens_grad_capacity(h, mode, B, WC_INFERENCE_PATH), b = ens_grad_capacity(h, mode, B, WC_SAMPLING_PATH);
+    return a < b ? a : b;
+}
+// the save times first (with a NULL handle too), then: these calls have no per-member span
+static cnf_status ens_path_entry(cnf_handle h, const cnf_solve_opts* opts, const float* saveat_host, int K, int M, int per_member,
+                                 const float* times_host) {
+    if (const char* bad = saveat_error_many(opts, saveat_host, K, M, per_member)) return h ? fail(h, CNF_ERR_BAD_ARG, bad) : CNF_ERR_BAD_ARG;
+    if (times_host) return fail(h, CNF_ERR_BAD_ARG, "the ensemble path calls take no per-member start or end times");
+    return CNF_OK;
+}
+extern "C" cnf_status cnf_inference_path_many(cnf_handle h, int mode, int M, const float* params_dev, const float* xs, const float* eps,
+                                              int B, const cnf_solve_opts* opts, const float* t1_host, float* logpx_dev, float* regs_dev,
+                                              float* loss_out, int* status_out, cnf_solve_stats* stats_out, int trace_cap, void* stream,
+                                              const float* saveat_host, int K, int saveat_per_member, float* path_out_dev) {
+    const cnf_status s = ens_path_entry(h, opts, saveat_host, K, M, saveat_per_member, t1_host);
+    if (s != CNF_OK) return s;
+    const EnsPath ep{saveat_host, K, nullptr, path_out_dev, saveat_per_member != 0, true};
+    return ens_eval(h, false, mode, M, params_dev, xs, eps, B, opts, nullptr, logpx_dev, regs_dev, loss_out, status_out, stats_out, trace_cap,
+                    stream, &ep);
+}
+extern "C" cnf_status cnf_generate_path_many(cnf_handle h, int mode, int M, const float* params_dev, const float* z0, const float* eps,
+                                             int B, const cnf_solve_opts* opts, const float* t0_host, float* xs_out, float* logq_out,
+                                             int* status_out, cnf_solve_stats* stats_out, int trace_cap, void* stream,
+                                             const float* saveat_host, int K, int saveat_per_member, float* path_out_dev) {
+    const cnf_status s = ens_path_entry(h, opts, saveat_host, K, M, saveat_per_member, t0_host);
+    if (s != CNF_OK) return s;
+    const EnsPath ep{saveat_host, K, nullptr, path_out_dev, saveat_per_member != 0, true};
+    return ens_eval(h, true, mode, M, params_dev, z0, eps, B, opts, nullptr, xs_out, logq_out, nullptr, status_out, stats_out, trace_cap,
+                    stream, &ep);
+}
+extern "C" cnf_status cnf_inference_path_vjp_many(cnf_handle h, int mode, int M, const float* params_dev, const float* xs,
+                                                  const float* eps, int B, const cnf_solve_opts* opts, const float* saveat_host, int K,
+                                                  int saveat_per_member, const float* cot_dev, const float* path_cot_dev,
+                                                  float* logpx_dev, float* regs_dev, float* path_out_dev, float* grad_dev,
+                                                  float* grad_x_dev, int* status_out, cnf_solve_stats* stats_out, void* stream) {
+    const cnf_status s = ens_path_entry(h, opts, saveat_host, K, M, saveat_per_member, nullptr);
+    if (s != CNF_OK) return s;
+    const EnsPath ep{saveat_host, K, path_cot_dev, path_out_dev, saveat_per_member != 0, true};
+    return ens_grad(h, WC_INFERENCE_PATH, mode, M, params_dev, xs, eps, B, opts, nullptr, cot_dev, nullptr, nullptr, logpx_dev, regs_dev,
+                    grad_dev, grad_x_dev, status_out, stats_out, stream, &ep);
+}
+extern "C" cnf_status cnf_generate_path_vjp_many(cnf_handle h, int mode, int M, const float* params_dev, const float* z0,
+                                                 const float* eps, int B, const cnf_solve_opts* opts, const float* saveat_host, int K,
+                                                 int saveat_per_member, const float* cot_z_dev, const float* cot_logq_dev,
+                                                 const float* path_cot_dev, float* x_out, float* logq_out, float* path_out_dev,
+                                                 float* grad_dev, float* grad_z0_dev, int* status_out, cnf_solve_stats* stats_out,
+                                                 void* stream) {
+    const cnf_status s = ens_path_entry(h, opts, saveat_host, K, M, saveat_per_member, nullptr);
+    if (s != CNF_OK) return s;
+    const EnsPath ep{saveat_host, K, path_cot_dev, path_out_dev, saveat_per_member != 0, true};
+    return ens_grad(h, WC_SAMPLING_PATH, mode, M, params_dev, z0, eps, B, opts, nullptr, cot_z_dev, cot_logq_dev, nullptr, x_out, logq_out,
+                    grad_dev, grad_z0_dev, status_out, stats_out, stream, &ep);
+}
+// (read from the device when first asked for, all members at once)
+extern "C" int cnf_ensemble_path_steps(cnf_handle h, int member, float* t_host, float* h_host, int cap) {
+    if (!h || member < 0 || member >= h->epath_M) return -1;
+    const int n = h->epath_nacc[(size_t)member];
+    if (n < 0 || n > h->epath_cap) return -1;
+    const int take = n < cap ? n : cap;
+    if (take > 0 && (t_host || h_host)) {
+        if (h->epath_rows < 0) {                           // every member's pairs in one strided copy (a copy per member costs a
+            int rows = 0;                                  // synchronisation each: 1.2 ms of a 1.5 ms call at 64 members)
+            for (int v : h->epath_nacc) if (v > rows && v <= h->epath_cap) rows = v;
+            h->epath_host.resize((size_t)h->epath_M * 2 * (size_t)rows);
+            if (hipSetDevice(h->device) != hipSuccess ||
+                hipMemcpy2D(h->epath_host.data(), (size_t)2 * rows * sizeof(float), h->ens_psteps.data(),
+                            (size_t)2 * h->epath_cap * sizeof(float), (size_t)2 * rows * sizeof(float), (size_t)h->epath_M,
+                            hipMemcpyDeviceToHost) != hipSuccess) {
+                (void)hipGetLastError();
+                return -1;
+            }
+            h->epath_rows = rows;
+        }
+        const float* pairs = h->epath_host.data() + (size_t)member * 2 * (size_t)h->epath_rows;
+        for (int i = 0; i < take; ++i) {
+            if (t_host) t_host[i] = pairs[2 * (size_t)i];
+            if (h_host) h_host[i] = pairs[2 * (size_t)i + 1];
         }
     }
     return n;

@@ -72,7 +72,8 @@ int wave_ens_capacity(const NetDesc& nd, bool train, int B, WaveCot cw = WC_LOSS
 // Without `grad`, `ens` launches the PLAIN ensemble form (cnf_inference_many / cnf_generate_many): either an inference (sv.xs,
 // sv.logpx [M][B], sv.regs [M][3][B], sv.sums5 [5 M]) or a bare solve (sv.u0 -> sv.u_out, [M][B][D] each); sv.trace, when
 // set, is [M][sv.trace_cap][4].  Its capacity: workgroups of one wave the device holds at once / tiles, at most 512 tiles.
-int wave_ens_eval_capacity(const NetDesc& nd, bool train, int B);
+// path: of the plain form that also stores the members' paths (cnf_inference_path_many, cnf_generate_path_many; its own kernels)
+int wave_ens_eval_capacity(const NetDesc& nd, bool train, int B, bool path = false);
 // The path of a plain solve in the same launch (k_solve_wave<.., PATH>; cnf_solve_path): every accepted step evaluates Tsit5's
 // interpolant at the save times it serves, from the k_1 .. k_7 it holds in registers, and stores those columns.
 struct WavePathArgs {
@@ -84,11 +85,17 @@ struct WavePathArgs {
     // the PATH forms of the ensemble gradient (WC_INFERENCE_PATH, WC_SAMPLING_PATH) only: the cotangent of the slices, in the
     // layout of `out` (null: nothing is injected); there `out` and `steps` may be null too (nothing is stored)
     const float* cot = nullptr;
+    // ENS forms (M members): `times` is [M][K] (one set for all members: laid out M times by the caller), `out` / `cot` are
+    // [M][K][B][D] and `steps` is [M][steps_cap][2]
 };
 // `path`: the PATH form -- a plain solve (no grad, no ens) of one tile per workgroup, whatever the batch (B <= 8192), on the
 // tanh networks with one input tile; CNF_ERR_UNSUPPORTED for everything else (the caller takes the streamed path).
-// `path` with `grad` and `ens` (M = 1): the PATH form of the per-sample-cotangent gradient -- ens->cw / ens->cot_z / ens->cot_logq
-// may then all be null (no terminal cotangent).
+// `path` with `grad` and `ens`: the PATH form of the per-sample-cotangent gradient -- ens->cw / ens->cot_z / ens->cot_logq
+// may then all be null (no terminal cotangent).  `path` with `ens` alone: the plain ensemble form with the members' paths.
+// LAYOUT CONTRACT of `path` with `ens`: path->times holds ens->M x path->K floats, member m's set at [m K, m K + K) -- also when
+// all members share one set (the caller lays it out M times: cnf_abi.hip's ens_path_args is the one caller and does) --,
+// path->out / path->cot hold M slabs [K][B][D] and path->steps M x steps_cap pairs.  The launch cannot see the sizes of these
+// device arrays: a [K] array with M > 1 would be read past its end.
 cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_params, const float* cond, int cbs, StepState* st_out,
                              float* U0, const float* eps, int B, hipStream_t s, void* mirror, unsigned seq, const Solve3Args& sv,
                              const WaveGradArgs* grad = nullptr, const WaveEnsLaunch* ens = nullptr, const WavePathArgs* path = nullptr);

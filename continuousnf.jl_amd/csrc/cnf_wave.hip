@@ -35,7 +35,8 @@
 //   ENS   M independent models of one architecture in one launch, the grid M x tiles: the recomputing GRAD forms
 //         (cnf_loss_grad_many) and the plain one-tile-per-workgroup forms (cnf_inference_many, cnf_generate_many);
 //   PATH  the plain one-tile-per-workgroup solve that also stores the flow at the caller's save times, from Tsit5's interpolant
-//         over the k_1 .. k_7 of every accepted step (cnf_solve_path).
+//         over the k_1 .. k_7 of every accepted step (cnf_solve_path); with ENS, the plain ensemble form doing so for every
+//         member (cnf_inference_path_many, cnf_generate_path_many).
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -182,7 +183,17 @@ __device__ __forceinline__ float wv_quad_sum(float v) {
 // contraction, the stores, the meetings, lam_out = d / d u(t_start) -- is the CW form's.  logq and d / d z0 are column kernels
 // over the M B columns behind the launch (cnf_dist.hip).
 //
-// CW = WC_INFERENCE_PATH / WC_SAMPLING_PATH (CWP; cnf_inference_path_vjp, cnf_generate_path_vjp; one member): the two CW forms
+// ENS + PATH (plain; cnf_inference_path_many, cnf_generate_path_many): the plain ENS form with the PATH block behind every
+// accepted step.  The path's arrays carry a member axis -- pa.out / pa.cot [M][K][B][D], pa.times [M][K] (a caller's one set of
+// save times is laid out M times by the host), pa.steps [M][steps_cap][2] -- and the member is folded into the INDEX, not into
+// the pointers: a member's save indices are pK0 = member K .. pK0 + K - 1 of the flat [M K] arrays, so the cursor starts at pK0
+// and everything that indexes with it (the times, the slices, their cotangents, the backward walk) is the single model's code
+// with two other loop bounds; the step pairs are indexed member steps_cap + n.  Two scalars outlive the prologue.  (Moving the
+// four pointers there, as the other arrays are moved, has them outlive it in registers of forms that have none to spare: three
+// CWP forms answered with a scratch frame; indexing every touch with member K + k cost five.  With the cursor form none
+// gains scratch: profiles/ensemble_path_kernel_resources.md.)  The cursor is per workgroup, hence per member.
+//
+// CW = WC_INFERENCE_PATH / WC_SAMPLING_PATH (CWP; cnf_inference_path_vjp(_many), cnf_generate_path_vjp(_many)): the two CW forms
 // plus the path in both halves.  Forward: the PATH block above on the CW form's solve (pa.out may be null), and t_att filed
 // beside h_att per accepted step (tsL beside hsL).  Backward: the adjoint of the interpolant -- with pbar_j = pa.cot[j] the
 // cotangent of slice j, theta_j = (tau_j - t_n) / h_n a constant of the frozen step sequence and the forward's bracketing found
@@ -200,7 +211,7 @@ template <int NI, int NH, int MODE, bool TANH, bool GRAD = false, bool ID2 = fal
           int CW = WC_LOSS>
 __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wave(WaveArgs a, Solve3Args sv, const WvTab tab, const WaveEnsArgs en, const WavePathArgs pa) {
     constexpr bool HELP = GRAD && WGW == 1;
-    static_assert(!PATH || (!GRAD && !ENS && WGW == 1), "PATH is a form of the plain solve with one tile per workgroup");
+    static_assert(!PATH || (!GRAD && WGW == 1), "PATH is a form of the plain solve (or plain ensemble) with one tile per workgroup");
     static_assert(!ENS || (WGW == 1 && !RICH), "ENS forms have one tile per workgroup and no rich store");
     static_assert(CW == WC_LOSS || (GRAD && ENS), "CW is a form of the ensemble gradient");
     // per-sample cotangents of inference | of sampling;  CWP: ... and of the path (the launch also stores it)
@@ -215,6 +226,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
     constexpr bool TRAIN = MODE != WV_TEST;
     constexpr int NS = TRAIN ? 3 : 1;                      // scalar rows of the state
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
+    int pmem = 0, pK0 = 0;                                 // ENS with a path: this workgroup's member and its first save index, member K
     // WGW > 1: the waves of a workgroup are consecutive tiles.  One workgroup (B <= 64): they meet through LDS alone; SEVERAL
     // workgroups (large batches: up to 512 workgroups x WGW tiles): LDS inside the workgroup, the tagged words between them
     const int wloc = WGW > 1 ? (int)(threadIdx.x >> 6) : 0, nwg = WGW > 1 ? (int)(blockDim.x >> 6) : 1;
@@ -248,10 +260,11 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
             }
         }
         sv.part += mb * en.part_stride; sv.base_dev += mb; sv.abort_flag += mb;
+        if constexpr (PATH || CWP) { pmem = member; pK0 = member * pa.K; }       // (see ENS + PATH above)
         // a member's own batch size, regularisers and tolerances: the body behind the prologue is the single model's at that batch
         // (a workgroup beyond the member's tiles is no party of its meetings: it leaves before it touches a word of the member's)
-        // (compiled out of the PATH forms of the gradient, which run one member and are never given the arrays: two of them paid
-        // for the null tests with a scratch frame)
+        // (compiled out of the PATH forms of the gradient, whose calls take no such arrays: two of them paid for the null tests
+        // with a scratch frame)
         if constexpr (!CWP) {
             if (en.counts) {
                 const int cnt = en.counts[mb];
@@ -701,7 +714,8 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
         }
     }
     // ---- PATH: one slice of the path (this lane's z rows; the scalar rows from the lane groups that own them) ----
-    int pcur = 0;                                          // the next save time: the same in every lane and wave
+    int pcur = pK0;                                        // the next save time (of this member's: pK0 .. pKend - 1): the same in every lane and wave
+    const int pKend = pK0 + pa.K;
     auto path_store = [&](int k, const f32x4 (&z)[NI], float s) __attribute__((always_inline)) {
         if (!live) return;
         float* o = pa.out + ((size_t)k * (size_t)a.B + (size_t)smp) * D;
@@ -712,9 +726,10 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
         if (sown) o[n_in + q] = s;
     };
     const bool pstore = PATH || (CWP && pa.out != nullptr);   // (a CWP launch may be asked for the gradient alone)
+    auto ptime = [&](int k) __attribute__((always_inline)) { return uni(pa.times[k]); };
     if constexpr (PATH || CWP) {                           // save times at the start of the span: u0 itself
         const float t_start = uni(ns.t0);
-        while (pstore && pcur < pa.K && uni(pa.times[pcur]) == t_start) { path_store(pcur, uz, us); ++pcur; }
+        while (pstore && pcur < pKend && ptime(pcur) == t_start) { path_store(pcur, uz, us); ++pcur; }
     }
     // ---- step attempts ----
     constexpr float BT[7] = {TS_BT1, TS_BT2, TS_BT3, TS_BT4, TS_BT5, TS_BT6, TS_BT7};
@@ -825,12 +840,12 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
             } else gover = true;
         }
         if constexpr (PATH || CWP) {
-            if (accepted && wid == 0 && lane == 0 && acc0 < pa.steps_cap) { pa.steps[2 * acc0] = t_att; pa.steps[2 * acc0 + 1] = h_att; }
+            if (accepted && wid == 0 && lane == 0 && acc0 < pa.steps_cap) { float* pr = pa.steps + 2 * ((size_t)pmem * (size_t)pa.steps_cap + (size_t)acc0); pr[0] = t_att; pr[1] = h_att; }
             if (accepted && pstore) {
                 const float t_end = uni(ns.t), tdir = uni(ns.tdir);       // (the last step's end is t1 itself)
                 const bool last = __builtin_amdgcn_readfirstlane(ns.done) != 0;
-                while (pcur < pa.K) {
-                    const float tau = uni(pa.times[pcur]);
+                while (pcur < pKend) {
+                    const float tau = ptime(pcur);
                     if (!last && tdir * (tau - t_end) > 0.f) break;
                     const float th = (tau - t_att) / h_att;
                     if (tau == t_end || !(th < 1.f)) {     // the end of the step: the accepted state itself
@@ -948,19 +963,19 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
         const bool run_bwd = alive && !gover && __builtin_amdgcn_readfirstlane(ns.done) && !__builtin_amdgcn_readfirstlane(ns.nonfinite);
         // ---- CWP: which accepted step served which save times, found again from the filed (t_n, h_n) -- the forward's cursor walked
         // backwards.  Step n took the indices [path_lo(n, hi), hi): what lies strictly behind its start along the direction and
-        // was not taken by a later step (hi: the later step's lo; K for the last one, which takes everything left); the indices
-        // below path_lo(0, .) are the save times at t_start.  path_theta: the forward's theta of save time j in step n, and
+        // was not taken by a later step (hi: the later step's lo; pKend for the last one, which takes everything left); the indices
+        // below path_lo(0, .), from pK0 on, are the save times at t_start.  path_theta: the forward's theta of save time j in step n, and
         // whether the slice is the interpolant (true) or the accepted state u_{n+1} itself (false), by the forward's own rule. ----
         const float p_tdir = uni(ns.tdir), p_tfin = uni(ns.t);
         const int p_nacc = __builtin_amdgcn_readfirstlane(ns.naccept);
         auto path_lo = [&](int n, int hi) __attribute__((always_inline)) {
             const float tn = uni(tsL[n]);
             int lo = hi;
-            while (lo > 0 && p_tdir * (uni(pa.times[lo - 1]) - tn) > 0.f) --lo;
+            while (lo > pK0 && p_tdir * (ptime(lo - 1) - tn) > 0.f) --lo;
             return lo;
         };
         auto path_theta = [&](int j, int n, float& th) __attribute__((always_inline)) {
-            const float tau = uni(pa.times[j]), t_end = n == p_nacc - 1 ? p_tfin : uni(tsL[n + 1]);
+            const float tau = ptime(j), t_end = n == p_nacc - 1 ? p_tfin : uni(tsL[n + 1]);
             th = (tau - uni(tsL[n])) / uni(hsL[n]);
             return !(tau == t_end || !(th < 1.f));
         };
@@ -970,7 +985,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
         bool extra = false;
         if constexpr (CWP) {
             if (inject && run_bwd && p_nacc > 0) {
-                for (int j = path_lo(p_nacc - 1, pa.K); j < pa.K; ++j) { float th; if (path_theta(j, p_nacc - 1, th)) extra = true; }
+                for (int j = path_lo(p_nacc - 1, pKend); j < pKend; ++j) { float th; if (path_theta(j, p_nacc - 1, th)) extra = true; }
             }
         }
         if constexpr (HELP) {                              // the helper learns how many stage evaluations it will be handed
@@ -1121,7 +1136,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
             // CWP: the cotangents of the scalar rows are running values (the path's cotangents join them on the way back), and this
             // lane's part of the cotangent of slice j: its z rows of its column, and the column's scalar rows
             float cl = cl0, cE = cE0, cn = cn0;
-            int pend = CWP ? pa.K : 0;                     // the save indices below pend are still to be injected
+            int pend = CWP ? pKend : 0;                     // the save indices below pend are still to be injected
             auto pc_load = [&](int j, f32x4 (&pz)[NI], float (&psc)[3]) __attribute__((always_inline)) {
                 const float* pc = pa.cot + ((size_t)j * (size_t)a.B + sb) * D;
 #pragma unroll
@@ -1494,7 +1509,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
             // CWP: the save times at t_start (the slice is u0): their cotangent reaches d / d u(t_start) alone
             if constexpr (CWP) {
                 if (inject) {
-                    for (int j = 0; j < pend; ++j) pc_add(j);
+                    for (int j = pK0; j < pend; ++j) pc_add(j);
                 }
             }
             (void)cl; (void)cE; (void)cn; (void)pend;
@@ -1614,11 +1629,14 @@ wave_fn wave_instance_tiles(int ni, int nh, int mode) {
     return nullptr;
 }
 // One row per set of flags that is instantiated, each for the tiles above and the modes it names: these rows ARE the library's
-// k_solve_wave kernels (172 of them).  nullptr: no such kernel -- wave_variant does not return such a tuple.
+// k_solve_wave kernels (187 of them).  nullptr: no such kernel -- wave_variant does not return such a tuple.
 // cw: the CW forms (per-sample cotangents: WC_INFERENCE of cnf_inference_vjp_many, WC_SAMPLING of cnf_generate_vjp_many).  They
 // are no WaveForm of their own: a caller selects one as "the WF_ENS_GRAD answer of wave_variant, with CW" -- the same fifteen
 // tuples, instantiated once more for each, and once more for the PATH form of each (WC_INFERENCE_PATH, WC_SAMPLING_PATH:
 // cnf_inference_path_vjp, cnf_generate_path_vjp); with any other answer there is no such kernel.
+// The plain ensemble form WITH THE PATH (cnf_inference_path_many, cnf_generate_path_many) is selected the same way: "the
+// WF_ENS_PLAIN answer of wave_variant, with the path" -- wave_kernel sets v.path on that answer where WF_PATH answers too (the
+// envelope the two forms share); its fifteen tuples are the last two rows.
 wave_fn wave_instance(const WaveVariant& v, WaveCot cw = WC_LOSS) {
 #define WV_ROW(MODES, TANH, GRAD, ID2, WGW, RICH, ENS, PATH, CW)                                                                         \
     if (v.tanh == TANH && v.grad == GRAD && v.id2 == ID2 && v.wgw == WGW && v.rich == RICH && v.ens == ENS && v.path == PATH && cw == CW) \
@@ -1647,6 +1665,8 @@ wave_fn wave_instance(const WaveVariant& v, WaveCot cw = WC_LOSS) {
     WV_ROW(WV_M_ALL,  true,  false, true,  1, false, true,  false, WC_LOSS);
     WV_ROW(WV_M_ALL,  true,  false, false, 1, false, false, true, WC_LOSS);      // WF_PATH
     WV_ROW(WV_M_ALL,  true,  false, true,  1, false, false, true, WC_LOSS);
+    WV_ROW(WV_M_ALL,  true,  false, false, 1, false, true,  true, WC_LOSS);      // WF_ENS_PLAIN with the path (wave_kernel's `path`)
+    WV_ROW(WV_M_ALL,  true,  false, true,  1, false, true,  true, WC_LOSS);
 #undef WV_ROW
     return nullptr;
 }
@@ -1656,8 +1676,15 @@ wave_fn wave_instance(const WaveVariant& v, WaveCot cw = WC_LOSS) {
 bool is_id2(const NetDesc& nd) { return nd.n_layers == 2 && nd.acts[0] == 1 && nd.acts[1] == 0; }
 int wave_mode(const NetDesc& nd, bool train) { return !train ? WV_TEST : (nd.jvp ? WV_JVP : WV_VJP); }
 // the kernel of `form` for this two-layer network and mode (nullptr: there is none)
-wave_fn wave_kernel(WaveForm form, const NetDesc& nd, bool train, WaveCot cw = WC_LOSS) {
-    const auto v = wave_variant(form, (nd.n_in + 15) / 16, (nd.dims[1] + 15) / 16, wave_mode(nd, train), nd.acts[0] == 1 && nd.acts[1] == 1, is_id2(nd));
+// path: the WF_ENS_PLAIN answer with the path behind every accepted step (no other form takes it)
+wave_fn wave_kernel(WaveForm form, const NetDesc& nd, bool train, WaveCot cw = WC_LOSS, bool path = false) {
+    const int ni = (nd.n_in + 15) / 16, nh = (nd.dims[1] + 15) / 16, mode = wave_mode(nd, train);
+    const bool tanh2 = nd.acts[0] == 1 && nd.acts[1] == 1;
+    auto v = wave_variant(form, ni, nh, mode, tanh2, is_id2(nd));
+    if (path) {
+        if (form != WF_ENS_PLAIN || !v || !wave_variant(WF_PATH, ni, nh, mode, tanh2, is_id2(nd))) return nullptr;
+        v->path = true;
+    }
     return v ? wave_instance(*v, cw) : nullptr;
 }
 // CNF_PERSISTENT=0 / CNF_WAVE=0: no one-launch solve / none of this file's
@@ -1720,10 +1747,10 @@ bool wave_grad_supported(const NetDesc& nd, int B, bool train) {
 // ---- the ensemble form (cnf_loss_grad_many): M x tiles workgroups, each member's tiles meeting among themselves ----
 // (the envelope below -- two layers, tanh then tanh or identity, one input tile, up to four hidden tiles, one with the identity --
 // is restated in continuousnf.jl_amd/ensemble.py `_refusal`, which has to refuse before a handle exists: change both together)
-static wave_fn ens_fn(WaveForm form, const NetDesc& nd, bool train, WaveCot cw = WC_LOSS) {
+static wave_fn ens_fn(WaveForm form, const NetDesc& nd, bool train, WaveCot cw = WC_LOSS, bool path = false) {
     if (nd.n_layers != 2 || nd.n_cond > 0 || nd.id2) return nullptr;      // (an APPENDED identity layer lives behind the handle's own parameters)
     if (nd.acts[0] != 1 || !(nd.acts[1] == 1 || is_id2(nd))) return nullptr;
-    return wave_kernel(form, nd, train, cw);
+    return wave_kernel(form, nd, train, cw, path);
 }
 int wave_ens_capacity(const NetDesc& nd, bool train, int B, WaveCot cw) {
     wave_fn fn = ens_fn(WF_ENS_GRAD, nd, train, cw);
@@ -1731,8 +1758,8 @@ int wave_ens_capacity(const NetDesc& nd, bool train, int B, WaveCot cw) {
     return wave_resident_workgroups(fn, 128) / wave_grad_waves(B);     // (main wave + helper)
 }
 // ... and its plain form (cnf_inference_many, cnf_generate_many): the same envelope, 64 threads per workgroup
-int wave_ens_eval_capacity(const NetDesc& nd, bool train, int B) {
-    wave_fn fn = ens_fn(WF_ENS_PLAIN, nd, train);
+int wave_ens_eval_capacity(const NetDesc& nd, bool train, int B, bool path) {
+    wave_fn fn = ens_fn(WF_ENS_PLAIN, nd, train, WC_LOSS, path);
     if (wave_off() || !fn || B < 1 || B > 16 * 512) return 0;    // (a member's meeting has at most 512 parties)
     return wave_resident_workgroups(fn, 64) / ((B + 15) / 16);
 }
@@ -1741,10 +1768,11 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
                              float* U0, const float* eps, int B, hipStream_t s, void* mirror, unsigned seq, const Solve3Args& sv_,
                              const WaveGradArgs* grad, const WaveEnsLaunch* ens, const WavePathArgs* path) {
     if (!wave_solve_supported(nd, train, B)) return CNF_ERR_UNSUPPORTED;
-    // the PATH form of the per-sample-cotangent gradient: one member, with its gradient; it may store nothing and inject nothing
+    // the PATH forms of the per-sample-cotangent gradient: with its gradient; it may store nothing and inject nothing
     const bool gpath = path && grad && ens;
-    if (path && !gpath && (grad || ens || !path->out || path->cot)) return CNF_ERR_BAD_ARG;
-    if (path && (!path->times || path->K < 1 || (path->steps_cap > 0 && !path->steps) || (gpath && ens->M != 1))) return CNF_ERR_BAD_ARG;
+    const bool epath = path && !grad && ens;               // the plain ensemble form with the path
+    if (path && !gpath && (grad || !path->out || path->cot)) return CNF_ERR_BAD_ARG;
+    if (path && (!path->times || path->K < 1 || (path->steps_cap > 0 && !path->steps))) return CNF_ERR_BAD_ARG;
     // the CW form of the ensemble gradient: per-sample cotangents of inference, or of sampling -- and of the path
     const WaveCot cw = !ens ? WC_LOSS : ens->sampling ? (gpath ? WC_SAMPLING_PATH : WC_SAMPLING)
                                       : gpath ? WC_INFERENCE_PATH : ens->cw ? WC_INFERENCE : WC_LOSS;
@@ -1753,7 +1781,7 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
         const bool gcot = ens->cot_z || ens->cot_logq;     // (sampling: its own cotangents, at least one, and start times only)
         if (ens->sampling ? (ens->cw || ens->t1 || (!gcot && !gpath)) : gcot) return CNF_ERR_BAD_ARG;
     }
-    if (ens && (cond || mirror || ens->M < 1 || ens->M > (grad ? wave_ens_capacity(nd, train, B, cw) : wave_ens_eval_capacity(nd, train, B))))
+    if (ens && (cond || mirror || ens->M < 1 || ens->M > (grad ? wave_ens_capacity(nd, train, B, cw) : wave_ens_eval_capacity(nd, train, B, epath))))
         return CNF_ERR_UNSUPPORTED;
     if (grad && nd.n_cond > 0 && !grad->ys) return CNF_ERR_BAD_ARG;
     if (grad && (!wave_grad_supported(nd, B, train) || !grad->traj || !grad->gpart || !grad->lam_out || !grad->hs_out || grad->traj_cap < 1))
@@ -1763,7 +1791,7 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
     const int tiles = (B + 15) / 16;
     bool xwg = false;                                      // WF_WG4: workgroups of four tiles (false: one workgroup of `tiles` waves)
     WaveForm form = WF_PLAIN;
-    if (path && !gpath) form = WF_PATH;                    // one tile per workgroup, whatever the batch
+    if (path && !ens) form = WF_PATH;                      // one tile per workgroup, whatever the batch
     else if (ens) form = grad ? WF_ENS_GRAD : WF_ENS_PLAIN;       // (one tile per workgroup -- and its helper, as every gradient)
     else if (grad)                                         // the forward pass files its intermediates: the RICH instantiations
         form = grad->rich && wave_mode(nd, train) == WV_VJP && nd.n_in <= 16 ? WF_GRAD_RICH : WF_GRAD;
@@ -1781,7 +1809,7 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
     }
     if (tiles > 512 && !xwg) return CNF_ERR_UNSUPPORTED;     // (a meeting has at most 512 parties)
     // ---- the kernel ----
-    wave_fn fn = wave_kernel(form, nd, train, cw);
+    wave_fn fn = wave_kernel(form, nd, train, cw, epath);
     if (!fn) return form == WF_GRAD_RICH ? CNF_ERR_BAD_ARG : CNF_ERR_UNSUPPORTED;       // (wave_grad_rich_floats said it exists)
     // ---- grid and block: a gradient's tile has its main wave and its helper ----
     int grid = form == WF_WG4 ? (xwg ? (tiles + 3) / 4 : 1) : tiles;
@@ -1817,7 +1845,7 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
     }
     WavePathArgs pa{};
     if (path) {
-        if (!gpath && (sv.xs || !sv.u0)) return CNF_ERR_BAD_ARG;       // (a bare solve: the path starts from the caller's columns)
+        if (!ens && (sv.xs || !sv.u0)) return CNF_ERR_BAD_ARG;         // (a bare solve: the path starts from the caller's columns)
         pa = *path;
     }
     void* args[] = {&a, &sv, &tab, &en, &pa};

@@ -256,13 +256,15 @@ def _device_capacity(who, capacity_fn, h, m, B):
     return cap
 
 
-def _settle_density(icnf: ICNF, mode, xs, ps, eps, t1, who, single, capacity_fn=None, cot_rows=None, shared=True, members=None):
+def _settle_density(icnf: ICNF, mode, xs, ps, eps, t1, who, single, capacity_fn=None, cot_rows=None, shared=True, members=None,
+                    steer=True):
     """The inputs of a density-direction ensemble call, checked, placed and drawn, in the one order the callers promise: the
     host-side refusals and shape checks (``_check_inputs``, then ``cot_rows(M, B)``: the call's cotangent tensors) -- nothing is
     drawn, no handle is made --; the handle (no device: cnf_create's error, as everywhere); the device check; the capacity
     (``capacity_fn`` of the C ABI; None: not asked, for the ``differentiable_*`` entries, whose forward asks); the probes and
     end times (``_probes_and_ends``).  ``shared``: ``xs`` may be one (nvars, B) data set for all members.  ``members``: the
-    keywords ``counts``, ``lambdas``, ``reltol``, ``abstol`` of the call (``_members`` checks them with the shapes).  Returns a
+    keywords ``counts``, ``lambdas``, ``reltol``, ``abstol`` of the call (``_members`` checks them with the shapes).
+    ``steer=False``: no steer variate is drawn (the path calls).  Returns a
     namespace: ``m, M, B, n_in, train, cot, cap, dev, stream, xr, pr, er, t1, het``."""
     import torch
     if shared and _is_torch(xs) and _is_torch(ps) and xs.dim() == 2 and ps.dim() == 2 and _refusal(icnf) is None:
@@ -277,7 +279,7 @@ def _settle_density(icnf: ICNF, mode, xs, ps, eps, t1, who, single, capacity_fn=
     train, dev = m == _lib.MODE_TRAIN, xs.device
     xr = _rows(xs)
     pr = ps.detach().to(torch.float32).contiguous()
-    er, t1 = _probes_and_ends(icnf, mode, train, M, B, n_in, xr, eps, t1, counts=het.counts if het is not None else None)
+    er, t1 = _probes_and_ends(icnf, mode, train, M, B, n_in, xr, eps, t1, steer=steer, counts=het.counts if het is not None else None)
     return SimpleNamespace(m=m, M=M, B=B, n_in=n_in, train=train, cot=cot, cap=cap, dev=dev, xr=xr, pr=pr, er=er, t1=t1, het=het,
                            stream=_stream(_Buf(xr, icnf.nvars, M * B, torch)))
 
@@ -683,10 +685,11 @@ def _sampling_draws(icnf: ICNF, mode, train, M, n, n_in, dev, z0, eps, t0, steer
     return zr, er, t0
 
 
-def _settle_sampling(icnf: ICNF, mode, ps, n, z0, eps, t0, who, single, capacity_fn=None, cot_pair=None, members=None):
+def _settle_sampling(icnf: ICNF, mode, ps, n, z0, eps, t0, who, single, capacity_fn=None, cot_pair=None, members=None, steer=True):
     """``_settle_density`` for the sampling direction, in the same order: ``_check_sampling_inputs`` and ``cot_pair(M, n)``
     (the call's cotangent tensors); the handle; the device check; the capacity (None: not asked); ``_sampling_draws``.
-    ``members``: the call's ``counts``, ``reltol``, ``abstol`` (``_members``).  Returns a namespace: ``m, M, n, n_in, train, cot,
+    ``members``: the call's ``counts``, ``reltol``, ``abstol`` (``_members``).  ``steer=False``: no steer variate is drawn (the path
+    calls).  Returns a namespace: ``m, M, n, n_in, train, cot,
     cap, dev, stream, pr, zr, er, t0, het``."""
     import torch
     m, M, n, n_in, t0 = _check_sampling_inputs(icnf, mode, ps, n, z0, eps, t0, who, single)
@@ -698,7 +701,7 @@ def _settle_sampling(icnf: ICNF, mode, ps, n, z0, eps, t0, who, single, capacity
     cap = _device_capacity(who, capacity_fn, h, m, n) if capacity_fn is not None else None
     train, dev = m == _lib.MODE_TRAIN, ps.device
     pr = ps.detach().to(torch.float32).contiguous()
-    zr, er, t0 = _sampling_draws(icnf, mode, train, M, n, n_in, dev, z0, eps, t0, counts=het.counts if het is not None else None)
+    zr, er, t0 = _sampling_draws(icnf, mode, train, M, n, n_in, dev, z0, eps, t0, steer=steer, counts=het.counts if het is not None else None)
     return SimpleNamespace(m=m, M=M, n=n, n_in=n_in, train=train, cot=cot, cap=cap, dev=dev, pr=pr, zr=zr, er=er, t0=t0, het=het,
                            stream=_stream(_Buf(pr, pr.shape[1], M, torch)))
 

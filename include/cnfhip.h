@@ -390,6 +390,11 @@ cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int B, float* 
  * (declared in cnfhip_path_vjp.h, part of this header) ---- */
 #include "cnfhip_path_vjp.h"
 
+/* ---- ensemble flow paths: M members' paths and their VJP in one launch -- cnf_ensemble_path_capacity /
+ * cnf_ensemble_path_vjp_capacity / cnf_inference_path_many / cnf_generate_path_many / cnf_inference_path_vjp_many /
+ * cnf_generate_path_vjp_many / cnf_ensemble_path_steps (declared in cnfhip_ensemble_path.h, part of this header) ---- */
+#include "cnfhip_ensemble_path.h"
+
 /* ---- device random numbers ------------------------------------------
  *
  * The library's own counter-based generator, the counterpart of the device RNG the reference draws eps and
