@@ -143,6 +143,39 @@ __device__ __forceinline__ void s3b_mm(f32x4 (&acc)[NC], const S3bOp& a, const S
     for (int n = 0; n < NC; ++n) acc[n] = s3b_term<5>(a, b[n], acc[n]);
 }
 
+// A narrow product (K = 128, four k-blocks) of a wave that is ALONE on its SIMD: rows `A` x rows `B` of two split images
+// (+ (rd ^ 64 kb): k-block kb), on two accumulation chains (terms 0-2 / 3-5), k-blocks ascending.  No other wave covers an
+// LDS round trip there, so the wave covers its own: the operands of k-block kb + 1 are requested in front of the MFMAs of
+// k-block kb (the compiler's counted lgkmcnt waits then leave them in flight), and `a0`, the A operand of k-block 0, comes
+// from the caller, who requests it in FRONT of the barrier that publishes B -- the A images are constant for the solve.
+// `tail()` is issued behind the last operand request, in front of the last k-block's MFMAs: reads the caller's epilogue
+// needs that do not depend on the product.
+template <class Tail>
+__device__ __forceinline__ void s3b_narrow(f32x4& z0, f32x4& z1, const S3bOp& a0, const char* A, const char* B, int rd,
+                                           int piece_bytes, Tail&& tail) {
+    S3bOp av = a0, bv = s3b_load(B + rd, piece_bytes);
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb) {
+        S3bOp an = av, bn = bv;
+        if (kb < 3) {
+            an = s3b_load(A + (rd ^ (64 * (kb + 1))), piece_bytes);
+            bn = s3b_load(B + (rd ^ (64 * (kb + 1))), piece_bytes);
+        } else {
+            tail();
+        }
+        S3_SB();
+        z0 = s3b_term<0>(av, bv, z0); z1 = s3b_term<3>(av, bv, z1);
+        z0 = s3b_term<1>(av, bv, z0); z1 = s3b_term<4>(av, bv, z1);
+        z0 = s3b_term<2>(av, bv, z0); z1 = s3b_term<5>(av, bv, z1);
+        // Both chains are pinned to their k-block: an MFMA has no side effect, so instruction selection is free to emit it
+        // anywhere behind its operands, whatever the scheduling fences say -- left alone, the second chain's twelve MFMAs
+        // are emitted as one dependent run BEHIND the loop, with the operands of all four k-blocks (96 VGPRs) held for it.
+        asm volatile("" : "+v"(z0), "+v"(z1));
+        S3_SB();
+        av = an; bv = bn;
+    }
+}
+
 // 4 rows of one sample back from the three images: the pieces sum to the fp32 value exactly
 __device__ __forceinline__ f32x4 s3b_load4(const char* img, int piece_bytes) {
     const bf16x4 h = *(const bf16x4*)img, m = *(const bf16x4*)(img + piece_bytes), l = *(const bf16x4*)(img + 2 * piece_bytes);

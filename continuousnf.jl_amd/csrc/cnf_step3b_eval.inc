@@ -4,6 +4,7 @@
 // S3B_RECORDS: a compile-time constant, with it `float* dmpw` and `size_t dmp_stride`).
         for (int stg = 1; stg <= nstg; ++stg) {
             f32x4 d2a, d2b;                                                  // sigma'_2 at this lane's h2 entries (interval 1 -> 3)
+            S3bOp nA0;                                                       // narrow products: k-block 0 of the constant operand (s3b_narrow)
             // ---- interval 0: first layer, tile `wave`, both halves (K = 32: one k-block)
             {
                 // conditional models (S3B_COND): the first layer's bias is a row per SAMPLE, W1[:, n_in:] ys + b1 (cnf_set_cond;
@@ -45,28 +46,33 @@
                 d2a = s3_dtanh4(h2a); d2b = s3_dtanh4(h2b);
                 s3b_store4(ldsb + s3v::H2G + wb_wr, s3v::WP, h2a);
                 s3b_store4(ldsb + s3v::H2G + wb_wr + HBW, s3v::WP, h2b);
+                // (W3 rows, k-block 0, for interval 2: nothing the barrier publishes; it lands while the stores drain)
+                S3_SB();
+                if (zown) nA0 = s3b_load(nrA + wb_rd, s3v::WP);
             }
             S3T(2);
             s3_bar();
             S3T(3);                                                          // h2 visible
             // ---- interval 2: last layer on waves 0-3 (one per SIMD): zdot rows r0..r0+3 of sample smp
             if (zown) {
-                const f32x4 bv3 = *(const f32x4*)(bias + 256 + r0);
                 f32x4 z0 = zero4, z1 = zero4;                                  // two chains (terms 0-2 / 3-5)
+                // what the epilogue reads that does not depend on the product is requested behind the last operands: the bias
+                // and the Runge-Kutta rows u, k1..k4 (k5, the last of the stage sum, follows the loop: a seventh row in
+                // flight there spills weight fragments in k_step3b and the several-tiles forms)
+                f32x4 bv3, rku, rkk[5];
+                s3b_narrow(z0, z1, nA0, nrA, nrB, wb_rd, s3v::WP, [&]() {
+                    bv3 = *(const f32x4*)(bias + 256 + r0);
+                    rku = *(const f32x4*)rkw; rkk[0] = *(const f32x4*)(rkw + 32);
 #pragma unroll
-                for (int kb = 0; kb < 4; ++kb) {
-                    const S3bOp av = s3b_load(nrA + (wb_rd ^ (64 * kb)), s3v::WP), bvv = s3b_load(nrB + (wb_rd ^ (64 * kb)), s3v::WP);
-                    S3_SB();
-                    z0 = s3b_term<0>(av, bvv, z0); z1 = s3b_term<3>(av, bvv, z1);
-                    z0 = s3b_term<1>(av, bvv, z0); z1 = s3b_term<4>(av, bvv, z1);
-                    z0 = s3b_term<2>(av, bvv, z0); z1 = s3b_term<5>(av, bvv, z1);
-                    S3_SB();
-                }
+                    for (int j = 1; j < 4; ++j) rkk[j] = *(const f32x4*)(kzw + 32 * (j - 1));
+                });
+                rkk[4] = *(const f32x4*)(kzw + 32 * 3);
+                S3T(12);                                                     // (stamped builds: barrier exit -> last MFMA issued)
                 // stage sum without the k this evaluation will produce: pre = u + h sum_{j<stg} a_{stg+1,j} k_j
                 const float* A = tab.a[stg < 6 ? stg + 1 : 6];
-                f32x4 pre = *(const f32x4*)rkw + (hstep * A[0]) * *(const f32x4*)(rkw + 32);
+                f32x4 pre = rku + (hstep * A[0]) * rkk[0];
 #pragma unroll
-                for (int j = 1; j < 5; ++j) pre += (hstep * A[j]) * *(const f32x4*)(kzw + 32 * (j - 1));
+                for (int j = 1; j < 5; ++j) pre += (hstep * A[j]) * rkk[j];
                 const f32x4 zd = s3_tanh4(z0 + z1 + bv3);                      // padded rows: zero weights and bias -> 0
                 s3b_store4(g3w, s3v::NP, epsr * s3_dtanh4(zd));               // g3 = eps .* sigma'_3
                 const f32x4 xnext = pre + (hstep * A[stg]) * zd;
@@ -108,6 +114,9 @@
                 }
                 s3b_store4(ldsb + s3v::H1G + wb_wr, s3v::WP, acc[0] * s3_dtanh4(h1a));
                 s3b_store4(ldsb + s3v::H1G + wb_wr + HBW, s3v::WP, acc[1] * s3_dtanh4(h1b));
+                // (W1^T rows, k-block 0, for interval 5: as W3's in front of interval 2)
+                S3_SB();
+                if (!zown) nA0 = s3b_load(nrA + wb_rd, s3v::WP);
             }
             S3T(8);
             s3_bar();
@@ -115,15 +124,8 @@
             // ---- interval 5: eJ = W1^T g1 on waves 4-7 (one per SIMD): trace and norm partials (src/icnf.jl:334, :343)
             if (!zown) {
                 f32x4 j0 = zero4, j1 = zero4;
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb) {
-                    const S3bOp av = s3b_load(nrA + (wb_rd ^ (64 * kb)), s3v::WP), bvv = s3b_load(nrB + (wb_rd ^ (64 * kb)), s3v::WP);
-                    S3_SB();
-                    j0 = s3b_term<0>(av, bvv, j0); j1 = s3b_term<3>(av, bvv, j1);
-                    j0 = s3b_term<1>(av, bvv, j0); j1 = s3b_term<4>(av, bvv, j1);
-                    j0 = s3b_term<2>(av, bvv, j0); j1 = s3b_term<5>(av, bvv, j1);
-                    S3_SB();
-                }
+                s3b_narrow(j0, j1, nA0, nrA, nrB, wb_rd, s3v::WP, []() {});
+                S3T(13);                                                     // (stamped builds: barrier exit -> last MFMA issued)
                 const f32x4 ej = j0 + j1;
                 redw[32 * 8] = -s3_dot4(ej, epsr);
                 redw[2 * 32 * 8] = s3_dot4(ej, ej);
