@@ -74,6 +74,8 @@ from . import ensemble_path
 from .ensemble_path import differentiable_generate_path_many, differentiable_inference_path_many, ensemble_path_capacity, \
     ensemble_path_steps, ensemble_path_vjp_capacity, generate_path_many, generate_path_vjp_many, inference_path_many, \
     inference_path_vjp_many
+from . import jvp
+from .jvp import generate_jvp, inference_jvp, jvp_steps, loss_jvp
 from .mlj import (Adam, CondICNFModel, ICNFModel, Lion, Machine, fit, fit_, fitted_params, load_params, machine, save_params,
                   transform)
 

@@ -205,6 +205,16 @@ _ENSEMBLE_PATH_SIGNATURES = {
     "cnf_ensemble_path_steps": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.c_int]),
 }
 ENSEMBLE_PATH_EXPORTS = tuple(_ENSEMBLE_PATH_SIGNATURES)
+# forward-mode derivatives (include/cnfhip_jvp.h): likewise
+_JVP_SIGNATURES = {
+    "cnf_inference_jvp": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), C.c_int, _fp, _fp,
+                                    _fp, C.POINTER(cnf_solve_stats), C.c_void_p]),
+    "cnf_generate_jvp": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts), C.c_int, _fp, _fp,
+                                   _fp, _fp, C.POINTER(cnf_solve_stats), C.c_void_p]),
+    "cnf_jvp_steps": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int]),
+}
+JVP_EXPORTS = tuple(_JVP_SIGNATURES)
+JVP_MAX_R = 65535                  # directions of one call (include/cnfhip_jvp.h)
 
 _lib = None
 
@@ -245,7 +255,7 @@ def lib():
         for name, (res, args) in list(_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) + list(_BASEGRAD_SIGNATURES.items()) + \
                 list(_ENSEMBLE_SIGNATURES.items()) + list(_ENSEMBLE_EVAL_SIGNATURES.items()) + list(_ENSEMBLE_VJP_SIGNATURES.items()) + \
                 list(_ENSEMBLE_GENERATE_VJP_SIGNATURES.items()) + list(_PATH_SIGNATURES.items()) + list(_PATH_VJP_SIGNATURES.items()) + \
-                list(_ENSEMBLE_HETERO_SIGNATURES.items()) + list(_ENSEMBLE_PATH_SIGNATURES.items()):
+                list(_ENSEMBLE_HETERO_SIGNATURES.items()) + list(_ENSEMBLE_PATH_SIGNATURES.items()) + list(_JVP_SIGNATURES.items()):
             f = getattr(l, name)
             f.restype, f.argtypes = res, args
         _lib = l

@@ -10,6 +10,7 @@
 #include "cnf_buf.h"
 #include "cnf_record.h"
 #include "cnf_wave.h"
+#include "cnf_tangent.h"
 #include "cnf_bcast.h"
 #include "cnf_gradt.h"
 #include "cnf_condgrad.h"
@@ -205,6 +206,11 @@ struct cnf_ctx {
     std::vector<float> epath_host;   // [M][epath_rows][2]: the pairs on the host, fetched by ONE strided copy when first asked for
     int epath_rows = -1;          //   pairs per member in epath_host (-1: not fetched yet)
     std::vector<float> saveat_rep;   // one set of save times laid out M times, on its way to the device
+    // cnf_inference_jvp / cnf_generate_jvp (include/cnfhip_jvp.h): solve_core's `jvp` argument says what it does for such a call
+    DevBuf<float> jvp_trace;      // [trace_cap][4]: (t, signed h, EEst, accepted) per attempt
+    DevBuf<float> jvp_buf;        // the primal outputs until the call is known to succeed
+    std::vector<float> jvp_t, jvp_h;   // the accepted steps of the last such call (cnf_jvp_steps)
+    bool jvp_valid = false;
     std::string err;
 };
 static const int PATH_STEPS_CAP = 16384;
@@ -212,6 +218,17 @@ static const int PATH_STEPS_CAP = 16384;
 static const int ENS_PATH_STEPS_CAP = 4096, ENS_PATH_VJP_STEPS_CAP = 1024;
 
 static const int MAX_PARTIALS = 1024;
+// One cnf_inference_jvp in flight, handed to solve_core as `jvp` beside `rec` and `path`: the solve then files its step attempts in
+// the handle's jvp_trace (not in the caller's cnf_set_step_trace buffer), takes the wave kernel as its only one-launch route,
+// enqueues the tangent launch right behind that launch, and on the one-attempt-at-a-time route files the accepted steps here
+struct JvpCall {
+    TangentArgs ta{};             // everything of the tangent launch but where the solve leaves its state and its attempts
+    bool train = false;
+    int trace_cap = 0;
+    bool enqueued = false;        // the tangent launch went out behind a one-launch solve
+    bool host_steps = false;      // the solve ran one attempt at a time: its accepted steps are in t, h
+    std::vector<float> t, h;
+};
 
 #define HIPCHK(h, call)                                                                  \
     do {                                                                                 \
@@ -940,7 +957,7 @@ struct PathHook {
 };
 static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const float* eps, float* u_out, int B,
                              const cnf_solve_opts* opts, cnf_solve_stats* stats, void* stream, Recorder* rec,
-                             bool final_sync = true, PostHook* post = nullptr, PathHook* path = nullptr);
+                             bool final_sync = true, PostHook* post = nullptr, PathHook* path = nullptr, JvpCall* jvp = nullptr);
 
 // One-launch solves of this process: one at a time (two would each hold CUs the other is waiting for), except that
 // submitted launches may queue up behind each other on ONE stream.
@@ -1042,7 +1059,7 @@ static StepState init_step_state(const cnf_solve_opts* opts, int n_partials) {
 
 static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const float* eps, float* u_out, int B,
                              const cnf_solve_opts* opts, cnf_solve_stats* stats, void* stream, Recorder* rec,
-                             bool final_sync, PostHook* post, PathHook* path) {
+                             bool final_sync, PostHook* post, PathHook* path, JvpCall* jvp) {
     cnf_status s = check_call(h, mode, B);
     if (s != CNF_OK) return s;
     h->rec.end();                      // (every solve may overwrite what a record consists of)
@@ -1110,7 +1127,8 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
     // ... or of the 32-128-128-32 network in TestMode (exact trace: k_trace3s<SOLVE>, cnf_trace.hip)
     const bool tsolve_ok = trace_fused && !wave_ok && !bcast_ok && !use_mfma && (!h->nd.n_cond) &&
                            trace_solve_supported(h->nd, adj_mfma_layout(h->nd, grad_layout(h->nd)), B, h->device);
-    if ((use_mfma || wave_ok || bcast_ok || tsolve_ok) && !lockstep && !h->no_persist) {
+    // (a tangent call's one-launch solve is the wave kernel's: cnf_tangent.hip reads what that kernel leaves)
+    if ((use_mfma || wave_ok || bcast_ok || tsolve_ok) && !lockstep && !h->no_persist && (!jvp || wave_ok)) {
         // one such kernel at a time in this process: two of them would each hold CUs the other is waiting for.  Launches
         // queued on ONE stream run one after the other by themselves (submitted inferences); a launch on another stream
         // waits for those first.
@@ -1128,6 +1146,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
         // solve starts).  CNF_SOLVE_WAIT_US overrides; CNF_SOLVE_POLL_LIMIT bounds the number of polls instead (tests: 1).
         set_wait_bounds(h, sv);
         sv.trace = h->step_trace; sv.trace_cap = h->step_trace_cap;
+        if (jvp) { sv.trace = h->jvp_trace; sv.trace_cap = jvp->trace_cap; }
         // (k_trace3s<SOLVE> works on the integrator's buffers: u0 is assembled / copied into U[0] in front of it, the
         // post-processing follows it -- three launches per inference)
         if (tsolve_ok) {
@@ -1179,7 +1198,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
                                    h->d_bstore, h->nd.n_cond > 0 ? h->d_cond : nullptr, h->cbs, rec ? &brec : nullptr);
             if (s == CNF_OK && rec && u_out) sv.u_out = u_out;
         }
-        if (s == CNF_ERR_UNSUPPORTED && use_mfma)
+        if (s == CNF_ERR_UNSUPPORTED && use_mfma && !jvp)
             s = mfma_solve_persistent(h->mfma, h->nd, train, h->d_state, h->U, eps, B, st, h->d_mirror + mslot, base, sv, h->device,
                                       dump, n, slot, dcap, h->traj_hs, h->K1);
         if (s == CNF_OK) {
@@ -1188,6 +1207,15 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
             ++h->one_launch_count;
             h->last_state = h->d_state;
             HIPCHK(h, hipGetLastError());
+            if (jvp) {
+                // the tangent launch, right behind the solve on its stream: no host wait in between.  It reads the solve's final
+                // state first and writes nothing for a solve that gave up (the streamed route below then files the steps)
+                JvpCall& jc = *jvp;
+                jc.ta.st = h->d_state; jc.ta.trace = h->jvp_trace; jc.ta.trace_cap = jc.trace_cap; jc.ta.n_rows = -1;
+                if ((s = tangent_launch(jc.ta, jc.train, st)) != CNF_OK) return fail(h, s, "the tangent launch failed to start");
+                jc.enqueued = true;
+                ++launches;
+            }
             if (h->submitting && rec && rec->wg) {
                 // a submitted gradient: the launch is on its way; cnf_loss_grad_collect reads its outcome from its mirror slot
                 cnf_ctx::Submitted sub;
@@ -1354,7 +1382,7 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
 
     StepState* cur_state = h->d_state;   // slot holding the live integrator state
     int pp = 0;                          // partials buffer the NEXT launch reads
-    if (lockstep || (rec && !use_mfma) || path) {
+    if (lockstep || (rec && !use_mfma) || path || jvp) {
         // one attempt at a time.  Lock-step: every shard must see the same global error norm before
         // the next attempt is sized.  Recording (gradient path): the host files the state after
         // every accepted step.  A path: the host enqueues the interpolation of an accepted step (k_dense_out) before the next
@@ -1364,11 +1392,12 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
         int seen_accept = 0;
         int pcur = 0;                                    // the next save time
         std::vector<float> path_t, path_h;
-        if (path) {
+        if (path || jvp) {
             HIPCHK(h, hipMemcpyAsync(snap, h->d_state, sizeof(StepState), hipMemcpyDeviceToHost, st));
             HIPCHK(h, hipStreamSynchronize(st));
             h_attempt = snap->h; t_attempt = snap->t;
-            for (; pcur < path->K && path->saveat[pcur] == opts->t0; ++pcur)      // save times at the start: u0 itself
+            if (jvp) { jvp->enqueued = false; jvp->host_steps = true; jvp->t.clear(); jvp->h.clear(); }
+            for (; path && pcur < path->K && path->saveat[pcur] == opts->t0; ++pcur)      // save times at the start: u0 itself
                 HIPCHK(h, hipMemcpyAsync(path->out + (size_t)pcur * n, h->U[0], n * sizeof(float), hipMemcpyDeviceToDevice, st));
         }
         if (rec) {
@@ -1419,6 +1448,10 @@ static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const floa
                 HIPCHK(h, hipMemcpyAsync(slot, h->U[snap->cur], n * sizeof(float), hipMemcpyDeviceToDevice, st));
                 rec->hs.push_back(h_attempt);
                 rec->n = seen_accept;
+            }
+            if (jvp && !rec && !path && snap->naccept > seen_accept) {       // a tangent call: the accepted step, for its replay
+                seen_accept = snap->naccept;
+                jvp->t.push_back(t_attempt); jvp->h.push_back(h_attempt);
             }
             if (path && snap->naccept > seen_accept) {
                 // the accepted step (t_attempt, h_attempt) serves every save time up to its end -- the last step everything left;
@@ -1657,7 +1690,7 @@ extern "C" cnf_status cnf_inference_post(cnf_handle h, int mode, const float* u_
 
 static cnf_status inference_impl(cnf_handle h, int mode, const float* xs, const float* eps,
                                  float* logpx, float* regs, float* u_final, float* sums5, int B,
-                                 const cnf_solve_opts* opts, cnf_solve_stats* stats, void* stream) {
+                                 const cnf_solve_opts* opts, cnf_solve_stats* stats, void* stream, JvpCall* jvp = nullptr) {
     cnf_status s = check_call(h, mode, B);
     if (s != CNF_OK) return s;
     if (!xs || !logpx || !regs || !opts) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
@@ -1671,7 +1704,7 @@ static cnf_status inference_impl(cnf_handle h, int mode, const float* xs, const 
     // no allocations and no copies on this path: u0 is assembled in the integrator's own state buffer, and the
     // post-processing reads the final state from wherever the integrator left it
     PostHook ph{logpx, regs, sums5, xs};
-    if (s == CNF_OK) s = solve_core(h, mode, h->U[0], eps, u_final, B, opts, stats, stream, nullptr, false, &ph);
+    if (s == CNF_OK) s = solve_core(h, mode, h->U[0], eps, u_final, B, opts, stats, stream, nullptr, false, &ph, nullptr, jvp);
     if (s == CNF_OK && !ph.launched) {                      // (the one-attempt-at-a-time drivers leave it to the caller)
         enqueue_post(h, mode == CNF_MODE_TRAIN, h->last_state, ph, B, false, (hipStream_t)stream);   // stream-ordered
         HIPCHK(h, hipGetLastError());
@@ -3334,6 +3367,155 @@ extern "C" int cnf_ensemble_path_steps(cnf_handle h, int member, float* t_host, 
             if (t_host) t_host[i] = pairs[2 * (size_t)i];
             if (h_host) h_host[i] = pairs[2 * (size_t)i + 1];
         }
+    }
+    return n;
+}
+
+// ---- forward-mode derivatives (include/cnfhip_jvp.h; cnf_tangent.hip) ------------------------------------------------------------
+// Both entry points are: the solve of the call they extend -- inference's with solve_core's `jvp` argument: it keeps the step
+// attempts in jvp_trace and enqueues k_tangent_wave behind a one-launch solve, or files the accepted steps of the
+// one-attempt-at-a-time route --, the tangent launch over the host-filed steps where it has not gone out yet, and the primal
+// outputs handed over once nothing can fail any more.
+static const int JVP_TRACE_DEFAULT = 4096, JVP_TRACE_MAX = 65536;
+// what both calls check before any device is asked for, and the envelope
+static cnf_status jvp_check(cnf_handle h, int mode, int B, bool ptrs_ok, const float* d_ps, const float* d_x, int R, int trace_cap) {
+    if (!h) return CNF_ERR_BAD_ARG;
+    if (mode != CNF_MODE_TEST && mode != CNF_MODE_TRAIN) return fail(h, CNF_ERR_BAD_ARG, "unknown mode");
+    if (!ptrs_ok) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    if (!d_ps && !d_x) return fail(h, CNF_ERR_BAD_ARG, "both directions are null");
+    if (R < 1 || R > TG_MAX_R) return fail(h, CNF_ERR_BAD_ARG, "R must be within [1, 65535]");
+    if (trace_cap < 0 || trace_cap > JVP_TRACE_MAX) return fail(h, CNF_ERR_BAD_ARG, "trace_cap must be within [0, 65536]");
+    if (B < 1) return fail(h, CNF_ERR_BAD_SHAPE, "a tangent call needs B >= 1");
+    if (!tangent_supported(h->nd_wave))
+        return fail(h, CNF_ERR_UNSUPPORTED, "tangents: two layers, tanh then tanh or identity, n_in <= 16, at most 64 hidden units (16 with the identity), no conditioning");
+    if (h->bd.kind) return fail(h, CNF_ERR_UNSUPPORTED, "tangents: the default base distribution only");
+    if (h->shard_reduce != nullptr || h->shard_comm != nullptr) return fail(h, CNF_ERR_UNSUPPORTED, "tangents: no lock-step shards");
+    return CNF_OK;
+}
+// behind the solve: the tangent launch where the solve's route left it to the caller, then the accepted steps onto the handle
+static cnf_status jvp_finish(cnf_handle h, JvpCall& jc, const cnf_solve_stats& sst, int* launches, hipStream_t st) {
+    if (jc.enqueued) {
+        const int att = sst.naccept + sst.nreject;
+        if (att > jc.trace_cap) return fail(h, CNF_ERR_UNSUPPORTED, "the solve made more step attempts than trace_cap");
+        std::vector<float> rows((size_t)4 * att);
+        if (att > 0) HIPCHK(h, hipMemcpyAsync(rows.data(), h->jvp_trace, rows.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+        h->jvp_t.clear(); h->jvp_h.clear();
+        for (int i = 0; i < att; ++i)
+            if (rows[4 * (size_t)i + 3] != 0.f) { h->jvp_t.push_back(rows[4 * (size_t)i]); h->jvp_h.push_back(rows[4 * (size_t)i + 1]); }
+        return CNF_OK;
+    }
+    if (!jc.host_steps) return fail(h, CNF_ERR_UNSUPPORTED, "tangents: the solve took a route that files no steps");
+    const size_t n = jc.t.size();
+    if (n > (size_t)jc.trace_cap) return fail(h, CNF_ERR_UNSUPPORTED, "the solve took more steps than trace_cap");
+    std::vector<float> rows(4 * n);
+    for (size_t i = 0; i < n; ++i) { rows[4 * i] = jc.t[i]; rows[4 * i + 1] = jc.h[i]; rows[4 * i + 2] = 0.f; rows[4 * i + 3] = 1.f; }
+    if (n > 0) HIPCHK(h, hipMemcpyAsync(h->jvp_trace, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    jc.ta.st = h->last_state; jc.ta.trace = h->jvp_trace; jc.ta.trace_cap = jc.trace_cap; jc.ta.n_rows = (int)n;
+    const cnf_status s = tangent_launch(jc.ta, jc.train, st);
+    if (s != CNF_OK) return fail(h, s, "the tangent launch failed to start");
+    ++*launches;
+    HIPCHK(h, hipStreamSynchronize(st));                   // (`rows` is on its way until here)
+    h->jvp_t = jc.t; h->jvp_h = jc.h;
+    return CNF_OK;
+}
+
+extern "C" cnf_status cnf_inference_jvp(cnf_handle h, int mode, const float* xs, const float* eps, int B, const float* d_ps,
+                                        const float* d_xs, int R, const cnf_solve_opts* opts, int trace_cap, float* logpx, float* regs,
+                                        float* d_out, cnf_solve_stats* stats, void* stream) {
+    const bool train = mode == CNF_MODE_TRAIN;
+    cnf_status s = jvp_check(h, mode, B, xs && opts && logpx && regs && d_out && (!train || eps), d_ps, d_xs, R, trace_cap);
+    if (s != CNF_OK) return s;
+    h->jvp_valid = false;
+    if (!wave_solve_supported(h->nd_wave, train, B)) return fail(h, CNF_ERR_UNSUPPORTED, "tangents: no one-launch solve of this batch size");
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(h, hipSetDevice(h->device));
+    JvpCall jc;
+    jc.train = train; jc.trace_cap = trace_cap > 0 ? trace_cap : JVP_TRACE_DEFAULT;
+    const size_t Bz = (size_t)B;
+    if ((size_t)4 * jc.trace_cap > h->jvp_trace.capacity() || 4 * Bz > h->jvp_buf.capacity()) {
+        HIPCHK(h, hipStreamSynchronize(st));
+        RESERVE(h, h->jvp_trace, (size_t)4 * jc.trace_cap);
+        RESERVE(h, h->jvp_buf, (4 * Bz + 1023) & ~(size_t)1023);
+    }
+    float* p_logpx = h->jvp_buf; float* p_regs = p_logpx + Bz;
+    TangentArgs& ta = jc.ta;
+    ta.nd = h->nd_wave; ta.P = h->d_params; ta.dP = d_ps; ta.n_params = (int)h->n_params; ta.eps = train ? eps : nullptr;
+    ta.B = B; ta.R = R; ta.sampling = 0; ta.x = xs; ta.dX = d_xs; ta.out = d_out;
+    cnf_solve_stats sst{};
+    s = inference_impl(h, mode, xs, eps, p_logpx, p_regs, nullptr, nullptr, B, opts, &sst, stream, &jc);
+    if (s != CNF_OK) return s;
+    int launches = sst.launches;
+    if ((s = jvp_finish(h, jc, sst, &launches, st)) != CNF_OK) return s;
+    HIPCHK(h, hipMemcpyAsync(logpx, p_logpx, Bz * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(regs, p_regs, 3 * Bz * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    h->jvp_valid = true;
+    if (stats) { *stats = sst; stats->launches = launches; }
+    return CNF_OK;
+}
+
+// Sampling.  Its primal half is cnf_generate_record's own RECORDED solve, not the plain one-launch solve: `generate(with_logp)` is
+// that call, and the two routes differ in the last bits (and sometimes by a step) -- so that (z, logq) are that call's bit for
+// bit, the solve is taken on its route, the accepted steps come back with the record's step sizes, and the tangent launch
+// follows over them.  Like every solve it ends the record on the handle; the step sizes cnf_grad_steps reports are put back.
+extern "C" cnf_status cnf_generate_jvp(cnf_handle h, int mode, const float* z0, const float* eps, int B, const float* d_ps,
+                                       const float* d_z0, int R, const cnf_solve_opts* opts, int trace_cap, float* z_out, float* logq,
+                                       float* d_z, float* d_logq, cnf_solve_stats* stats, void* stream) {
+    const bool train = mode == CNF_MODE_TRAIN;
+    cnf_status s = jvp_check(h, mode, B, z0 && opts && z_out && logq && d_z && d_logq && (!train || eps), d_ps, d_z0, R, trace_cap);
+    if (s != CNF_OK) return s;
+    h->jvp_valid = false;
+    hipStream_t st = (hipStream_t)stream;
+    if ((s = grad_prologue(h, mode, B, true, "a tangent call needs B >= 1", train, st)) != CNF_OK) return s;
+    HIPCHK(h, hipSetDevice(h->device));
+    JvpCall jc;
+    jc.train = train; jc.trace_cap = trace_cap > 0 ? trace_cap : JVP_TRACE_DEFAULT;
+    const int n_in = h->nd.n_in, D = rows_of(h, mode);
+    const size_t Bz = (size_t)B, nz = (size_t)n_in * Bz;
+    if ((size_t)4 * jc.trace_cap > h->jvp_trace.capacity() || nz + Bz > h->jvp_buf.capacity()) {
+        HIPCHK(h, hipStreamSynchronize(st));
+        RESERVE(h, h->jvp_trace, (size_t)4 * jc.trace_cap);
+        RESERVE(h, h->jvp_buf, (nz + Bz + 1023) & ~(size_t)1023);
+    }
+    float* p_z = h->jvp_buf; float* p_logq = p_z + nz;
+    // u0 = [z0; 0] where cnf_generate_record assembles it
+    float* u0 = h->g_US[0];
+    HIPCHK(h, hipMemsetAsync(u0, 0, (size_t)D * Bz * sizeof(float), st));
+    HIPCHK(h, hipMemcpy2DAsync(u0, (size_t)D * sizeof(float), z0, (size_t)n_in * sizeof(float), (size_t)n_in * sizeof(float), Bz,
+                               hipMemcpyDeviceToDevice, st));
+    TangentArgs& ta = jc.ta;
+    ta.nd = h->nd_wave; ta.P = h->d_params; ta.dP = d_ps; ta.n_params = (int)h->n_params; ta.eps = train ? eps : nullptr;
+    ta.B = B; ta.R = R; ta.sampling = 1; ta.x = z0; ta.dX = d_z0; ta.out = d_z; ta.out_logq = d_logq;
+    Recorder rec;
+    cnf_solve_stats sst{};
+    const std::vector<float> kept_hs = h->last_hs;
+    s = record_solve(h, mode, u0, train ? eps : nullptr, B, opts, rec, sst, stream);
+    h->last_hs = kept_hs;
+    if (s != CNF_OK) return s;
+    int launches = sst.launches;
+    launch_generate_post(n_in, D, h->bd, h->g_US[1], z0, p_z, p_logq, B, st);
+    HIPCHK(h, hipGetLastError());
+    ++launches;
+    // the accepted steps: the record's signed sizes, the times as the controller adds them up (the last step ends at t1)
+    jc.host_steps = true;
+    float t = opts->t0;
+    for (float hn : rec.hs) { jc.t.push_back(t); jc.h.push_back(hn); t += hn; }
+    if ((s = jvp_finish(h, jc, sst, &launches, st)) != CNF_OK) return s;
+    HIPCHK(h, hipMemcpyAsync(z_out, p_z, nz * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(logq, p_logq, Bz * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    h->jvp_valid = true;
+    if (stats) { *stats = sst; stats->launches = launches; }
+    return CNF_OK;
+}
+
+extern "C" int cnf_jvp_steps(cnf_handle h, float* t_host, float* h_host, int cap) {
+    if (!h || !h->jvp_valid) return -1;
+    const int n = (int)h->jvp_t.size();
+    for (int i = 0; i < n && i < cap; ++i) {
+        if (t_host) t_host[i] = h->jvp_t[i];
+        if (h_host) h_host[i] = h->jvp_h[i];
     }
     return n;
 }

@@ -395,6 +395,10 @@ cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int B, float* 
  * cnf_generate_path_vjp_many / cnf_ensemble_path_steps (declared in cnfhip_ensemble_path.h, part of this header) ---- */
 #include "cnfhip_ensemble_path.h"
 
+/* ---- forward-mode derivatives: inference / sampling plus R tangents of their outputs in one more launch --
+ * cnf_inference_jvp / cnf_generate_jvp / cnf_jvp_steps (declared in cnfhip_jvp.h, part of this header) ---- */
+#include "cnfhip_jvp.h"
+
 /* ---- device random numbers ------------------------------------------
  *
  * The library's own counter-based generator, the counterpart of the device RNG the reference draws eps and
