@@ -9,6 +9,7 @@
 #include "cnf_mirror.h"
 #include "cnf_buf.h"
 #include "cnf_record.h"
+#include "cnf_solve_plan.h"
 #include "cnf_wave.h"
 #include "cnf_tangent.h"
 #include "cnf_bcast.h"
@@ -19,8 +20,8 @@
 #include "cnf_dist.h"
 #include "cnf_basegrad.h"
 #include <immintrin.h>
+#include <algorithm>
 #include <sched.h>
-#include <vector>
 
 #include <cmath>
 #include <cstdlib>
@@ -122,9 +123,6 @@ struct cnf_ctx {
     DevBuf<float> d_gt;           // k_adj_test: one partial of the flat gradient and a scratch per workgroup (cnf_gradt.hip)
     DevBuf<float> d_bstore;       // ... and the store of its tiles' Runge-Kutta rows when a workgroup carries several (bcast_store_floats)
     bool bimg_valid = false;
-    bool trace_on = false;        // this call evaluates through an auxiliary MFMA kernel (cnf_trace.hip) behind the generic driver
-    bool aux_train = false;       //   false: TestMode exact trace; true: TrainMode JVP
-    const float* aux_eps = nullptr;
     DevBuf<float> traj;                // trajectory store: traj_cap slots of 6 (n_in + 3) grad_cap_B floats (u_n, U_2..U_6)
     DevBuf<float> traj_hs;             // device: signed size of accepted step n (written by the step kernel)
     int traj_cap = 0;
@@ -206,7 +204,7 @@ struct cnf_ctx {
     std::vector<float> epath_host;   // [M][epath_rows][2]: the pairs on the host, fetched by ONE strided copy when first asked for
     int epath_rows = -1;          //   pairs per member in epath_host (-1: not fetched yet)
     std::vector<float> saveat_rep;   // one set of save times laid out M times, on its way to the device
-    // cnf_inference_jvp / cnf_generate_jvp (include/cnfhip_jvp.h): solve_core's `jvp` argument says what it does for such a call
+    // cnf_inference_jvp / cnf_generate_jvp (include/cnfhip_jvp.h): SolveCall's `jvp` hook says what the solve does for such a call
     DevBuf<float> jvp_trace;      // [trace_cap][4]: (t, signed h, EEst, accepted) per attempt
     DevBuf<float> jvp_buf;        // the primal outputs until the call is known to succeed
     std::vector<float> jvp_t, jvp_h;   // the accepted steps of the last such call (cnf_jvp_steps)
@@ -218,7 +216,7 @@ static const int PATH_STEPS_CAP = 16384;
 static const int ENS_PATH_STEPS_CAP = 4096, ENS_PATH_VJP_STEPS_CAP = 1024;
 
 static const int MAX_PARTIALS = 1024;
-// One cnf_inference_jvp in flight, handed to solve_core as `jvp` beside `rec` and `path`: the solve then files its step attempts in
+// One cnf_inference_jvp in flight, SolveCall's `jvp` hook beside `rec` and `path`: the solve then files its step attempts in
 // the handle's jvp_trace (not in the caller's cnf_set_step_trace buffer), takes the wave kernel as its only one-launch route,
 // enqueues the tangent launch right behind that launch, and on the one-attempt-at-a-time route files the accepted steps here
 struct JvpCall {
@@ -646,11 +644,17 @@ struct TraceFuse {          // norms / controller / the whole attempt inside the
     void* mirror = nullptr;
     unsigned seq = 0;
 };
-static bool trace_fused_ok(cnf_handle h, int B) {
+// how a call evaluates through an auxiliary MFMA kernel behind the generic driver (on: it does)
+struct AuxEval {
+    bool on = false;
+    bool train = false;           // false: TestMode exact trace; true: TrainMode JVP
+    const float* eps = nullptr;
+};
+static bool trace_fused_ok(cnf_handle h, const AuxEval& aux, int B) {
     const GradLayout g = grad_layout(h->nd);
-    return !h->aux_train && trace_fused_supported(h->nd, adj_mfma_layout(h->nd, g), B);
+    return !aux.train && trace_fused_supported(h->nd, adj_mfma_layout(h->nd, g), B);
 }
-static cnf_status launch_trace(cnf_handle h, const float* u, float* du, bool in_solve, bool du_is_k7, int B, hipStream_t st,
+static cnf_status launch_trace(cnf_handle h, const AuxEval& aux, const float* u, float* du, bool in_solve, bool du_is_k7, int B, hipStream_t st,
                                int nk = 0, const float* coef = nullptr, bool also_unew = false, const TraceFuse* fuse = nullptr) {
     const GradLayout g = grad_layout(h->nd);
     const AdjMfmaLayout m = adj_mfma_layout(h->nd, g);
@@ -670,7 +674,7 @@ static cnf_status launch_trace(cnf_handle h, const float* u, float* du, bool in_
         a.n_total = (float)((size_t)rows_of(h, CNF_MODE_TEST) * B);
         a.mirror = fuse->mirror; a.seq = fuse->seq;
     }
-    if (h->aux_train && h->nd.jvp) HIPCHK(h, launch_jvp_mfma(h->nd, g, m, h->d_adj_img, a, h->aux_eps, st));
+    if (aux.train && h->nd.jvp) HIPCHK(h, launch_jvp_mfma(h->nd, g, m, h->d_adj_img, a, aux.eps, st));
     else HIPCHK(h, launch_trace_mfma(h->nd, g, m, h->d_adj_img, a, st));
     return CNF_OK;
 }
@@ -791,8 +795,8 @@ extern "C" cnf_status cnf_rhs(cnf_handle h, int mode, int kernel, const float* u
     if (k == CNF_KERNEL_MFMA && !mfma_supported(h->mfma, h->nd, mode == CNF_MODE_TRAIN, B)) {
         // TestMode, three or more layers: exact trace on MFMA; TrainMode/JVP beyond LDS (cnf_trace.hip)
         if ((s = ensure_adj_images(h, st)) != CNF_OK) return s;
-        h->aux_train = mode == CNF_MODE_TRAIN; h->aux_eps = eps;
-        if ((s = launch_trace(h, u, du, false, false, B, st)) != CNF_OK) return s;
+        const AuxEval aux{true, mode == CNF_MODE_TRAIN, eps};
+        if ((s = launch_trace(h, aux, u, du, false, false, B, st)) != CNF_OK) return s;
     } else if (k == CNF_KERNEL_MFMA) {
         s = mfma_rhs(h->mfma, h->nd, mode == CNF_MODE_TRAIN, u, eps, du, B, st);
         if (s != CNF_OK) return fail(h, s, "MFMA RHS launch failed");
@@ -833,7 +837,7 @@ extern "C" cnf_status cnf_rhs_host(cnf_handle h, int mode, int kernel, const flo
 // ---------------------------------------------------------------------------------------
 // Tsit5 driver (a7: base_sol, src/base_icnf.jl:137-143)
 // ---------------------------------------------------------------------------------------
-static int enqueue_attempt_generic(cnf_handle h, int train, const float* eps, int B,
+static int enqueue_attempt_generic(cnf_handle h, const AuxEval& aux, int train, const float* eps, int B,
                                     int nblk, hipStream_t s, bool with_controller = true,
                                     float* dump = nullptr, size_t dump_stride = 0, void* mirror = nullptr,
                                     unsigned seq = 0) {
@@ -841,18 +845,18 @@ static int enqueue_attempt_generic(cnf_handle h, int train, const float* eps, in
     a.st = h->d_state; a.B = B; a.S = h->cap_B; a.train = train; a.ws = h->ws; a.eps = eps;
     a.cond = h->mfma.cond; a.cbs = h->cbs;
     set_rk_buffers(h, a);
-    if (h->trace_on && with_controller && !dump && trace_fused_ok(h, B)) {
+    if (aux.on && with_controller && !dump && trace_fused_ok(h, aux, B)) {
         // TestMode on the 32-128-128-32 shape: the six stage evaluations, the error norm and the controller in ONE launch
         TraceFuse f; f.norm_kind = 2; f.step = true; f.mirror = mirror; f.seq = seq;
-        (void)launch_trace(h, nullptr, nullptr, true, false, B, s, 0, nullptr, false, &f);
+        (void)launch_trace(h, aux, nullptr, nullptr, true, false, B, s, 0, nullptr, false, &f);
         return 1;
     }
-    for (int stage = 1; stage <= 6 && h->trace_on; ++stage) {     // the auxiliary kernel forms its stage state itself
+    for (int stage = 1; stage <= 6 && aux.on; ++stage) {     // the auxiliary kernel forms its stage state itself
         float coef[6];
         tsit5_row(stage, coef);
-        (void)launch_trace(h, nullptr, stage < 6 ? h->Ks[stage - 1] : nullptr, true, stage == 6, B, s, stage, coef, stage == 6);
+        (void)launch_trace(h, aux, nullptr, stage < 6 ? h->Ks[stage - 1] : nullptr, true, stage == 6, B, s, stage, coef, stage == 6);
     }
-    for (int stage = 1; stage <= 6 && !h->trace_on; ++stage) {      // computes k_{stage+1}
+    for (int stage = 1; stage <= 6 && !aux.on; ++stage) {      // computes k_{stage+1}
         a.nk = stage;
         tsit5_row(stage, a.coef);
         a.ustage = (dump && stage < 6) ? dump + (size_t)(stage - 1) * dump_stride : nullptr;   // stage states 2..6
@@ -955,9 +959,19 @@ struct PathHook {
     int K;
     float* out;                    // device, [K][B][D]
 };
-static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const float* eps, float* u_out, int B,
-                             const cnf_solve_opts* opts, cnf_solve_stats* stats, void* stream, Recorder* rec,
-                             bool final_sync = true, PostHook* post = nullptr, PathHook* path = nullptr, JvpCall* jvp = nullptr);
+// What a caller asks of solve_core: the solve itself, then the hooks (at most one of rec / path / jvp) and whether the call
+// waits for the stream before it returns
+struct SolveCall {
+    int mode, B;
+    const float *u0, *eps;
+    float* u_out;                  // may be null: the state stays in U[cur]
+    const cnf_solve_opts* opts;
+    cnf_solve_stats* stats;
+    void* stream;
+    Recorder* rec = nullptr; PostHook* post = nullptr; PathHook* path = nullptr; JvpCall* jvp = nullptr;
+    bool final_sync = true;
+};
+static cnf_status solve_core(cnf_handle h, const SolveCall& call);
 
 // One-launch solves of this process: one at a time (two would each hold CUs the other is waiting for), except that
 // submitted launches may queue up behind each other on ONE stream.
@@ -1021,7 +1035,7 @@ extern "C" cnf_status cnf_solve_tsit5(cnf_handle h, int mode, const float* u0,
                                       const cnf_solve_opts* opts, cnf_solve_stats* stats,
                                       void* stream) {
     if (h && !u_out) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
-    return solve_core(h, mode, u0, eps, u_out, B, opts, stats, stream, nullptr);
+    return solve_core(h, SolveCall{mode, B, u0, eps, u_out, opts, stats, stream});
 }
 
 // the bounds of a wait inside a one-launch solve of this handle (cnf_set_solve_wait; CNF_SOLVE_WAIT_US, CNF_SOLVE_POLL_LIMIT)
@@ -1057,541 +1071,528 @@ static StepState init_step_state(const cnf_solve_opts* opts, int n_partials) {
     return init;
 }
 
-static cnf_status solve_core(cnf_handle h, int mode, const float* u0, const float* eps, float* u_out, int B,
-                             const cnf_solve_opts* opts, cnf_solve_stats* stats, void* stream, Recorder* rec,
-                             bool final_sync, PostHook* post, PathHook* path, JvpCall* jvp) {
-    cnf_status s = check_call(h, mode, B);
+// One call on its way through the drivers below: the call, its route (cnf_solve_plan.h) and what the drivers share
+struct SolveRun {
+    const SolveCall& c;
+    SolveRoute rt;
+    AuxEval aux;
+    int k = 0, train = 0, D = 0, nblk = 0;     // nblk: error partials = blocks of whichever kernel writes them
+    size_t n = 0;                  // floats of the state
+    hipStream_t st = nullptr;
+    StepState* init = nullptr;     // the state the solve starts from (pinned)
+    bool final_sync = true;
+    int launches = 0, nf = 0;
+};
+
+// Gradient path on the device-indexed routes: every attempt files u_n and its stage states in the slot of step `naccept`; the
+// store is sized beforehand and the solve repeated if it took more steps than fit
+struct TrajDump { float* dump = nullptr; size_t slot = 0; int dcap = 0; };
+static cnf_status traj_dump(cnf_handle h, size_t n, TrajDump* d) {
+    const cnf_status s = traj_reserve(h, 64);
     if (s != CNF_OK) return s;
-    h->rec.end();                      // (every solve may overwrite what a record consists of)
-    if (!u0 || !opts) return fail(h, CNF_ERR_BAD_ARG, "null pointer");      // u_out may be null: the state stays in U[cur]
-    const int train = mode == CNF_MODE_TRAIN;
-    if (train && !eps) return fail(h, CNF_ERR_BAD_ARG, "eps is required in TrainMode");
-    if ((s = check_solve_opts(h, opts)) != CNF_OK) return s;
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (B == 0) return CNF_OK;
-    int k;
-    if ((s = resolve_kernel(h, mode, B, opts->kernel, &k)) != CNF_OK) return s;
-    if ((s = ensure_capacity(h, B)) != CNF_OK) return s;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    const int D = rows_of(h, mode);
-    const size_t n = (size_t)D * B;
-    int launches = 0;
+    d->slot = traj_slot_floats(h); d->dcap = h->traj_cap;
+    d->dump = h->traj + n;                           // stage area of slot 0; u_n sits one array before
+    return CNF_OK;
+}
+// ... and its step sizes back from the device into rec->hs (enqueued: the caller waits for the stream)
+static cnf_status recorder_fetch_hs(cnf_handle h, Recorder* rec, const StepState& fin, hipStream_t st) {
+    rec->n = fin.naccept;
+    rec->overflow = !rec->wg && fin.naccept > h->traj_cap;
+    rec->hs.assign((size_t)(rec->overflow ? 0 : fin.naccept), 0.f);
+    if (!rec->overflow && fin.naccept > 0)
+        HIPCHK(h, hipMemcpyAsync(rec->hs.data(), rec->wg ? rec->wg->hs_out : h->traj_hs, (size_t)fin.naccept * sizeof(float),
+                                 hipMemcpyDeviceToHost, st));
+    return CNF_OK;
+}
+// the accepted steps of a path call, as cnf_path_steps hands them out
+static void path_keep_steps(cnf_handle h, std::vector<float>& t, std::vector<float>& hh, bool nonfinite) { h->path_t.swap(t); h->path_h.swap(hh); h->path_valid = !nonfinite; }
+// ... of the in-launch route: the pairs the launch filed, back from the device
+static cnf_status path_fetch_steps(cnf_handle h, const StepState& fin, hipStream_t st) {
+    std::vector<float> pairs((size_t)2 * fin.naccept), t((size_t)fin.naccept), hh((size_t)fin.naccept);
+    if (fin.naccept > 0) HIPCHK(h, hipMemcpyAsync(pairs.data(), h->d_path_steps, pairs.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    for (int i = 0; i < fin.naccept; ++i) { t[i] = pairs[2 * i]; hh[i] = pairs[2 * i + 1]; }
+    path_keep_steps(h, t, hh, fin.nonfinite != 0);
+    return CNF_OK;
+}
 
-    // (a path needs k_2 .. k_6 of every accepted step in the handle's buffers: where the fused step kernel would run, its solve
-    // takes the per-stage generic kernel instead)
-    const bool mfma_ok = k == CNF_KERNEL_MFMA && mfma_supported(h->mfma, h->nd, train, B);
-    const bool use_mfma = mfma_ok && !path;
-    // generic driver + an auxiliary MFMA kernel per stage.  Not for the recorded TrainMode solve of the gradient path: k_jvp_mfma
-    // does not file the stage states the pullback starts from (k_mfma and the generic stage kernel do), so that solve runs the
-    // generic stage kernel
-    h->trace_on = k == CNF_KERNEL_MFMA && !mfma_ok && !(rec && train);
-    h->aux_train = train != 0; h->aux_eps = eps;
-    if (h->trace_on && (s = ensure_adj_images(h, (hipStream_t)stream)) != CNF_OK) return s;
-    // lock-step over shards only matters when the controller decides something
-    const bool lockstep = (h->shard_reduce != nullptr || h->shard_comm != nullptr) && opts->adaptive;
-    // number of error partials = blocks of whichever kernel writes them
-    int nblk = (int)((n + 255) / 256);
-    if (nblk > 256) nblk = 256;
-    if (use_mfma) nblk = mfma_grid_for(h->mfma, B, rec != nullptr, train != 0);
-    // TestMode on k_trace3s: the trace launches write the error partials themselves (one pair per workgroup)
-    const bool trace_fused = h->trace_on && !lockstep && !rec && !path && trace_fused_ok(h, B);
-    if (trace_fused) nblk = trace_fused_grid(B);
-
-    // initial state
-    StepState* init = init_state(h);
-    *init = init_step_state(opts, nblk);
-    const bool hairer = opts->adaptive && opts->dt == 0.f;
-    // The whole solve in ONE launch where the handle and the batch allow it (k_solve3b / k_solve3jb): the weights and the
-    // Runge-Kutta rows stay on the CUs for all attempts, the workgroups exchange two floats per attempt.
-    // ... or of a small two-layer network, one wave per 16-sample tile, registers only (k_solve_wave, cnf_wave.hip)
-    // (a one-layer tanh network has no other MFMA kernel: AUTO resolves to GENERIC for it, and the wave kernels take it
-    // through its appended identity layer unless GENERIC was asked for)
-    const bool wave_k = k == CNF_KERNEL_MFMA || (h->nd_wave.id2 && opts->kernel != CNF_KERNEL_GENERIC);
-    const bool wave_ok = wave_k && (!rec || (rec->wg && post && post->xs && wave_grad_supported(h->nd_wave, B, train != 0))) &&
-                         wave_solve_supported(h->nd_wave, train != 0, B);
-    if (rec && rec->wg && !(wave_ok && !lockstep && !h->no_persist)) { rec->wg_failed = true; return CNF_OK; }
-    // ... or of config 5's network at eight columns per CU (k_solve_bcast, cnf_bcast.hip)
-    // (the gradient's recorded forward too, where one tile per workgroup holds the batch)
-    const bool bcast_rec = rec && !rec->wg && train && bcast_store_floats(B, h->device) == 0;
-    const bool bcast_ok = k == CNF_KERNEL_MFMA && (!rec || bcast_rec) && !wave_ok && !path && bcast_solve_supported(h->nd, train != 0, B, h->device);
-    if (bcast_ok && !lockstep && !h->no_persist) {
-        RESERVE(h, h->d_bimg, bcast_img_floats());          // (allocated on first use)
-        if (!h->bimg_valid) { bcast_pack(h->nd, h->d_params, h->d_bimg, st); HIPCHK(h, hipGetLastError()); h->bimg_valid = true; }
-        const size_t need = bcast_store_floats(B, h->device);        // several tiles per workgroup: their rows live in global memory
-        if (need > h->d_bstore.capacity()) {
-            HIPCHK(h, hipStreamSynchronize(st));
-            RESERVE(h, h->d_bstore, need);
-        }
+// What every driver ends with: the final state to u_out (copy), what a device-indexed route filed on the device back to the host
+// (device_steps: the recorder's step sizes, the path's step pairs), the wait, the statistics, the non-finite return
+static cnf_status finish_solve(cnf_handle h, SolveRun& r, const StepState* state_dev, const StepState& fin, bool copy, bool device_steps,
+                               int nf, int kernel_used) {
+    Recorder* rec = r.c.rec;
+    if (copy) { launch_copy_final(state_dev, h->U[0], h->U[1], r.c.u_out, r.n, r.st); ++r.launches; }
+    HIPCHK(h, hipGetLastError());
+    if (device_steps && rec) {
+        const cnf_status s = recorder_fetch_hs(h, rec, fin, r.st);
+        if (s != CNF_OK) return s;
+        if (rec->wg) rec->wg_done = true;
+        else r.final_sync = true;
     }
-    // ... or of the 32-128-128-32 network in TestMode (exact trace: k_trace3s<SOLVE>, cnf_trace.hip)
-    const bool tsolve_ok = trace_fused && !wave_ok && !bcast_ok && !use_mfma && (!h->nd.n_cond) &&
-                           trace_solve_supported(h->nd, adj_mfma_layout(h->nd, grad_layout(h->nd)), B, h->device);
-    // (a tangent call's one-launch solve is the wave kernel's: cnf_tangent.hip reads what that kernel leaves)
-    if ((use_mfma || wave_ok || bcast_ok || tsolve_ok) && !lockstep && !h->no_persist && (!jvp || wave_ok)) {
-        // one such kernel at a time in this process: two of them would each hold CUs the other is waiting for.  Launches
-        // queued on ONE stream run one after the other by themselves (submitted inferences); a launch on another stream
-        // waits for those first.
-        std::unique_lock<std::mutex> persist_lock(g_persist_mu);
-        if (g_submitted_inflight > 0 && g_submitted_stream != st) HIPCHK(h, hipStreamSynchronize(g_submitted_stream));
-        const unsigned base = h->mirror_base;
-        const int mslot = 1 + (int)(h->one_launch_count % 3);
-        Solve3Args sv{};
-        sv.part = h->partials; sv.base_dev = sums_word<unsigned>(h, SUMS_MEET_BASE); sv.abort_flag = sums_word<int>(h, SUMS_ABORT);
-        sv.t_out = h->time_kernel ? sums_word<unsigned long long>(h, SUMS_CLOCK) : nullptr;
-        sv.maxiters = (int)opts->maxiters; sv.hairer = hairer ? 1 : 0; sv.init = *init;
-        // How long a wait inside the kernel lasts before it gives up: bounded in TIME (the kernel's 100 MHz clock) -- 2 ms per
-        // tile a workgroup carries (a meeting's arrivals are microseconds apart when every workgroup is placed; a workgroup
-        // that is not placed because another tenant holds its CU makes the launch give up after that long, and the streamed
-        // solve starts).  CNF_SOLVE_WAIT_US overrides; CNF_SOLVE_POLL_LIMIT bounds the number of polls instead (tests: 1).
-        set_wait_bounds(h, sv);
-        sv.trace = h->step_trace; sv.trace_cap = h->step_trace_cap;
-        if (jvp) { sv.trace = h->jvp_trace; sv.trace_cap = jvp->trace_cap; }
-        // (k_trace3s<SOLVE> works on the integrator's buffers: u0 is assembled / copied into U[0] in front of it, the
-        // post-processing follows it -- three launches per inference)
-        if (tsolve_ok) {
-            if (post && post->xs) launch_build_u0(post->xs, h->U[0], h->nd.nvars, D, B, st);
-            else if (u0 != h->U[0]) HIPCHK(h, hipMemcpyAsync(h->U[0], u0, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-            ++launches;
-        }
-        const bool fused_io = post && post->xs && !tsolve_ok;   // inference: u0 from the data columns and the post-processing in the launch
-        if (fused_io) { sv.xs = post->xs; sv.logpx = post->logpx; sv.regs = post->regs; sv.sums5 = post->sums5; if (rec) sv.u_out = u_out; }
-        else { sv.u0 = u0; sv.u_out = tsolve_ok ? nullptr : u_out; }   // (the launcher reads u0 in place or copies it into U[0])
-        // gradient path: every attempt files u_n and its stage states in the slot of step `naccept` (as the streamed
-        // recording does); the store is sized beforehand and the solve repeated if it took more steps than fit
-        float* dump = nullptr; size_t slot = 0; int dcap = 0;
-        if (rec && !rec->wg) {
-            if ((s = traj_reserve(h, 64)) != CNF_OK) return s;
-            slot = traj_slot_floats(h); dcap = h->traj_cap;
-            dump = h->traj + n;                      // stage area of slot 0; u_n sits one array before
-        }
-        s = CNF_ERR_UNSUPPORTED;
-        WavePathArgs wp{};
-        if (path && wave_ok) {                           // the save times to the device; the launch files its accepted steps
-            RESERVE(h, h->d_saveat, (size_t)path->K);
-            RESERVE(h, h->d_path_steps, (size_t)2 * PATH_STEPS_CAP);
-            HIPCHK(h, hipMemcpyAsync(h->d_saveat, path->saveat, (size_t)path->K * sizeof(float), hipMemcpyHostToDevice, st));
-            wp.times = h->d_saveat; wp.K = path->K; wp.out = path->out; wp.steps = h->d_path_steps; wp.steps_cap = PATH_STEPS_CAP;
-        }
-        if (wave_ok)
-            s = wave_solve_launch(h->nd_wave, train != 0, h->d_params, h->nd.n_cond > 0 ? h->d_cond : nullptr, h->cbs, h->d_state, h->U[0],
-                                  eps, B, st, h->d_mirror + mslot, base, sv, rec ? rec->wg : nullptr, nullptr, path ? &wp : nullptr);
-        // (the gradient in the launch of the solve exists on the wave kernel only: if that launch could not start, the caller
-        // runs the streamed gradient path)
-        if (rec && rec->wg && s != CNF_OK) { rec->wg_failed = true; return CNF_OK; }
-        if (tsolve_ok) {
-            const GradLayout g = grad_layout(h->nd);
-            const AdjMfmaLayout m = adj_mfma_layout(h->nd, g);
-            TraceArgs ta{};
-            ta.B = B;
-            set_rk_buffers(h, ta);
-            ta.norm_kind = -1; ta.st_mut = h->d_state; ta.n_total = (float)n;
-            ta.mirror = h->d_mirror + mslot; ta.seq = base;
-            s = launch_trace_solve(h->nd, g, m, h->d_adj_img, ta, sv, st) == hipSuccess ? CNF_OK : CNF_ERR_UNSUPPORTED;
-            if (s != CNF_OK) (void)hipGetLastError();
-        }
-        if (bcast_ok) {
-            BcastRecord brec{dump, n, slot, dcap, h->traj_hs};
-            Solve3Args svb = sv;
-            if (rec && u_out) svb.u_out = u_out;         // (this kernel writes the final state where it is wanted)
-            s = bcast_solve_launch(h->nd, train != 0, h->d_params, h->d_bimg, h->d_state, h->U[0], eps, B, st, h->d_mirror + mslot, base, svb, h->device,
-                                   h->d_bstore, h->nd.n_cond > 0 ? h->d_cond : nullptr, h->cbs, rec ? &brec : nullptr);
-            if (s == CNF_OK && rec && u_out) sv.u_out = u_out;
-        }
-        if (s == CNF_ERR_UNSUPPORTED && use_mfma && !jvp)
-            s = mfma_solve_persistent(h->mfma, h->nd, train, h->d_state, h->U, eps, B, st, h->d_mirror + mslot, base, sv, h->device,
-                                      dump, n, slot, dcap, h->traj_hs, h->K1);
-        if (s == CNF_OK) {
-            ++launches;
-            h->mirror_base = base + 1;
-            ++h->one_launch_count;
-            h->last_state = h->d_state;
-            HIPCHK(h, hipGetLastError());
-            if (jvp) {
-                // the tangent launch, right behind the solve on its stream: no host wait in between.  It reads the solve's final
-                // state first and writes nothing for a solve that gave up (the streamed route below then files the steps)
-                JvpCall& jc = *jvp;
-                jc.ta.st = h->d_state; jc.ta.trace = h->jvp_trace; jc.ta.trace_cap = jc.trace_cap; jc.ta.n_rows = -1;
-                if ((s = tangent_launch(jc.ta, jc.train, st)) != CNF_OK) return fail(h, s, "the tangent launch failed to start");
-                jc.enqueued = true;
-                ++launches;
-            }
-            if (h->submitting && rec && rec->wg) {
-                // a submitted gradient: the launch is on its way; cnf_loss_grad_collect reads its outcome from its mirror slot
-                cnf_ctx::Submitted sub;
-                sub.launched = true; sub.grad = true; sub.seq = base; sub.slot = mslot; sub.hairer = hairer; sub.mode = mode; sub.B = B;
-                sub.k = CNF_KERNEL_MFMA; sub.opts = *opts; sub.st = st;
-                h->submitted.push_back(sub);
-                h->sub_taken = true;
-                ++g_submitted_inflight; g_submitted_stream = st;
-                if (post) post->launched = true;
-                rec->wg_submitted = true;
-                return CNF_OK;
-            }
-            if (h->submitting && fused_io && !rec && !u_out) {
-                // submitted: the launch is on its way; cnf_inference_collect reads its outcome from its mirror slot
-                cnf_ctx::Submitted sub;
-                sub.launched = true; sub.seq = base; sub.slot = mslot; sub.hairer = hairer; sub.mode = mode; sub.B = B; sub.k = k;
-                sub.xs = post->xs; sub.eps = eps; sub.logpx = post->logpx; sub.regs = post->regs; sub.sums5 = post->sums5;
-                sub.opts = *opts; sub.st = st;
-                h->submitted.push_back(sub);
-                h->sub_taken = true;
-                ++g_submitted_inflight; g_submitted_stream = st;
-                post->launched = true;
-                return CNF_OK;
-            }
-            StepState fin{};
-            bool aborted = false;
-            if ((s = finish_one_launch(h, base, mslot, st, &fin, &aborted)) != CNF_OK) return s;
-            const int attempts = fin.naccept + fin.nreject;
-            if (!aborted) {
-                if (fused_io) post->launched = true;
-                else if (post) { enqueue_post(h, train, h->d_state, *post, B, false, st); ++launches; post->launched = true; }
-                if (u_out && !sv.u_out) { launch_copy_final(h->d_state, h->U[0], h->U[1], u_out, n, st); ++launches; }
-                HIPCHK(h, hipGetLastError());
-                if (rec) {                               // step sizes back from the device
-                    rec->n = fin.naccept;
-                    rec->overflow = !rec->wg && fin.naccept > h->traj_cap;
-                    rec->hs.assign((size_t)(rec->overflow ? 0 : fin.naccept), 0.f);
-                    if (!rec->overflow && fin.naccept > 0)
-                        HIPCHK(h, hipMemcpyAsync(rec->hs.data(), rec->wg ? rec->wg->hs_out : h->traj_hs, (size_t)fin.naccept * sizeof(float),
-                                                 hipMemcpyDeviceToHost, st));
-                    if (rec->wg) rec->wg_done = true;
-                    else final_sync = true;
-                }
-                if (path && fin.naccept <= PATH_STEPS_CAP) {   // the accepted steps back from the device (cnf_path_steps)
-                    std::vector<float> pairs((size_t)2 * fin.naccept);
-                    if (fin.naccept > 0)
-                        HIPCHK(h, hipMemcpyAsync(pairs.data(), h->d_path_steps, pairs.size() * sizeof(float), hipMemcpyDeviceToHost, st));
-                    HIPCHK(h, hipStreamSynchronize(st));
-                    h->path_t.resize((size_t)fin.naccept); h->path_h.resize((size_t)fin.naccept);
-                    for (int i = 0; i < fin.naccept; ++i) { h->path_t[i] = pairs[2 * i]; h->path_h[i] = pairs[2 * i + 1]; }
-                    h->path_valid = !fin.nonfinite;
-                }
-                if (final_sync) HIPCHK(h, hipStreamSynchronize(st));
-                fill_stats(stats, fin, (hairer ? 2 : 1) + 6 * attempts, wave_ok ? CNF_KERNEL_MFMA : k, launches);
-                if (fin.nonfinite) {
-                    // (the step sizes above may still be on their way into rec->hs, which the caller drops on this return)
-                    if (rec && rec->wg) HIPCHK(h, hipStreamSynchronize(st));
-                    return fail(h, CNF_ERR_NONFINITE, "solver state became NaN/Inf");
-                }
-                return CNF_OK;
-            }
-            // A workgroup did not arrive within the wait bound: something else holds CUs (another stream or process, a CU
-            // mask).  The launch has ended (every wait is bounded); nothing of its result is used.  The solve runs again from
-            // u0 on the streamed driver below, which needs no co-residency.
-            ++h->fallbacks;
-            if (rec && rec->wg) { rec->wg_failed = true; return CNF_OK; }      // (the caller runs the streamed gradient path)
-            // (u0 == h->U[0] was solved in place; it can only be rebuilt when the caller's data columns are still at hand --
-            // `inference_impl` passes them in post->xs, the streamed driver below assembles u0 from them again)
-            if (!fused_io && u0 == h->U[0] && !(post && post->xs))
-                return fail(h, CNF_ERR_HIP, "one-launch solve: a workgroup did not arrive and u0 was solved in place (set CNF_PERSISTENT=0)");
-        } else if (s != CNF_ERR_UNSUPPORTED) return fail(h, s, "one-launch solve failed to start");
-        persist_lock.unlock();
+    if (device_steps && r.c.path && fin.naccept <= PATH_STEPS_CAP) {
+        const cnf_status s = path_fetch_steps(h, fin, r.st);
+        if (s != CNF_OK) return s;
     }
-    if (post && post->xs) launch_build_u0(post->xs, h->U[0], h->nd.nvars, D, B, st, h->d_state, init);   // (u0 == h->U[0])
-    else launch_set_state(h->d_state, *init, st);
-    if (u0 != h->U[0]) HIPCHK(h, hipMemcpyAsync(h->U[0], u0, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    // the step count is already known from the last mirror; the copy is stream-ordered work.  Callers that
+    // hand u_out to the host wait here, cnf_inference goes straight on to the post-processing kernel.
+    if (r.final_sync) HIPCHK(h, hipStreamSynchronize(r.st));
+    fill_stats(r.c.stats, fin, nf, kernel_used, r.launches);
+    if (fin.nonfinite) {
+        // (the step sizes above may still be on their way into rec->hs, which the caller drops on this return)
+        if (rec && rec->wg) HIPCHK(h, hipStreamSynchronize(r.st));
+        return fail(h, CNF_ERR_NONFINITE, "solver state became NaN/Inf");
+    }
+    return CNF_OK;
+}
 
-    // k1 = f(u0).  With the automatic initial dt on the fused path, the two norms and their controller phases
-    // ride in the RHS launches themselves (the last workgroup to finish runs the phase): 2 launches, not 4.
+// A submitted inference or gradient (grad): the one-launch solve with index `seq` is on its way; cnf_inference_collect /
+// cnf_loss_grad_collect read its outcome from its mirror slot.  Under g_persist_mu.
+static void leave_in_flight(cnf_handle h, const SolveRun& r, unsigned seq, int mslot, bool grad) {
+    const SolveCall& c = r.c;
+    cnf_ctx::Submitted sub;
+    sub.launched = true; sub.grad = grad; sub.seq = seq; sub.slot = mslot; sub.hairer = r.rt.hairer; sub.mode = c.mode; sub.B = c.B;
+    sub.k = grad ? CNF_KERNEL_MFMA : r.k; sub.opts = *c.opts; sub.st = r.st;
+    if (!grad) { sub.xs = c.post->xs; sub.eps = c.eps; sub.logpx = c.post->logpx; sub.regs = c.post->regs; sub.sums5 = c.post->sums5; }
+    h->submitted.push_back(sub);
+    h->sub_taken = true;
+    ++g_submitted_inflight; g_submitted_stream = r.st;
+    if (c.post) c.post->launched = true;
+    if (grad) c.rec->wg_submitted = true;
+}
+
+// The whole solve in ONE launch where the handle and the batch allow it (k_solve3b / k_solve3jb): the weights and the
+// Runge-Kutta rows stay on the CUs for all attempts, the workgroups exchange two floats per attempt;
+// ... or of a small two-layer network, one wave per 16-sample tile, registers only (k_solve_wave, cnf_wave.hip)
+// ... or of config 5's network at eight columns per CU (k_solve_bcast, cnf_bcast.hip)
+// ... or of the 32-128-128-32 network in TestMode (exact trace: k_trace3s<SOLVE>, cnf_trace.hip).
+// The call ends here with the status returned -- finished, left in flight (submitted), or handed back to the gradient's caller
+// (rec->wg_failed) -- unless *host_driven: no kernel took the batch, or the launch gave up, and a host-driven driver runs the
+// solve (from u0 again).  One such kernel at a time in this process (two would each hold CUs the other is waiting for), except
+// that launches queued on ONE stream run one after the other by themselves (submitted inferences): the lock is held until this
+// function returns, whichever way.
+static cnf_status solve_one_launch(cnf_handle h, SolveRun& r, bool* host_driven) {
+    const SolveCall& c = r.c;
+    const SolveRoute& rt = r.rt;
+    Recorder* rec = c.rec; PostHook* post = c.post; PathHook* path = c.path; JvpCall* jvp = c.jvp;
+    const cnf_solve_opts* opts = c.opts;
+    const int B = c.B, train = r.train;  const size_t n = r.n;  hipStream_t st = r.st;
+    cnf_status s = CNF_OK;
+    *host_driven = false;
+    std::unique_lock<std::mutex> persist_lock(g_persist_mu);
+    if (g_submitted_inflight > 0 && g_submitted_stream != st) HIPCHK(h, hipStreamSynchronize(g_submitted_stream));
+    const unsigned base = h->mirror_base;
+    const int mslot = 1 + (int)(h->one_launch_count % 3);
+    Solve3Args sv{};
+    sv.part = h->partials; sv.base_dev = sums_word<unsigned>(h, SUMS_MEET_BASE); sv.abort_flag = sums_word<int>(h, SUMS_ABORT);
+    sv.t_out = h->time_kernel ? sums_word<unsigned long long>(h, SUMS_CLOCK) : nullptr;
+    sv.maxiters = (int)opts->maxiters; sv.hairer = rt.hairer ? 1 : 0; sv.init = *r.init;
+    // How long a wait inside the kernel lasts before it gives up: bounded in TIME (the kernel's 100 MHz clock) -- 2 ms per
+    // tile a workgroup carries (a meeting's arrivals are microseconds apart when every workgroup is placed; a workgroup
+    // that is not placed because another tenant holds its CU makes the launch give up after that long, and the streamed
+    // solve starts).  CNF_SOLVE_WAIT_US overrides; CNF_SOLVE_POLL_LIMIT bounds the number of polls instead (tests: 1).
+    set_wait_bounds(h, sv);
+    sv.trace = h->step_trace; sv.trace_cap = h->step_trace_cap;
+    if (jvp) { sv.trace = h->jvp_trace; sv.trace_cap = jvp->trace_cap; }
+    // (k_trace3s<SOLVE> works on the integrator's buffers: u0 is assembled / copied into U[0] in front of it, the
+    // post-processing follows it -- three launches per inference)
+    if (rt.tsolve_ok) {
+        if (post && post->xs) launch_build_u0(post->xs, h->U[0], h->nd.nvars, r.D, B, st);
+        else if (c.u0 != h->U[0]) HIPCHK(h, hipMemcpyAsync(h->U[0], c.u0, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        ++r.launches;
+    }
+    const bool fused_io = post && post->xs && !rt.tsolve_ok;   // inference: u0 from the data columns and the post-processing in the launch
+    if (fused_io) { sv.xs = post->xs; sv.logpx = post->logpx; sv.regs = post->regs; sv.sums5 = post->sums5; if (rec) sv.u_out = c.u_out; }
+    else { sv.u0 = c.u0; sv.u_out = rt.tsolve_ok ? nullptr : c.u_out; }   // (the launcher reads u0 in place or copies it into U[0])
+    TrajDump td;
+    if (rec && !rec->wg && (s = traj_dump(h, n, &td)) != CNF_OK) return s;
+    s = CNF_ERR_UNSUPPORTED;
+    WavePathArgs wp{};
+    if (path && rt.wave_ok) {                        // the save times to the device; the launch files its accepted steps
+        RESERVE(h, h->d_saveat, (size_t)path->K);
+        RESERVE(h, h->d_path_steps, (size_t)2 * PATH_STEPS_CAP);
+        HIPCHK(h, hipMemcpyAsync(h->d_saveat, path->saveat, (size_t)path->K * sizeof(float), hipMemcpyHostToDevice, st));
+        wp.times = h->d_saveat; wp.K = path->K; wp.out = path->out; wp.steps = h->d_path_steps; wp.steps_cap = PATH_STEPS_CAP;
+    }
+    if (rt.wave_ok)
+        s = wave_solve_launch(h->nd_wave, train != 0, h->d_params, h->nd.n_cond > 0 ? h->d_cond : nullptr, h->cbs, h->d_state, h->U[0],
+                              c.eps, B, st, h->d_mirror + mslot, base, sv, rec ? rec->wg : nullptr, nullptr, path ? &wp : nullptr);
+    // (the gradient in the launch of the solve exists on the wave kernel only: if that launch could not start, the caller
+    // runs the streamed gradient path)
+    if (rec && rec->wg && s != CNF_OK) { rec->wg_failed = true; return CNF_OK; }
+    if (rt.tsolve_ok) {
+        const GradLayout g = grad_layout(h->nd);
+        const AdjMfmaLayout m = adj_mfma_layout(h->nd, g);
+        TraceArgs ta{};
+        ta.B = B; set_rk_buffers(h, ta);
+        ta.norm_kind = -1; ta.st_mut = h->d_state; ta.n_total = (float)n;
+        ta.mirror = h->d_mirror + mslot; ta.seq = base;
+        s = launch_trace_solve(h->nd, g, m, h->d_adj_img, ta, sv, st) == hipSuccess ? CNF_OK : CNF_ERR_UNSUPPORTED;
+        if (s != CNF_OK) (void)hipGetLastError();
+    }
+    if (rt.bcast_ok) {
+        BcastRecord brec{td.dump, n, td.slot, td.dcap, h->traj_hs};
+        Solve3Args svb = sv;
+        if (rec && c.u_out) svb.u_out = c.u_out;     // (this kernel writes the final state where it is wanted)
+        s = bcast_solve_launch(h->nd, train != 0, h->d_params, h->d_bimg, h->d_state, h->U[0], c.eps, B, st, h->d_mirror + mslot, base, svb, h->device,
+                               h->d_bstore, h->nd.n_cond > 0 ? h->d_cond : nullptr, h->cbs, rec ? &brec : nullptr);
+        if (s == CNF_OK && rec && c.u_out) sv.u_out = c.u_out;
+    }
+    if (s == CNF_ERR_UNSUPPORTED && rt.use_mfma && !jvp)
+        s = mfma_solve_persistent(h->mfma, h->nd, train, h->d_state, h->U, c.eps, B, st, h->d_mirror + mslot, base, sv, h->device,
+                                  td.dump, n, td.slot, td.dcap, h->traj_hs, h->K1);
+    if (s == CNF_ERR_UNSUPPORTED) { *host_driven = true; return CNF_OK; }
+    if (s != CNF_OK) return fail(h, s, "one-launch solve failed to start");
+    ++r.launches;
+    h->mirror_base = base + 1;
+    ++h->one_launch_count;
+    h->last_state = h->d_state;
+    HIPCHK(h, hipGetLastError());
+    if (jvp) {
+        // the tangent launch, right behind the solve on its stream: no host wait in between.  It reads the solve's final
+        // state first and writes nothing for a solve that gave up (the stepwise driver then files the steps)
+        JvpCall& jc = *jvp;
+        jc.ta.st = h->d_state; jc.ta.trace = h->jvp_trace; jc.ta.trace_cap = jc.trace_cap; jc.ta.n_rows = -1;
+        if ((s = tangent_launch(jc.ta, jc.train, st)) != CNF_OK) return fail(h, s, "the tangent launch failed to start");
+        jc.enqueued = true;
+        ++r.launches;
+    }
+    const bool sub_grad = rec && rec->wg;
+    if (h->submitting && (sub_grad || (fused_io && !rec && !c.u_out))) { leave_in_flight(h, r, base, mslot, sub_grad); return CNF_OK; }
+    StepState fin{}; bool aborted = false;
+    if ((s = finish_one_launch(h, base, mslot, st, &fin, &aborted)) != CNF_OK) return s;
+    if (!aborted) {
+        if (fused_io) post->launched = true;
+        else if (post) { enqueue_post(h, train, h->d_state, *post, B, false, st); ++r.launches; post->launched = true; }
+        return finish_solve(h, r, h->d_state, fin, c.u_out && !sv.u_out, true, (rt.hairer ? 2 : 1) + 6 * (fin.naccept + fin.nreject),
+                            rt.wave_ok ? CNF_KERNEL_MFMA : r.k);
+    }
+    // A workgroup did not arrive within the wait bound: something else holds CUs (another stream or process, a CU
+    // mask).  The launch has ended (every wait is bounded); nothing of its result is used.  The solve runs again from
+    // u0 on a host-driven driver, which needs no co-residency.
+    ++h->fallbacks;
+    if (rec && rec->wg) { rec->wg_failed = true; return CNF_OK; }      // (the caller runs the streamed gradient path)
+    // (u0 == h->U[0] was solved in place; it can only be rebuilt when the caller's data columns are still at hand --
+    // `inference_impl` passes them in post->xs, solve_start assembles u0 from them again)
+    if (!fused_io && c.u0 == h->U[0] && !(post && post->xs))
+        return fail(h, CNF_ERR_HIP, "one-launch solve: a workgroup did not arrive and u0 was solved in place (set CNF_PERSISTENT=0)");
+    *host_driven = true;
+    return CNF_OK;
+}
+
+// One right-hand side of the start of a host-driven solve, on the route's kernel.  Stage 0: k1 = f(u0) -> K1[0]; stage 1: f1 = f(u0 + h k1) -> Ks[0].  *fuse, in: the
+// norm of the automatic initial dt that belongs to the stage and its controller phase ride in the launch (the last workgroup to
+// finish runs the phase); out: they did (the fused step kernel may answer "not this batch" for stage 0).
+static cnf_status eval_rhs(cnf_handle h, SolveRun& r, int stage, bool* fuse) {
+    const int B = r.c.B, train = r.train;
+    const float* eps = r.c.eps;
+    hipStream_t st = r.st;
     unsigned* ticket = sums_word<unsigned>(h, SUMS_NORM_TICKET);
-    bool fused_init = false;
-    if (use_mfma && hairer && !lockstep) {
-        s = mfma_rhs_init0(h->mfma, h->nd, train, h->d_state, h->U[0], eps, h->K1[0], h->partials, ticket, B, st);
-        if (s == CNF_OK) fused_init = true;
-        else if (s != CNF_ERR_UNSUPPORTED) return fail(h, s, "MFMA RHS launch failed");
+    cnf_status s = CNF_OK;
+    ++r.launches;
+    if (r.rt.use_mfma) {
+        if (stage == 0 && *fuse) {
+            s = mfma_rhs_init0(h->mfma, h->nd, train, h->d_state, h->U[0], eps, h->K1[0], h->partials, ticket, B, st);
+            if (s == CNF_OK) return s;
+            if (s != CNF_ERR_UNSUPPORTED) return fail(h, s, "MFMA RHS launch failed");
+            *fuse = false;
+        }
+        if (stage == 0) s = mfma_rhs(h->mfma, h->nd, train, h->U[0], eps, h->K1[0], B, st);
+        else if (*fuse) s = mfma_rhs_stage(h->mfma, h->nd, train, h->d_state, h->U, h->K1, h->Ks, eps, 1, B, st, h->d_state, h->partials, ticket);
+        else s = mfma_rhs_stage(h->mfma, h->nd, train, h->d_state, h->U, h->K1, h->Ks, eps, 1, B, st);
+        return s == CNF_OK ? s : fail(h, s, "MFMA RHS launch failed");
     }
-    if (fused_init) {
-    } else if (use_mfma) {
-        s = mfma_rhs(h->mfma, h->nd, train, h->U[0], eps, h->K1[0], B, st);
-        if (s != CNF_OK) return fail(h, s, "MFMA RHS launch failed");
-    } else if (h->trace_on && trace_fused && hairer) {       // k1 = f(u0) with the first norm of the automatic initial dt
-        TraceFuse f; f.norm_kind = 0;
-        if ((s = launch_trace(h, h->U[0], h->K1[0], true, false, B, st, 0, nullptr, false, &f)) != CNF_OK) return s;
-        fused_init = true;
-    } else if (h->trace_on) {
-        if ((s = launch_trace(h, h->U[0], h->K1[0], false, false, B, st)) != CNF_OK) return s;
-    } else {
-        RhsArgs a{};
-        a.B = B; a.S = h->cap_B; a.train = train; a.ws = h->ws; a.eps = eps;
-        a.cond = h->mfma.cond; a.cbs = h->cbs;
-        a.u = h->U[0]; a.du = h->K1[0];
-        launch_rhs_generic(h->nd, h->d_params, a, st);
-    }
-    launches += 1;
-    int nf = 1;
-
-    NormArgs na{};
-    na.st = h->d_state; na.n = n; na.partials = h->partials;
-    set_rk_buffers(h, na);
-
-    if (hairer && fused_init && h->trace_on) {
-        // f1 = f(u0 + h*f0) -> Ks[0] with the second norm and the controller phase that sets dt, in the trace launch
+    if (r.aux.on) {
         const float one = 1.f;
-        TraceFuse f; f.norm_kind = 1;
-        if ((s = launch_trace(h, nullptr, h->Ks[0], true, false, B, st, 1, &one, false, &f)) != CNF_OK) return s;
-        launches += 1;
-        nf += 1;
-    } else if (hairer && fused_init) {
-        // f1 = f(u0 + h*f0) -> Ks[0], with the second norm and the controller phase that sets dt
-        s = mfma_rhs_stage(h->mfma, h->nd, train, h->d_state, h->U, h->K1, h->Ks, eps, 1, B, st, h->d_state,
-                           h->partials, ticket);
-        if (s != CNF_OK) return fail(h, s, "MFMA RHS launch failed");
-        launches += 1;
-        nf += 1;
-    } else if (hairer) {
-        // automatic initial dt (Hairer; OrdinaryDiffEq's ode_determine_initdt, third party)
-        na.kind = 0;
-        if (lockstep) {
-            launch_norm_partials(na, nblk, st);
-            if ((s = lockstep_controller(h, h->d_state, h->partials, 0, (float)n, st)) != CNF_OK) return s;
-        } else {        // norm + controller in one launch (the last block to finish runs the controller)
-            na.ticket = ticket; na.st_mut = h->d_state; na.ctrl_phase = 0; na.n_total = (float)n;
-            launch_norm_partials(na, nblk, st);
-            na.ticket = nullptr;
-        }
-        // f1 = f(u0 + h*f0) -> Ks[0]
-        if (use_mfma) {
-            s = mfma_rhs_stage(h->mfma, h->nd, train, h->d_state, h->U, h->K1, h->Ks, eps, 1, B, st);
-            if (s != CNF_OK) return fail(h, s, "MFMA RHS launch failed");
-        } else if (h->trace_on) {
-            const float one = 1.f;
-            if ((s = launch_trace(h, nullptr, h->Ks[0], true, false, B, st, 1, &one)) != CNF_OK) return s;
-        } else {
-            RhsArgs a{};
-            a.st = h->d_state; a.B = B; a.S = h->cap_B; a.train = train; a.ws = h->ws; a.eps = eps;
-            a.cond = h->mfma.cond; a.cbs = h->cbs;
-            set_rk_buffers(h, a);
-            a.nk = 1; a.coef[0] = 1.f; a.du = h->Ks[0];
-            launch_rhs_generic(h->nd, h->d_params, a, st);
-        }
-        na.kind = 1;
-        if (lockstep) {
-            launch_norm_partials(na, nblk, st);
-            if ((s = lockstep_controller(h, h->d_state, h->partials, 1, (float)n, st)) != CNF_OK) return s;
-        } else {
-            na.ticket = ticket; na.st_mut = h->d_state; na.ctrl_phase = 1; na.n_total = (float)n;
-            launch_norm_partials(na, nblk, st);
-            na.ticket = nullptr;
-        }
-        launches += lockstep ? 5 : 3;
-        nf += 1;
+        TraceFuse f; f.norm_kind = stage;
+        if (stage == 0) return launch_trace(h, r.aux, h->U[0], h->K1[0], *fuse, false, B, st, 0, nullptr, false, *fuse ? &f : nullptr);
+        return launch_trace(h, r.aux, nullptr, h->Ks[0], true, false, B, st, 1, &one, false, *fuse ? &f : nullptr);
+    }
+    RhsArgs a{};
+    a.B = B; a.S = h->cap_B; a.train = train; a.ws = h->ws; a.eps = eps; a.cond = h->mfma.cond; a.cbs = h->cbs;
+    if (stage == 0) { a.u = h->U[0]; a.du = h->K1[0]; }
+    else { a.st = h->d_state; set_rk_buffers(h, a); a.nk = 1; a.coef[0] = 1.f; a.du = h->Ks[0]; }
+    launch_rhs_generic(h->nd, h->d_params, a, st);
+    return CNF_OK;
+}
+// One norm of the automatic initial dt (kind 0 / 1) and the controller phase of the same number: lock-step through the shards'
+// sum, else in the launch of the norm (the last block to finish runs the controller)
+static cnf_status initdt_norm(cnf_handle h, SolveRun& r, int kind) {
+    NormArgs na{};
+    na.st = h->d_state; na.n = r.n; na.partials = h->partials; na.kind = kind;
+    set_rk_buffers(h, na);
+    if (r.rt.lockstep) {
+        launch_norm_partials(na, r.nblk, r.st);
+        r.launches += 2;
+        return lockstep_controller(h, h->d_state, h->partials, kind, (float)r.n, r.st);
+    }
+    na.ticket = sums_word<unsigned>(h, SUMS_NORM_TICKET); na.st_mut = h->d_state; na.ctrl_phase = kind; na.n_total = (float)r.n;
+    launch_norm_partials(na, r.nblk, r.st);
+    r.launches += 1;
+    return CNF_OK;
+}
+// The initial state and u0, k1 = f(u0), and the automatic initial dt (Hairer; OrdinaryDiffEq's ode_determine_initdt, third
+// party).  On the fused step kernel and on k_trace3s the two norms and their controller phases ride in the two RHS launches:
+// 2 launches, not 4.
+static cnf_status solve_start(cnf_handle h, SolveRun& r) {
+    const SolveCall& c = r.c;
+    const SolveRoute& rt = r.rt;
+    cnf_status s = CNF_OK;
+    if (c.post && c.post->xs) launch_build_u0(c.post->xs, h->U[0], h->nd.nvars, r.D, c.B, r.st, h->d_state, r.init);   // (u0 == h->U[0])
+    else launch_set_state(h->d_state, *r.init, r.st);
+    if (c.u0 != h->U[0]) HIPCHK(h, hipMemcpyAsync(h->U[0], c.u0, r.n * sizeof(float), hipMemcpyDeviceToDevice, r.st));
+    bool fused = rt.hairer && ((rt.use_mfma && !rt.lockstep) || (r.aux.on && rt.trace_fused));
+    if ((s = eval_rhs(h, r, 0, &fused)) != CNF_OK) return s;
+    r.nf = 1;
+    if (rt.hairer && fused) {
+        if ((s = eval_rhs(h, r, 1, &fused)) != CNF_OK) return s;
+        r.nf += 1;
+    } else if (rt.hairer) {
+        if ((s = initdt_norm(h, r, 0)) != CNF_OK) return s;
+        if ((s = eval_rhs(h, r, 1, &fused)) != CNF_OK) return s;
+        if ((s = initdt_norm(h, r, 1)) != CNF_OK) return s;
+        r.nf += 1;
     }
     HIPCHK(h, hipGetLastError());
+    return CNF_OK;
+}
 
-    StepState* cur_state = h->d_state;   // slot holding the live integrator state
-    int pp = 0;                          // partials buffer the NEXT launch reads
-    if (lockstep || (rec && !use_mfma) || path || jvp) {
-        // one attempt at a time.  Lock-step: every shard must see the same global error norm before
-        // the next attempt is sized.  Recording (gradient path): the host files the state after
-        // every accepted step.  A path: the host enqueues the interpolation of an accepted step (k_dense_out) before the next
-        // attempt overwrites k_2 .. k_6.
-        StepState* snap = &h->h_state[0];
-        float h_attempt = 0.f, t_attempt = 0.f;
-        int seen_accept = 0;
-        int pcur = 0;                                    // the next save time
-        std::vector<float> path_t, path_h;
-        if (path || jvp) {
-            HIPCHK(h, hipMemcpyAsync(snap, h->d_state, sizeof(StepState), hipMemcpyDeviceToHost, st));
-            HIPCHK(h, hipStreamSynchronize(st));
-            h_attempt = snap->h; t_attempt = snap->t;
-            if (jvp) { jvp->enqueued = false; jvp->host_steps = true; jvp->t.clear(); jvp->h.clear(); }
-            for (; path && pcur < path->K && path->saveat[pcur] == opts->t0; ++pcur)      // save times at the start: u0 itself
-                HIPCHK(h, hipMemcpyAsync(path->out + (size_t)pcur * n, h->U[0], n * sizeof(float), hipMemcpyDeviceToDevice, st));
-        }
-        if (rec) {
-            float* slot0;
-            if ((s = traj_slot(h, 0, &slot0)) != CNF_OK) return s;
-            HIPCHK(h, hipMemcpyAsync(slot0, h->U[0], n * sizeof(float), hipMemcpyDeviceToDevice, st));
-            HIPCHK(h, hipMemcpyAsync(snap, h->d_state, sizeof(StepState), hipMemcpyDeviceToHost, st));
-            HIPCHK(h, hipStreamSynchronize(st));
-            h_attempt = snap->h;
-            rec->hs.clear(); rec->n = 0;
-        }
-        // Lock-step over an RCCL communicator: nothing of an attempt leaves the stream (step kernel, the reduction of the
-        // partials, the all-reduce of three floats, the controller), so FOUR attempts are enqueued per look at the state --
-        // every shard holds the same state bit for bit, sees `done` in the same attempt and enqueues the same number of
-        // collectives; attempts queued past the end find `done` and change nothing.
-        const int chunk = (lockstep && h->shard_comm && use_mfma && !rec) ? 4 : 1;
-        for (long it = 0;; it += chunk) {
-            if (it >= (long)opts->maxiters) return fail(h, CNF_ERR_MAXITERS, "maxiters reached before t1");
-          for (int c = 0; c < chunk && it + c < (long)opts->maxiters; ++c) {
+// The interpolation of the accepted step (t_attempt, h_attempt) at every save time up to its end -- the last step everything left
+// (k_dense_out); u_n, k_1 sit in the buffer set the controller has just left, u_{n+1}, k_7 in the current one
+static void path_dense_out(cnf_handle h, SolveRun& r, const StepState& snap, float t_attempt, float h_attempt, int* pcur) {
+    const PathHook* path = r.c.path;
+    const float t_end = snap.t, tdir = snap.tdir;
+    const int cur = snap.cur;
+    DenseOutArgs da{};
+    da.u = h->U[cur ^ 1]; da.unew = h->U[cur]; da.k[0] = h->K1[cur ^ 1]; da.k[6] = h->K1[cur];
+    for (int i = 0; i < 5; ++i) da.k[1 + i] = h->Ks[i];
+    da.n = r.n; da.out = path->out; da.h = h_attempt;
+    for (; *pcur < path->K; ++*pcur) {
+        const float tau = path->saveat[*pcur];
+        if (!snap.done && tdir * (tau - t_end) > 0.f) break;
+        const float th = (tau - t_attempt) / h_attempt;
+        const int c = da.count++;
+        da.slice[c] = *pcur; da.exact[c] = (tau == t_end || !(th < 1.f)) ? 1 : 0;
+        tsit5_dense_b(th, da.b[c]);
+        if (da.count == DENSE_OUT_MAX) { launch_dense_out(da, r.st); ++r.launches; da.count = 0; }
+    }
+    if (da.count > 0) { launch_dense_out(da, r.st); ++r.launches; }
+}
+
+// One attempt at a time, the host reading the state after each (who needs that: cnf_solve_plan.h, `stepwise`)
+static cnf_status solve_stepwise(cnf_handle h, SolveRun& r) {
+    const SolveCall& c = r.c;
+    const SolveRoute& rt = r.rt;
+    Recorder* rec = c.rec; PathHook* path = c.path; JvpCall* jvp = c.jvp;
+    const cnf_solve_opts* opts = c.opts;
+    const int B = c.B, train = r.train;  const size_t n = r.n;  hipStream_t st = r.st;
+    cnf_status s = CNF_OK;
+    StepState* snap = &h->h_state[0];
+    float h_attempt = 0.f, t_attempt = 0.f;
+    int seen_accept = 0, pcur = 0;                   // pcur: the next save time
+    std::vector<float> path_t, path_h;
+    if (path || jvp) {
+        HIPCHK(h, hipMemcpyAsync(snap, h->d_state, sizeof(StepState), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+        h_attempt = snap->h; t_attempt = snap->t;
+        if (jvp) { jvp->enqueued = false; jvp->host_steps = true; jvp->t.clear(); jvp->h.clear(); }
+        for (; path && pcur < path->K && path->saveat[pcur] == opts->t0; ++pcur)      // save times at the start: u0 itself
+            HIPCHK(h, hipMemcpyAsync(path->out + (size_t)pcur * n, h->U[0], n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    if (rec) {
+        float* slot0;
+        if ((s = traj_slot(h, 0, &slot0)) != CNF_OK) return s;
+        HIPCHK(h, hipMemcpyAsync(slot0, h->U[0], n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(snap, h->d_state, sizeof(StepState), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+        h_attempt = snap->h;
+        rec->hs.clear(); rec->n = 0;
+    }
+    // Lock-step over an RCCL communicator: nothing of an attempt leaves the stream (step kernel, the reduction of the
+    // partials, the all-reduce of three floats, the controller), so FOUR attempts are enqueued per look at the state --
+    // every shard holds the same state bit for bit, sees `done` in the same attempt and enqueues the same number of
+    // collectives; attempts queued past the end find `done` and change nothing.
+    const int chunk = (rt.lockstep && h->shard_comm && rt.use_mfma && !rec) ? 4 : 1;
+    for (long it = 0;; it += chunk) {
+        if (it >= (long)opts->maxiters) return fail(h, CNF_ERR_MAXITERS, "maxiters reached before t1");
+        for (int ci = 0; ci < chunk && it + ci < (long)opts->maxiters; ++ci) {
             float* dump = nullptr;
-            if (rec) {                                   // stage states of the attempt from u_{seen_accept}
+            if (rec) {                               // stage states of the attempt from u_{seen_accept}
                 float* slot;
                 if ((s = traj_slot(h, seen_accept, &slot)) != CNF_OK) return s;
                 dump = slot + n;
             }
-            if (use_mfma) {
-                s = mfma_step(h->mfma, h->nd, train, h->d_state, h->d_state + 1, h->U, h->K1, h->Ks, eps,
+            if (rt.use_mfma) {
+                s = mfma_step(h->mfma, h->nd, train, h->d_state, h->d_state + 1, h->U, h->K1, h->Ks, c.eps,
                               h->partials, h->partials, false, false, B, st, dump, n);
                 if (s != CNF_OK) return fail(h, s, "MFMA step launch failed");
-                launches += 1;
-            } else {
-                launches += enqueue_attempt_generic(h, train, eps, B, nblk, st, false, dump, n);
-            }
-            if (lockstep) {
-                if ((s = lockstep_controller(h, h->d_state, h->partials, 2, (float)n, st)) != CNF_OK) return s;
-                launches += 2;
-            } else {
-                launch_controller(h->d_state, h->partials, 2, (float)n, st);
-                launches += 1;
-            }
-          }
-            HIPCHK(h, hipMemcpyAsync(snap, h->d_state, sizeof(StepState), hipMemcpyDeviceToHost, st));
-            HIPCHK(h, hipStreamSynchronize(st));
-            if (rec && snap->naccept > seen_accept) {
-                seen_accept = snap->naccept;
-                float* slot;
-                if ((s = traj_slot(h, seen_accept, &slot)) != CNF_OK) return s;
-                HIPCHK(h, hipMemcpyAsync(slot, h->U[snap->cur], n * sizeof(float), hipMemcpyDeviceToDevice, st));
-                rec->hs.push_back(h_attempt);
-                rec->n = seen_accept;
-            }
-            if (jvp && !rec && !path && snap->naccept > seen_accept) {       // a tangent call: the accepted step, for its replay
-                seen_accept = snap->naccept;
-                jvp->t.push_back(t_attempt); jvp->h.push_back(h_attempt);
-            }
-            if (path && snap->naccept > seen_accept) {
-                // the accepted step (t_attempt, h_attempt) serves every save time up to its end -- the last step everything left;
-                // u_n, k_1 sit in the buffer set the controller has just left, u_{n+1}, k_7 in the current one
-                seen_accept = snap->naccept;
-                path_t.push_back(t_attempt); path_h.push_back(h_attempt);
-                const float t_end = snap->t, tdir = snap->tdir;
-                const int cur = snap->cur;
-                DenseOutArgs da{};
-                da.u = h->U[cur ^ 1]; da.unew = h->U[cur]; da.k[0] = h->K1[cur ^ 1]; da.k[6] = h->K1[cur];
-                for (int i = 0; i < 5; ++i) da.k[1 + i] = h->Ks[i];
-                da.n = n; da.out = path->out; da.h = h_attempt;
-                for (; pcur < path->K; ++pcur) {
-                    const float tau = path->saveat[pcur];
-                    if (!snap->done && tdir * (tau - t_end) > 0.f) break;
-                    const float th = (tau - t_attempt) / h_attempt;
-                    const int c = da.count++;
-                    da.slice[c] = pcur; da.exact[c] = (tau == t_end || !(th < 1.f)) ? 1 : 0;
-                    tsit5_dense_b(th, da.b[c]);
-                    if (da.count == DENSE_OUT_MAX) { launch_dense_out(da, st); ++launches; da.count = 0; }
-                }
-                if (da.count > 0) { launch_dense_out(da, st); ++launches; }
-            }
-            h_attempt = snap->h; t_attempt = snap->t;
-            if (snap->done) break;
+                r.launches += 1;
+            } else r.launches += enqueue_attempt_generic(h, r.aux, train, c.eps, B, r.nblk, st, false, dump, n);
+            if (rt.lockstep && (s = lockstep_controller(h, h->d_state, h->partials, 2, (float)n, st)) != CNF_OK) return s;
+            if (!rt.lockstep) launch_controller(h->d_state, h->partials, 2, (float)n, st);
+            r.launches += rt.lockstep ? 2 : 1;
         }
-        if (path) { h->path_t.swap(path_t); h->path_h.swap(path_h); h->path_valid = !snap->nonfinite; }
-        h->last_state = h->d_state;
-        if (u_out) {
-            launch_copy_final(h->d_state, h->U[0], h->U[1], u_out, n, st);
-            launches += 1;
-        }
-        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(snap, h->d_state, sizeof(StepState), hipMemcpyDeviceToHost, st));
         HIPCHK(h, hipStreamSynchronize(st));
-        fill_stats(stats, *snap, nf + 6 * (snap->naccept + snap->nreject),
-                   (k == CNF_KERNEL_MFMA && !use_mfma && !h->trace_on) ? CNF_KERNEL_GENERIC : k, launches);
-        if (snap->nonfinite) return fail(h, CNF_ERR_NONFINITE, "solver state became NaN/Inf");
-        return CNF_OK;
-    }
-    // Streamed solve: launches are kept a few attempts ahead of the last state the host has seen.  The controller of an
-    // attempt runs on the device -- inside the NEXT launch of the fused step kernel, or in the last block of the error-norm
-    // kernel on the per-stage paths -- and whoever ran it mirrors the new state to pinned host memory under the launch
-    // index; the host polls that index: no events, no copies, no stand-alone controller, no chunk boundaries.
-    // Launches queued past the end find `done` and exit at once.
-    bool done = false;
-    StepState fin{};
-    long post_at = -1, seen_done = -1;  // launches enqueued when the post-processing was last enqueued; the launch that published `done`
-    {
-        const int AHEAD = 3;
-        const volatile cnf_ctx::HostMirror* hm = h->h_mirror;
-        const unsigned base = h->mirror_base;
-        long sent = 0, seen = 0;       // launches (fused) / attempts (per-stage) enqueued; newest mirror index read
-        const long max_sent = (long)opts->maxiters + (use_mfma ? 1 : 0);   // fused: one more launch runs the last controller
-        // gradient path: every attempt files u_n and its stage states in the slot of step `naccept`, indexed on
-        // the device; the store is sized beforehand and the solve repeated if it took more steps than fit
-        float* dump = nullptr; size_t slot = 0; int dcap = 0;
-        if (rec) {
-            if ((s = traj_reserve(h, 64)) != CNF_OK) return s;
-            slot = traj_slot_floats(h); dcap = h->traj_cap;
-            dump = h->traj + n;                      // stage area of slot 0; u_n sits one array before
+        const bool accepted = snap->naccept > seen_accept;
+        if (accepted) seen_accept = snap->naccept;
+        if (rec && accepted) {
+            float* slot;
+            if ((s = traj_slot(h, seen_accept, &slot)) != CNF_OK) return s;
+            HIPCHK(h, hipMemcpyAsync(slot, h->U[snap->cur], n * sizeof(float), hipMemcpyDeviceToDevice, st));
+            rec->hs.push_back(h_attempt);
+            rec->n = seen_accept;
         }
-        // attempts the newest snapshot says are still needed, (t1 - t)/dt rounded up (the controller rarely shrinks dt
-        // near the end); -1 = no snapshot yet.  Launches beyond that would only find `done` and exit.
-        long need = -1;
-        for (;;) {
-            while (sent < max_sent && sent - seen < AHEAD && !done &&
-                   (need < 0 || sent - seen < need + (use_mfma ? 1 : 0))) {      // fused: + the launch that runs the last controller
-                if (use_mfma) {
-                    // launch i applies the controller of attempt i-1 and publishes under index i
-                    const bool apply = sent > 0;
-                    StepState* st_next = cur_state == h->d_state ? h->d_state + 1 : h->d_state;
-                    s = mfma_step(h->mfma, h->nd, train, cur_state, st_next, h->U, h->K1, h->Ks, eps,
-                                  h->partials + 2 * MAX_PARTIALS * pp, h->partials + 2 * MAX_PARTIALS * (pp ^ 1), apply,
-                                  false, B, st, dump, n, h->d_mirror, base + (unsigned)sent, slot, dcap, h->traj_hs);
-                    if (s != CNF_OK) return fail(h, s, "MFMA step launch failed");
-                    if (apply) cur_state = st_next;
-                    pp ^= 1;
-                    ++launches;
-                } else {
-                    // attempt i ends with its own controller and publishes under index i + 1
-                    launches += enqueue_attempt_generic(h, train, eps, B, nblk, st, true, nullptr, 0, h->d_mirror,
-                                                        base + (unsigned)sent + 1);
-                }
-                ++sent;
+        if (jvp && !rec && !path && accepted) { jvp->t.push_back(t_attempt); jvp->h.push_back(h_attempt); }   // for its replay
+        if (path && accepted) {
+            path_t.push_back(t_attempt); path_h.push_back(h_attempt);
+            path_dense_out(h, r, *snap, t_attempt, h_attempt, &pcur);
+        }
+        h_attempt = snap->h; t_attempt = snap->t;
+        if (snap->done) break;
+    }
+    if (path) path_keep_steps(h, path_t, path_h, snap->nonfinite != 0);
+    h->last_state = h->d_state;
+    r.final_sync = true;
+    return finish_solve(h, r, h->d_state, *snap, c.u_out != nullptr, false, r.nf + 6 * (snap->naccept + snap->nreject),
+                        (r.k == CNF_KERNEL_MFMA && !rt.use_mfma && !r.aux.on) ? CNF_KERNEL_GENERIC : r.k);
+}
+
+// Streamed solve: launches are kept a few attempts ahead of the last state the host has seen.  The controller of an
+// attempt runs on the device -- inside the NEXT launch of the fused step kernel, or in the last block of the error-norm
+// kernel on the per-stage paths -- and whoever ran it mirrors the new state to pinned host memory under the launch
+// index; the host polls that index: no events, no copies, no stand-alone controller, no chunk boundaries.
+// Launches queued past the end find `done` and exit at once.
+static cnf_status solve_streamed(cnf_handle h, SolveRun& r) {
+    const SolveCall& c = r.c;
+    const bool use_mfma = r.rt.use_mfma;
+    Recorder* rec = c.rec; PostHook* post = c.post;
+    const cnf_solve_opts* opts = c.opts;
+    const int B = c.B, train = r.train;  const size_t n = r.n;  hipStream_t st = r.st;
+    cnf_status s = CNF_OK;
+    StepState* cur_state = h->d_state;   // slot holding the live integrator state
+    int pp = 0;                          // partials buffer the NEXT launch reads
+    bool done = false; StepState fin{};
+    long post_at = -1, seen_done = -1;  // launches enqueued when the post-processing was last enqueued; the launch that published `done`
+    const int AHEAD = 3;
+    const volatile cnf_ctx::HostMirror* hm = h->h_mirror;
+    const unsigned base = h->mirror_base;
+    long sent = 0, seen = 0;       // launches (fused) / attempts (per-stage) enqueued; newest mirror index read
+    const long max_sent = (long)opts->maxiters + (use_mfma ? 1 : 0);   // fused: one more launch runs the last controller
+    TrajDump td;
+    if (rec && (s = traj_dump(h, n, &td)) != CNF_OK) return s;
+    // attempts the newest snapshot says are still needed, (t1 - t)/dt rounded up (the controller rarely shrinks dt
+    // near the end); -1 = no snapshot yet.  Launches beyond that would only find `done` and exit.
+    long need = -1;
+    for (;;) {
+        while (sent < max_sent && sent - seen < AHEAD && !done &&
+               (need < 0 || sent - seen < need + (use_mfma ? 1 : 0))) {      // fused: + the launch that runs the last controller
+            if (use_mfma) {
+                // launch i applies the controller of attempt i-1 and publishes under index i
+                const bool apply = sent > 0;
+                StepState* st_next = cur_state == h->d_state ? h->d_state + 1 : h->d_state;
+                s = mfma_step(h->mfma, h->nd, train, cur_state, st_next, h->U, h->K1, h->Ks, c.eps,
+                              h->partials + 2 * MAX_PARTIALS * pp, h->partials + 2 * MAX_PARTIALS * (pp ^ 1), apply,
+                              false, B, st, td.dump, n, h->d_mirror, base + (unsigned)sent, td.slot, td.dcap, h->traj_hs);
+                if (s != CNF_OK) return fail(h, s, "MFMA step launch failed");
+                if (apply) cur_state = st_next;
+                pp ^= 1;
+                ++r.launches;
+            } else {
+                // attempt i ends with its own controller and publishes under index i + 1
+                r.launches += enqueue_attempt_generic(h, r.aux, train, c.eps, B, r.nblk, st, true, nullptr, 0, h->d_mirror,
+                                                      base + (unsigned)sent + 1);
             }
-            h->mirror_base = base + (unsigned)sent + 1;
-            // everything the estimate asks for is in the queue: the post-processing goes right behind it (fused path: the
-            // state slot the newest launch writes is the one a `done` would be published in)
-            if (post && !rec && use_mfma && !done && need >= 0 && sent - seen >= need + 1 && post_at != sent) {
-                enqueue_post(h, train, cur_state, *post, B, true, st);
-                post_at = sent;
-                ++launches;
-            }
-            if (done) break;
-            if (seen >= (long)opts->maxiters) {
-                HIPCHK(h, hipStreamSynchronize(st));
-                return fail(h, CNF_ERR_MAXITERS, "maxiters reached before t1");
-            }
-            // wait for a consistent snapshot newer than the last one read
-            unsigned sq = 0;
-            StepState snap;
-            if ((s = mirror_wait(h, hm, st, &snap, &sq, [base, seen](unsigned tag) { return (int)(tag - base) > (int)seen; },
-                                 "step kernels finished without publishing a state")) != CNF_OK) return s;
-            seen = (long)(sq - base);
-            if (snap.done) { fin = snap; done = true; seen_done = seen; }
-            need = 1;
-            if (snap.dt > 0.f) {
-                const double left = std::fabs((double)snap.t1 - (double)snap.t) / (double)snap.dt;
-                need = left > 1e6 ? 1000000 : (long)std::ceil(left - 1e-6);
-                if (need < 1) need = 1;
-            }
+            ++sent;
+        }
+        h->mirror_base = base + (unsigned)sent + 1;
+        // everything the estimate asks for is in the queue: the post-processing goes right behind it (fused path: the
+        // state slot the newest launch writes is the one a `done` would be published in)
+        if (post && !rec && use_mfma && !done && need >= 0 && sent - seen >= need + 1 && post_at != sent) {
+            enqueue_post(h, train, cur_state, *post, B, true, st);
+            post_at = sent;
+            ++r.launches;
+        }
+        if (done) break;
+        if (seen >= (long)opts->maxiters) {
+            HIPCHK(h, hipStreamSynchronize(st));
+            return fail(h, CNF_ERR_MAXITERS, "maxiters reached before t1");
+        }
+        // wait for a consistent snapshot newer than the last one read
+        unsigned sq = 0; StepState snap;
+        if ((s = mirror_wait(h, hm, st, &snap, &sq, [base, seen](unsigned tag) { return (int)(tag - base) > (int)seen; },
+                             "step kernels finished without publishing a state")) != CNF_OK) return s;
+        seen = (long)(sq - base);
+        if (snap.done) { fin = snap; done = true; seen_done = seen; }
+        need = 1;
+        if (snap.dt > 0.f) {
+            const double left = std::fabs((double)snap.t1 - (double)snap.t) / (double)snap.dt;
+            need = left > 1e6 ? 1000000 : (long)std::ceil(left - 1e-6);
+            if (need < 1) need = 1;
         }
     }
     h->last_state = cur_state;
     if (post) {
         // the speculative launch counts if it was enqueued behind the launch that published `done` (mirror index
         // `seen`, i.e. launch number seen on the fused path: the launches are numbered from 0)
-        if (!(post_at > seen_done)) { enqueue_post(h, train, cur_state, *post, B, false, st); ++launches; }
+        if (!(post_at > seen_done)) { enqueue_post(h, train, cur_state, *post, B, false, st); ++r.launches; }
         post->launched = true;
     }
-    if (rec) {            // streamed recording: step sizes back from the device
-        rec->n = fin.naccept;
-        rec->overflow = fin.naccept > h->traj_cap;
-        rec->hs.assign((size_t)(rec->overflow ? 0 : fin.naccept), 0.f);
-        if (!rec->overflow && fin.naccept > 0)
-            HIPCHK(h, hipMemcpyAsync(rec->hs.data(), h->traj_hs, (size_t)fin.naccept * sizeof(float),
-                                     hipMemcpyDeviceToHost, st));
-        final_sync = true;
+    return finish_solve(h, r, cur_state, fin, c.u_out != nullptr, true, r.nf + 6 * (fin.naccept + fin.nreject), r.k);
+}
+
+// Every solve: the call's checks, its route (cnf_solve_plan.h), then the drivers.
+static cnf_status solve_core(cnf_handle h, const SolveCall& c) {
+    cnf_status s = check_call(h, c.mode, c.B);
+    if (s != CNF_OK) return s;
+    h->rec.end();                      // (every solve may overwrite what a record consists of)
+    if (!c.u0 || !c.opts) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    const bool train = c.mode == CNF_MODE_TRAIN;
+    if (train && !c.eps) return fail(h, CNF_ERR_BAD_ARG, "eps is required in TrainMode");
+    if ((s = check_solve_opts(h, c.opts)) != CNF_OK) return s;
+    if (c.stats) memset(c.stats, 0, sizeof *c.stats);
+    if (c.B == 0) return CNF_OK;
+    SolveRun r{c};
+    if ((s = resolve_kernel(h, c.mode, c.B, c.opts->kernel, &r.k)) != CNF_OK) return s;
+    if ((s = ensure_capacity(h, c.B)) != CNF_OK) return s;
+    HIPCHK(h, hipSetDevice(h->device));
+    r.st = (hipStream_t)c.stream; r.train = train; r.D = rows_of(h, c.mode); r.n = (size_t)r.D * c.B; r.final_sync = c.final_sync;
+    const SolveAsk ask{r.k == CNF_KERNEL_MFMA, c.opts->kernel == CNF_KERNEL_GENERIC, train, c.opts->adaptive != 0, c.opts->dt == 0.f,
+                       h->shard_reduce != nullptr || h->shard_comm != nullptr, h->no_persist, c.rec != nullptr, c.rec && c.rec->wg,
+                       c.post && c.post->xs, c.path != nullptr, c.jvp != nullptr, h->nd.n_cond != 0, h->nd_wave.id2 != 0};
+    SolveCaps caps{};
+    caps.mfma_ok = mfma_supported(h->mfma, h->nd, train, c.B);
+    caps.wave_solve_ok = wave_solve_supported(h->nd_wave, train, c.B);
+    caps.wave_grad_ok = ask.rec_wg && wave_grad_supported(h->nd_wave, c.B, train);
+    caps.bcast_solve_ok = bcast_solve_supported(h->nd, train, c.B, h->device);
+    caps.bcast_store_is_zero = bcast_store_floats(c.B, h->device) == 0;
+    const AuxEval may{ask.k_mfma && !caps.mfma_ok, train, c.eps};      // (the auxiliary kernels cannot run otherwise)
+    caps.trace_fused_ok = may.on && trace_fused_ok(h, may, c.B);
+    caps.trace_solve_ok = caps.trace_fused_ok && trace_solve_supported(h->nd, adj_mfma_layout(h->nd, grad_layout(h->nd)), c.B, h->device);
+    r.rt = solve_route(ask, caps);
+    r.aux = AuxEval{r.rt.trace_on, train, c.eps};
+    if (r.aux.on && (s = ensure_adj_images(h, r.st)) != CNF_OK) return s;
+    r.nblk = r.rt.partials == PARTIALS_TRACE_GRID ? trace_fused_grid(c.B)
+           : r.rt.partials == PARTIALS_MFMA_GRID ? mfma_grid_for(h->mfma, c.B, c.rec != nullptr, train)
+           : (int)std::min<size_t>((r.n + 255) / 256, 256);
+    r.init = init_state(h);
+    *r.init = init_step_state(c.opts, r.nblk);
+    if (r.rt.wg_refused) { c.rec->wg_failed = true; return CNF_OK; }
+    if (r.rt.bcast_prepare) {
+        RESERVE(h, h->d_bimg, bcast_img_floats());          // (allocated on first use)
+        if (!h->bimg_valid) { bcast_pack(h->nd, h->d_params, h->d_bimg, r.st); HIPCHK(h, hipGetLastError()); h->bimg_valid = true; }
+        const size_t need = bcast_store_floats(c.B, h->device);        // several tiles per workgroup: their rows live in global memory
+        if (need > h->d_bstore.capacity()) {
+            HIPCHK(h, hipStreamSynchronize(r.st));
+            RESERVE(h, h->d_bstore, need);
+        }
     }
-    if (u_out) {
-        launch_copy_final(cur_state, h->U[0], h->U[1], u_out, n, st);
-        launches += 1;
+    if (r.rt.one_launch) {
+        bool host_driven = false;
+        s = solve_one_launch(h, r, &host_driven);
+        if (!host_driven) return s;
     }
-    HIPCHK(h, hipGetLastError());
-    // the step count is already known from the last mirror; the copy is stream-ordered work.  Callers that
-    // hand u_out to the host wait here, cnf_inference goes straight on to the post-processing kernel.
-    if (final_sync) HIPCHK(h, hipStreamSynchronize(st));
-    fill_stats(stats, fin, nf + 6 * (fin.naccept + fin.nreject), k, launches);
-    if (fin.nonfinite) return fail(h, CNF_ERR_NONFINITE, "solver state became NaN/Inf");
-    return CNF_OK;
+    if ((s = solve_start(h, r)) != CNF_OK) return s;
+    return r.rt.stepwise ? solve_stepwise(h, r) : solve_streamed(h, r);
 }
 
 // ---- flow paths (include/cnfhip_path.h) ----
@@ -1622,17 +1623,24 @@ extern "C" cnf_status cnf_solve_path(cnf_handle h, int mode, const float* u0, co
         return fail(h, CNF_ERR_UNSUPPORTED, "cnf_solve_path: lock-step shards have no path");
     h->path_valid = false;
     PathHook ph{saveat_host, K, path_out_dev};
-    return solve_core(h, mode, u0, eps, u_out, B, opts, stats, stream, nullptr, true, nullptr, &ph);
+    SolveCall call{mode, B, u0, eps, u_out, opts, stats, stream};
+    call.path = &ph;
+    return solve_core(h, call);
 }
 
-extern "C" int cnf_path_steps(cnf_handle h, float* t_host, float* h_host, int cap) {
-    if (!h || !h->path_valid) return -1;
-    const int n = (int)h->path_t.size();
+// The host step readers (cnf_path_steps, cnf_path_vjp_steps, cnf_jvp_steps, cnf_grad_steps): the accepted steps (t_n, h_n) a call
+// left on the host, up to `cap` of them into whichever array is not null; the number there is, or -1 when there is none
+static int copy_steps(bool valid, const std::vector<float>& t, const std::vector<float>& hh, float* t_host, float* h_host, int cap) {
+    if (!valid) return -1;
+    const int n = (int)t.size();
     for (int i = 0; i < n && i < cap; ++i) {
-        if (t_host) t_host[i] = h->path_t[i];
-        if (h_host) h_host[i] = h->path_h[i];
+        if (t_host) t_host[i] = t[i];
+        if (h_host) h_host[i] = hh[i];
     }
     return n;
+}
+extern "C" int cnf_path_steps(cnf_handle h, float* t_host, float* h_host, int cap) {
+    return h ? copy_steps(h->path_valid, h->path_t, h->path_h, t_host, h_host, cap) : -1;
 }
 
 extern "C" cnf_status cnf_solve_tsit5_host(cnf_handle h, int mode, const float* u0, const float* eps,
@@ -1704,7 +1712,9 @@ static cnf_status inference_impl(cnf_handle h, int mode, const float* xs, const 
     // no allocations and no copies on this path: u0 is assembled in the integrator's own state buffer, and the
     // post-processing reads the final state from wherever the integrator left it
     PostHook ph{logpx, regs, sums5, xs};
-    if (s == CNF_OK) s = solve_core(h, mode, h->U[0], eps, u_final, B, opts, stats, stream, nullptr, false, &ph, nullptr, jvp);
+    SolveCall call{mode, B, h->U[0], eps, u_final, opts, stats, stream};
+    call.post = &ph; call.jvp = jvp; call.final_sync = false;
+    if (s == CNF_OK) s = solve_core(h, call);
     if (s == CNF_OK && !ph.launched) {                      // (the one-attempt-at-a-time drivers leave it to the caller)
         enqueue_post(h, mode == CNF_MODE_TRAIN, h->last_state, ph, B, false, (hipStream_t)stream);   // stream-ordered
         HIPCHK(h, hipGetLastError());
@@ -1986,7 +1996,9 @@ static cnf_status wave_loss_grad(cnf_handle h, int mode, const float* xs, const 
         rec.wg = &wg;
         cnf_solve_stats sst{};
         PostHook ph{h->tmp_logpx, h->tmp_regs, h->d_sums, xs};
-        if ((s = solve_core(h, mode, h->U[0], eps, nullptr, B, opts, &sst, stream, &rec, false, &ph)) != CNF_OK) return s;
+        SolveCall call{mode, B, h->U[0], eps, nullptr, opts, &sst, stream};
+        call.rec = &rec; call.post = &ph; call.final_sync = false;
+        if ((s = solve_core(h, call)) != CNF_OK) return s;
         if (rec.wg_submitted) {
             HIPCHK(h, launch_grad_finish(wg.gpart, grad, (int)h->n_params, waves, h->d_state, h->d_sums, h->lam[0], h->lam[1], h->lam[2],
                                          train ? 1 : 0, loss_dev, st));
@@ -2035,7 +2047,7 @@ static const char* const EMPTY_LOSS_BATCH = "the loss is a mean over the batch: 
 
 // The RECORDED solve of the gradient entry points, from u0: stage states in the trajectory store, the final state in g_US[1],
 // the signed step sizes in last_hs.  A solve of more steps than the store has slots grows it and runs again.
-// TestMode records in solve_core's recording branch of the streamed driver (host-driven, one attempt at a time), the one place
+// TestMode records in solve_stepwise (host-driven, one attempt at a time), the one place
 // where a TestMode solve records: networks whose TestMode otherwise runs inside the fused step kernels (two layers, closed-form
 // trace) take the generic right-hand side there.
 static cnf_status record_solve(cnf_handle h, int mode, const float* u0, const float* eps, int B, const cnf_solve_opts* opts, Recorder& rec,
@@ -2045,7 +2057,9 @@ static cnf_status record_solve(cnf_handle h, int mode, const float* u0, const fl
     if (mode == CNF_MODE_TEST && mfma_supported(h->mfma, h->nd, false, B)) ropts.kernel = CNF_KERNEL_GENERIC;
     for (;;) {
         if (ph) ph->launched = false;
-        if ((s = solve_core(h, mode, u0, eps, h->g_US[1], B, &ropts, &sst, stream, &rec, true, ph)) != CNF_OK) return s;
+        SolveCall call{mode, B, u0, eps, h->g_US[1], &ropts, &sst, stream};
+        call.rec = &rec; call.post = ph;
+        if ((s = solve_core(h, call)) != CNF_OK) return s;
         if (!rec.overflow) break;
         if ((s = traj_reserve(h, rec.n + 8)) != CNF_OK) return s;       // more steps than slots: grow, solve again
     }
@@ -2675,10 +2689,7 @@ extern "C" cnf_status cnf_grad_ys(cnf_handle h, float* gy, int B, void* stream) 
 }
 
 extern "C" int cnf_grad_steps(cnf_handle h, float* hs, int cap) {
-    if (!h) return -1;
-    const int n = (int)h->last_hs.size();
-    if (hs) for (int i = 0; i < n && i < cap; ++i) hs[i] = h->last_hs[i];
-    return n;
+    return h ? copy_steps(true, h->last_hs, h->last_hs, hs, nullptr, cap) : -1;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3124,13 +3135,7 @@ extern "C" cnf_status cnf_generate_path_vjp(cnf_handle h, int mode, const float*
     return path_vjp_status(h, s, status);
 }
 extern "C" int cnf_path_vjp_steps(cnf_handle h, float* t_host, float* h_host, int cap) {
-    if (!h || !h->pvjp_valid) return -1;
-    const int n = (int)h->pvjp_t.size();
-    for (int i = 0; i < n && i < cap; ++i) {
-        if (t_host) t_host[i] = h->pvjp_t[i];
-        if (h_host) h_host[i] = h->pvjp_h[i];
-    }
-    return n;
+    return h ? copy_steps(h->pvjp_valid, h->pvjp_t, h->pvjp_h, t_host, h_host, cap) : -1;
 }
 
 // Heterogeneous ensembles (include/cnfhip_ensemble_hetero.h): the members' own batch sizes, regularisers and tolerances for the
@@ -3372,7 +3377,7 @@ extern "C" int cnf_ensemble_path_steps(cnf_handle h, int member, float* t_host, 
 }
 
 // ---- forward-mode derivatives (include/cnfhip_jvp.h; cnf_tangent.hip) ------------------------------------------------------------
-// Both entry points are: the solve of the call they extend -- inference's with solve_core's `jvp` argument: it keeps the step
+// Both entry points are: the solve of the call they extend -- inference's with SolveCall's `jvp` hook: it keeps the step
 // attempts in jvp_trace and enqueues k_tangent_wave behind a one-launch solve, or files the accepted steps of the
 // one-attempt-at-a-time route --, the tangent launch over the host-filed steps where it has not gone out yet, and the primal
 // outputs handed over once nothing can fail any more.
@@ -3511,11 +3516,5 @@ extern "C" cnf_status cnf_generate_jvp(cnf_handle h, int mode, const float* z0, 
 }
 
 extern "C" int cnf_jvp_steps(cnf_handle h, float* t_host, float* h_host, int cap) {
-    if (!h || !h->jvp_valid) return -1;
-    const int n = (int)h->jvp_t.size();
-    for (int i = 0; i < n && i < cap; ++i) {
-        if (t_host) t_host[i] = h->jvp_t[i];
-        if (h_host) h_host[i] = h->jvp_h[i];
-    }
-    return n;
+    return h ? copy_steps(h->jvp_valid, h->jvp_t, h->jvp_h, t_host, h_host, cap) : -1;
 }
