@@ -65,6 +65,8 @@ from .ensemble import EnsembleDist, ensemble_eval_capacity, ensemble_eval_steps,
 from .ensemble import differentiable_inference_many, ensemble_vjp_capacity, inference_vjp_many
 from .ensemble import differentiable_generate_many, ensemble_generate_vjp_capacity, generate_vjp_many, reverse_kl_many
 from .ensemble import member_loss_from_sums, member_twin, pad_columns      # heterogeneous members: counts, lambdas, tolerances
+from . import ensemble_base
+from .ensemble_base import EnsembleBases                                   # a base distribution per member: bases=
 from . import path
 from .path import generate_path, inference_path, solve_path
 from . import path_vjp

@@ -190,6 +190,16 @@ _ENSEMBLE_HETERO_SIGNATURES = {
     "cnf_ensemble_clear_members": (C.c_int, [C.c_void_p]),
 }
 ENSEMBLE_HETERO_EXPORTS = tuple(_ENSEMBLE_HETERO_SIGNATURES)
+# ensembles with a base per member (include/cnfhip_ensemble_base.h): likewise
+_ENSEMBLE_BASE_SIGNATURES = {
+    "cnf_ensemble_set_bases": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_void_p]),
+    "cnf_ensemble_clear_bases": (C.c_int, [C.c_void_p]),
+    "cnf_ensemble_base_capacity": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "cnf_ensemble_base_sample": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.c_int, C.c_void_p]),
+    "cnf_ensemble_base_logpdf_pullback": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int, _fp, _fp, C.c_void_p]),
+    "cnf_ensemble_base_sample_pullback": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp, _fp, _fp, C.c_void_p]),
+}
+ENSEMBLE_BASE_EXPORTS = tuple(_ENSEMBLE_BASE_SIGNATURES)
 # ensemble flow paths (include/cnfhip_ensemble_path.h): likewise
 _ENSEMBLE_PATH_SIGNATURES = {
     "cnf_ensemble_path_capacity": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -255,7 +265,7 @@ def lib():
         for name, (res, args) in list(_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) + list(_BASEGRAD_SIGNATURES.items()) + \
                 list(_ENSEMBLE_SIGNATURES.items()) + list(_ENSEMBLE_EVAL_SIGNATURES.items()) + list(_ENSEMBLE_VJP_SIGNATURES.items()) + \
                 list(_ENSEMBLE_GENERATE_VJP_SIGNATURES.items()) + list(_PATH_SIGNATURES.items()) + list(_PATH_VJP_SIGNATURES.items()) + \
-                list(_ENSEMBLE_HETERO_SIGNATURES.items()) + list(_ENSEMBLE_PATH_SIGNATURES.items()) + list(_JVP_SIGNATURES.items()):
+                list(_ENSEMBLE_HETERO_SIGNATURES.items()) + list(_ENSEMBLE_BASE_SIGNATURES.items()) + list(_ENSEMBLE_PATH_SIGNATURES.items()) + list(_JVP_SIGNATURES.items()):
             f = getattr(l, name)
             f.restype, f.argtypes = res, args
         _lib = l

@@ -19,6 +19,7 @@
 #include "cnf_step3.h"
 #include "cnf_dist.h"
 #include "cnf_basegrad.h"
+#include "cnf_ens_base.h"
 #include <immintrin.h>
 #include <algorithm>
 #include <sched.h>
@@ -186,6 +187,18 @@ struct cnf_ctx {
     std::vector<float> het_tols;  //   [M][2] (abstol, reltol), or empty: the options'
     DevBuf<float> ens_het;        // [M] counts (ints) | [M][3] lambdas | [M][2] tolerances
     PinnedBuf<float> ens_hhet;
+    // the members' own bases (include/cnfhip_ensemble_base.h): what cnf_ensemble_set_bases prepared for the NEXT ensemble call
+    // (`pend`), which takes it away at its entry; and the bases of the last call that ran with some (`last`), with what
+    // cnf_ensemble_base_logpdf_pullback needs of that call.  Two buffers that change places: preparing the next call's bases
+    // does not touch the last call's.
+    DevBuf<float> ens_bases_pend, ens_bases_last;   // [M][WV_ENS_BASE_FLOATS]
+    int base_M = 0, base_kind = 0;                  //   pending: members (0: nothing) and kind
+    int lbase_M = 0, lbase_kind = 0, lbase_B = 0, lbase_stride = 0;   // the last call: members, kind, B, floats per column of ...
+    size_t lbase_off = 0;                           //   ... the columns the pullback reads, at this offset of ens_cols
+    bool lbase_counts = false;                      //   it had counts of its own: still in ens_het, which only a later ensemble call
+                                                    //   overwrites -- and that call ends this state (ens_take_members)
+    DevBuf<int> ens_bcounts;                        // [M] the members' flags (k_ens_base_flags), gathered for ...
+    PinnedBuf<int> ens_hbflags;                     // ... their [M] landing place on the host
     // cnf_solve_path (include/cnfhip_path.h): the save times on the device and the step pairs the in-launch route files (both
     // allocated on first use), and the accepted steps of the last call on either route (cnf_path_steps)
     DevBuf<float> d_saveat;
@@ -2738,6 +2751,9 @@ struct EnsCall {
     const int* d_counts = nullptr;         // ... on the device, from ens_begin on (null: not given)
     const float *d_lams = nullptr, *d_tols = nullptr;
     bool path_many = false;        // one of the four calls of include/cnfhip_ensemble_path.h: their own capacities
+    // the members' own bases: what cnf_ensemble_set_bases prepared for this call (ens_take_members); M = 0: none
+    int base_M = 0, base_kind = 0;
+    const float* d_bases = nullptr;        // [M][WV_ENS_BASE_FLOATS], device
 };
 // The one-shot state changes hands: whatever becomes of the call, no later call is steered by these arrays.
 static void ens_take_members(cnf_handle h, EnsCall& c) {
@@ -2745,6 +2761,9 @@ static void ens_take_members(cnf_handle h, EnsCall& c) {
     c.het_M = h->het_M; h->het_M = 0;
     c.counts.swap(h->het_counts); c.lams.swap(h->het_lams); c.tols.swap(h->het_tols);
     h->het_counts.clear(); h->het_lams.clear(); h->het_tols.clear();
+    // ... and the bases: the pending buffer becomes the last call's; whatever an earlier call left for the base pullback is gone
+    c.base_M = h->base_M; c.base_kind = h->base_kind; h->base_M = 0; h->lbase_M = 0;
+    if (c.base_M > 0) { h->ens_bases_pend.swap(h->ens_bases_last); c.d_bases = h->ens_bases_last; }
 }
 constexpr size_t ENS_ST_F = (sizeof(StepState) + 3) / 4;     // floats of one member's final state in ens_fin / ens_hfin ...
 static size_t ens_fin_floats(int M) { return (size_t)M * (ENS_ST_F + 5); }      // ... and of all M, their five loss sums behind them
@@ -2769,6 +2788,7 @@ static cnf_status ens_check(cnf_handle h, const EnsCall& c, bool null_ptr, const
             if (!std::isfinite(c.lams[i]) || (c.lams[i] == 0.f) != (h->lam[i % 3] == 0.f))
                 return fail(h, CNF_ERR_BAD_ARG, "a member's lambda must be finite, and zero exactly where the handle's is");
     }
+    if (c.base_M > 0 && c.base_M != c.M) return fail(h, CNF_ERR_BAD_ARG, "cnf_ensemble_set_bases was called for another number of members");
     if (c.times)
         for (int m = 0; m < c.M; ++m)
             if (!std::isfinite(c.times[m]) || c.times[m] == (c.gen ? c.opts->t1 : c.opts->t0))
@@ -2777,7 +2797,8 @@ static cnf_status ens_check(cnf_handle h, const EnsCall& c, bool null_ptr, const
         if ((s = collect_one(h, nullptr)) != CNF_OK) return s;
     if (c.opts->kernel == CNF_KERNEL_GENERIC) return fail(h, CNF_ERR_UNSUPPORTED, "the ensemble form exists on the wave kernels only");
     const int capacity = c.path_many ? (c.grad ? cnf_ensemble_path_vjp_capacity(h, c.mode, c.B) : cnf_ensemble_path_capacity(h, c.mode, c.B))
-                         : c.grad    ? ens_grad_capacity(h, c.mode, c.B, c.cot) : cnf_ensemble_eval_capacity(h, c.mode, c.B);
+                         : c.grad    ? ens_grad_capacity(h, c.mode, c.B, c.base_M > 0 ? wave_cot_based(c.cot) : c.cot)
+                                     : cnf_ensemble_eval_capacity(h, c.mode, c.B);
     if (capacity < 1) return fail(h, CNF_ERR_UNSUPPORTED, "no ensemble form for this model, mode or batch");
     if (c.M > capacity)
         return fail(h, CNF_ERR_UNSUPPORTED, (std::string("more members than one launch takes (") + capacity_fn + ")").c_str());
@@ -2889,6 +2910,29 @@ static cnf_status ens_finish(cnf_handle h, EnsCall& c, int launches, bool sums, 
     return CNF_OK;
 }
 
+// The members' own bases (cnf_ensemble_set_bases), in front of ens_finish: the flags k_ens_base_prepare left -- a member whose mean
+// or scale was no valid Gaussian -- on their way to the host behind everything the call enqueued ...
+static cnf_status ens_base_flags_enqueue(cnf_handle h, const EnsCall& c) {
+    if (!c.d_bases) return CNF_OK;
+    launch_ens_base_flags(c.d_bases, h->ens_bcounts, c.M, c.st);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(h->ens_hbflags, h->ens_bcounts, (size_t)c.M * sizeof(int), hipMemcpyDeviceToHost, c.st));
+    return CNF_OK;
+}
+// ... and behind it (the stream has been waited for): such a member is CNF_ERR_BAD_ARG, whatever its solve did; and what
+// cnf_ensemble_base_logpdf_pullback needs of this call -- the columns it reads are at `off` of the column store, `stride` floats
+// each (an inference: the final columns; sampling: u0 = [z0; 0])
+static void ens_base_close(cnf_handle h, const EnsCall& c, float* loss_out, int* status_out, size_t off, int stride) {
+    if (!c.d_bases) return;
+    for (int m = 0; m < c.M; ++m)
+        if (h->ens_hbflags[m]) {
+            status_out[m] = CNF_ERR_BAD_ARG;
+            if (loss_out) loss_out[m] = NAN;
+        }
+    h->lbase_M = c.M; h->lbase_kind = c.base_kind; h->lbase_B = c.B; h->lbase_stride = stride; h->lbase_off = off;
+    h->lbase_counts = c.d_counts != nullptr;
+}
+
 // Nothing of a member that is not CNF_OK is valid: NaN in its own columns of the two outputs (out1 may be null) -- out0 [B][nv]
 // and out1 [B] of sampling, out0 [B] and out1 [3][B] of an inference; a heterogeneous member's columns behind its count stay
 // as the caller left them.
@@ -2982,6 +3026,7 @@ static cnf_status ens_grad(cnf_handle h, WaveCot cot, int mode, int M, const flo
     c.cot = cot; c.path_many = ep && ep->many;
     ens_take_members(h, c);
     if (ep) { c.het_M = 0; c.counts.clear(); c.lams.clear(); c.tols.clear(); }      // (the path calls take no such arrays: taken and dropped)
+    if (ep && c.base_M > 0) return fail(h, CNF_ERR_UNSUPPORTED, "the path calls take no bases (cnf_ensemble_set_bases): they were dropped");
     cnf_status s = ens_check(h, c, !params_dev || !src || !opts || !grad_dev || !status_out || (train && !eps) ||
                                        (gen ? (!ep && !cot0 && !cot1) || !out0 || !out1 : vjp ? (!ep && !cot0) || !out0 || !out1 : !loss_out),
                              vjp ? "B must be >= 1" : "the loss is a mean over the batch: B must be >= 1",
@@ -3018,7 +3063,7 @@ static cnf_status ens_grad(cnf_handle h, WaveCot cot, int mode, int M, const flo
     ens.counts = c.d_counts; ens.lams = c.d_lams; ens.tols = c.d_tols;
     (gen ? ens.t0 : ens.t1) = times_host ? h->ens_t1.data() : nullptr;
     if (gen) { ens.sampling = true; ens.cot_z = cot0; ens.cot_logq = cot1; }
-    else ens.cw = vjp ? cot0 : nullptr;
+    else { ens.cw = vjp ? cot0 : nullptr; ens.bases = c.d_bases; }      // (sampling: the cotangent of the final state is an input)
     ens.p_stride = np; ens.traj_stride = per_step * cap; ens.part_stride = WV_ENS_PART_FLOATS;
     WavePathArgs wp{};
     if (ep && (s = ens_path_args(h, *ep, M, true, c.st, wp)) != CNF_OK) return s;
@@ -3030,16 +3075,24 @@ static cnf_status ens_grad(cnf_handle h, WaveCot cot, int mode, int M, const flo
     HIPCHK(h, launch_grad_reduce_many(wg.gpart, grad_dev, (int)np, tiles, fin_dev, M, c.st, c.d_counts));
     ++launches;
     if (gen) {                                             // the column kernels: x and logq off the final state, then the z0 tail
-        launch_generate_post_rows((int)n_in, (int)nv, (int)D, fsol, src, out0, out1, Mz * Bz, c.st, c.d_counts, B);
+        if (c.d_bases) launch_ens_base_generate_post((int)n_in, (int)nv, (int)D, c.d_bases, fsol, src, out0, out1, B, c.d_counts, M, c.st);
+        else launch_generate_post_rows((int)n_in, (int)nv, (int)D, fsol, src, out0, out1, Mz * Bz, c.st, c.d_counts, B);
         HIPCHK(h, hipGetLastError());
         ++launches;
         if (grad_in) {
-            launch_generate_z0_grad((int)n_in, BaseDist{}, wg.lam_out, cot1, src, grad_in, Mz * Bz, c.st, c.d_counts, B);
+            if (c.d_bases) launch_ens_base_z0_grad((int)n_in, c.d_bases, wg.lam_out, cot1, src, grad_in, B, c.d_counts, M, c.st);
+            else launch_generate_z0_grad((int)n_in, BaseDist{}, wg.lam_out, cot1, src, grad_in, Mz * Bz, c.st, c.d_counts, B);
             HIPCHK(h, hipGetLastError());
             ++launches;
         }
+    } else if (c.d_bases) {                                // logpx under the members' bases, and their loss sums, afresh
+        launch_ens_base_post((int)n_in, (int)D, c.d_bases, fin_dev, fsol, sv.logpx, sv.regs, B, c.d_counts, sv.sums5, M, c.st);
+        HIPCHK(h, hipGetLastError());
+        ++launches;
     }
+    if ((s = ens_base_flags_enqueue(h, c)) != CNF_OK) return s;
     if ((s = ens_finish(h, c, launches, !gen, loss_out, status_out, stats_out, h->ens_nacc, false)) != CNF_OK) return s;
+    ens_base_close(h, c, loss_out, status_out, gen ? 0 : (size_t)(fsol - cols), (int)D);
     h->ens_M = M; h->ens_cap = cap;
     if (vjp) {                                             // nothing of a member that is not CNF_OK is valid: NaN outputs, zero gradients
         bool any_bad = false;
@@ -3158,6 +3211,79 @@ extern "C" cnf_status cnf_ensemble_clear_members(cnf_handle h) {
     return CNF_OK;
 }
 
+// Ensembles with a base per member (include/cnfhip_ensemble_base.h): N(mean_m, L_m L_m') for the NEXT ensemble call on the
+// handle.  Unlike the members' counts these are DEVICE arrays, reduced on the device (k_ens_base_prepare) in stream order: a
+// learnable base costs no host wait per step.
+extern "C" cnf_status cnf_ensemble_set_bases(cnf_handle h, int M, int kind, const float* mean_dev, const float* chol_dev, void* stream) {
+    if (!h) return CNF_ERR_BAD_ARG;
+    h->base_M = 0;
+    if (M < 1) return fail(h, CNF_ERR_BAD_ARG, "cnf_ensemble_set_bases: an ensemble has at least one member");
+    if (kind != 1 && kind != 2) return fail(h, CNF_ERR_BAD_ARG, "cnf_ensemble_set_bases: kind must be 1 (diagonal) or 2 (dense)");
+    if (!mean_dev || !chol_dev) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    if (h->nd.n_in > 16) return fail(h, CNF_ERR_UNSUPPORTED, "no ensemble form for this model (n_in > 16)");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t Mz = (size_t)M;
+    RESERVE(h, h->ens_bases_pend, Mz * WV_ENS_BASE_FLOATS);      // (grow-only: a steady-state call allocates nothing)
+    RESERVE(h, h->ens_bcounts, Mz);
+    RESERVE(h, h->ens_hbflags, Mz);
+    launch_ens_base_prepare(h->nd.n_in, kind, mean_dev, chol_dev, h->ens_bases_pend, M, (hipStream_t)stream);
+    HIPCHK(h, hipGetLastError());
+    h->base_M = M; h->base_kind = kind;
+    return CNF_OK;
+}
+extern "C" cnf_status cnf_ensemble_clear_bases(cnf_handle h) {
+    if (!h) return CNF_ERR_BAD_ARG;
+    h->base_M = 0;
+    return CNF_OK;
+}
+// the largest M of cnf_loss_grad_many (per_sample = 0) / cnf_inference_vjp_many (1) with bases: the BASE kernels' own budget
+extern "C" int cnf_ensemble_base_capacity(cnf_handle h, int mode, int B, int per_sample) {
+    return ens_grad_capacity(h, mode, B, per_sample ? WC_INFERENCE_BASE : WC_LOSS_BASE);
+}
+// the bases a base call finds: the pending ones (they stay pending), else the last call's
+static const float* ens_bases_for(cnf_handle h, int M, int* kind) {
+    if (h->base_M > 0) { *kind = h->base_kind; return h->base_M == M ? h->ens_bases_pend.data() : nullptr; }
+    if (h->lbase_M > 0) { *kind = h->lbase_kind; return h->lbase_M == M ? h->ens_bases_last.data() : nullptr; }
+    return nullptr;
+}
+extern "C" cnf_status cnf_ensemble_base_sample(cnf_handle h, int M, const float* normals_dev, float* z0_dev, int B, void* stream) {
+    if (!h) return CNF_ERR_BAD_ARG;
+    if (!normals_dev || !z0_dev || normals_dev == z0_dev) return fail(h, CNF_ERR_BAD_ARG, "normals and z0 must be distinct buffers");
+    if (M < 1 || B < 1) return fail(h, CNF_ERR_BAD_SHAPE, "M and B must be >= 1");
+    int kind = 0;
+    const float* bases = ens_bases_for(h, M, &kind);
+    if (!bases) return fail(h, CNF_ERR_BAD_ARG, "cnf_ensemble_base_sample: no bases of M members are pending or on record");
+    HIPCHK(h, hipSetDevice(h->device));
+    launch_ens_base_sample(h->nd.n_in, kind, bases, normals_dev, z0_dev, B, M, (hipStream_t)stream);
+    HIPCHK(h, hipGetLastError());
+    return CNF_OK;
+}
+extern "C" cnf_status cnf_ensemble_base_logpdf_pullback(cnf_handle h, int M, const float* w_dev, int B, float* g_mean_dev, float* g_chol_dev,
+                                                        void* stream) {
+    if (!h) return CNF_ERR_BAD_ARG;
+    if (!w_dev || !g_mean_dev || !g_chol_dev) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    if (h->lbase_M < 1 || h->lbase_M != M || h->lbase_B != B)
+        return fail(h, CNF_ERR_BAD_ARG, "cnf_ensemble_base_logpdf_pullback: the last ensemble call had no bases, or another M or B");
+    HIPCHK(h, hipSetDevice(h->device));
+    launch_ens_base_logpdf_pullback(h->nd.n_in, h->lbase_kind, h->ens_bases_last, h->ens_cols + h->lbase_off, h->lbase_stride, w_dev, B,
+                                    h->lbase_counts ? reinterpret_cast<const int*>(h->ens_het.data()) : nullptr, g_mean_dev, g_chol_dev, M,
+                                    (hipStream_t)stream);
+    HIPCHK(h, hipGetLastError());
+    return CNF_OK;
+}
+extern "C" cnf_status cnf_ensemble_base_sample_pullback(cnf_handle h, int M, int kind, const float* normals_dev, const float* g_z0_dev, int B,
+                                                        const int* counts_dev, float* g_mean_dev, float* g_chol_dev, void* stream) {
+    if (!h) return CNF_ERR_BAD_ARG;
+    if (!normals_dev || !g_z0_dev || !g_mean_dev || !g_chol_dev) return fail(h, CNF_ERR_BAD_ARG, "null pointer");
+    if (kind != 1 && kind != 2) return fail(h, CNF_ERR_BAD_ARG, "kind must be 1 (diagonal) or 2 (dense)");
+    if (M < 1 || B < 1) return fail(h, CNF_ERR_BAD_SHAPE, "M and B must be >= 1");
+    if (h->nd.n_in > 16) return fail(h, CNF_ERR_UNSUPPORTED, "no ensemble form for this model (n_in > 16)");
+    HIPCHK(h, hipSetDevice(h->device));
+    launch_ens_base_sample_pullback(h->nd.n_in, kind, normals_dev, g_z0_dev, B, counts_dev, g_mean_dev, g_chol_dev, M, (hipStream_t)stream);
+    HIPCHK(h, hipGetLastError());
+    return CNF_OK;
+}
+
 // the signed accepted step sizes of member `member` of the last ensemble gradient call -- cnf_loss_grad_many,
 // cnf_inference_vjp_many or cnf_generate_vjp_many -- (read from the device when asked for)
 extern "C" int cnf_ensemble_steps(cnf_handle h, int member, float* hs, int cap) {
@@ -3197,6 +3323,7 @@ static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float*
     c.path_many = ep != nullptr;
     ens_take_members(h, c);
     if (ep) { c.het_M = 0; c.counts.clear(); c.lams.clear(); c.tols.clear(); }      // (the path calls take no such arrays: taken and dropped)
+    if (ep && c.base_M > 0) return fail(h, CNF_ERR_UNSUPPORTED, "the path calls take no bases (cnf_ensemble_set_bases): they were dropped");
     cnf_status s = ens_check(h, c, !params_dev || !src || !opts || !out0 || (!gen && !out1) || !status_out || (train && !eps) || (ep && !ep->out),
                              "B must be >= 1", ep ? "cnf_ensemble_path_capacity" : "cnf_ensemble_eval_capacity");
     if (s != CNF_OK) return s;
@@ -3231,12 +3358,20 @@ static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float*
     ++launches;
     HIPCHK(h, hipGetLastError());
     if (gen) {
-        launch_generate_post_rows((int)n_in, (int)nv, (int)D, fsol, src, out0, out1, Mz * Bz, st, c.d_counts, B);
+        if (c.d_bases) launch_ens_base_generate_post((int)n_in, (int)nv, (int)D, c.d_bases, fsol, src, out0, out1, B, c.d_counts, M, st);
+        else launch_generate_post_rows((int)n_in, (int)nv, (int)D, fsol, src, out0, out1, Mz * Bz, st, c.d_counts, B);
+        HIPCHK(h, hipGetLastError());
+        ++launches;
+    } else if (c.d_bases) {                                // logpx under the members' bases, and their loss sums, afresh
+        launch_ens_base_post((int)n_in, (int)D, c.d_bases, reinterpret_cast<StepState*>(h->ens_fin.data()), cols, out0, out1, B, c.d_counts,
+                             sv.sums5, M, st);
         HIPCHK(h, hipGetLastError());
         ++launches;
     }
     std::vector<int> att, nacc;
+    if ((s = ens_base_flags_enqueue(h, c)) != CNF_OK) return s;
     if ((s = ens_finish(h, c, launches, !gen, loss_out, status_out, stats_out, att, true, ep ? &nacc : nullptr)) != CNF_OK) return s;
+    ens_base_close(h, c, loss_out, status_out, 0, (int)D);
     bool any_bad = false;
     for (int m = 0; m < M; ++m)
         if (status_out[m] != CNF_OK) {                     // nothing of such a member is valid: NaN, whatever the kernel left

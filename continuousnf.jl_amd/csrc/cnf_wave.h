@@ -40,7 +40,11 @@ bool wave_solve_supported(const NetDesc& nd, bool train, int B);
 // the kernel) of inference's four outputs, or of sampling's (z, logq)
 // ... and the two PATH forms of those (cnf_inference_path_vjp, cnf_generate_path_vjp): the same launch also stores the flow at the
 // caller's save times and injects a cotangent of those slices into the backward sweep (the adjoint of Tsit5's interpolant)
-enum WaveCot { WC_LOSS = 0, WC_INFERENCE = 1, WC_SAMPLING = 2, WC_INFERENCE_PATH = 3, WC_SAMPLING_PATH = 4 };
+// ... and the BASE forms of the first two (cnf_ensemble_set_bases): the members have Gaussian bases of their own, so the terminal
+// cotangent's z is P_m (z - mu_m).  They are kernels of their own, so that the forms without bases stay the code they were.
+enum WaveCot { WC_LOSS = 0, WC_INFERENCE = 1, WC_SAMPLING = 2, WC_INFERENCE_PATH = 3, WC_SAMPLING_PATH = 4, WC_LOSS_BASE = 5,
+               WC_INFERENCE_BASE = 6 };
+inline WaveCot wave_cot_based(WaveCot c) { return c == WC_LOSS ? WC_LOSS_BASE : c == WC_INFERENCE ? WC_INFERENCE_BASE : c; }
 inline bool wave_cot_sampling(WaveCot c) { return c == WC_SAMPLING || c == WC_SAMPLING_PATH; }
 inline bool wave_cot_path(WaveCot c) { return c == WC_INFERENCE_PATH || c == WC_SAMPLING_PATH; }
 struct WaveEnsLaunch {
@@ -63,7 +67,20 @@ struct WaveEnsLaunch {
     const int* counts = nullptr;
     const float* lams = nullptr;
     const float* tols = nullptr;
+    // the members' own bases (cnf_ensemble_set_bases), device, [M][WV_ENS_BASE_FLOATS] as k_ens_base_prepare leaves them; the
+    // loss and inference-cotangent forms of the gradient only (their BASE kernels are launched: WC_LOSS_BASE, WC_INFERENCE_BASE):
+    // the terminal cotangent becomes P_m (z - mu_m).  null: N(0, I), the kernels of before
+    const float* bases = nullptr;
 };
+// A member's prepared base (cnf_ens_base.hip), floats: mu [16] | P = W' W [16][16] | W = inv(L) [16][16] | L [16][16], row-major,
+// zero beyond n_in rows / columns | c = sum log W_ii - n_in / 2 log(2 pi) | the member's flag (an int: 0, or 1 = not a valid base)
+#define WV_ENS_BASE_MU 0
+#define WV_ENS_BASE_P 16
+#define WV_ENS_BASE_W 272
+#define WV_ENS_BASE_L 528
+#define WV_ENS_BASE_C 784
+#define WV_ENS_BASE_FLAG 785
+#define WV_ENS_BASE_FLOATS 800
 #define WV_ENS_PART_FLOATS 8192    // a member's meeting words: 2 x 1024 of the meetings + 2048 of the loss-sum partials, 8 bytes each
 // the largest M a launch takes at batch B: workgroups the device holds at once / tiles (0: no ensemble form of this network
 // or mode, or the one-launch solves are switched off)

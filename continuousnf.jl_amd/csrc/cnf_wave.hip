@@ -78,11 +78,17 @@ struct WaveEnsArgs {
                            // (last: the fields the gradient forms read keep their places among the kernel arguments)
     const float* cw;       // CW forms: the members' per-sample cotangents [M][4][B], rows (logpx, E, n, A) (behind t0, for the same reason)
     const float* gz;       // sampling CW forms: null, or the members' cotangents of the final state rows [M][B][n_in] ...
+                           // (the BASE forms: the members' prepared bases, see below)
     const float* gl;       // ... and null, or those of logq [M][B]
     // heterogeneous members (cnf_ensemble_set_members; behind gl, for the same reason; null: the launch's own for every member)
     const int* counts;     // the members' own batch sizes [M], 1 <= counts[m] <= B: the strides stay the launch's B, [M][B]..
     const float* lams;     // the members' own lambda_1..3 [M][3] (the loss forms of the gradient)
     const float* tols;     // the members' own (abstol, reltol) [M][2]
+    // The members' own Gaussian bases (cnf_ensemble_set_bases) have NO field here: the BASE forms (WC_LOSS_BASE,
+    // WC_INFERENCE_BASE), which are never sampling forms, find the prepared bases [M][WV_ENS_BASE_FLOATS] in `gz`.  A field of
+    // their own at the end moved the kernel arguments behind this struct and changed the register allocation of 39 existing
+    // instantiations (more SGPR spills, up to 6 more AGPRs: profiles/ensemble_base_kernel_resources.md); so did a run-time test
+    // of a null pointer in the existing loss / CW forms.
 };
 
 // NI / NH: 16-row tiles of n_in / of the hidden layer;  TANH: tanh on both layers (compile time: the evaluation is then one
@@ -177,7 +183,11 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
     static_assert(!ENS || (WGW == 1 && !RICH), "ENS forms have one tile per workgroup and no rich store");
     static_assert(CW == WC_LOSS || (GRAD && ENS), "CW is a form of the ensemble gradient");
     // per-sample cotangents of inference | of sampling;  CWP: ... and of the path (the launch also stores it)
-    constexpr bool CWI = CW == WC_INFERENCE || CW == WC_INFERENCE_PATH, CWS = CW == WC_SAMPLING || CW == WC_SAMPLING_PATH;
+    // BASE: the loss form and the inference CW form with the members' own Gaussian bases (cnf_ensemble_set_bases): the terminal
+    // cotangent's z becomes P_m (z - mu_m); everything else is the form's without it
+    constexpr bool BASE = CW == WC_LOSS_BASE || CW == WC_INFERENCE_BASE;
+    static_assert(!BASE || NI == 1, "the BASE forms are instantiated for one input tile");
+    constexpr bool CWI = CW == WC_INFERENCE || CW == WC_INFERENCE_PATH || CW == WC_INFERENCE_BASE, CWS = CW == WC_SAMPLING || CW == WC_SAMPLING_PATH;
     constexpr bool CWP = CW == WC_INFERENCE_PATH || CW == WC_SAMPLING_PATH;
     static_assert(!RICH || (GRAD && MODE == WV_VJP), "RICH is a form of the TrainMode / VJP gradient");
     constexpr int RR = 3 * NH + 3 * NI;                     // f32x4 per lane and stage evaluation in the rich store
@@ -234,7 +244,7 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
                 if (wid_ >= ens_tiles) return;
                 a.B = cnt; a.n_total = (float)((size_t)(a.nd.n_in + (MODE != WV_TEST ? 3 : 1)) * (size_t)cnt);
             }
-            if constexpr (GRAD && CW == WC_LOSS) {
+            if constexpr (GRAD && (CW == WC_LOSS || CW == WC_LOSS_BASE)) {
                 if (en.lams) { a.g.lam1 = en.lams[3 * mb]; a.g.lam2 = en.lams[3 * mb + 1]; a.g.lam3 = en.lams[3 * mb + 2]; }
             }
             if (en.tols) { sv.init.abstol = en.tols[2 * mb]; sv.init.reltol = en.tols[2 * mb + 1]; }
@@ -991,12 +1001,27 @@ __global__ void __launch_bounds__(GRAD && WGW == 1 ? 128 : 64 * WGW) k_solve_wav
                     for (int j = 0; j < 4; ++j) { const int r = 16 * m + 4 * q + j; if (aug && r >= nd.nvars) sa = fmaf(uz[m][j], uz[m][j], sa); }
                 sa = wv_quad_sum(sa);
                 const float nrm = sqrtf(sa);
+                // -d logpdf / d z of the member's own base N(mu, L L') (cnf_ensemble_set_bases): P (z - mu) in place of z, one 16 x 16
+                // product on the final-state tile with P as the A operand (mu and P padded to 16 rows with zeros: the rows at and
+                // behind n_in stay 0).  mu = 0, P = I gives z back bit for bit (products with 1 and 0, sums with 0).  The BASE forms
+                // only (en.gz: the members' prepared bases, see WaveEnsArgs); in every other form zb is uz and the code is what it was.
+                f32x4 zb[NI];
+#pragma unroll
+                for (int m = 0; m < NI; ++m) zb[m] = uz[m];
+                if constexpr (BASE) {
+                    const float* bm = en.gz + (size_t)((int)blockIdx.x / en.tiles) * WV_ENS_BASE_FLOATS;
+                    float fP[4];
+                    f32x4 dz;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { fP[j] = bm[WV_ENS_BASE_P + 16 * c + 4 * q + j]; dz[j] = uz[0][j] - bm[WV_ENS_BASE_MU + 4 * q + j]; }
+                    zb[0] = mm4(fP, dz, zero4);
+                }
 #pragma unroll
                 for (int m = 0; m < NI; ++m)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int r = 16 * m + 4 * q + j;
-                        float v = uz[m][j];
+                        float v = zb[m][j];
                         if constexpr (CWI) {
                             v *= cl0;
                             if (aug && r >= nd.nvars && nrm > 0.f) v = fmaf(cwv[3], uz[m][j] / nrm, v);
@@ -1591,7 +1616,7 @@ wave_fn wave_instance_tiles(int ni, int nh, int mode) {
     return nullptr;
 }
 // One row per set of flags that is instantiated, each for the tiles above and the modes it names: these rows ARE the library's
-// k_solve_wave kernels (187 of them).  nullptr: no such kernel -- wave_variant does not return such a tuple.
+// k_solve_wave kernels (217 of them).  nullptr: no such kernel -- wave_variant does not return such a tuple.
 // cw: the CW forms (per-sample cotangents: WC_INFERENCE of cnf_inference_vjp_many, WC_SAMPLING of cnf_generate_vjp_many).  They
 // are no WaveForm of their own: a caller selects one as "the WF_ENS_GRAD answer of wave_variant, with CW" -- the same fifteen
 // tuples, instantiated once more for each, and once more for the PATH form of each (WC_INFERENCE_PATH, WC_SAMPLING_PATH:
@@ -1623,6 +1648,10 @@ wave_fn wave_instance(const WaveVariant& v, WaveCot cw = WC_LOSS) {
     WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, true,  false, WC_INFERENCE_PATH);
     WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, true,  false, WC_SAMPLING_PATH);
     WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, true,  false, WC_SAMPLING_PATH);
+    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, true,  false, WC_LOSS_BASE);          // WF_ENS_GRAD with the members' own bases
+    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, true,  false, WC_LOSS_BASE);
+    WV_ROW(WV_M_ALL,  true,  true,  false, 1, false, true,  false, WC_INFERENCE_BASE);     // ... and its inference CW form
+    WV_ROW(WV_M_ALL,  true,  true,  true,  1, false, true,  false, WC_INFERENCE_BASE);
     WV_ROW(WV_M_ALL,  true,  false, false, 1, false, true,  false, WC_LOSS);     // WF_ENS_PLAIN
     WV_ROW(WV_M_ALL,  true,  false, true,  1, false, true,  false, WC_LOSS);
     WV_ROW(WV_M_ALL,  true,  false, false, 1, false, false, true, WC_LOSS);      // WF_PATH
@@ -1736,8 +1765,11 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
     if (path && !gpath && (grad || !path->out || path->cot)) return CNF_ERR_BAD_ARG;
     if (path && (!path->times || path->K < 1 || (path->steps_cap > 0 && !path->steps))) return CNF_ERR_BAD_ARG;
     // the CW form of the ensemble gradient: per-sample cotangents of inference, or of sampling -- and of the path
+    // ... and with the members' own bases (ens->bases: the loss form and the inference CW form only), the BASE form of either
+    const bool based = ens && ens->bases;
+    if (based && (!grad || ens->sampling || path)) return CNF_ERR_BAD_ARG;
     const WaveCot cw = !ens ? WC_LOSS : ens->sampling ? (gpath ? WC_SAMPLING_PATH : WC_SAMPLING)
-                                      : gpath ? WC_INFERENCE_PATH : ens->cw ? WC_INFERENCE : WC_LOSS;
+                                      : gpath ? WC_INFERENCE_PATH : ens->cw ? (based ? WC_INFERENCE_BASE : WC_INFERENCE) : (based ? WC_LOSS_BASE : WC_LOSS);
     if (cw != WC_LOSS && !grad) return CNF_ERR_BAD_ARG;
     if (ens) {
         const bool gcot = ens->cot_z || ens->cot_logq;     // (sampling: its own cotangents, at least one, and start times only)
@@ -1803,6 +1835,7 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
     if (ens) {                                             // M x tiles workgroups
         en.tiles = tiles; en.t1 = ens->t1; en.p_stride = ens->p_stride; en.part_stride = ens->part_stride;
         en.counts = ens->counts; en.lams = ens->lams; en.tols = ens->tols;
+        if (based) en.gz = ens->bases;                     // (the BASE forms: see WaveEnsArgs)
         grid *= ens->M;
     }
     WavePathArgs pa{};

@@ -23,6 +23,8 @@ import numpy as np
 from . import _lib
 from .base_icnf import ICNF, _Buf, _is_torch, _mode_id, _solve_opts, _stream, draw_eps, generate, inference, loss_and_grad, \
     n_augment_input, steer_tspan
+from .distributions import LearnableNormal
+from .ensemble_base import EnsembleBases
 from .gen_vjp import _cot_two
 from .layers import setup
 from .rng import HIPRNG
@@ -206,7 +208,56 @@ def _set_members(h, het, lo, n):
         part[1].ctypes.data if part[1] is not None else None, part[2].ctypes.data if part[2] is not None else None), h)
 
 
-def member_twin(icnf: ICNF, lambdas=None, tols=None):
+# ---- a base per member (include/cnfhip_ensemble_base.h) ----
+def _check_bases(icnf: ICNF, bases, M, who):
+    """``bases=`` of an ensemble call, checked.  Host logic only: nothing is drawn, no handle is made."""
+    if bases is None:
+        return None
+    if not isinstance(bases, EnsembleBases):
+        raise ValueError(f"{who}: bases must be an EnsembleBases, got {type(bases).__name__}")
+    n_in = icnf.nvars + n_augment_input(icnf)
+    if len(bases) != M or bases.n_in != n_in:
+        raise ValueError(f"{who}: bases must have M = {M} members of nvars + naugmented = {n_in} rows, got ({len(bases)}, {bases.n_in})")
+    return bases
+
+
+def _bases_on(bases, dev):
+    """The members' bases as the device reads them: a namespace ``src`` (the ``EnsembleBases``), ``kind``, ``mean`` (M, n_in) and
+    ``scale`` -- detached float32 tensors on ``dev`` holding the current values; None for None."""
+    if bases is None:
+        return None
+    mean, scale = bases.device_values(dev)
+    return SimpleNamespace(src=bases, kind=bases.kind, mean=mean, scale=scale)
+
+
+def _set_bases(h, b, lo, n, stream):
+    """cnf_ensemble_set_bases for the members ``lo .. lo + n - 1`` (stream-ordered: one small kernel, no host wait): the next
+    ensemble call on the handle takes them away."""
+    _lib.check(_lib.lib().cnf_ensemble_set_bases(h, n, b.kind, b.mean[lo].data_ptr(), b.scale[lo].data_ptr(), stream), h)
+
+
+def _base_grads(b, M, dev):
+    """Where the base pullbacks leave ``(g_mean (M, n_in), g_scale)``: zeros, so that a member that contributes nothing has none."""
+    import torch
+    return torch.zeros(tuple(b.mean.shape), dtype=torch.float32, device=dev), torch.zeros(tuple(b.scale.shape), dtype=torch.float32, device=dev)
+
+
+def _logpdf_pullback(h, b, lo, n, w, B, out, stream):
+    """cnf_ensemble_base_logpdf_pullback of the ensemble call just made for the members ``lo .. lo + n - 1``: ``w`` (n, B)
+    weights of the log-density of each column that call left in the column store; into ``out = (g_mean, g_scale)``."""
+    w = w.contiguous()
+    _lib.check(_lib.lib().cnf_ensemble_base_logpdf_pullback(h, n, w.data_ptr(), B, out[0][lo].data_ptr(), out[1][lo].data_ptr(), stream), h)
+
+
+def _member_base(b, i, learn=False):
+    """Member i's base as a single model's ``basedist``: the constant ``bases[i]``, or -- ``learn`` -- a ``LearnableNormal`` over
+    its current values, which the single-model calls return the base's gradient for."""
+    if not learn:
+        return b.src[i]
+    return LearnableNormal(b.mean[i].clone(), **{"std" if b.kind == 1 else "scale_tril": b.scale[i].clone()})
+
+
+def member_twin(icnf: ICNF, lambdas=None, tols=None, basedist=None):
     """A model of its own handle that is ``icnf`` with one member's regularisers (``lambdas``: three values) and tolerances
     (``tols``: abstol, reltol) -- what the member of a heterogeneous call is compared with and, when its part of a launch gave
     up, run again on.  It shares ``icnf``'s generator and network; the caller closes it."""
@@ -216,7 +267,7 @@ def member_twin(icnf: ICNF, lambdas=None, tols=None):
         kw["abstol"], kw["reltol"] = float(np.float32(tols[0])), float(np.float32(tols[1]))
     lam = (icnf.lambda1, icnf.lambda2, icnf.lambda3) if lambdas is None else tuple(float(np.float32(v)) for v in lambdas)
     return dataclasses.replace(icnf, sol_kwargs=kw, lambda1=lam[0], lambda2=lam[1], lambda3=lam[2], _handle=None, _cond_id=None,
-                               _params_id=None, _base_id=None)
+                               _params_id=None, _base_id=None, basedist=basedist if basedist is not None else icnf.basedist)
 
 
 def pad_columns(parts, B, fill=0.0):
@@ -248,16 +299,19 @@ def member_loss_from_sums(mode, sums5, lambdas):
     return np.float32(-s[0] / s[4])
 
 
-def _device_capacity(who, capacity_fn, h, m, B):
+_BASE_CAPACITY = {"cnf_ensemble_capacity": 0, "cnf_ensemble_vjp_capacity": 1}     # -> cnf_ensemble_base_capacity's `per_sample`
+
+
+def _device_capacity(who, capacity_fn, h, m, B, *more):
     """The members one launch takes on this device (``capacity_fn`` of the C ABI), or ``NotImplementedError``."""
-    cap = int(getattr(_lib.lib(), capacity_fn)(h, m, B))
+    cap = int(getattr(_lib.lib(), capacity_fn)(h, m, B, *more))
     if cap < 1:
         raise NotImplementedError(f"{who}: no ensemble form for this model, mode or batch on this device ({capacity_fn} is 0)")
     return cap
 
 
 def _settle_density(icnf: ICNF, mode, xs, ps, eps, t1, who, single, capacity_fn=None, cot_rows=None, shared=True, members=None,
-                    steer=True):
+                    steer=True, bases=None):
     """The inputs of a density-direction ensemble call, checked, placed and drawn, in the one order the callers promise: the
     host-side refusals and shape checks (``_check_inputs``, then ``cot_rows(M, B)``: the call's cotangent tensors) -- nothing is
     drawn, no handle is made --; the handle (no device: cnf_create's error, as everywhere); the device check; the capacity
@@ -272,16 +326,19 @@ def _settle_density(icnf: ICNF, mode, xs, ps, eps, t1, who, single, capacity_fn=
     m, M, B, n_in, t1 = _check_inputs(icnf, mode, xs, ps, eps, t1, who, single)
     cot = cot_rows(M, B) if cot_rows is not None else ()
     het = _members(icnf, M, B, who=who, **members) if members else None
+    bases = _check_bases(icnf, bases, M, who)
     h = icnf.handle() if capacity_fn is not None else None
     if not (xs.is_cuda and ps.is_cuda and all(a is None or a.is_cuda for a in (eps, *cot))):
         raise ValueError(f"{who}: torch tensors must live on the GPU")
     cap = _device_capacity(who, capacity_fn, h, m, B) if capacity_fn is not None else None
+    if cap is not None and bases is not None and capacity_fn in _BASE_CAPACITY:      # (the gradient launch with bases: kernels of its own)
+        cap = min(cap, _device_capacity(who, "cnf_ensemble_base_capacity", h, m, B, _BASE_CAPACITY[capacity_fn]))
     train, dev = m == _lib.MODE_TRAIN, xs.device
     xr = _rows(xs)
     pr = ps.detach().to(torch.float32).contiguous()
     er, t1 = _probes_and_ends(icnf, mode, train, M, B, n_in, xr, eps, t1, steer=steer, counts=het.counts if het is not None else None)
     return SimpleNamespace(m=m, M=M, B=B, n_in=n_in, train=train, cot=cot, cap=cap, dev=dev, xr=xr, pr=pr, er=er, t1=t1, het=het,
-                           stream=_stream(_Buf(xr, icnf.nvars, M * B, torch)))
+                           stream=_stream(_Buf(xr, icnf.nvars, M * B, torch)), bases=_bases_on(bases, dev))
 
 
 def _launch(icnf: ICNF, s, width, call, steps_of, times_key, times, **more):
@@ -291,7 +348,8 @@ def _launch(icnf: ICNF, s, width, call, steps_of, times_key, times, **more):
     reads the steps of member i of the call just made (asked for the members that succeeded; None: no steps); ``times``: the
     members' own times (None: ``tspan[1]`` for all), reported as ``info[times_key]``; ``width``: the columns of the call's rectangle.  Returns ``(info, steps)``; failures are
     ``_finish``'s, so that a caller may publish ``info`` before they are raised."""
-    h, M, het = icnf.handle(), s.M, getattr(s, "het", None)
+    h, M, het, bases = icnf.handle(), s.M, getattr(s, "het", None), getattr(s, "bases", None)
+    after = more.pop("after", None)                        # after(lo, n): behind the ABI call for those members (the base pullbacks)
     status = np.empty(M, dtype=np.int32)
     stats = (_lib.cnf_solve_stats * M)()
     calls, steps = 0, [] if steps_of is not None else None
@@ -299,8 +357,14 @@ def _launch(icnf: ICNF, s, width, call, steps_of, times_key, times, **more):
         n = min(s.cap, M - lo)
         if het is not None:                                # (a split slices the members' arrays with the members)
             _set_members(h, het, lo, n)
+        if bases is not None:                              # (... and the members' bases: one stream-ordered kernel, no host wait)
+            _set_bases(h, bases, lo, n, s.stream)
+            if getattr(s, "normals", None) is not None:    # a drawn z0: mu_m + L_m n with the bases just prepared (they stay pending)
+                _lib.check(_lib.lib().cnf_ensemble_base_sample(h, n, s.normals[lo].data_ptr(), s.zr[lo].data_ptr(), s.n, s.stream), h)
         _lib.check(call(lo, n, status[lo:].ctypes.data, C.byref(stats, lo * C.sizeof(_lib.cnf_solve_stats))), h)
         calls += 1
+        if after is not None:
+            after(lo, n)
         if steps_of is not None:
             steps += [steps_of(icnf, i) if status[lo + i] == _lib.OK else None for i in range(n)]
     if times is None:
@@ -310,7 +374,7 @@ def _launch(icnf: ICNF, s, width, call, steps_of, times_key, times, **more):
     return info, steps
 
 
-def _finish(icnf: ICNF, info, steps, times, rerun, het=None):
+def _finish(icnf: ICNF, info, steps, times, rerun, het=None, bases=None, learn=False):
     """The second half: a member that failed raises; the members whose part of the launch gave up are run again one at a
     time.  ``rerun(i, model, k)`` runs member i on the single-model route of ``model`` -- ``icnf``, or the twin that carries the
     member's own lambdas and tolerances -- at its ``k`` columns, writes its outputs and returns ``(stats, steps)`` as that
@@ -320,7 +384,7 @@ def _finish(icnf: ICNF, info, steps, times, rerun, het=None):
     _raise_failed(status)
     gave_up = [i for i in range(len(status)) if status[i] != _lib.OK]
     if gave_up:
-        with _one_member_at_a_time(icnf, times, het) as member:
+        with _one_member_at_a_time(icnf, times, het, bases, learn) as member:
             for i in gave_up:
                 stats_i, steps_i = rerun(i, member(i), int(info["counts"][i]))
                 status[i] = _lib.OK
@@ -338,16 +402,20 @@ def _raise_failed(status):
     for i, s in enumerate(status):
         if s in (_lib.ERR_NONFINITE, _lib.ERR_MAXITERS):
             raise _lib.CNFError(int(s), f"ensemble member {i}: " + l.cnf_status_string(int(s)).decode())
+        if s == _lib.ERR_BAD_ARG:                          # (what the device found in values the host could not look at)
+            raise _lib.CNFError(int(s), f"ensemble member {i}: its base is not a Gaussian (a non-finite entry, or a scale whose "
+                                        "diagonal is not positive)")
 
 
 @contextmanager
-def _one_member_at_a_time(icnf: ICNF, times, het=None):
+def _one_member_at_a_time(icnf: ICNF, times, het=None, bases=None, learn=False):
     """For the re-run of the members whose part of the launch gave up -- the existing route, its fallbacks included: ``tspan``
     and ``steer_rate`` are set aside and restored; ``member(i)`` of the yielded function puts member i's own time in and returns
     the model to run it on: ``icnf`` itself, or -- members with their own lambdas or tolerances -- a ``member_twin`` that carries
     them (closed when the next one is asked for, and at the end)."""
     span, steer = icnf.tspan, icnf.steer_rate
-    own = het is not None and (het.lambdas is not None or het.tols is not None)
+    hown = het is not None and (het.lambdas is not None or het.tols is not None)
+    own = hown or bases is not None                        # (a member's base is its twin's ``basedist``: the single-model route takes one)
     twin = []
 
     def member(i):
@@ -357,7 +425,9 @@ def _one_member_at_a_time(icnf: ICNF, times, het=None):
             return icnf
         while twin:
             twin.pop().close()
-        twin.append(member_twin(icnf, het.lambdas[i] if het.lambdas is not None else None, het.tols[i] if het.tols is not None else None))
+        twin.append(member_twin(icnf, het.lambdas[i] if hown and het.lambdas is not None else None,
+                                het.tols[i] if hown and het.tols is not None else None,
+                                _member_base(bases, i, learn) if bases is not None else None))
         return twin[0]                                     # (made behind the assignments above: it has the member's span, no steering)
     try:
         icnf.steer_rate = 0.0
@@ -369,7 +439,7 @@ def _one_member_at_a_time(icnf: ICNF, times, het=None):
 
 
 def loss_and_grad_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, with_steps=False, counts=None, lambdas=None,
-                       reltol=None, abstol=None):
+                       reltol=None, abstol=None, bases=None, with_base=False):
     """``loss_and_grad`` of M members at once: ``xs`` (M, nvars, B) and ``ps`` (M, n_params) device tensors, ``eps``
     (M, n_in, B; TrainMode, drawn with ``draw_eps`` when not given), ``t1`` one end time per member (with ``steer_rate > 0``
     and ``t1=None`` each member gets its own ``steer_tspan`` draw: on a host generator member by member, the member's probes and
@@ -388,30 +458,47 @@ def loss_and_grad_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, wit
     by the device (value outputs there are NaN, input gradients 0, cotangents there are ignored) and a loss is the mean over the
     member's own count; ``reltol`` / ``abstol`` -- a scalar or one per member, in place of ``sol_kwargs``'.  Member m computes, bit
     for bit, what the call with M = 1 at ``B = counts[m]`` computes on ``member_twin`` of it.  ``info["counts"]``,
-    ``info["lambdas"]`` and ``info["tols"]`` (abstol, reltol) report what was used.  ``lambdas`` -- (M, 3): the members' own lambda_1..3 (a sweep), zero exactly where the model's are."""
+    ``info["lambdas"]`` and ``info["tols"]`` (abstol, reltol) report what was used.  ``lambdas`` -- (M, 3): the members' own lambda_1..3 (a sweep), zero exactly where the model's are.
+
+    ``bases`` -- an ``EnsembleBases``: member m's base distribution is N(mean_m, L_m L_m') instead of N(0, I) (the model itself
+    keeps the default base; cnf_ensemble_set_bases, stream-ordered, no host wait).  The loss is the one under the member's base,
+    the gradient's terminal cotangent is formed inside the same launch; a member that is run again takes its base as its twin's
+    ``basedist``.  ``with_base`` appends ``(g_mean (M, n_in), g_scale)`` -- d loss_m / d (mean_m, scale_m), ``g_scale`` shaped like
+    the scale -- to the result, after ``info`` (cnf_ensemble_base_logpdf_pullback with the loss's weight ``-1 / counts[m]``)."""
     import torch
+    if with_base and bases is None:
+        raise ValueError("loss_and_grad_many: with_base needs bases")
     s = _settle_density(icnf, mode, xs, ps, eps, t1, "loss_and_grad_many", "loss_and_grad", "cnf_ensemble_capacity", shared=False,
-                        members=dict(counts=counts, lambdas=lambdas, reltol=reltol, abstol=abstol))
+                        members=dict(counts=counts, lambdas=lambdas, reltol=reltol, abstol=abstol), bases=bases)
     l, h = _lib.lib(), icnf.handle()
     m, M, B, xr, pr, er, t1 = s.m, s.M, s.B, s.xr, s.pr, s.er, s.t1
     opts = _solve_opts(icnf, icnf.tspan)
     grads = torch.empty((M, pr.shape[1]), dtype=torch.float32, device=s.dev)
     losses = np.empty(M, dtype=np.float32)
+    gb, after = None, None
+    if with_base:                                          # the loss is -mean(logpx) + what does not depend on the base: -1 / count per column
+        gb = _base_grads(s.bases, M, s.dev)
+        cnt = torch.as_tensor(np.asarray(s.het.counts if s.het is not None and s.het.counts is not None else np.full(M, B)), device=s.dev)
+        w = (-1.0 / cnt.to(torch.float32))[:, None].expand(M, B).contiguous()
+        after = lambda lo, n: _logpdf_pullback(h, s.bases, lo, n, w[lo:lo + n], B, gb, s.stream)
     info, steps = _launch(icnf, s, B, lambda lo, n, status, stats: l.cnf_loss_grad_many(
         h, m, n, pr[lo].data_ptr(), xr[lo].data_ptr(), er[lo].data_ptr() if er is not None else None, B, C.byref(opts),
         t1[lo:].ctypes.data if t1 is not None else None, losses[lo:].ctypes.data, grads[lo].data_ptr(), status, stats, s.stream),
-        ensemble_steps if with_steps else None, "t1", t1)
+        ensemble_steps if with_steps else None, "t1", t1, after=after)
 
     def rerun(i, model, k):
         args = dict(eps=er[i, :k].t()) if s.train else {}
-        val, g = loss_and_grad(model, mode, xr[i, :k].t(), pr[i], st, **args)
-        losses[i] = val
-        grads[i].copy_(g)
+        res = loss_and_grad(model, mode, xr[i, :k].t(), pr[i], st, with_base=with_base, **args)
+        losses[i] = res[0]
+        grads[i].copy_(res[1])
+        if with_base:
+            gb[0][i].copy_(res[2][0])
+            gb[1][i].copy_(res[2][1])
         return _stats_and_steps(model)
 
-    _finish(icnf, info, steps, t1, rerun, s.het)
+    _finish(icnf, info, steps, t1, rerun, s.het, s.bases, with_base)
     icnf.last_stats = info["stats"][0]
-    return losses, grads, info
+    return (losses, grads, info, gb) if with_base else (losses, grads, info)
 
 
 def _stats_and_steps(icnf: ICNF):
@@ -448,7 +535,7 @@ def _fit_batches(ns, use_batch, batch_size):
     return [(lo, np.minimum(bs, ns - lo)) for lo in range(0, int(ns.max()), bs)]
 
 
-def fit_many(model, verbosity: int, Xs, *, seeds=None, lambdas=None, reltol=None, abstol=None):
+def fit_many(model, verbosity: int, Xs, *, seeds=None, lambdas=None, reltol=None, abstol=None, bases=None):
     """``mlj.fit`` for M data sets (folds, bootstrap replicas, or one set M times), trained side by
     side: member m is initialised with ``setup(seeds[m], ...)``, shuffles with its own generator seeded by ``seeds[m]`` and has
     its own rows of the optimiser's state; an iteration is one ``loss_and_grad_many`` and one application of the optimiser to
@@ -458,7 +545,8 @@ def fit_many(model, verbosity: int, Xs, *, seeds=None, lambdas=None, reltol=None
     The data sets may have unequal numbers of rows as long as every member has the same number of batches per epoch
     (``ceil(n_m / batch_size)``; ``ValueError`` otherwise, before anything is drawn): the last batch of an epoch is then the one
     ragged call (``counts``).  ``lambdas`` (M, 3), ``reltol`` / ``abstol`` (scalar or M values) make the M members a sweep: they are
-    passed to every ``loss_and_grad_many``."""
+    passed to every ``loss_and_grad_many``.  ``bases``: the members' base distributions (an ``EnsembleBases``), kept constant --
+    ``ps`` alone is optimised, as ``fit`` keeps its model's base constant."""
     import torch
     from .base_icnf import loss as _builtin_loss
     from .mlj import _device_matrix
@@ -478,6 +566,7 @@ def fit_many(model, verbosity: int, Xs, *, seeds=None, lambdas=None, reltol=None
     batches = _fit_batches(ns, model.use_batch, model.batch_size)
     sweep = dict(lambdas=lambdas, reltol=reltol, abstol=abstol)
     _members(icnf, M, max(ns), who="fit_many", **sweep)                # (checked before anything is drawn or asks for a device)
+    sweep["bases"] = _check_bases(icnf, bases, M, "fit_many")
     mats = [_device_matrix(icnf, X) for X in Xs]
     ragged = len(set(ns)) > 1
     x = pad_columns(mats, max(ns)) if ragged else torch.stack(mats)   # (M, nvars, n)
@@ -547,7 +636,7 @@ def _trace_cap(opts, with_steps):
 
 
 def inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, with_steps=False, counts=None, lambdas=None, reltol=None,
-                   abstol=None):
+                   abstol=None, bases=None):
     """``inference`` of M members in one launch (cnf_inference_many).  ``xs`` (M, nvars, B): one data set per member (the
     held-out folds), or (nvars, B): one data set scored by every member (bagging; expanded here, the kernel reads M copies);
     ``ps`` (M, n_params); ``eps`` (M, n_in, B; TrainMode) and ``t1`` as ``loss_and_grad_many`` takes and draws them, in its
@@ -563,10 +652,14 @@ def inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, with_st
     by the device (value outputs there are NaN, input gradients 0, cotangents there are ignored) and a loss is the mean over the
     member's own count; ``reltol`` / ``abstol`` -- a scalar or one per member, in place of ``sol_kwargs``'.  Member m computes, bit
     for bit, what the call with M = 1 at ``B = counts[m]`` computes on ``member_twin`` of it.  ``info["counts"]``,
-    ``info["lambdas"]`` and ``info["tols"]`` (abstol, reltol) report what was used.  ``lambdas`` -- (M, 3): they weigh ``info["losses"]`` (``loss_many``)."""
+    ``info["lambdas"]`` and ``info["tols"]`` (abstol, reltol) report what was used.  ``lambdas`` -- (M, 3): they weigh ``info["losses"]`` (``loss_many``).
+
+    ``bases`` -- an ``EnsembleBases``: ``logpx[m]`` and ``info["losses"][m]`` are those under member m's own base N(mean_m, L_m
+    L_m'), computed afresh from the final states by a column pass behind the launch; the regulariser rows, the statistics and the
+    step sequences are those of the call without bases (the base does not enter the solve)."""
     import torch
     s = _settle_density(icnf, mode, xs, ps, eps, t1, "inference_many", "inference", "cnf_ensemble_eval_capacity",
-                        members=dict(counts=counts, lambdas=lambdas, reltol=reltol, abstol=abstol))
+                        members=dict(counts=counts, lambdas=lambdas, reltol=reltol, abstol=abstol), bases=bases)
     l, h = _lib.lib(), icnf.handle()
     m, M, B, dev, xr, pr, er, t1 = s.m, s.M, s.B, s.dev, s.xr, s.pr, s.er, s.t1
     opts = _solve_opts(icnf, icnf.tspan)
@@ -586,16 +679,17 @@ def inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, with_st
         losses[i] = member_loss_from_sums(mode, sums, info["lambdas"][i])
         return dict(model.last_stats), None            # (inference keeps no step trace: None for a member that was run again)
 
-    _finish(icnf, info, steps, t1, rerun, s.het)
+    _finish(icnf, info, steps, t1, rerun, s.het, s.bases)
     icnf.last_stats = info["stats"][0]
     return logpx, (regs[:, 0], regs[:, 1], regs[:, 2]), info
 
 
-def loss_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, counts=None, lambdas=None, reltol=None, abstol=None):
+def loss_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, counts=None, lambdas=None, reltol=None, abstol=None, bases=None):
     """The M members' losses (``loss`` of each on its own data): ``inference_many(...)[2]["losses"]``, a numpy vector -- with
-    ``counts`` means over the members' own counts, with ``lambdas`` weighed by the members' own regularisers."""
+    ``counts`` means over the members' own counts, with ``lambdas`` weighed by the members' own regularisers, with ``bases`` under
+    the members' own base distributions."""
     return inference_many(icnf, mode, xs, ps, st, eps=eps, t1=t1, counts=counts, lambdas=lambdas, reltol=reltol,
-                          abstol=abstol)[2]["losses"]
+                          abstol=abstol, bases=bases)[2]["losses"]
 
 
 def _values(het, shape, dev):
@@ -618,6 +712,11 @@ def _input_grads(het, shape, dev):
 def _host_gen(icnf: ICNF):
     """The numpy generator behind the model's scalar and index draws (a ``HIPRNG`` keeps one for them)."""
     return icnf.rng._host if isinstance(icnf.rng, HIPRNG) else icnf.rng
+
+
+def _normals_info(s):
+    """``info["normals"]`` of a sampling call whose base samples were drawn through the members' bases: (M, n_in, n)."""
+    return dict(normals=s.normals.permute(0, 2, 1)) if s.normals is not None else {}
 
 
 def _check_sampling_inputs(icnf: ICNF, mode, ps, n, z0, eps, t0, who, single):
@@ -685,16 +784,22 @@ def _sampling_draws(icnf: ICNF, mode, train, M, n, n_in, dev, z0, eps, t0, steer
     return zr, er, t0
 
 
-def _settle_sampling(icnf: ICNF, mode, ps, n, z0, eps, t0, who, single, capacity_fn=None, cot_pair=None, members=None, steer=True):
+def _settle_sampling(icnf: ICNF, mode, ps, n, z0, eps, t0, who, single, capacity_fn=None, cot_pair=None, members=None, steer=True,
+                     bases=None, normals=None):
     """``_settle_density`` for the sampling direction, in the same order: ``_check_sampling_inputs`` and ``cot_pair(M, n)``
     (the call's cotangent tensors); the handle; the device check; the capacity (None: not asked); ``_sampling_draws``.
     ``members``: the call's ``counts``, ``reltol``, ``abstol`` (``_members``).  ``steer=False``: no steer variate is drawn (the path
     calls).  Returns a namespace: ``m, M, n, n_in, train, cot,
     cap, dev, stream, pr, zr, er, t0, het``."""
     import torch
+    if normals is not None:                                # given standard normals in place of drawn ones: they go through the bases
+        if bases is None or z0 is not None:
+            raise ValueError(f"{who}: normals needs bases, and no z0")
+        z0 = normals
     m, M, n, n_in, t0 = _check_sampling_inputs(icnf, mode, ps, n, z0, eps, t0, who, single)
     cot = cot_pair(M, n) if cot_pair is not None else ()
     het = _members(icnf, M, n, who=who, **members) if members else None
+    bases = _check_bases(icnf, bases, M, who)
     h = icnf.handle() if capacity_fn is not None else None
     if not (ps.is_cuda and all(a is None or a.is_cuda for a in (z0, eps, *cot))):
         raise ValueError(f"{who}: torch tensors must live on the GPU")
@@ -702,12 +807,17 @@ def _settle_sampling(icnf: ICNF, mode, ps, n, z0, eps, t0, who, single, capacity
     train, dev = m == _lib.MODE_TRAIN, ps.device
     pr = ps.detach().to(torch.float32).contiguous()
     zr, er, t0 = _sampling_draws(icnf, mode, train, M, n, n_in, dev, z0, eps, t0, steer=steer, counts=het.counts if het is not None else None)
-    return SimpleNamespace(m=m, M=M, n=n, n_in=n_in, train=train, cot=cot, cap=cap, dev=dev, pr=pr, zr=zr, er=er, t0=t0, het=het,
-                           stream=_stream(_Buf(pr, pr.shape[1], M, torch)))
+    s = SimpleNamespace(m=m, M=M, n=n, n_in=n_in, train=train, cot=cot, cap=cap, dev=dev, pr=pr, zr=zr, er=er, t0=t0, het=het,
+                        stream=_stream(_Buf(pr, pr.shape[1], M, torch)), bases=_bases_on(bases, dev), normals=None)
+    if s.bases is not None and (z0 is None or normals is not None) and capacity_fn is not None:
+        # the standard normals the default would have drawn, at the same offsets, go through mu_m + L_m n: ``_launch`` fills
+        # ``s.zr`` from them behind the one cnf_ensemble_set_bases of each launch (cnf_ensemble_base_sample)
+        s.normals, s.zr = zr, torch.empty_like(zr)
+    return s
 
 
 def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, t0=None, with_logp=False, with_steps=False,
-                  counts=None, reltol=None, abstol=None):
+                  counts=None, reltol=None, abstol=None, bases=None, normals=None):
     """``generate`` of M members in one launch (cnf_generate_many): ``ps`` (M, n_params) on the device, ``z0`` and ``eps``
     (M, n_in, n) device tensors or drawn as ``generate_prob`` draws them -- on a host generator member by member: the member's
     base sample, its probes (drawn in TestMode too, and not used there), then its steered time; with a ``HIPRNG`` ONE draw of
@@ -718,10 +828,16 @@ def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, 
     the solve and the column kernel), ``calls``, ``rerun``, ``t0`` and the inputs used (``z0``, ``eps``); after ``with_steps``
     the members' step attempts are read with ``ensemble_eval_steps`` (``info["steps"]``).  Failures and refusals as
     ``inference_many``.  ``counts``, ``reltol``, ``abstol``: heterogeneous members, as ``loss_and_grad_many`` takes them (``n`` is then the rectangle's width: member m samples ``counts[m]``
-    columns, ``xs`` and ``logq`` behind them are NaN)."""
+    columns, ``xs`` and ``logq`` behind them are NaN).
+
+    ``bases`` -- an ``EnsembleBases``: member m samples its own base N(mean_m, L_m L_m').  A ``z0`` that is drawn is the standard
+    normals the default would have drawn, at the same offsets, passed through ``mean_m + L_m n`` on the device
+    (cnf_ensemble_base_sample; ``info["normals"]`` keeps them, ``info["z0"]`` the base samples); a given ``z0`` is taken as it
+    is.  ``logq`` is the density under the member's base.  ``normals`` (M, n_in, n; with ``bases``, without ``z0``): standard
+    normals to pass through the bases instead of drawing them."""
     import torch
     s = _settle_sampling(icnf, mode, ps, n, z0, eps, t0, "generate_many", "generate", "cnf_ensemble_eval_capacity",
-                         members=dict(counts=counts, reltol=reltol, abstol=abstol))
+                         members=dict(counts=counts, reltol=reltol, abstol=abstol), bases=bases, normals=normals)
     l, h = _lib.lib(), icnf.handle()
     m, M, n, dev, pr, zr, er, t0 = s.m, s.M, s.n, s.dev, s.pr, s.zr, s.er, s.t0
     opts = _solve_opts(icnf, (icnf.tspan[1], icnf.tspan[0]))              # reverse(tspan)
@@ -732,7 +848,7 @@ def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, 
         h, m, k, pr[lo].data_ptr(), zr[lo].data_ptr(), er[lo].data_ptr() if s.train else None, n, C.byref(opts),
         t0[lo:].ctypes.data if t0 is not None else None, xo[lo].data_ptr(), lq[lo].data_ptr() if with_logp else None,
         status, stats, tc, s.stream), ensemble_eval_steps if with_steps else None, "t0", t0,
-        z0=zr.permute(0, 2, 1), eps=er.permute(0, 2, 1))
+        z0=zr.permute(0, 2, 1), eps=er.permute(0, 2, 1), **_normals_info(s))
     icnf.last_ensemble_info = info                         # (published before a failed member raises: it says which)
 
     def rerun(i, model, k):
@@ -743,7 +859,7 @@ def generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, 
             lq[i, :k].copy_(torch.as_tensor(r[1], device=dev))
         return None, None                              # (generate reports no statistics: the launch's stay)
 
-    _finish(icnf, info, steps, t0, rerun, s.het)
+    _finish(icnf, info, steps, t0, rerun, s.het, s.bases)
     xs = xo.permute(0, 2, 1)                               # (generate does not set icnf.last_stats; nor does this)
     return (xs, lq) if with_logp else xs
 
@@ -774,7 +890,7 @@ def _cot_many(cot, M, B):
 
 
 def inference_vjp_many(icnf: ICNF, mode, xs, ps, st, cot, eps=None, t1=None, with_x=False, with_steps=False, counts=None,
-                       reltol=None, abstol=None):
+                       reltol=None, abstol=None, bases=None, with_base=False):
     """``inference`` of M members and its vector-Jacobian product for a per-sample cotangent, in ONE launch and one of the
     partial sums (cnf_inference_vjp_many): what ``inference_record`` + ``inference_pullback`` give for one model.  ``xs``
     (M, nvars, B) or (nvars, B): one data set shared by all members, as ``inference_many`` takes it; ``ps`` (M, n_params);
@@ -786,11 +902,14 @@ def inference_vjp_many(icnf: ICNF, mode, xs, ps, st, cot, eps=None, t1=None, wit
     as ``loss_and_grad_many``'s, with ``eps`` (M, n_in, B; None in TestMode): the probes used; a member whose part of the launch
     gave up is run again with ``inference_record`` + ``inference_pullback`` (``info["rerun"]``).  Failures and refusals as
     ``loss_and_grad_many``.  ``counts``, ``reltol``, ``abstol``: heterogeneous members, as ``loss_and_grad_many`` takes them (``grad_x`` is 0 behind a member's count, the cotangents there are
-    ignored)."""
+    ignored).  ``bases``: the members' own base distributions, as ``loss_and_grad_many`` takes them; ``with_base`` appends
+    ``(g_mean (M, n_in), g_scale)`` after ``info``: ``sum_b g_logpx[m, b] d logpx[m, b] / d (mean_m, scale_m)``."""
     import torch
+    if with_base and bases is None:
+        raise ValueError("inference_vjp_many: with_base needs bases")
     s = _settle_density(icnf, mode, xs, ps, eps, t1, "inference_vjp_many", "inference_record and inference_pullback",
                         "cnf_ensemble_vjp_capacity", cot_rows=lambda M, B: _cot_many(cot, M, B),
-                        members=dict(counts=counts, reltol=reltol, abstol=abstol))
+                        members=dict(counts=counts, reltol=reltol, abstol=abstol), bases=bases)
     l, h = _lib.lib(), icnf.handle()
     m, M, B, dev, xr, pr, er, t1 = s.m, s.M, s.B, s.dev, s.xr, s.pr, s.er, s.t1
     cm = torch.zeros((M, 4, B), dtype=torch.float32, device=dev)
@@ -801,30 +920,38 @@ def inference_vjp_many(icnf: ICNF, mode, xs, ps, st, cot, eps=None, t1=None, wit
     logpx, regs = _values(s.het, (M, B), dev), _values(s.het, (M, 3, B), dev)
     grads = torch.empty((M, pr.shape[1]), dtype=torch.float32, device=dev)
     gz = _input_grads(s.het, (M, B, s.n_in), dev) if with_x else None
+    gb, after = None, None
+    if with_base:                                          # (logpx alone depends on the base: its cotangent is the weight)
+        gb = _base_grads(s.bases, M, dev)
+        after = lambda lo, n: _logpdf_pullback(h, s.bases, lo, n, cm[lo:lo + n, 0], B, gb, s.stream)
     info, steps = _launch(icnf, s, B, lambda lo, n, status, stats: l.cnf_inference_vjp_many(
         h, m, n, pr[lo].data_ptr(), xr[lo].data_ptr(), er[lo].data_ptr() if er is not None else None, B, C.byref(opts),
         t1[lo:].ctypes.data if t1 is not None else None, cm[lo].data_ptr(), logpx[lo].data_ptr(), regs[lo].data_ptr(),
         grads[lo].data_ptr(), gz[lo].data_ptr() if with_x else None, status, stats, s.stream),
-        ensemble_steps if with_steps else None, "t1", t1, eps=er.permute(0, 2, 1) if er is not None else None)
+        ensemble_steps if with_steps else None, "t1", t1, eps=er.permute(0, 2, 1) if er is not None else None, after=after)
     icnf._record = None                                    # (the call ended whatever was recorded on the handle)
     gx = gz[:, :, :icnf.nvars].permute(0, 2, 1).contiguous() if with_x else None
 
     def rerun(i, model, k):
         from .vjp import inference_pullback, inference_record
         lp, rg = inference_record(model, mode, xr[i, :k].t(), pr[i], st, eps=er[i, :k].t() if s.train else None, tspan=icnf.tspan)
-        res = inference_pullback(model, cm[i, :, :k].contiguous(), with_x=with_x)
+        res = inference_pullback(model, cm[i, :, :k].contiguous(), with_x=with_x, with_base=with_base)
+        res = res if isinstance(res, tuple) else (res,)
         logpx[i, :k].copy_(lp)
         regs[i, :, :k].copy_(torch.stack(list(rg)))
-        grads[i].copy_(res[0] if with_x else res)
+        grads[i].copy_(res[0])
         if with_x:
             gx[i, :, :k].copy_(res[1])
+        if with_base:
+            gb[0][i].copy_(res[-1][0])
+            gb[1][i].copy_(res[-1][1])
         return _stats_and_steps(model)
 
-    _finish(icnf, info, steps, t1, rerun, s.het)
+    _finish(icnf, info, steps, t1, rerun, s.het, s.bases, with_base)
     icnf._record = None                                    # (the members' records are not the caller's)
     icnf.last_stats = info["stats"][0]
     out = (logpx, (regs[:, 0], regs[:, 1], regs[:, 2]), grads)
-    return out + ((gx, info) if with_x else (info,))
+    return out + ((gx, info) if with_x else (info,)) + ((gb,) if with_base else ())
 
 
 @functools.lru_cache(maxsize=None)
@@ -833,8 +960,11 @@ def _autograd_function_many():
 
     class _InferenceMany(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, icnf, mode, xs, ps, eps, t1, het):
-            logpx, (E, n, A), _ = inference_many(icnf, mode, xs.detach(), ps.detach(), None, eps=eps, t1=t1, **het)
+        def forward(ctx, icnf, mode, xs, ps, eps, t1, het, bases, bmean, bscale):
+            # (bmean / bscale: the tensors of the members' bases, here so that autograd routes their gradient; the backward
+            # launch is given the values the forward read)
+            ctx.bases = _frozen_bases(bases, bmean, bscale)
+            logpx, (E, n, A), _ = inference_many(icnf, mode, xs.detach(), ps.detach(), None, eps=eps, t1=t1, bases=ctx.bases, **het)
             ctx.icnf, ctx.mode, ctx.het = icnf, mode, het
             # what the backward launch solves again: the same data, parameters, probes and end times
             ctx.xs, ctx.ps, ctx.eps, ctx.t1 = xs.detach(), ps.detach().clone(), eps, t1
@@ -845,35 +975,57 @@ def _autograd_function_many():
         def backward(ctx, g_logpx, g_E, g_n, g_A):
             icnf = ctx.icnf
             need_x, need_ps = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
-            if not (need_x or need_ps):
-                return None, None, None, None, None, None, None
+            need_b = ctx.bases is not None and (ctx.needs_input_grad[8] or ctx.needs_input_grad[9])
+            if not (need_x or need_ps or need_b):
+                return (None,) * 10
             res = inference_vjp_many(icnf, ctx.mode, ctx.xs, ctx.ps, None, (g_logpx, (g_E, g_n, g_A)), eps=ctx.eps, t1=ctx.t1,
-                                     with_x=bool(need_x), **ctx.het)
+                                     with_x=bool(need_x), bases=ctx.bases, with_base=bool(need_b), **ctx.het)
             icnf.last_backward_logpx = res[0]              # (the backward launch's own logpx: compared with the forward's in the tests)
             gx = None
             if need_x:
                 gx = res[3] if ctx.xs.dim() == 3 else res[3].sum(dim=0)    # (a shared data set collects every member's)
-            return None, None, gx, res[2] if need_ps else None, None, None, None
+            gm, gs = res[-1] if need_b else (None, None)
+            return (None, None, gx, res[2] if need_ps else None, None, None, None, None,
+                    gm if ctx.needs_input_grad[8] else None, gs if ctx.needs_input_grad[9] else None)
 
     return _InferenceMany
 
 
-def differentiable_inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, counts=None, reltol=None, abstol=None):
+def _frozen_bases(bases, bmean, bscale):
+    """The members' bases with the values of now (detached copies): what a backward launch is given.  None for None."""
+    if bases is None:
+        return None
+    return EnsembleBases(bmean.detach().clone(), **{bases._name: bscale.detach().clone()})
+
+
+def _bases_tensors(bases, dev):
+    """``(mean, scale)`` of the members' bases on ``dev`` as float32 tensors in the caller's graph; ``(None, None)`` for None."""
+    import torch
+    if bases is None:
+        return None, None
+    return tuple(a.to(torch.float32) for a in bases.tensors(dev))
+
+
+def differentiable_inference_many(icnf: ICNF, mode, xs, ps, st=None, eps=None, t1=None, counts=None, reltol=None, abstol=None,
+                                  bases=None):
     """``inference_many`` as a differentiable function of ``ps`` (M, n_params) and, when it requires grad, ``xs`` ((M, nvars, B),
     or (nvars, B) shared by all members): the forward is ``inference_many``, keeping the probes and end times it used; the
     backward is ONE ``inference_vjp_many`` with those same draws.  Returns ``(logpx (M, B), (E, n, A))`` attached to the autograd
     graph.  The backward launch solves again: its gradient is the exact discrete adjoint of the steps IT accepts (the solve is
     deterministic, so they are the forward's for the same inputs; DESIGN 4.4 says how its ``logpx`` compares with the
     forward's -- ``icnf.last_backward_logpx`` keeps it).  ``counts``, ``reltol``, ``abstol``: heterogeneous members, as ``loss_and_grad_many`` takes them: the outputs behind a member's count are NaN
-    (mask them out of a loss: their cotangents are ignored) and the gradient of ``xs`` there is 0."""
+    (mask them out of a loss: their cotangents are ignored) and the gradient of ``xs`` there is 0.  ``bases``: the members' own base
+    distributions (an ``EnsembleBases``); when its tensors require grad the backward also returns their gradient -- one ensemble
+    call forward, one ensemble call plus the base pullback backward, no host wait for the base in either."""
     if not (_is_torch(xs) and _is_torch(ps)):
         raise NotImplementedError("differentiable_inference_many takes device tensors")
     # the probes and the steered end times are settled here, once (inference_many's order: the probes, then the end times), so
     # that forward and backward are given the very same ones
     het = dict(counts=counts, reltol=reltol, abstol=abstol)
-    s = _settle_density(icnf, mode, xs.detach(), ps, eps, t1, "differentiable_inference_many", "differentiable_inference", members=het)
+    s = _settle_density(icnf, mode, xs.detach(), ps, eps, t1, "differentiable_inference_many", "differentiable_inference", members=het,
+                        bases=bases)
     eps = s.er.permute(0, 2, 1) if s.er is not None else None
-    logpx, E, n, A = _autograd_function_many().apply(icnf, mode, xs, ps, eps, s.t1, het)
+    logpx, E, n, A = _autograd_function_many().apply(icnf, mode, xs, ps, eps, s.t1, het, bases, *_bases_tensors(bases, s.dev))
     return logpx, (E, n, A)
 
 
@@ -907,7 +1059,7 @@ def _cot_pair_many(icnf: ICNF, cot, M, n):
 
 
 def generate_vjp_many(icnf: ICNF, mode, ps, st, n, cot, z0=None, eps=None, t0=None, with_z0=False, with_steps=False, counts=None,
-                      reltol=None, abstol=None):
+                      reltol=None, abstol=None, bases=None, with_base=False, normals=None):
     """``generate`` of M members with the log-density of every sample, and the vector-Jacobian product of both for a per-sample
     cotangent, in ONE launch and one of the partial sums plus the column kernels (cnf_generate_vjp_many): what
     ``generate_record`` + ``generate_pullback`` give for one model.  ``ps`` (M, n_params) on the device; ``cot = (g_x, g_logq)``:
@@ -921,11 +1073,19 @@ def generate_vjp_many(icnf: ICNF, mode, ps, st, n, cot, z0=None, eps=None, t0=No
     ``with_steps`` also ``steps``: every member's signed accepted step sizes (cnf_ensemble_steps).  A member whose part of the
     launch gave up is run again with ``generate_record`` + ``generate_pullback`` (``info["rerun"]``).  Failures and refusals as
     ``generate_many``: ``NotImplementedError`` before anything is drawn.  ``counts``, ``reltol``, ``abstol``: heterogeneous members, as ``loss_and_grad_many`` takes them (``grad_z0`` is 0 behind a
-    member's count, the cotangents there are ignored)."""
+    member's count, the cotangents there are ignored).  ``bases``: the members' own base distributions, as ``generate_many``
+    takes them (a drawn ``z0`` goes through them; ``logq`` and the ``g_logq`` tail of ``grad_z0`` are the member's base's).
+    ``with_base`` appends ``(g_mean (M, n_in), g_scale)`` after ``info``: the log-density part at fixed ``z0``, ``sum_b g_logq[m, b]
+    d logpdf_m(z0_b) / d (mean_m, scale_m)``, plus -- when ``z0`` was drawn here -- the pullback of the draw ``mean_m + L_m n`` for
+    ``grad_z0``: the TOTAL derivative, as ``generate_pullback(..., with_base=True)`` composes it for one model.  ``normals``: as
+    ``generate_many`` takes them (they count as drawn here)."""
     import torch
+    if with_base and bases is None:
+        raise ValueError("generate_vjp_many: with_base needs bases")
     s = _settle_sampling(icnf, mode, ps, n, z0, eps, t0, "generate_vjp_many", "generate_record and generate_pullback",
                          "cnf_ensemble_generate_vjp_capacity", cot_pair=lambda M, n: _cot_pair_many(icnf, cot, M, n),
-                         members=dict(counts=counts, reltol=reltol, abstol=abstol))
+                         members=dict(counts=counts, reltol=reltol, abstol=abstol), bases=bases, normals=normals)
+    with_z0_asked, with_z0 = with_z0, bool(with_z0 or (with_base and s.normals is not None))
     l, h = _lib.lib(), icnf.handle()
     m, M, n, n_in, dev, pr, zr, er, t0 = s.m, s.M, s.n, s.n_in, s.dev, s.pr, s.zr, s.er, s.t0
     gx, gl = s.cot
@@ -940,12 +1100,17 @@ def generate_vjp_many(icnf: ICNF, mode, ps, st, n, cot, z0=None, eps=None, t0=No
     lq = _values(s.het, (M, n), dev)
     grads = torch.empty((M, pr.shape[1]), dtype=torch.float32, device=dev)
     gz = _input_grads(s.het, (M, n, n_in), dev) if with_z0 else None
+    gb, after = None, None
+    if with_base:
+        gb = _base_grads(s.bases, M, dev)
+        wl = cl if cl is not None else torch.zeros((M, n), dtype=torch.float32, device=dev)
+        after = lambda lo, k: _logpdf_pullback(h, s.bases, lo, k, wl[lo:lo + k], n, gb, s.stream)
     info, steps = _launch(icnf, s, n, lambda lo, k, status, stats: l.cnf_generate_vjp_many(
         h, m, k, pr[lo].data_ptr(), zr[lo].data_ptr(), er[lo].data_ptr() if s.train else None, n, C.byref(opts),
         t0[lo:].ctypes.data if t0 is not None else None, cz[lo].data_ptr() if cz is not None else None,
         cl[lo].data_ptr() if cl is not None else None, xo[lo].data_ptr(), lq[lo].data_ptr(), grads[lo].data_ptr(),
         gz[lo].data_ptr() if with_z0 else None, status, stats, s.stream), ensemble_steps if with_steps else None, "t0", t0,
-        z0=zr.permute(0, 2, 1), eps=er.permute(0, 2, 1))
+        z0=zr.permute(0, 2, 1), eps=er.permute(0, 2, 1), after=after, **_normals_info(s))
     icnf._record = None                                    # (the call ended whatever was recorded on the handle)
     icnf.last_ensemble_info = info
 
@@ -953,19 +1118,41 @@ def generate_vjp_many(icnf: ICNF, mode, ps, st, n, cot, z0=None, eps=None, t0=No
         from .gen_vjp import generate_pullback, generate_record
         x_i, lq_i = generate_record(model, mode, pr[i], st, k, z0=zr[i, :k].t(), eps=er[i, :k].t(), tspan=icnf.tspan)
         res = generate_pullback(model, (cz[i, :k].t() if cz is not None else None, cl[i, :k] if cl is not None else None),
-                                with_z0=with_z0)
+                                with_z0=with_z0, with_base=with_base)
+        res = res if isinstance(res, tuple) else (res,)
         xo[i, :k].copy_(x_i.t())
         lq[i, :k].copy_(lq_i)
-        grads[i].copy_(res[0] if with_z0 else res)
+        grads[i].copy_(res[0])
         if with_z0:
             gz[i, :k].copy_(res[1].t())
+        if with_base:                                      # (the log-density part at fixed z0: the record was given its z0)
+            gb[0][i].copy_(res[-1][0])
+            gb[1][i].copy_(res[-1][1])
         return _stats_and_steps(model)
 
-    _finish(icnf, info, steps, t0, rerun, s.het)
+    _finish(icnf, info, steps, t0, rerun, s.het, s.bases, with_base)
     icnf._record = None                                    # (the members' records are not the caller's)
     icnf.last_stats = info["stats"][0]
+    if with_base and s.normals is not None:                # ... plus the pullback of the draw z0 = mean_m + L_m n, for grad_z0
+        sm, ss = _sample_pullback(h, s, s.normals, gz)
+        gb = (gb[0] + sm, gb[1] + ss)
     out = (xo.permute(0, 2, 1), lq, grads)
-    return out + ((gz.permute(0, 2, 1), info) if with_z0 else (info,))
+    return out + ((gz.permute(0, 2, 1), info) if with_z0_asked else (info,)) + ((gb,) if with_base else ())
+
+
+def _sample_pullback(h, s, normals, g_z0):
+    """cnf_ensemble_base_sample_pullback: ``(sum_b g_z0[m, b], tril(sum_b g_z0[m, b] normals[m, b]'))`` per member, for
+    ``normals`` and ``g_z0`` [M][n][n_in]; the members' counts, when the call has some, mask the columns behind them."""
+    import torch
+    out = _base_grads(s.bases, s.M, s.dev)
+    cnt = None
+    if s.het is not None and s.het.counts is not None:
+        cnt = torch.as_tensor(s.het.counts, device=s.dev).to(torch.int32).contiguous()
+    g = g_z0.contiguous()
+    _lib.check(_lib.lib().cnf_ensemble_base_sample_pullback(h, s.M, s.bases.kind, normals.data_ptr(), g.data_ptr(), s.n,
+                                                            cnt.data_ptr() if cnt is not None else None, out[0].data_ptr(),
+                                                            out[1].data_ptr(), s.stream), h)
+    return out
 
 
 @functools.lru_cache(maxsize=None)
@@ -974,9 +1161,12 @@ def _autograd_function_generate_many():
 
     class _GenerateMany(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, icnf, mode, ps, z0, eps, t0, het):
+        def forward(ctx, icnf, mode, ps, z0, eps, t0, het, bases, bmean, bscale, drawn):
+            # (bases, bmean, bscale: as in _InferenceMany; drawn: z0 holds the standard normals that go through the bases)
             n = z0.shape[2]
-            xs, logq = generate_many(icnf, mode, ps.detach(), None, n, z0=z0.detach(), eps=eps, t0=t0, with_logp=True, **het)
+            ctx.bases = _frozen_bases(bases, bmean, bscale)
+            ctx.src = dict(normals=z0.detach()) if drawn else dict(z0=z0.detach())
+            xs, logq = generate_many(icnf, mode, ps.detach(), None, n, eps=eps, t0=t0, with_logp=True, bases=ctx.bases, **ctx.src, **het)
             ctx.icnf, ctx.mode, ctx.het = icnf, mode, het
             # what the backward launch solves again: the same parameters, base draws, probes and start times
             ctx.ps, ctx.z0, ctx.eps, ctx.t0 = ps.detach().clone(), z0.detach(), eps, t0
@@ -987,35 +1177,43 @@ def _autograd_function_generate_many():
         def backward(ctx, g_x, g_logq):
             icnf = ctx.icnf
             need_ps, need_z0 = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
-            if (g_x is None and g_logq is None) or not (need_ps or need_z0):
-                return None, None, None, None, None, None, None
-            res = generate_vjp_many(icnf, ctx.mode, ctx.ps, None, ctx.z0.shape[2], (g_x, g_logq), z0=ctx.z0, eps=ctx.eps, t0=ctx.t0,
-                                    with_z0=bool(need_z0), **ctx.het)
+            need_b = ctx.bases is not None and (ctx.needs_input_grad[8] or ctx.needs_input_grad[9])
+            if (g_x is None and g_logq is None) or not (need_ps or need_z0 or need_b):
+                return (None,) * 11
+            res = generate_vjp_many(icnf, ctx.mode, ctx.ps, None, ctx.z0.shape[2], (g_x, g_logq), eps=ctx.eps, t0=ctx.t0,
+                                    with_z0=bool(need_z0), bases=ctx.bases, with_base=bool(need_b), **ctx.src, **ctx.het)
             # (the backward launch's own outputs: compared with the forward's in the tests)
             icnf.last_backward_xs, icnf.last_backward_logq = res[0], res[1]
-            return None, None, res[2] if need_ps else None, res[3].contiguous() if need_z0 else None, None, None, None
+            gm, gs = res[-1] if need_b else (None, None)
+            return (None, None, res[2] if need_ps else None, res[3].contiguous() if need_z0 else None, None, None, None, None,
+                    gm if ctx.needs_input_grad[8] else None, gs if ctx.needs_input_grad[9] else None, None)
 
     return _GenerateMany
 
 
 def differentiable_generate_many(icnf: ICNF, mode, ps, st=None, n: int = 1, z0=None, eps=None, t0=None, counts=None, reltol=None,
-                                 abstol=None):
+                                 abstol=None, bases=None):
     """``generate_many(with_logp=True)`` as a differentiable function of ``ps`` (M, n_params) and, when it requires grad, ``z0``
     (M, n_in, n): the forward is ``generate_many`` with the base draws, probes and steered start times settled once (its order);
     the backward is ONE ``generate_vjp_many`` with those same draws.  Returns ``(xs (M, nvars, n), logq (M, n))`` attached to the
     autograd graph.  The backward launch solves again: its gradient is the exact discrete adjoint of the steps IT accepts (the
     solve is deterministic, so they are the forward's for the same inputs; DESIGN 4.4 says how its ``xs`` / ``logq`` compare with
     the forward's -- ``icnf.last_backward_logq`` and ``icnf.last_backward_xs`` keep them).  ``counts``, ``reltol``, ``abstol``: heterogeneous members, as ``loss_and_grad_many`` takes them: ``xs`` and
-    ``logq`` behind a member's count are NaN (mask them out of a loss) and the gradient of ``z0`` there is 0."""
+    ``logq`` behind a member's count are NaN (mask them out of a loss) and the gradient of ``z0`` there is 0.  ``bases``: the members'
+    own base distributions (an ``EnsembleBases``): a ``z0`` that is drawn here goes through them, and when its tensors require
+    grad the backward returns their TOTAL gradient (the log-density part plus the pullback of the draw) -- the location-scale
+    family of a variational fit, per member, with no host wait for the base."""
     het = dict(counts=counts, reltol=reltol, abstol=abstol)
     s = _settle_sampling(icnf, mode, ps, n, z0.detach() if _is_torch(z0) else z0, eps, t0, "differentiable_generate_many",
-                         "differentiable_generate", members=het)
+                         "differentiable_generate", members=het, bases=bases)
+    drawn = bases is not None and z0 is None               # (s.zr then holds the standard normals: the launches pass them through the bases)
     if not (z0 is not None and z0.requires_grad):          # (a z0 that asks for a gradient stays the caller's tensor)
         z0 = s.zr.permute(0, 2, 1)
-    return _autograd_function_generate_many().apply(icnf, mode, ps, z0, s.er.permute(0, 2, 1), s.t0, het)
+    return _autograd_function_generate_many().apply(icnf, mode, ps, z0, s.er.permute(0, 2, 1), s.t0, het, bases,
+                                                    *_bases_tensors(bases, s.dev), drawn)
 
 
-def reverse_kl_many(icnf: ICNF, mode, ps, st, n, target_logpdf, counts=None, reltol=None, abstol=None, **kw):
+def reverse_kl_many(icnf: ICNF, mode, ps, st, n, target_logpdf, counts=None, reltol=None, abstol=None, bases=None, **kw):
     """The M members' reverse Kullback-Leibler divergences to unnormalised targets, each estimated on ``n`` samples of its
     member: ``(logq - target_logpdf(xs)).mean(dim=1)``, an (M,) tensor, with ``(xs, logq) = differentiable_generate_many(icnf,
     mode, ps, st, n, **kw)`` -- M variational fits (restarts, targets of one family, a temperature ladder) differentiated by one
@@ -1023,9 +1221,10 @@ def reverse_kl_many(icnf: ICNF, mode, ps, st, n, target_logpdf, counts=None, rel
     the samples (M, nvars, n) and returns (M, n) log-densities, so that members with different targets index their own
     parameters by the leading axis (a per-member list would be M calls on slices of one tensor).  ``counts``, ``reltol``, ``abstol``: heterogeneous members, as ``loss_and_grad_many`` takes them: member
     m's divergence is the mean over its own ``counts[m]`` samples (``target_logpdf`` sees zeros in the columns behind them, and
-    what it returns there is not used)."""
+    what it returns there is not used).  ``bases``: the members' own (learnable) base distributions, as
+    ``differentiable_generate_many`` takes them: M restarts, each with its own location-scale family."""
     import torch
-    xs, logq = differentiable_generate_many(icnf, mode, ps, st, n, counts=counts, reltol=reltol, abstol=abstol, **kw)
+    xs, logq = differentiable_generate_many(icnf, mode, ps, st, n, counts=counts, reltol=reltol, abstol=abstol, bases=bases, **kw)
     if counts is None:
         t = target_logpdf(xs)
         if tuple(t.shape) != tuple(logq.shape):
@@ -1078,9 +1277,10 @@ def check_weights(weights, M):
 
 class EnsembleDist:
     """The bagged density of M members of one architecture: ``sum_m w_m p_m`` (``weights``: uniform by default).  ``ps`` is the
-    (M, n_params) device tensor ``fit_many`` trains (or a list of its ``(ps_m, st)`` results)."""
+    (M, n_params) device tensor ``fit_many`` trains (or a list of its ``(ps_m, st)`` results).  ``bases``: an ``EnsembleBases`` --
+    component m has the base N(mean_m, L_m L_m'): a mixture whose components sit in different places."""
 
-    def __init__(self, icnf: ICNF, mode, ps, st=None, weights=None):
+    def __init__(self, icnf: ICNF, mode, ps, st=None, weights=None, bases=None):
         why = _refusal(icnf)
         if why is not None:
             raise NotImplementedError("EnsembleDist: " + why)
@@ -1092,6 +1292,7 @@ class EnsembleDist:
         if not _is_torch(ps) or ps.dim() != 2:
             raise ValueError("ps must be an (M, n_params) tensor")
         self.m, self.mode, self.ps, self.st = icnf, mode, ps, st
+        self.bases = _check_bases(icnf, bases, int(ps.shape[0]), "EnsembleDist")      # the components' own base distributions
         # (a tensor of weights -- e.g. the softmax of logits that stacking trains -- is kept for log_prob; its values are checked
         # like any others)
         self.weights_t = weights if _is_torch(weights) else None
@@ -1102,7 +1303,7 @@ class EnsembleDist:
 
     def logpdf_members(self, A, *, eps=None):
         """Every member's ``logpdf`` of the columns of ``A`` (nvars, n): (M, n), one launch."""
-        return inference_many(self.m, self.mode, A, self.ps, self.st, eps=eps)[0]
+        return inference_many(self.m, self.mode, A, self.ps, self.st, eps=eps, bases=self.bases)[0]
 
     def logpdf(self, A, *, eps=None):
         return mixture_logpdf(self.logpdf_members(A, eps=eps), self.weights)
@@ -1117,7 +1318,7 @@ class EnsembleDist:
         business): ``differentiable_inference_many`` in TestMode -- one launch forward, one ``inference_vjp_many`` backward."""
         import torch
         from .types import TestMode
-        logp = differentiable_inference_many(self.m, TestMode(), xs, self.ps, self.st)[0]
+        logp = differentiable_inference_many(self.m, TestMode(), xs, self.ps, self.st, bases=self.bases)[0]
         w = self.weights_t if self.weights_t is not None else torch.as_tensor(self.weights)
         return torch.logsumexp(logp + torch.log(w.to(device=logp.device, dtype=logp.dtype))[:, None], dim=0)
 
@@ -1140,10 +1341,10 @@ class EnsembleDist:
         if ragged:
             live = np.flatnonzero(counts)
             xs = generate_many(self.m, self.mode, self.ps[torch.as_tensor(live, device=self.ps.device)], self.st, int(counts.max()),
-                               counts=counts[live])
+                               counts=counts[live], bases=self.bases.take(live) if self.bases is not None else None)
             out = torch.cat([xs[j, :, :counts[i]] for j, i in enumerate(live)], dim=1)
             return (out, np.repeat(np.arange(len(counts)), counts)) if with_members else out
-        xs = generate_many(self.m, self.mode, self.ps, self.st, int(counts.max()))
+        xs = generate_many(self.m, self.mode, self.ps, self.st, int(counts.max()), bases=self.bases)
         out = torch.cat([xs[i, :, :c] for i, c in enumerate(counts)], dim=1)
         if with_members:
             return out, np.repeat(np.arange(len(counts)), counts)

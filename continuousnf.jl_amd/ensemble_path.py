@@ -51,6 +51,14 @@ def ensemble_path_steps(icnf: ICNF, member: int):
     return t[:n], hs[:n]
 
 
+def _no_bases(who, bases):
+    """The ensemble path calls take no ``bases=`` (a base per member: include/cnfhip_ensemble_base.h): refused before anything is
+    drawn or asks for a device."""
+    if bases is not None:
+        raise NotImplementedError(f"{who}: the ensemble path calls take no bases= (score the members with inference_many / "
+                                  "inference_vjp_many, or one member at a time on a model constructed with basedist=)")
+
+
 def check_saveat_many(saveat, tspan, M):
     """``saveat`` as float32 ``(K,)`` -- one set for all members -- or ``(M, K)`` -- one per member --, every set checked by
     ``check_saveat`` against ``tspan``; ``ValueError`` otherwise (a member's index is named).  Touches no device."""
@@ -149,7 +157,7 @@ def _path_cot_many(given, names, M, K, B, n_in, train, dev):
 # ---------------------------------------------------------------------------------------
 # the plain calls
 # ---------------------------------------------------------------------------------------
-def inference_path_many(icnf: ICNF, mode, xs, ps, st=None, *, saveat, eps=None):
+def inference_path_many(icnf: ICNF, mode, xs, ps, st=None, *, saveat, eps=None, bases=None):
     """``inference_path`` of M members in ONE launch (cnf_inference_path_many).  ``xs`` (M, nvars, B), or (nvars, B) shared by all
     members; ``ps`` (M, n_params); ``eps`` (M, n_in, B; TrainMode) given or drawn in ``inference_many``'s order, without a steer
     variate; ``saveat`` (K,) or (M, K), from ``tspan[0]`` to ``tspan[1]``.  Returns ``(logpx (M, B), (E, n, A), path, info)``:
@@ -157,6 +165,7 @@ def inference_path_many(icnf: ICNF, mode, xs, ps, st=None, *, saveat, eps=None):
     ``E``, ``n`` --, ``t`` as it was given and ``steps`` a list of M ``(t_n, h_n)``.  ``logpx`` and the regularisers are
     ``inference_many``'s for the same inputs, bit for bit.  ``info`` as ``inference_many``'s (``launches`` is 1); a member whose
     part of the launch gave up is run again with ``inference_path`` on a twin of the model (``info["rerun"]``)."""
+    _no_bases("inference_path_many", bases)
     import torch
     who = "inference_path_many"
     box = {}
@@ -213,13 +222,14 @@ def _logq_path(zr, dlogp, n_in):
     return lp0[:, None, :] + dlogp
 
 
-def generate_path_many(icnf: ICNF, mode, ps, st=None, n: int = 1, *, saveat, z0=None, eps=None):
+def generate_path_many(icnf: ICNF, mode, ps, st=None, n: int = 1, *, saveat, z0=None, eps=None, bases=None):
     """``generate_path`` of M members in one launch and the column kernel (cnf_generate_path_many).  ``ps`` (M, n_params);
     ``z0`` / ``eps`` (M, n_in, n) given or drawn in ``generate_many``'s order, without a steer variate; ``saveat`` (K,) or (M, K),
     from ``tspan[1]`` to ``tspan[0]``.  Returns ``(xs (M, nvars, n), logq (M, n), path, info)``: ``xs`` and ``logq`` are
     ``generate_many(with_logp=True)``'s, bit for bit; ``path`` as ``inference_path_many``'s plus ``logq`` (M, K, n).  ``info`` as
     ``generate_many``'s (``z0``, ``eps``: the inputs used); a member whose part of the launch gave up is run again with
     ``generate_path`` on a twin of the model."""
+    _no_bases("generate_path_many", bases)
     import torch
     who = "generate_path_many"
     box = {}
@@ -270,7 +280,7 @@ def generate_path_many(icnf: ICNF, mode, ps, st=None, n: int = 1, *, saveat, z0=
 # ---------------------------------------------------------------------------------------
 # the vector-Jacobian products
 # ---------------------------------------------------------------------------------------
-def inference_path_vjp_many(icnf: ICNF, mode, xs, ps, st=None, *, saveat, cot=None, path_cot=None, eps=None, with_x=False):
+def inference_path_vjp_many(icnf: ICNF, mode, xs, ps, st=None, *, saveat, cot=None, path_cot=None, eps=None, with_x=False, bases=None):
     """``inference_path_vjp`` of M members in ONE launch and one of the partial sums (cnf_inference_path_vjp_many).  ``xs``
     (M, nvars, B) or (nvars, B) shared; ``ps`` (M, n_params); ``saveat`` (K,) or (M, K); ``cot = (g_logpx, (g_E, g_n, g_A))``,
     each (M, B) or None, or None for no cotangent of the outputs; ``path_cot``: a dict with any of ``z`` (M, K, n_in, B),
@@ -278,6 +288,7 @@ def inference_path_vjp_many(icnf: ICNF, mode, xs, ps, st=None, *, saveat, cot=No
     grad_x (M, nvars, B)], info)``, member m's as ``inference_path_vjp`` gives them for it alone -- with M = 1 the very same
     launch.  A member whose part of the launch gave up is run again with ``inference_path_vjp`` on a twin of the model
     (``info["rerun"]``); if that raises, the error names the member."""
+    _no_bases("inference_path_vjp_many", bases)
     import torch
     who = "inference_path_vjp_many"
     box = {}
@@ -351,7 +362,7 @@ def inference_path_vjp_many(icnf: ICNF, mode, xs, ps, st=None, *, saveat, cot=No
 
 
 def generate_path_vjp_many(icnf: ICNF, mode, ps, st=None, n: int = 1, *, saveat, cot=None, path_cot=None, z0=None, eps=None,
-                           with_z0=False):
+                           with_z0=False, bases=None):
     """``generate_path_vjp`` of M members in ONE launch, one of the partial sums and the column kernels
     (cnf_generate_path_vjp_many).  ``ps`` (M, n_params); ``saveat`` (K,) or (M, K) from ``tspan[1]`` to ``tspan[0]``;
     ``cot = (g_x, g_logq)`` as ``generate_vjp_many`` takes it (None: no cotangent of the outputs); ``path_cot``: a dict with any of
@@ -362,6 +373,7 @@ def generate_path_vjp_many(icnf: ICNF, mode, ps, st=None, n: int = 1, *, saveat,
     ``logq`` path cotangent and ``path["logq"]`` agree with it to rounding, every other output bit for bit.  Returns ``(xs (M, nvars, n), logq
     (M, n), path, grads (M, n_params)[, grad_z0 (M, n_in, n)], info)``.  Re-runs and failures as ``inference_path_vjp_many``
     (with ``generate_path_vjp``)."""
+    _no_bases("generate_path_vjp_many", bases)
     import torch
     who = "generate_path_vjp_many"
     box = {}
@@ -482,12 +494,13 @@ def _autograd_inference_many():
     return _InferencePathMany
 
 
-def differentiable_inference_path_many(icnf: ICNF, mode, xs, ps, st=None, *, saveat, eps=None):
+def differentiable_inference_path_many(icnf: ICNF, mode, xs, ps, st=None, *, saveat, eps=None, bases=None):
     """``inference_path_many`` as a differentiable function of ``ps`` (M, n_params) and, when it requires grad, ``xs``: returns
     ``(logpx, (E, n, A), path)`` attached to the autograd graph, ``path`` a dict with ``t``, ``z`` (M, K, n_in, B), ``dlogp``
     (M, K, B) and in TrainMode ``E``, ``n``.  The forward is the one-launch ``inference_path_many`` with the probes settled once;
     the backward is ONE ``inference_path_vjp_many`` with the same draws (``icnf.last_forward_info`` / ``last_backward_info``
     keep the two calls' ``info``).  As for ``differentiable_inference_path``, the backward launch solves again."""
+    _no_bases("differentiable_inference_path_many", bases)
     box = {}
 
     def saveat_check(M, B):
@@ -540,11 +553,12 @@ def _autograd_generate_many():
     return _GeneratePathMany
 
 
-def differentiable_generate_path_many(icnf: ICNF, mode, ps, st=None, n: int = 1, *, saveat, z0=None, eps=None):
+def differentiable_generate_path_many(icnf: ICNF, mode, ps, st=None, n: int = 1, *, saveat, z0=None, eps=None, bases=None):
     """``generate_path_many`` as a differentiable function of ``ps`` (M, n_params) and of a ``z0`` (M, n_in, n) that requires grad:
     returns ``(xs, logq, path)`` attached to the autograd graph, ``path`` a dict with ``t``, ``z`` (M, K, n_in, n), ``logq``
     (M, K, n) and in TrainMode ``E``, ``n`` (running integrals: no outputs of sampling, they take no cotangent).  The forward is
     the one-launch ``generate_path_many`` with the draws kept; the backward is ONE ``generate_path_vjp_many``."""
+    _no_bases("differentiable_generate_path_many", bases)
     box = {}
     t0, t1 = icnf.tspan
 

@@ -382,6 +382,11 @@ cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int B, float* 
  * tolerances for the next ensemble call (declared in cnfhip_ensemble_hetero.h, part of this header) ---- */
 #include "cnfhip_ensemble_hetero.h"
 
+/* ---- ensembles with a base per member: cnf_ensemble_set_bases / cnf_ensemble_clear_bases / cnf_ensemble_base_capacity /
+ * cnf_ensemble_base_sample / cnf_ensemble_base_logpdf_pullback / cnf_ensemble_base_sample_pullback -- a Gaussian base of its own
+ * for every member of the next ensemble call (declared in cnfhip_ensemble_base.h, part of this header) ---- */
+#include "cnfhip_ensemble_base.h"
+
 /* ---- flow paths: the solve's columns at caller-given times, from Tsit5's interpolant (declared in cnfhip_path.h, part of this
  * header) ---- */
 #include "cnfhip_path.h"
