@@ -78,6 +78,8 @@ from .ensemble_path import differentiable_generate_path_many, differentiable_inf
     inference_path_vjp_many
 from . import jvp
 from .jvp import generate_jvp, inference_jvp, jvp_steps, loss_jvp
+from . import ensemble_jvp
+from .ensemble_jvp import ensemble_jvp_steps, generate_jvp_many, inference_jvp_many, loss_jvp_many, loss_jvp_reduce
 from .mlj import (Adam, CondICNFModel, ICNFModel, Lion, Machine, fit, fit_, fitted_params, load_params, machine, save_params,
                   transform)
 

@@ -225,6 +225,15 @@ _JVP_SIGNATURES = {
 }
 JVP_EXPORTS = tuple(_JVP_SIGNATURES)
 JVP_MAX_R = 65535                  # directions of one call (include/cnfhip_jvp.h)
+# ensemble forward-mode (include/cnfhip_ensemble_jvp.h): likewise
+_ENSEMBLE_JVP_SIGNATURES = {
+    "cnf_inference_jvp_many": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts),
+                                         _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cnf_generate_jvp_many": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, _fp, _fp, C.c_int, C.POINTER(cnf_solve_opts),
+                                        _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cnf_ensemble_jvp_steps": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.c_int]),
+}
+ENSEMBLE_JVP_EXPORTS = tuple(_ENSEMBLE_JVP_SIGNATURES)
 
 _lib = None
 
@@ -265,7 +274,8 @@ def lib():
         for name, (res, args) in list(_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) + list(_BASEGRAD_SIGNATURES.items()) + \
                 list(_ENSEMBLE_SIGNATURES.items()) + list(_ENSEMBLE_EVAL_SIGNATURES.items()) + list(_ENSEMBLE_VJP_SIGNATURES.items()) + \
                 list(_ENSEMBLE_GENERATE_VJP_SIGNATURES.items()) + list(_PATH_SIGNATURES.items()) + list(_PATH_VJP_SIGNATURES.items()) + \
-                list(_ENSEMBLE_HETERO_SIGNATURES.items()) + list(_ENSEMBLE_BASE_SIGNATURES.items()) + list(_ENSEMBLE_PATH_SIGNATURES.items()) + list(_JVP_SIGNATURES.items()):
+                list(_ENSEMBLE_HETERO_SIGNATURES.items()) + list(_ENSEMBLE_BASE_SIGNATURES.items()) + list(_ENSEMBLE_PATH_SIGNATURES.items()) + list(_JVP_SIGNATURES.items()) + \
+                list(_ENSEMBLE_JVP_SIGNATURES.items()):
             f = getattr(l, name)
             f.restype, f.argtypes = res, args
         _lib = l

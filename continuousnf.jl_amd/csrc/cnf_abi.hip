@@ -216,6 +216,10 @@ struct cnf_ctx {
     std::vector<int> epath_nacc;  //   accepted steps per member (-1: the member was not CNF_OK)
     std::vector<float> epath_host;   // [M][epath_rows][2]: the pairs on the host, fetched by ONE strided copy when first asked for
     int epath_rows = -1;          //   pairs per member in epath_host (-1: not fetched yet)
+    // cnf_inference_jvp_many / cnf_generate_jvp_many (include/cnfhip_ensemble_jvp.h): the attempts are ens_trace's
+    int ejvp_M = 0;               // members of the last such call (0: none, or the trace has been written over since)
+    std::vector<float> ejvp_host; // [M][ejvp_rows][4]: the members' attempts on the host, fetched by ONE strided copy when first asked for
+    int ejvp_rows = -1;           //   rows per member in ejvp_host (-1: not fetched yet)
     std::vector<float> saveat_rep;   // one set of save times laid out M times, on its way to the device
     // cnf_inference_jvp / cnf_generate_jvp (include/cnfhip_jvp.h): SolveCall's `jvp` hook says what the solve does for such a call
     DevBuf<float> jvp_trace;      // [trace_cap][4]: (t, signed h, EEst, accepted) per attempt
@@ -2817,7 +2821,7 @@ static cnf_status ens_grow(cnf_handle h, const EnsCall& c, size_t cols_f, size_t
         return CNF_OK;
     HIPCHK(h, hipDeviceSynchronize());
     if (c.grad) h->ens_M = 0;
-    if (trace_f > h->ens_trace.capacity()) h->ensv_M = 0;
+    if (trace_f > h->ens_trace.capacity()) { h->ensv_M = 0; h->ejvp_M = 0; }
     RESERVE(h, h->ens_traj, traj_f);
     RESERVE(h, h->ens_hs, hs_f);
     RESERVE(h, h->ens_gpart, gpart_f);
@@ -3314,26 +3318,57 @@ extern "C" int cnf_ensemble_eval_capacity(cnf_handle h, int mode, int B) {
 
 // What the two calls share.  gen = false: src = xs [M][B][nvars], out0 = logpx [M][B], out1 = regs [M][3][B], times = the end
 // times; gen = true: src = z0 [M][B][n_in], out0 = xs_out [M][B][nvars], out1 = logq [M][B] or null, times = the start times.
+// jv (cnf_inference_jvp_many / cnf_generate_jvp_many, include/cnfhip_ensemble_jvp.h): the same call with every member's attempts
+// kept, and the ENS form of k_tangent_wave enqueued right behind the solve (sampling: behind its column kernel) on the same
+// stream, no host wait in between -- it reads the members' final states and attempts where the solve left them.  Sampling's out0
+// is then z_out [M][B][n_in], all rows of the final state.
+struct EnsJvp {
+    const float *d_ps, *d_x;       // device, [M][R][n_params] | [M][R][B][rows]; either may be null
+    int R;
+    float *d_out, *d_logq;         // device, [M][R][4][B] | sampling: [M][R][B][n_in] and [M][R][B]
+};
+static const int ENS_JVP_TRACE_DEFAULT = 1024, ENS_JVP_TRACE_MAX = 65536;
 static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float* params_dev, const float* src, const float* eps, int B,
                            const cnf_solve_opts* opts, const float* times_host, float* out0, float* out1, float* loss_out,
-                           int* status_out, cnf_solve_stats* stats_out, int trace_cap, void* stream, const EnsPath* ep = nullptr) {
+                           int* status_out, cnf_solve_stats* stats_out, int trace_cap, void* stream, const EnsPath* ep = nullptr,
+                           const EnsJvp* jv = nullptr) {
     const bool train = mode == CNF_MODE_TRAIN;
     if (h && ep) h->epath_M = 0;
+    if (h && jv) h->ejvp_M = 0;
     EnsCall c{false, gen, mode, M, B, trace_cap, opts, times_host, (hipStream_t)stream};
     c.path_many = ep != nullptr;
     ens_take_members(h, c);
     if (ep) { c.het_M = 0; c.counts.clear(); c.lams.clear(); c.tols.clear(); }      // (the path calls take no such arrays: taken and dropped)
     if (ep && c.base_M > 0) return fail(h, CNF_ERR_UNSUPPORTED, "the path calls take no bases (cnf_ensemble_set_bases): they were dropped");
-    cnf_status s = ens_check(h, c, !params_dev || !src || !opts || !out0 || (!gen && !out1) || !status_out || (train && !eps) || (ep && !ep->out),
+    if (jv) {                                              // (arguments before anything asks for a device; the taken arrays are gone either way)
+        if (!jv->d_ps && !jv->d_x) return fail(h, CNF_ERR_BAD_ARG, "both directions are null");
+        if (jv->R < 1 || jv->R > TG_MAX_R) return fail(h, CNF_ERR_BAD_ARG, "R must be within [1, 65535]");
+        if (trace_cap > ENS_JVP_TRACE_MAX) return fail(h, CNF_ERR_BAD_ARG, "trace_cap must be within [0, 65536]");
+    }
+    cnf_status s = ens_check(h, c, !params_dev || !src || !opts || !out0 || (!gen && !out1) || !status_out || (train && !eps) || (ep && !ep->out) ||
+                                       (jv && (!jv->d_out || (gen && (!jv->d_logq || !out1)))),
                              "B must be >= 1", ep ? "cnf_ensemble_path_capacity" : "cnf_ensemble_eval_capacity");
     if (s != CNF_OK) return s;
+    if (jv) {
+        if (c.base_M > 0) return fail(h, CNF_ERR_UNSUPPORTED, "the tangent calls take no bases (cnf_ensemble_set_bases): they were dropped");
+        if (!tangent_supported(h->nd_wave))
+            return fail(h, CNF_ERR_UNSUPPORTED, "tangents: two layers, tanh then tanh or identity, n_in <= 16, at most 64 hidden units (16 with the identity), no conditioning");
+        if (trace_cap == 0) trace_cap = opts->maxiters < ENS_JVP_TRACE_DEFAULT ? (int)opts->maxiters : ENS_JVP_TRACE_DEFAULT;
+        if (trace_cap < 1) trace_cap = 1;
+    }
     const NetDesc& nd = h->nd_wave;
-    const size_t Mz = (size_t)M, Bz = (size_t)B, n_in = (size_t)nd.n_in, nv = (size_t)nd.nvars, D = n_in + (train ? 3 : 1);
+    // (a tangent call's samples are all rows of the final state)
+    const size_t Mz = (size_t)M, Bz = (size_t)B, n_in = (size_t)nd.n_in, nv = jv && gen ? n_in : (size_t)nd.nvars, D = n_in + (train ? 3 : 1);
     // the column store: final columns (an inference) | u0 and the final columns (sampling)
     if ((s = ens_grow(h, c, Mz * Bz * (gen ? 2 * D : D), 0, 0, 0, Mz * 4 * (size_t)trace_cap)) != CNF_OK) return s;
-    if (trace_cap > 0) h->ensv_M = 0;                      // (the trace on record is about to be overwritten)
+    if (trace_cap > 0) { h->ensv_M = 0; h->ejvp_M = 0; }   // (the trace on record is about to be overwritten)
     if ((s = ens_begin(h, c)) != CNF_OK) return s;
     hipStream_t st = c.st;
+    if (jv) {                                              // NaN wherever the tangent launch writes nothing: a member its guard turns away, columns behind a count
+        const size_t MR = Mz * (size_t)jv->R;
+        HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)jv->d_out, 0x7fc00000, MR * (gen ? Bz * n_in : 4 * Bz), st));
+        if (gen) HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)jv->d_logq, 0x7fc00000, MR * Bz, st));
+    }
     Solve3Args& sv = c.sv;
     if (trace_cap > 0) { sv.trace = h->ens_trace; sv.trace_cap = trace_cap; }
     float* cols = h->ens_cols;
@@ -3368,10 +3403,27 @@ static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float*
         HIPCHK(h, hipGetLastError());
         ++launches;
     }
+    if (jv) {
+        TangentArgs ta;
+        ta.nd = nd; ta.P = params_dev; ta.dP = jv->d_ps; ta.n_params = (int)h->n_params; ta.eps = train ? eps : nullptr;
+        ta.B = B; ta.R = jv->R; ta.sampling = gen ? 1 : 0; ta.x = src; ta.dX = jv->d_x;
+        ta.st = reinterpret_cast<const StepState*>(h->ens_fin.data()); ta.trace = h->ens_trace; ta.trace_cap = trace_cap; ta.n_rows = -1;
+        ta.out = jv->d_out; ta.out_logq = jv->d_logq;
+        TangentEns te;
+        te.M = M; te.p_stride = h->n_params; te.x_stride = Bz * (gen ? n_in : (size_t)nd.nvars); te.counts = c.d_counts;
+        if ((s = tangent_launch_many(ta, te, train, st)) != CNF_OK) return fail(h, s, "the tangent launch failed to start");
+        ++launches;
+    }
     std::vector<int> att, nacc;
     if ((s = ens_base_flags_enqueue(h, c)) != CNF_OK) return s;
     if ((s = ens_finish(h, c, launches, !gen, loss_out, status_out, stats_out, att, true, ep ? &nacc : nullptr)) != CNF_OK) return s;
     ens_base_close(h, c, loss_out, status_out, 0, (int)D);
+    if (jv)                                                // more attempts than the member had rows for: its tangent launch wrote nothing
+        for (int m = 0; m < M; ++m)
+            if (status_out[m] == CNF_OK && att[(size_t)m] > trace_cap) {
+                status_out[m] = CNF_ERR_UNSUPPORTED; att[(size_t)m] = -1;
+                if (loss_out) loss_out[m] = NAN;
+            }
     bool any_bad = false;
     for (int m = 0; m < M; ++m)
         if (status_out[m] != CNF_OK) {                     // nothing of such a member is valid: NaN, whatever the kernel left
@@ -3386,6 +3438,7 @@ static cnf_status ens_eval(cnf_handle h, bool gen, int mode, int M, const float*
         h->epath_nacc.swap(nacc); h->epath_M = M; h->epath_cap = wp.steps_cap; h->epath_rows = -1;
     }
     if (trace_cap > 0) { h->ensv_att.swap(att); h->ensv_M = M; h->ensv_tcap = trace_cap; }
+    if (jv) { h->ejvp_M = M; h->ejvp_rows = -1; }
     return CNF_OK;
 }
 
@@ -3507,6 +3560,57 @@ extern "C" int cnf_ensemble_path_steps(cnf_handle h, int member, float* t_host, 
             if (t_host) t_host[i] = pairs[2 * (size_t)i];
             if (h_host) h_host[i] = pairs[2 * (size_t)i + 1];
         }
+    }
+    return n;
+}
+
+// ---------------------------------------------------------------------------------------
+// Ensemble forward-mode (include/cnfhip_ensemble_jvp.h): cnf_inference_many / cnf_generate_many with every member's attempts kept
+// and the ENS form of k_tangent_wave behind the solve (ens_eval's `jv`).
+// ---------------------------------------------------------------------------------------
+extern "C" cnf_status cnf_inference_jvp_many(cnf_handle h, int mode, int M, const float* params_dev, const float* xs, const float* eps,
+                                             int B, const float* d_ps, const float* d_xs, int R, const cnf_solve_opts* opts,
+                                             const float* t1_host, int trace_cap, float* logpx_dev, float* regs_dev, float* d_out_dev,
+                                             float* loss_out, int* status_out, cnf_solve_stats* stats_out, void* stream) {
+    const EnsJvp jv{d_ps, d_xs, R, d_out_dev, nullptr};
+    return ens_eval(h, false, mode, M, params_dev, xs, eps, B, opts, t1_host, logpx_dev, regs_dev, loss_out, status_out, stats_out,
+                    trace_cap, stream, nullptr, &jv);
+}
+extern "C" cnf_status cnf_generate_jvp_many(cnf_handle h, int mode, int M, const float* params_dev, const float* z0, const float* eps,
+                                            int B, const float* d_ps, const float* d_z0, int R, const cnf_solve_opts* opts,
+                                            const float* t0_host, int trace_cap, float* z_out, float* logq_out, float* d_z, float* d_logq,
+                                            int* status_out, cnf_solve_stats* stats_out, void* stream) {
+    const EnsJvp jv{d_ps, d_z0, R, d_z, d_logq};
+    return ens_eval(h, true, mode, M, params_dev, z0, eps, B, opts, t0_host, z_out, logq_out, nullptr, status_out, stats_out,
+                    trace_cap, stream, nullptr, &jv);
+}
+// (read from the device when first asked for, all members at once, as cnf_ensemble_path_steps reads its pairs)
+extern "C" int cnf_ensemble_jvp_steps(cnf_handle h, int member, float* t_host, float* h_host, int cap) {
+    if (!h || member < 0 || member >= h->ejvp_M || member >= h->ensv_M) return -1;
+    const int natt = h->ensv_att[(size_t)member];
+    if (natt < 0 || natt > h->ensv_tcap) return -1;
+    if (h->ejvp_rows < 0) {
+        int rows = 0;
+        for (int v : h->ensv_att) if (v > rows && v <= h->ensv_tcap) rows = v;
+        h->ejvp_host.resize((size_t)h->ejvp_M * 4 * (size_t)rows);
+        if (rows > 0 &&
+            (hipSetDevice(h->device) != hipSuccess ||
+             hipMemcpy2D(h->ejvp_host.data(), (size_t)4 * rows * sizeof(float), h->ens_trace.data(), (size_t)4 * h->ensv_tcap * sizeof(float),
+                         (size_t)4 * rows * sizeof(float), (size_t)h->ejvp_M, hipMemcpyDeviceToHost) != hipSuccess)) {
+            (void)hipGetLastError();
+            return -1;
+        }
+        h->ejvp_rows = rows;
+    }
+    const float* rows = h->ejvp_host.data() + (size_t)member * 4 * (size_t)h->ejvp_rows;
+    int n = 0;
+    for (int i = 0; i < natt; ++i) {
+        if (rows[4 * (size_t)i + 3] == 0.f) continue;
+        if (n < cap) {
+            if (t_host) t_host[n] = rows[4 * (size_t)i];
+            if (h_host) h_host[n] = rows[4 * (size_t)i + 1];
+        }
+        ++n;
     }
     return n;
 }

@@ -28,11 +28,38 @@ namespace {
 
 constexpr int TG_VJP = 0, TG_JVP = 1, TG_TEST = 2;
 
-template <int NI, int NH, int MODE, bool ID2>
-__global__ void __launch_bounds__(64) k_tangent_wave(const TangentArgs a, const WvTab tab) {
+// ENS (cnf_inference_jvp_many / cnf_generate_jvp_many, include/cnfhip_ensemble_jvp.h): M independent members in one launch, the
+// grid (tiles, R, M).  Everything a launch has ONE of, a member has its own copy of, at the strides of TangentEns: the prologue
+// moves the input pointers on to the member's copy -- scalar arithmetic on the kernel arguments and the block index alone -- and
+// the body behind it is the single model's; the trace rows are indexed by member in the step loop and the outputs move on at
+// the stores (see there).  The guard is the member's own: it reads the member's own StepState.  `counts`: a member's
+// own batch size; tiles at or beyond ceil(counts[m] / 16) leave at once, no column at or behind the count is read or written,
+// and the row strides of the [R][4][B] / [R][B][rows] arrays stay the launch's B.  The other instantiations take an empty third
+// argument and are the code they were.
+struct TangentNoEns {};
+template <bool ENS> struct TangentEnsArg { typedef TangentNoEns type; };
+template <> struct TangentEnsArg<true> { typedef TangentEns type; };
+
+template <int NI, int NH, int MODE, bool ID2, bool ENS = false>
+__global__ void __launch_bounds__(64) k_tangent_wave(const TangentArgs a_, const WvTab tab, const typename TangentEnsArg<ENS>::type en) {
     constexpr bool TRAIN = MODE != TG_TEST;
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
     const int wid = (int)blockIdx.x, dir = (int)blockIdx.y;
+    TangentArgs a = a_;
+    int nlive = a.B;                                       // the columns that exist (ENS with counts: the member's own)
+    if constexpr (ENS) {
+        const size_t mb = (size_t)blockIdx.z;
+        a.P += mb * en.p_stride;
+        if (a.dP) a.dP += mb * en.dp_stride;
+        if (a.eps) a.eps += mb * en.eps_stride;
+        a.x += mb * en.x_stride;
+        if (a.dX) a.dX += mb * en.dx_stride;
+        a.st += mb;
+        if (en.counts) {
+            nlive = en.counts[mb];
+            if (wid >= ((nlive + 15) >> 4)) return;
+        }
+    }
     // ---- the guard: the solve's own final state.  Nothing is written for a solve that gave up (n_partials < 0), did not reach
     // t1, went non-finite, or made more attempts than the trace holds; the count is read here, once. ----
     const int s_done = __builtin_amdgcn_readfirstlane(a.st->done), s_nonf = __builtin_amdgcn_readfirstlane(a.st->nonfinite);
@@ -84,7 +111,7 @@ __global__ void __launch_bounds__(64) k_tangent_wave(const TangentArgs a, const 
             }
     // biases and their tangents in the accumulator layout (rows 16 m + 4 q + j)
     const int smp = wid * 16 + c;
-    const bool live = smp < a.B;                           // a column at or behind B is neither read nor written
+    const bool live = smp < nlive;                         // a column at or behind B is neither read nor written
     const size_t sb = live ? (size_t)smp : 0;
     f32x4 b1v[NH], gb1[NH], b2v[NI], gb2[NI], rmask[NI];
 #pragma unroll
@@ -257,7 +284,9 @@ __global__ void __launch_bounds__(64) k_tangent_wave(const TangentArgs a, const 
 #pragma unroll
     for (int m = 0; m < NI; ++m) { zt[m] = zero4; tzt[m] = zero4; }
     for (int it = 0; it < natt; ++it) {
-        const float* tr = a.trace + 4 * (size_t)it;
+        // (ENS: the member's rows are indexed here -- a trace pointer moved on in the prologue and held across the loop costs
+        // the 64-hidden-unit VJP form a scratch frame)
+        const float* tr = a.trace + 4 * ((size_t)it + (ENS ? (size_t)blockIdx.z * (size_t)a.trace_cap : (size_t)0));
         const float hstep = uni(tr[1]);
         if (uni(tr[3]) == 0.f) continue;                   // a rejected attempt changed nothing (wave-uniform)
         float sacc = 0.f;
@@ -297,6 +326,11 @@ __global__ void __launch_bounds__(64) k_tangent_wave(const TangentArgs a, const 
 
     // ---- the tangent of the post-processing ----
     const float t1s = __shfl(tus, c + 16, 64), t2s = __shfl(tus, c + 32, 64);     // DE, Dn to lane group 0
+    if constexpr (ENS) {
+        // (the outputs move on to the member's copy here, not in the prologue: no more pointers held across the step loop)
+        a.out += (size_t)blockIdx.z * en.out_stride;
+        if (a.sampling) a.out_logq += (size_t)blockIdx.z * en.logq_stride;
+    }
     if (a.sampling) {
         // Dx = the rows of Dz;  Dlogq = -z0 . Dz0 + D(dlogp)
         if (live) {
@@ -330,21 +364,22 @@ __global__ void __launch_bounds__(64) k_tangent_wave(const TangentArgs a, const 
     }
 }
 
-typedef void (*tangent_fn)(const TangentArgs, const WvTab);
-template <int NH, bool ID2>
+typedef const void* tangent_fn;
+template <int NH, bool ID2, bool ENS>
 tangent_fn tangent_mode(int mode) {
-    if (mode == TG_VJP) return (tangent_fn)k_tangent_wave<1, NH, TG_VJP, ID2>;
-    if (mode == TG_JVP) return (tangent_fn)k_tangent_wave<1, NH, TG_JVP, ID2>;
-    return (tangent_fn)k_tangent_wave<1, NH, TG_TEST, ID2>;
+    if (mode == TG_VJP) return (tangent_fn)k_tangent_wave<1, NH, TG_VJP, ID2, ENS>;
+    if (mode == TG_JVP) return (tangent_fn)k_tangent_wave<1, NH, TG_JVP, ID2, ENS>;
+    return (tangent_fn)k_tangent_wave<1, NH, TG_TEST, ID2, ENS>;
 }
+template <bool ENS>
 tangent_fn tangent_kernel(const NetDesc& nd, bool train) {
     const int nh = (nd.dims[1] + 15) / 16, mode = !train ? TG_TEST : (nd.jvp ? TG_JVP : TG_VJP);
-    if (nd.acts[1] == 0) return nh == 1 ? tangent_mode<1, true>(mode) : nullptr;
+    if (nd.acts[1] == 0) return nh == 1 ? tangent_mode<1, true, ENS>(mode) : nullptr;
     switch (nh) {
-        case 1: return tangent_mode<1, false>(mode);
-        case 2: return tangent_mode<2, false>(mode);
-        case 3: return tangent_mode<3, false>(mode);
-        case 4: return tangent_mode<4, false>(mode);
+        case 1: return tangent_mode<1, false, ENS>(mode);
+        case 2: return tangent_mode<2, false, ENS>(mode);
+        case 3: return tangent_mode<3, false, ENS>(mode);
+        case 4: return tangent_mode<4, false, ENS>(mode);
     }
     return nullptr;
 }
@@ -357,17 +392,41 @@ bool tangent_supported(const NetDesc& nd) {
     return nd.dims[1] <= (nd.acts[1] == 0 ? 16 : 64);
 }
 
+static bool tangent_args_ok(const TangentArgs& a, bool train) {
+    return !(a.B < 1 || a.R < 1 || a.R > TG_MAX_R || !a.P || !a.x || !a.st || !a.trace || a.trace_cap < 1 || !a.out || (train && !a.eps) ||
+             (a.sampling && !a.out_logq) || (a.dP && a.n_params < 1));
+}
+
 cnf_status tangent_launch(const TangentArgs& a, bool train, hipStream_t s) {
     if (!tangent_supported(a.nd)) return CNF_ERR_UNSUPPORTED;
-    if (a.B < 1 || a.R < 1 || a.R > TG_MAX_R || !a.P || !a.x || !a.st || !a.trace || a.trace_cap < 1 || !a.out || (train && !a.eps) ||
-        (a.sampling && !a.out_logq) || (a.dP && a.n_params < 1))
-        return CNF_ERR_BAD_ARG;
-    tangent_fn fn = tangent_kernel(a.nd, train);
+    if (!tangent_args_ok(a, train)) return CNF_ERR_BAD_ARG;
+    tangent_fn fn = tangent_kernel<false>(a.nd, train);
     if (!fn) return CNF_ERR_UNSUPPORTED;
     TangentArgs ka = a;
     WvTab tab = kWvTab;
-    void* args[] = {&ka, &tab};
-    if (hipLaunchKernel((const void*)fn, dim3((a.B + 15) / 16, a.R), dim3(64), args, 0, s) != hipSuccess) {
+    TangentNoEns none;
+    void* args[] = {&ka, &tab, &none};
+    if (hipLaunchKernel(fn, dim3((a.B + 15) / 16, a.R), dim3(64), args, 0, s) != hipSuccess) {
+        (void)hipGetLastError();
+        return CNF_ERR_HIP;
+    }
+    return CNF_OK;
+}
+
+cnf_status tangent_launch_many(const TangentArgs& a, const TangentEns& en, bool train, hipStream_t s) {
+    if (!tangent_supported(a.nd)) return CNF_ERR_UNSUPPORTED;
+    // (the members read their own StepState's attempt count: no route files rows for M members from the host)
+    if (!tangent_args_ok(a, train) || en.M < 1 || en.M > TG_MAX_M || a.n_rows >= 0) return CNF_ERR_BAD_ARG;
+    tangent_fn fn = tangent_kernel<true>(a.nd, train);
+    if (!fn) return CNF_ERR_UNSUPPORTED;
+    TangentArgs ka = a;
+    WvTab tab = kWvTab;
+    TangentEns ke = en;
+    const size_t Bz = (size_t)a.B, Rz = (size_t)a.R, nz = (size_t)a.nd.n_in, xr = a.sampling ? nz : (size_t)a.nd.nvars;
+    ke.dp_stride = Rz * (size_t)a.n_params; ke.eps_stride = Bz * nz; ke.dx_stride = Rz * Bz * xr;
+    ke.out_stride = Rz * (a.sampling ? Bz * nz : 4 * Bz); ke.logq_stride = Rz * Bz;
+    void* args[] = {&ka, &tab, &ke};
+    if (hipLaunchKernel(fn, dim3((a.B + 15) / 16, a.R, en.M), dim3(64), args, 0, s) != hipSuccess) {
         (void)hipGetLastError();
         return CNF_ERR_HIP;
     }

@@ -404,6 +404,10 @@ cnf_status cnf_inference_pullback(cnf_handle h, const float* cot, int B, float* 
  * cnf_inference_jvp / cnf_generate_jvp / cnf_jvp_steps (declared in cnfhip_jvp.h, part of this header) ---- */
 #include "cnfhip_jvp.h"
 
+/* ---- ensemble forward-mode: the tangents of M members in one more launch -- cnf_inference_jvp_many / cnf_generate_jvp_many /
+ * cnf_ensemble_jvp_steps (declared in cnfhip_ensemble_jvp.h, part of this header) ---- */
+#include "cnfhip_ensemble_jvp.h"
+
 /* ---- device random numbers ------------------------------------------
  *
  * The library's own counter-based generator, the counterpart of the device RNG the reference draws eps and
