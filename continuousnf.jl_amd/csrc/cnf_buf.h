@@ -1,8 +1,8 @@
-// An owning, grow-only buffer for the handle's device and pinned allocations (cnf_abi.hip), and the one table of Runge-Kutta
+// An owning, grow-only buffer for the handle's device and pinned allocations (cnf_abi_int.h), and the one table of Runge-Kutta
 // coefficients the adjoint's host code reads.
 //
 // Plain C++ (no HIP): the allocator is a policy with static `int alloc(void**, size_t bytes)` (0 = success) and
-// `void free(void*)`; cnf_abi.hip instantiates it over hipMalloc / hipFree and hipHostMalloc / hipHostFree,
+// `void free(void*)`; cnf_abi_int.h instantiates it over hipMalloc / hipFree and hipHostMalloc / hipHostFree,
 // tests/support/buf_test.cpp over a counting fake.
 #pragma once
 #include <cstddef>

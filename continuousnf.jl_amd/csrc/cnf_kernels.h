@@ -1,5 +1,5 @@
 // Kernel argument blocks and launch wrappers shared between the kernel translation units
-// (cnf_generic.hip, cnf_mfma.hip) and the C ABI (cnf_abi.hip).
+// (cnf_generic.hip, cnf_mfma.hip) and the C ABI (cnf_abi*.hip).
 #pragma once
 #include "cnf_dev.h"
 

@@ -110,7 +110,7 @@ struct WavePathArgs {
 // `path` with `grad` and `ens`: the PATH form of the per-sample-cotangent gradient -- ens->cw / ens->cot_z / ens->cot_logq
 // may then all be null (no terminal cotangent).  `path` with `ens` alone: the plain ensemble form with the members' paths.
 // LAYOUT CONTRACT of `path` with `ens`: path->times holds ens->M x path->K floats, member m's set at [m K, m K + K) -- also when
-// all members share one set (the caller lays it out M times: cnf_abi.hip's ens_path_args is the one caller and does) --,
+// all members share one set (the caller lays it out M times: cnf_abi_ens.hip's ens_path_args is the one caller and does) --,
 // path->out / path->cot hold M slabs [K][B][D] and path->steps M x steps_cap pairs.  The launch cannot see the sizes of these
 // device arrays: a [K] array with M > 1 would be read past its end.
 cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_params, const float* cond, int cbs, StepState* st_out,

@@ -3,6 +3,7 @@ calls here (this suite runs without a GPU)."""
 import ctypes
 import os
 import re
+import subprocess
 
 import pytest
 
@@ -30,6 +31,23 @@ def test_every_declared_symbol_is_exported_and_bound():
     for n in names:
         assert hasattr(l, n), f"{n} declared in cnfhip.h but not exported"
     assert set(names) == set(_lib.EXPORTS), set(names) ^ set(_lib.EXPORTS)
+
+
+def _dynamic_symbols():
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    return [line.split()[-1] for line in out.splitlines() if line.strip()]
+
+
+def test_exported_cnf_symbols_are_the_recorded_set():
+    """The C ABI is one set of names however csrc/ divides the source: the dynamic `cnf_*` symbols of the built library equal
+    tests/golden/abi/exports.txt (recorded with `nm -D --defined-only`, names only, from the build before the ABI source was
+    split into csrc/cnf_abi*.hip), and nothing of the files' private namespace `cnfabi` (csrc/cnf_abi_int.h) is exported."""
+    recorded = open(os.path.join(ROOT, "tests", "golden", "abi", "exports.txt")).read().split()
+    assert len(recorded) == len(set(recorded)) and len(recorded) >= 100
+    names = _dynamic_symbols()
+    built = {n for n in names if n.startswith("cnf_")}
+    assert built == set(recorded), sorted(built ^ set(recorded))
+    assert [n for n in names if "cnfabi" in n] == []
 
 
 def test_abi_version_and_status_strings():
