@@ -221,10 +221,11 @@ __device__ __forceinline__ float cnf_tanh(float a) {
 // tanh(a) = 1 - 2/(exp(2a) + 1): v_mul, v_exp, v_add, v_rcp, v_fma.  Absolute error
 // <= 2e-7 (one rounding of values near 1), which is what every other fp32 activation value
 // carries; measured against the parity metric it is indistinguishable from libm's tanh.
-__device__ __forceinline__ float tanh_fast(float a) {
-    const float t = __builtin_amdgcn_exp2f(a * 2.8853900817779268f);
-    return fmaf(-2.0f, __builtin_amdgcn_rcpf(t + 1.0f), 1.0f);
-}
+// (its three dependent steps, one transcendental in each of the first two: callers that place them by hand -- s3b_wide)
+__device__ __forceinline__ float tanh_fast_exp(float a) { return __builtin_amdgcn_exp2f(a * 2.8853900817779268f); }
+__device__ __forceinline__ float tanh_fast_rcp(float t) { return __builtin_amdgcn_rcpf(t + 1.0f); }
+__device__ __forceinline__ float tanh_fast_out(float r) { return fmaf(-2.0f, r, 1.0f); }
+__device__ __forceinline__ float tanh_fast(float a) { return tanh_fast_out(tanh_fast_rcp(tanh_fast_exp(a))); }
 
 // tanh for the gradient path: the exp2 / rcp form loses RELATIVE accuracy near 0 (1 - 2/(t + 1) with t ~ 1: an absolute
 // 6e-8), which a long span turns into 1e-4 of the gradient's scale on the 2-6-2 network, and which s'' = -2 h s' carries straight

@@ -1707,9 +1707,9 @@ __global__ void __launch_bounds__(512, 2) k_step3b(MfmaArgs a, const char* __res
 #ifdef S3_STAMPS
     S3T(22);
     if (blockIdx.x == 7 && lane == 0 && (wave == 0 || wave == 5))
-        printf("k_step3b wave %d total %llu | issue %llu landed %llu bar %llu ctrl %llu bar %llu rest %llu tileprep %llu tail %llu | F1 %llu+%llu F2 %llu+%llu F3 %llu+%llu B3 %llu+%llu B2 %llu+%llu B1 %llu+%llu | narrow products, barrier exit to last MFMA issued: F3 %llu B1 %llu\n",
-               wave, s3last - s3start, s3acc[23], s3acc[24], s3acc[25], s3acc[26], s3acc[27], s3acc[20], s3acc[21], s3acc[22], s3acc[0], s3acc[1], s3acc[2], s3acc[3], s3acc[12] + s3acc[4], s3acc[5],
-               s3acc[6], s3acc[7], s3acc[8], s3acc[9], s3acc[13] + s3acc[10], s3acc[11], s3acc[12], s3acc[13]);
+        printf("k_step3b wave %d total %llu | issue %llu landed %llu bar %llu ctrl %llu bar %llu rest %llu tileprep %llu tail %llu | F1 %llu+%llu F2 %llu+%llu F3 %llu+%llu B3 %llu+%llu B2 %llu+%llu B1 %llu+%llu | narrow products, barrier exit to last MFMA issued: F3 %llu B1 %llu | wide products, barrier exit to last MFMA of half a, from there to the last of half b: F2 %llu %llu B2 %llu %llu\n",
+               wave, s3last - s3start, s3acc[23], s3acc[24], s3acc[25], s3acc[26], s3acc[27], s3acc[20], s3acc[21], s3acc[22], s3acc[0], s3acc[1], s3acc[14] + s3acc[15] + s3acc[2], s3acc[3], s3acc[12] + s3acc[4], s3acc[5],
+               s3acc[6], s3acc[7], s3acc[16] + s3acc[17] + s3acc[8], s3acc[9], s3acc[13] + s3acc[10], s3acc[11], s3acc[12], s3acc[13], s3acc[14], s3acc[15], s3acc[16], s3acc[17]);
 #endif
 }
 

@@ -176,12 +176,130 @@ __device__ __forceinline__ void s3b_narrow(f32x4& z0, f32x4& z1, const S3bOp& a0
     }
 }
 
+// A wide product (K = 128, four k-blocks) of a wave that owns one 16-row tile of BOTH sample halves: the resident A
+// fragments `w` x the rows at `B0` (half a, into acc[0]) and at `B1` (half b, into acc[1]) of a split image.  The halves run
+// one after the other -- a single accumulation chain of this MFMA issues at full rate -- so that half a's epilogue (bias,
+// activation, the three-piece split, the stores) has half b's 24 MFMAs to hide under: an MFMA holds vector issue for half
+// of its 16 cycles, and interleaved term-major both accumulators finish on the last two MFMAs of the interval, with the
+// matrix pipe empty under the whole epilogue.  Each accumulator takes the same MFMAs on the same operands in the same
+// order as in s3b_mm<2> per k-block: k-blocks ascending, terms 0 to 5.
+// Operands are requested one k-block ahead across both halves, as in s3b_narrow, and nothing is drained inside.  The
+// caller places its own instructions through `at`, called with S3C<i>:
+//   i = -2            in front of the last k-block of half a, behind its operand requests (reads that half a's epilogue needs)
+//   i = -1            half a's last MFMA is issued
+//   i = 0 .. 23       behind MFMA i of half b: a group of half a's epilogue, at most about three instructions' worth of
+//                     issue (a transcendental counts as two).  A group stays where it is put only if the caller pins what
+//                     it computes (s3_hold): see the comment in s3b_narrow on what the scheduling fences do not hold.
+//   i = 24            half b's last MFMA is issued
+// Half b's epilogue is the caller's, behind the call.
+template <int I> struct S3C { static constexpr int value = I; };
+__device__ __forceinline__ void s3_hold(float& x) { asm volatile("" : "+v"(x)); }
+__device__ __forceinline__ void s3_hold(unsigned& x) { asm volatile("" : "+v"(x)); }
+template <int KB, class At>
+__device__ __forceinline__ void s3b_wide_b(f32x4& acc, const S3bOp& a, const S3bOp& b, At& at) {
+    acc = s3b_term<0>(a, b, acc); asm volatile("" : "+v"(acc)); at(S3C<6 * KB + 0>{}); S3_SB();
+    acc = s3b_term<1>(a, b, acc); asm volatile("" : "+v"(acc)); at(S3C<6 * KB + 1>{}); S3_SB();
+    acc = s3b_term<2>(a, b, acc); asm volatile("" : "+v"(acc)); at(S3C<6 * KB + 2>{}); S3_SB();
+    acc = s3b_term<3>(a, b, acc); asm volatile("" : "+v"(acc)); at(S3C<6 * KB + 3>{}); S3_SB();
+    acc = s3b_term<4>(a, b, acc); asm volatile("" : "+v"(acc)); at(S3C<6 * KB + 4>{}); S3_SB();
+    acc = s3b_term<5>(a, b, acc); asm volatile("" : "+v"(acc)); at(S3C<6 * KB + 5>{}); S3_SB();
+}
+template <class At>
+__device__ __forceinline__ void s3b_wide(f32x4 (&acc)[2], const S3bOp (&w)[4], const char* B0, const char* B1, int rd,
+                                         int piece_bytes, At&& at) {
+    S3bOp bv = s3b_load(B0 + rd, piece_bytes), bn;
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb) {                                   // half a
+        bn = s3b_load((kb < 3 ? B0 : B1) + (rd ^ (64 * ((kb + 1) & 3))), piece_bytes);
+        if (kb == 3) at(S3C<-2>{});
+        S3_SB();
+        acc[0] = s3b_term<0>(w[kb], bv, acc[0]); acc[0] = s3b_term<1>(w[kb], bv, acc[0]); acc[0] = s3b_term<2>(w[kb], bv, acc[0]);
+        acc[0] = s3b_term<3>(w[kb], bv, acc[0]); acc[0] = s3b_term<4>(w[kb], bv, acc[0]); acc[0] = s3b_term<5>(w[kb], bv, acc[0]);
+        asm volatile("" : "+v"(acc[0]));                               // pinned to its k-block (s3b_narrow)
+        S3_SB();
+        bv = bn;
+    }
+    at(S3C<-1>{});
+    S3_SB();
+    // half b: every MFMA is a group of its own, with the caller's instructions behind it
+    bn = s3b_load(B1 + (rd ^ 64), piece_bytes); S3_SB(); s3b_wide_b<0>(acc[1], w[0], bv, at); bv = bn;
+    bn = s3b_load(B1 + (rd ^ 128), piece_bytes); S3_SB(); s3b_wide_b<1>(acc[1], w[1], bv, at); bv = bn;
+    bn = s3b_load(B1 + (rd ^ 192), piece_bytes); S3_SB(); s3b_wide_b<2>(acc[1], w[2], bv, at); bv = bn;
+    s3b_wide_b<3>(acc[1], w[3], bv, at);
+    at(S3C<24>{});
+}
+// tanh_fast's three dependent steps, for epilogues placed by hand (s3_tanh4 is their composition per value)
+__device__ __forceinline__ float s3_tanh_exp(float a) {
+#ifdef S3_ABL_NOEPI
+    return a * 0.25f;
+#endif
+    return tanh_fast_exp(a);
+}
+__device__ __forceinline__ float s3_tanh_rcp(float t) {
+#ifdef S3_ABL_NOEPI
+    return t;
+#endif
+    return tanh_fast_rcp(t);
+}
+__device__ __forceinline__ float s3_tanh_out(float r) {
+#ifdef S3_ABL_NOEPI
+    return r;
+#endif
+    return tanh_fast_out(r);
+}
+// s3b_store4 in groups to place by hand: `v` holds the four values and ends as scratch; group G (0 .. 11) is
+//   pair P = G / 6 (values 2P, 2P + 1), step G % 6:  0 leading piece | 1, 2 what each value keeps | 3 middle piece, what
+//   value 2P keeps | 4 what value 2P + 1 keeps | 5 last piece
+// (issue weights 1, 2, 2, 3, 2, 1: a remainder is a widening and a subtraction), then s3b_store4s_put<0 .. 2> stores piece h, m, l.
+struct S3bStore4s { u32x2_ h, m, l; };
+template <int G>
+__device__ __forceinline__ void s3b_store4s_step(S3bStore4s& st, float (&v)[4]) {
+    constexpr int P = G / 6, S = G % 6;
+    unsigned h = st.h[P], m = st.m[P], l = st.l[P];
+    float v0 = v[2 * P], v1 = v[2 * P + 1];
+    if (S == 0) { h = s3b_split2_lead(v0, v1); s3_hold(h); }
+    if (S == 1) { v0 = s3b_split2_rest<0>(v0, h); s3_hold(v0); }
+    if (S == 2) { v1 = s3b_split2_rest<1>(v1, h); s3_hold(v1); }
+    if (S == 3) { m = s3b_split2_lead(v0, v1); v0 = s3b_split2_rest<0>(v0, m); s3_hold(m); s3_hold(v0); }
+    if (S == 4) { v1 = s3b_split2_rest<1>(v1, m); s3_hold(v1); }
+    if (S == 5) { l = s3b_split2_last(v0, v1); s3_hold(l); }
+    st.h[P] = h; st.m[P] = m; st.l[P] = l; v[2 * P] = v0; v[2 * P + 1] = v1;
+}
+// Groups 1, 2 (7, 8) where value J is a product a * b formed for this store: what it keeps of the UNROUNDED product.  That is
+// what s3b_store4(a * b) computes -- under -ffp-contract=fast the compiler folds the product into the first subtraction of the
+// split -- and the bits of every build so far; a group placed by hand has to say so.
+template <int J>
+__device__ __forceinline__ void s3b_store4s_rest_of_product(const S3bStore4s& st, float (&v)[4], float a, float b) {
+#ifdef S3_ABL_NOEPI
+    v[J] = 0.f; return;
+#endif
+    const unsigned p = st.h[J / 2];
+    v[J] = fmaf(a, b, -__uint_as_float(J & 1 ? p & 0xFFFF0000u : p << 16));
+    s3_hold(v[J]);
+}
+template <int PIECE>
+__device__ __forceinline__ void s3b_store4s_put(const S3bStore4s& st, char* img, int piece_bytes) {
+#ifdef S3_ABL_NOSTORE
+    { asm volatile("" :: "v"(st.h), "v"((unsigned)(size_t)img)); return; }
+#endif
+    *(u32x2_*)(img + PIECE * piece_bytes) = PIECE == 0 ? st.h : (PIECE == 1 ? st.m : st.l);
+}
+
 // 4 rows of one sample back from the three images: the pieces sum to the fp32 value exactly
-__device__ __forceinline__ f32x4 s3b_load4(const char* img, int piece_bytes) {
-    const bf16x4 h = *(const bf16x4*)img, m = *(const bf16x4*)(img + piece_bytes), l = *(const bf16x4*)(img + 2 * piece_bytes);
+// (request, then per value the low sum and the value: three steps a caller can place by hand)
+struct S3bPieces4 { bf16x4 h, m, l; };
+__device__ __forceinline__ S3bPieces4 s3b_load4_request(const char* img, int piece_bytes) {
+    return S3bPieces4{*(const bf16x4*)img, *(const bf16x4*)(img + piece_bytes), *(const bf16x4*)(img + 2 * piece_bytes)};
+}
+__device__ __forceinline__ float s3b_load4_low(const S3bPieces4& p, int j) { return (float)p.m[j] + (float)p.l[j]; }
+__device__ __forceinline__ float s3b_load4_value(const S3bPieces4& p, int j, float low) { return (float)p.h[j] + low; }
+__device__ __forceinline__ f32x4 s3b_load4_values(const S3bPieces4& p) {
     f32x4 v;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (float)h[j] + ((float)m[j] + (float)l[j]);
+    for (int j = 0; j < 4; ++j) v[j] = s3b_load4_value(p, j, s3b_load4_low(p, j));
     return v;
+}
+__device__ __forceinline__ f32x4 s3b_load4(const char* img, int piece_bytes) {
+    return s3b_load4_values(s3b_load4_request(img, piece_bytes));
 }
 

@@ -33,19 +33,57 @@
                 // scalar rows of the PREVIOUS evaluation from its RED partials (complete since the last barrier of it)
                 if (stg > 1 && sown) sc_set(stg, read_scalars());              // slot j holds k_j
                 f32x4 acc[2] = {zero4, zero4};
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb) {
-                    S3bOp b[2];
-                    b[0] = s3b_load(ldsb + s3v::H1G + (wb_rd ^ (64 * kb)), s3v::WP);
-                    b[1] = s3b_load(ldsb + s3v::H1G + HBW + (wb_rd ^ (64 * kb)), s3v::WP);
-                    S3_SB();
-                    s3b_mm<2>(acc, wF2[kb], b);
-                    S3_SB();
-                }
-                const f32x4 h2a = s3_tanh4(acc[0] + bv2), h2b = s3_tanh4(acc[1] + bv2);
-                d2a = s3_dtanh4(h2a); d2b = s3_dtanh4(h2b);
-                s3b_store4(ldsb + s3v::H2G + wb_wr, s3v::WP, h2a);
-                s3b_store4(ldsb + s3v::H2G + wb_wr + HBW, s3v::WP, h2b);
+                // half a's epilogue, h2a = tanh(acc[0] + b2) -> sigma'_2, the split, the stores, in groups behind half b's
+                // MFMAs (s3b_wide): per value j  A add the bias | E, R, O the three steps of tanh | D sigma'; then the steps
+                // of the split of either pair.  Issue weight of the groups: 2 or 3, 61 over 23 groups; none behind half b's first MFMA,
+                // where a read of acc[0] would still wait for half a's last one.
+                float x[4] = {0.f, 0.f, 0.f, 0.f};
+                float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f;
+                S3bStore4s sa{};
+                // (both halves' stores go through this ONE pointer value, h2w and h2w + HBW: the image base lies above the 16-bit
+                // offset of ds_write_b64, and with half b's address written out on its own the compiler keeps an address register
+                // per piece live across the stage loop -- profiles/wide_epilogue_kernel_resources.md)
+                char* const h2w = ldsb + s3v::H2G + wb_wr;
+#define S3W_A(j) { x[j] = acc[0][j] + bv2[j]; s3_hold(x[j]); }
+#define S3W_E(j) { x[j] = s3_tanh_exp(x[j]); s3_hold(x[j]); }
+#define S3W_R(j) { x[j] = s3_tanh_rcp(x[j]); s3_hold(x[j]); }
+#define S3W_OD(j, d) { x[j] = s3_tanh_out(x[j]); d = fmaf(-x[j], x[j], 1.f); s3_hold(x[j]); s3_hold(d); }
+                s3b_wide(acc, wF2, ldsb + s3v::H1G, ldsb + s3v::H1G + HBW, wb_rd, s3v::WP, [&](auto I) {
+                    constexpr int i = decltype(I)::value;
+                    if constexpr (i == -1) S3T(14);
+                    if constexpr (i == 1) { S3W_A(0); S3W_A(1); }
+                    if constexpr (i == 2) S3W_E(0);
+                    if constexpr (i == 3) S3W_E(1);
+                    if constexpr (i == 4) S3W_R(0);
+                    if constexpr (i == 5) S3W_R(1);
+                    if constexpr (i == 6) S3W_OD(0, d0);
+                    if constexpr (i == 7) { S3W_OD(1, d1); s3b_store4s_step<0>(sa, x); }
+                    if constexpr (i == 8) { S3W_A(2); S3W_A(3); }
+                    if constexpr (i == 9) S3W_E(2);
+                    if constexpr (i == 10) s3b_store4s_step<1>(sa, x);
+                    if constexpr (i == 11) S3W_E(3);
+                    if constexpr (i == 12) s3b_store4s_step<2>(sa, x);
+                    if constexpr (i == 13) S3W_R(2);
+                    if constexpr (i == 14) s3b_store4s_step<3>(sa, x);
+                    if constexpr (i == 15) S3W_R(3);
+                    if constexpr (i == 16) { s3b_store4s_step<4>(sa, x); s3b_store4s_step<5>(sa, x); }
+                    if constexpr (i == 17) { S3W_OD(2, d2); x[3] = s3_tanh_out(x[3]); s3_hold(x[3]); }
+                    if constexpr (i == 18) { d3 = fmaf(-x[3], x[3], 1.f); s3_hold(d3); s3b_store4s_step<6>(sa, x); }
+                    if constexpr (i == 19) { s3b_store4s_step<7>(sa, x); s3b_store4s_put<0>(sa, h2w, s3v::WP); }
+                    if constexpr (i == 20) s3b_store4s_step<8>(sa, x);
+                    if constexpr (i == 21) s3b_store4s_step<9>(sa, x);
+                    if constexpr (i == 22) { s3b_store4s_step<10>(sa, x); s3b_store4s_put<1>(sa, h2w, s3v::WP); }
+                    if constexpr (i == 23) { s3b_store4s_step<11>(sa, x); s3b_store4s_put<2>(sa, h2w, s3v::WP); }
+                    if constexpr (i == 24) S3T(15);
+                });
+#undef S3W_A
+#undef S3W_E
+#undef S3W_R
+#undef S3W_OD
+                d2a = f32x4{d0, d1, d2, d3};
+                const f32x4 h2b = s3_tanh4(acc[1] + bv2);
+                d2b = s3_dtanh4(h2b);
+                s3b_store4(h2w + HBW, s3v::WP, h2b);
                 // (W3 rows, k-block 0, for interval 2: nothing the barrier publishes; it lands while the stores drain)
                 S3_SB();
                 if (zown) nA0 = s3b_load(nrA + wb_rd, s3v::WP);
@@ -101,19 +139,50 @@
             S3T(7);                                                          // g2 visible
             // ---- interval 4: reverse of the second layer, tile `wave` of W2^T; g1 over h1 in place
             {
-                const f32x4 h1a = s3b_load4(ldsb + s3v::H1G + wb_wr, s3v::WP), h1b = s3b_load4(ldsb + s3v::H1G + wb_wr + HBW, s3v::WP);
                 f32x4 acc[2] = {zero4, zero4};
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb) {
-                    S3bOp b[2];
-                    b[0] = s3b_load(ldsb + s3v::H2G + (wb_rd ^ (64 * kb)), s3v::WP);
-                    b[1] = s3b_load(ldsb + s3v::H2G + HBW + (wb_rd ^ (64 * kb)), s3v::WP);
-                    S3_SB();
-                    s3b_mm<2>(acc, wB2[kb], b);
-                    S3_SB();
-                }
-                s3b_store4(ldsb + s3v::H1G + wb_wr, s3v::WP, acc[0] * s3_dtanh4(h1a));
-                s3b_store4(ldsb + s3v::H1G + wb_wr + HBW, s3v::WP, acc[1] * s3_dtanh4(h1b));
+                // half a's epilogue, g1a = acc[0] .* sigma'_1(h1a) -> the split, the stores, in groups behind half b's MFMAs
+                // (s3b_wide): per value j  L, V h1a back from its three pieces | D sigma'_1 | G the product; then the steps of
+                // the split of either pair, P for the first remainder of a product (s3b_store4s_rest_of_product).  h1a is requested in front of half a's last k-block, h1b -- needed only behind
+                // the call -- once half a's stores are out.  Issue weight of the groups: 2 or 3, 56 over 20 groups.
+                float x[4] = {0.f, 0.f, 0.f, 0.f}, dd[4] = {0.f, 0.f, 0.f, 0.f};
+                S3bStore4s sa{};
+                S3bPieces4 pa, pb;
+                char* const g1w = ldsb + s3v::H1G + wb_wr;
+#define S3W_L(j) { x[j] = s3b_load4_low(pa, j); s3_hold(x[j]); }
+#define S3W_VD(j) { dd[j] = s3b_load4_value(pa, j, x[j]); dd[j] = fmaf(-dd[j], dd[j], 1.f); s3_hold(dd[j]); }
+#define S3W_G(j) { x[j] = acc[0][j] * dd[j]; s3_hold(x[j]); }
+#define S3W_P(j) s3b_store4s_rest_of_product<j>(sa, x, acc[0][j], dd[j])
+                s3b_wide(acc, wB2, ldsb + s3v::H2G, ldsb + s3v::H2G + HBW, wb_rd, s3v::WP, [&](auto I) {
+                    constexpr int i = decltype(I)::value;
+                    if constexpr (i == -2) pa = s3b_load4_request(g1w, s3v::WP);
+                    if constexpr (i == -1) S3T(16);
+                    if constexpr (i == 0) S3W_L(0);
+                    if constexpr (i == 1) S3W_VD(0);
+                    if constexpr (i == 2) S3W_L(1);
+                    if constexpr (i == 3) S3W_VD(1);
+                    if constexpr (i == 4) { S3W_G(0); S3W_G(1); s3b_store4s_step<0>(sa, x); }
+                    if constexpr (i == 5) S3W_L(2);
+                    if constexpr (i == 6) S3W_P(0);
+                    if constexpr (i == 7) S3W_VD(2);
+                    if constexpr (i == 8) S3W_P(1);
+                    if constexpr (i == 9) S3W_L(3);
+                    if constexpr (i == 10) s3b_store4s_step<3>(sa, x);
+                    if constexpr (i == 11) S3W_VD(3);
+                    if constexpr (i == 12) { s3b_store4s_step<4>(sa, x); s3b_store4s_step<5>(sa, x); }
+                    if constexpr (i == 13) { S3W_G(2); S3W_G(3); s3b_store4s_step<6>(sa, x); }
+                    if constexpr (i == 14) { S3W_P(2); s3b_store4s_put<0>(sa, g1w, s3v::WP); }
+                    if constexpr (i == 15) S3W_P(3);
+                    if constexpr (i == 16) s3b_store4s_step<9>(sa, x);
+                    if constexpr (i == 17) { s3b_store4s_step<10>(sa, x); s3b_store4s_put<1>(sa, g1w, s3v::WP); }
+                    if constexpr (i == 18) { s3b_store4s_step<11>(sa, x); s3b_store4s_put<2>(sa, g1w, s3v::WP); }
+                    if constexpr (i == 19) pb = s3b_load4_request(g1w + HBW, s3v::WP);
+                    if constexpr (i == 24) S3T(17);
+                });
+#undef S3W_L
+#undef S3W_VD
+#undef S3W_G
+#undef S3W_P
+                s3b_store4(g1w + HBW, s3v::WP, acc[1] * s3_dtanh4(s3b_load4_values(pb)));
                 // (W1^T rows, k-block 0, for interval 5: as W3's in front of interval 2)
                 S3_SB();
                 if (!zown) nA0 = s3b_load(nrA + wb_rd, s3v::WP);
