@@ -3,6 +3,7 @@
 // families built on top of these have files of their own: cnf_abi_ens.hip (ensembles), cnf_abi_jvp.hip (forward mode); what
 // they use of this file is declared in cnf_abi_int.h.
 #include "cnf_abi_int.h"
+#include "cnf_switch.h"
 using namespace cnfabi;
 
 #define CNF_ABI_VERSION 1
@@ -760,10 +761,8 @@ static cnf_status finish_one_launch(cnf_handle h, unsigned seq, int slot, hipStr
 
 // the bounds of a wait inside a one-launch solve of this handle (cnf_set_solve_wait; CNF_SOLVE_WAIT_US, CNF_SOLVE_POLL_LIMIT)
 void cnfabi::set_wait_bounds(cnf_handle h, Solve3Args& sv) {
-    static const int spin_limit = [] { const char* e = getenv("CNF_SOLVE_POLL_LIMIT"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 0x7fffffff; }();
-    static const int wait_us = [] { const char* e = getenv("CNF_SOLVE_WAIT_US"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 2000; }();
-    sv.spin_limit = h->poll_limit > 0 ? h->poll_limit : spin_limit;
-    const int wus = h->wait_us > 0 ? h->wait_us : wait_us;
+    sv.spin_limit = h->poll_limit > 0 ? h->poll_limit : cnf_switch<SW_SOLVE_POLL_LIMIT>();
+    const int wus = h->wait_us > 0 ? h->wait_us : cnf_switch<SW_SOLVE_WAIT_US>();
     sv.wait_ticks = wus < 20000000 ? 100u * (unsigned)wus : 2000000000u;   // (per tile: the launcher scales it)
 }
 // what every solve asks of its options
@@ -1865,7 +1864,7 @@ static cnf_status train_backward(cnf_handle h, const float* eps, int B, int kern
     // capacity is in samples of cap_B; with B <= cap_B at least grad_fsteps steps fit
     // (CNF_GRAD_FSTEPS=n: contract after every n steps instead -- measurements: fewer steps per contraction keep the factor rows
     // in the infinity cache, more amortise its launch)
-    static const int fsteps_env = [] { const char* e = getenv("CNF_GRAD_FSTEPS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 0; }();
+    const int fsteps_env = cnf_switch<SW_GRAD_FSTEPS>();
     int fsteps = (int)std::min<size_t>(32, (size_t)h->grad_fsteps * h->grad_cap_B / (size_t)B);
     if (fsteps_env > 0 && fsteps_env < fsteps) fsteps = fsteps_env;
     int ksplit = 1, filed = 0;

@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "cnf_adj3b.h"
+#include "cnf_switch.h"
 #include "cnf_step3_dev.h"
 #include "cnf_mfma_dev.h"
 
@@ -169,12 +170,11 @@ k_adj3b(NetDesc nd, GradLayout gl, const char* __restrict__ imgb, Adj3bSteps M) 
         else if (cnt > 0) st4(arr + (size_t)(b0 + r) * row_len + off + k, v, cnt);
     };
     // One 32-row product (K = 128) of this wave: rows 16 t .. of W3 / W1^T against the wave's sample half, both from split images.
-    // -DA3B_NARROW_PREFETCH (A/B, round 5): the operands of k-block kb + 1 requested before the MFMAs of k-block kb issue (double
-    // buffer) and two PAIRS of accumulators in turn.  Measured: 2.52 against 2.20 ms per gradient at B = 32, 5.4 against 4.2 at
+    // (Measured in round 5 and not kept: the operands of k-block kb + 1 requested before the MFMAs of k-block kb issue (double
+    // buffer) and two PAIRS of accumulators in turn -- 2.52 against 2.20 ms per gradient at B = 32, 5.4 against 4.2 at
     // 8192 -- the extra live registers push three more weight pieces into scratch (320 against 168 bytes per lane), and every
-    // reload waits behind the stores in front of it.  At 256 registers this kernel pays for each one.
+    // reload waits behind the stores in front of it.  At 256 registers this kernel pays for each one.)
     auto narrow = [&]() __attribute__((always_inline)) -> f32x4 {
-#ifndef A3B_NARROW_PREFETCH
         f32x4 z0 = zero4, z1 = zero4;
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) {
@@ -186,23 +186,6 @@ k_adj3b(NetDesc nd, GradLayout gl, const char* __restrict__ imgb, Adj3bSteps M) 
             S3_SB();
         }
         return z0 + z1;
-#else
-        f32x4 z[4] = {zero4, zero4, zero4, zero4};
-        S3bOp av = s3b_load(nrA + wb_rd, a3b::WP), bvv = s3b_load(nrB + wb_rd, a3b::WP);
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-            S3bOp an = av, bn = bvv;
-            if (kb + 1 < 4) { an = s3b_load(nrA + (wb_rd ^ (64 * (kb + 1))), a3b::WP); bn = s3b_load(nrB + (wb_rd ^ (64 * (kb + 1))), a3b::WP); }
-            S3_SB();
-            f32x4& za = z[2 * (kb & 1)]; f32x4& zb_ = z[2 * (kb & 1) + 1];
-            za = s3b_term<0>(av, bvv, za); zb_ = s3b_term<3>(av, bvv, zb_);
-            za = s3b_term<1>(av, bvv, za); zb_ = s3b_term<4>(av, bvv, zb_);
-            za = s3b_term<2>(av, bvv, za); zb_ = s3b_term<5>(av, bvv, zb_);
-            S3_SB();
-            av = an; bvv = bn;
-        }
-        return (z[0] + z[1]) + (z[2] + z[3]);
-#endif
     };
     // (measured, round 5: waiting here for the stores' acknowledgements -- the flushing waves idle until the barrier anyway -- costs
     // nothing at B <= 2048 and 18 % at B = 8192, where the 226 MB of factor rows per step keep the write path busy: no wait)
@@ -585,8 +568,7 @@ k_adj3b(NetDesc nd, GradLayout gl, const char* __restrict__ imgb, Adj3bSteps M) 
 }  // namespace
 
 bool adj3b_supported(const NetDesc& nd) {
-    static const bool off = [] { const char* e = getenv("CNF_ADJ3B"); return e && e[0] == '0'; }();
-    if (off || nd.n_layers != 3 || nd.n_cond > 0 || nd.jvp) return false;
+    if (!cnf_switch<SW_ADJ3B>() || nd.n_layers != 3 || nd.n_cond > 0 || nd.jvp) return false;
     if (nd.dims[0] > 32 || nd.dims[1] != 128 || nd.dims[2] != 128 || nd.dims[3] > 32 || nd.dims[0] != nd.dims[3]) return false;
     if (nd.n_in != nd.dims[0]) return false;
     for (int l = 0; l < 3; ++l) if (nd.acts[l] != 1) return false;

@@ -28,6 +28,7 @@
 #include <mutex>
 
 #include "cnf_bcast.h"
+#include "cnf_switch.h"
 #include "cnf_mfma_dev.h"
 
 namespace {
@@ -915,7 +916,7 @@ void bcast_pack(const NetDesc& nd, const float* d_params, float* d_img, hipStrea
 
 // workgroups the device holds at once: one per CU (four waves of 512 registers)
 // CNF_BCAST_FORCE_MULTI=1 (measurements): the several-tiles-per-workgroup form even when every tile has a CU of its own
-static bool bcast_force_multi() { static const bool v = [] { const char* e = getenv("CNF_BCAST_FORCE_MULTI"); return e && e[0] == '1'; }(); return v; }
+static bool bcast_force_multi() { return cnf_switch<SW_BCAST_FORCE_MULTI>(); }
 static int bcast_resident(int device) {
     constexpr int MAXDEV = 64;
     static std::mutex mu;
@@ -933,8 +934,7 @@ static int bcast_resident(int device) {
 bool bcast_solve_supported(const NetDesc& nd, bool train, int B, int device) {
     if (nd.n_layers != 2 || nd.acts[0] != 1 || nd.acts[1] != 1) return false;
     if (nd.n_in <= 64 || nd.n_in > 128 || nd.dims[1] <= 256 || nd.dims[1] > 384) return false;
-    static const bool off = [] { const char* e = getenv("CNF_PERSISTENT"); const char* w = getenv("CNF_BCAST"); return (e && e[0] == '0') || (w && w[0] == '0'); }();
-    if (off || B < 1) return false;
+    if (!cnf_switch<SW_PERSISTENT>() || !cnf_switch<SW_BCAST>() || B < 1) return false;
     const int res = bcast_resident(device);
     if (res <= 0) return false;
     const bool multi = (B + 7) / 8 > res || bcast_force_multi();

@@ -21,6 +21,7 @@
 //   weight transpose.
 // DESIGN.md section 4.4 has the measurements.
 #include "cnf_grad.h"
+#include "cnf_switch.h"
 #include <atomic>
 #include <type_traits>
 
@@ -744,12 +745,9 @@ k_wgrad_wave(NetDesc nd, GradLayout gl, const float* __restrict__ AB, const floa
     const auto dH = rsrc(HS, gl.sum_in, io + i0), dT = rsrc(TSb, gl.sum_in, io + i0);
     auto fetch = [&](f32x4 (&x)[8], decltype(dA) d, int sum, unsigned off, int kb) {
 #pragma unroll
-#ifndef WGW_AUX
-#define WGW_AUX 0
-#endif
         // the row offset is part of the CHECKED offset (voffset): soffset takes no part in the range check on gfx9 raw buffers,
         // so a row past the split would otherwise come back as whatever an earlier, larger contraction left there
-        for (int j = 0; j < 8; ++j) x[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(d, (int)(off + (unsigned)((kb - k0 + j) * sum * 4)), 0, WGW_AUX));
+        for (int j = 0; j < 8; ++j) x[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(d, (int)(off + (unsigned)((kb - k0 + j) * sum * 4)), 0, 0));
     };
     auto split8 = [&](const f32x4 (&r)[8], int c) {         // column c of the lane's four: its 8 samples -> three bf16x8 pieces
         typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
@@ -983,7 +981,7 @@ int grad_wgrad_tiles(const NetDesc& nd, const GradLayout& g) {
 }
 
 static bool wgrad_wave_ok(const NetDesc& nd, const GradLayout& g);
-static bool wgrad_lds_form() { static const bool v = getenv("CNF_WGRAD_LDS") != nullptr; return v; }   // A/B: k_wgrad_mfma_b
+static bool wgrad_lds_form() { return cnf_switch<SW_WGRAD_LDS>(); }   // A/B: k_wgrad_mfma_b
 void grad_ksplit(const NetDesc& nd, const GradLayout& g, int B, int* ksplit, int* chunk) {
     const int tiles = grad_wgrad_tiles(nd, g);
     int ks = (1024 + tiles - 1) / tiles;                 // aim at ~1024 workgroups: one wave per SIMD of k_wgrad_wave ...
@@ -991,7 +989,7 @@ void grad_ksplit(const NetDesc& nd, const GradLayout& g, int B, int* ksplit, int
     if (ks > maxks) ks = maxks;
     const int cap = (wgrad_wave_ok(nd, g) && !wgrad_lds_form()) ? GRAD_MAX_KSPLIT : 64;   // ... or two 256-thread workgroups per CU
     if (ks > cap) ks = cap;
-    { static const int force = [] { const char* e = getenv("CNF_WGRAD_KS"); return e ? atoi(e) : 0; }(); if (force > 0 && force <= GRAD_MAX_KSPLIT) ks = force; }
+    { const int force = cnf_switch<SW_WGRAD_KS>(); if (force > 0 && force <= GRAD_MAX_KSPLIT) ks = force; }
     if (ks < 1) ks = 1;
     int ch = (B + ks - 1) / ks;
     ch = (ch + WB_K - 1) / WB_K * WB_K;                  // whole 32-sample groups (a multiple of the fp32 kernels' 16 too)
@@ -1001,8 +999,7 @@ void grad_ksplit(const NetDesc& nd, const GradLayout& g, int B, int* ksplit, int
 
 hipError_t launch_wgrad(const NetDesc& nd, const GradLayout& g, const float* AB, const float* PB, const float* HS,
                         const float* TS, float* gpart, int n_params, int B, int ksplit, int chunk, hipStream_t s) {
-    static const bool valu = getenv("CNF_WGRAD_VALU") != nullptr;     // A/B switches; default: split-bf16 MFMA
-    static const bool fp32 = getenv("CNF_WGRAD_FP32") != nullptr;
+    const bool valu = cnf_switch<SW_WGRAD_VALU>(), fp32 = cnf_switch<SW_WGRAD_FP32>();     // A/B switches; default: split-bf16 MFMA
     if (!valu && !fp32) {
         // 64 x 64 output tiles.  (128 x 128 -- every factor column read by one workgroup per K-split, 1.11x instead of
         // 1.56x the minimum traffic -- was measured: 96 KB of LDS leave one workgroup per CU and the launch 1.5 rounds of
@@ -1123,8 +1120,8 @@ AdjMfmaLayout adj_mfma_layout(const NetDesc& nd, const GradLayout& g) {
         if (m.dp[l + 1] > mx) mx = m.dp[l + 1];
     }
     for (int l = 0; l < m.L; ++l) {
-        m.ff_off[l] = off; off += m.dp[l + 1] * (m.dp[l] + AM_IMG_PAD);
-        m.fr_off[l] = off; off += m.dp[l] * (m.dp[l + 1] + AM_IMG_PAD);
+        m.ff_off[l] = off; off += m.dp[l + 1] * m.dp[l];
+        m.fr_off[l] = off; off += m.dp[l] * m.dp[l + 1];
     }
     m.img_floats = off;
     m.sum_o = oo; m.maxd = mx; m.nin_p = pad16(nd.n_in);
@@ -1161,11 +1158,7 @@ __global__ void k_pack_adj_images(NetDesc nd, GradLayout gl, AdjMfmaLayout m, co
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e < outp * inp) {
         // (row r, column k) of a [rows][kp] image in fragment order: tile r / 16, k-block k / 16, lane 16 (k % 16 / 4) + r % 16
-#ifdef AM_ROWPAD
-        auto frag = [](int r, int k, int kp) { return r * (kp + AM_IMG_PAD) + k; };
-#else
         auto frag = [](int r, int k, int kp) { return (((r >> 4) * (kp >> 4) + (k >> 4)) * 64 + 16 * ((k & 15) >> 2) + (r & 15)) * 4 + (k & 3); };
-#endif
         {   // forward image [o][k]
             const int o = e / inp, k = e % inp;
             const float v = (o < out && k < in) ? P[nd.w_off[l] + o + (size_t)k * out] : 0.f;
@@ -2047,8 +2040,7 @@ hipError_t launch_adj_mfma_step(const NetDesc& nd, const GradLayout& g, const Ad
     const size_t lds = adj_mfma_lds_bytes(m);
     bool all_tanh = true;
     for (int l = 0; l < nd.n_layers; ++l) all_tanh = all_tanh && nd.acts[l] == 1;
-    static const bool generic_only = [] { const char* e = getenv("CNF_ADJ_GENERIC"); return e && e[0] == '1'; }();
-    if (adj3_shape(nd, m) && !generic_only && S.first == 5 && S.last == 0 && S.lam_update && S.lam_out) {   // (whole steps: the zbar stay in the kernel)          // resident-fragment pullback (A/B switch: CNF_ADJ_GENERIC=1)
+    if (adj3_shape(nd, m) && !cnf_switch<SW_ADJ_GENERIC>() && S.first == 5 && S.last == 0 && S.lam_update && S.lam_out) {   // (whole steps: the zbar stay in the kernel)          // resident-fragment pullback (A/B switch: CNF_ADJ_GENERIC=1)
         const bool cw3 = S.st[0].cw != nullptr;
         const void* f3 = all_tanh ? (cw3 ? (const void*)k_adj3<true, true> : (const void*)k_adj3<true>)
                                   : (cw3 ? (const void*)k_adj3<false, true> : (const void*)k_adj3<false>);
@@ -2082,8 +2074,7 @@ hipError_t launch_adj_mfma_step(const NetDesc& nd, const GradLayout& g, const Ad
 // DESIGN 4.4).
 bool adj_mfma_run_split(const NetDesc& nd, const AdjMfmaLayout& m, int B, int nsteps) {
     const int mode = adj_split_mode();
-    static const bool generic_only = [] { const char* e = getenv("CNF_ADJ_GENERIC"); return e && e[0] == '1'; }();
-    if (mode == 0 || nsteps < 1 || B < 1 || (adj3_shape(nd, m) && !generic_only)) return false;      // (k_adj3 has one form)
+    if (mode == 0 || nsteps < 1 || B < 1 || (adj3_shape(nd, m) && !cnf_switch<SW_ADJ_GENERIC>())) return false;      // (k_adj3 has one form)
     if (mode == 1) return true;
     static int cus = 0;
     if (!cus) {
@@ -2130,6 +2121,6 @@ hipError_t launch_adj_mfma_run(const NetDesc& nd, const GradLayout& g, const Adj
 
 size_t adj_mfma_scratch_floats(const AdjMfmaLayout& m, size_t B, int nsteps) { return (size_t)6 * nsteps * B * (size_t)m.SR; }
 
-static std::atomic<int> g_adj_split{[] { const char* e = getenv("CNF_ADJ_SPLIT"); return e ? (e[0] == '0' ? 0 : 1) : -1; }()};
+static std::atomic<int> g_adj_split{cnf_switch<SW_ADJ_SPLIT>()};
 int adj_split_mode() { return g_adj_split.load(std::memory_order_relaxed); }
 void set_adj_split_mode(int mode) { g_adj_split.store(mode < 0 ? -1 : (mode > 0 ? 1 : 0), std::memory_order_relaxed); }

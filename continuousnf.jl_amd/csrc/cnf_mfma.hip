@@ -39,6 +39,7 @@
 // registers (cnf_step3.hip: k_step3, k_step3j); launch() below routes to them.
 #include "cnf_mfma_dev.h"
 #include "cnf_step3.h"
+#include "cnf_switch.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -1419,8 +1420,7 @@ bool mfma_supported(const MfmaPlan& p, const NetDesc&, bool train, int) {
 
 // CNF_STEP_V1=1: the first-generation step kernel (k_mfma) for the headline shape too -- A/B measurements only
 static bool step_v1() {
-    static const bool v = [] { const char* e = getenv("CNF_STEP_V1"); return e && e[0] == '1'; }();
-    return v;
+    return cnf_switch<SW_STEP_V1>();
 }
 
 // Networks whose weights stream from L2 run 16-sample workgroups (one team of 8 waves): the two teams of a
@@ -1483,7 +1483,7 @@ static cnf_status launch(const MfmaPlan& p, const MfmaArgs& a0, hipStream_t s) {
         }
         // k_step3jb: the same schedule with every fp32 product formed from six bf16 MFMA terms on exactly split operands
         // (CNF_STEP_FP32=1 keeps the fp32 MFMA kernel k_step3j: A/B measurements)
-        static const bool fp32_only = [] { const char* e = getenv("CNF_STEP_FP32"); return e && e[0] == '1'; }();
+        const bool fp32_only = cnf_switch<SW_STEP_FP32>();
         if (use_j && p.d_img3b && !fp32_only) step3jb_launch(a, p.d_img3b, p.ly.n_in, p.ly.norm_z, p.ly.norm_j, grid, s, single);
         else if (use_j) step3j_launch(a, p.d_img3, p.ly.n_in, p.ly.norm_z, p.ly.norm_j, grid, s, single);
         else if (p.d_img3b && !fp32_only && !a.dump) step3b_launch(a, p.d_img3b, p.ly.n_in, p.ly.norm_z, p.ly.norm_j, grid, s, single);
@@ -1561,15 +1561,13 @@ cnf_status mfma_solve_persistent(const MfmaPlan& p, const NetDesc& nd, bool trai
                                  const float* eps, int B, hipStream_t s, void* mirror, unsigned seq, Solve3Args& sv, int device,
                                  float* dump, size_t dump_stride, size_t dump_step_stride, int dump_cap, float* hs_out,
                                  float* const* K1) {
-    static const bool off = [] { const char* e = getenv("CNF_PERSISTENT"); return e && e[0] == '0'; }();
-    static const bool fp32_only = [] { const char* e = getenv("CNF_STEP_FP32"); return e && e[0] == '1'; }();
     // k_solve3jb (one forward sweep of state and tangent columns): JVP handles, and VJP handles without the |eps^T J| row
     // (FFJORD: zdot and ldot do not depend on the mode); k_solve3b: VJP handles with that row
     const bool vjp_ok = p.variant == 2 && !p.ly.jvp;
     const bool jvp = (p.shape3 && p.ly.jvp) || (vjp_ok && !p.ly.norm_j && !dump);
     // recording (gradient path): k_solve3b<RECORD> for VJP handles, k_solve3jb<.., RECORD> for JVP handles of the shape
     if (dump && !(vjp_ok || (p.shape3 && p.ly.jvp))) return CNF_ERR_UNSUPPORTED;
-    if (off || fp32_only || step_v1() || !train || !p.d_img3b || !(jvp || vjp_ok))
+    if (!cnf_switch<SW_PERSISTENT>() || cnf_switch<SW_STEP_FP32>() || step_v1() || !train || !p.d_img3b || !(jvp || vjp_ok))
         return CNF_ERR_UNSUPPORTED;
     if (p.cond && dump) return CNF_ERR_UNSUPPORTED;         // (conditional recording solves: k_mfma's step launches)
     const int ntile = (B + 31) / 32;

@@ -12,6 +12,7 @@
 #include "cnf_trace.h"
 #include "cnf_mfma.h"
 #include "cnf_am.h"
+#include "cnf_switch.h"
 
 #define TR_NCMAX 8
 
@@ -735,9 +736,7 @@ k_trace3s(NetDesc nd, GradLayout gl, AdjMfmaLayout m, TraceLayout tl, const floa
             c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am_[t], bc.h, c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[t], bc.m, c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[t], bc.h, c, 0, 0, 0);
-#ifndef TR3S_INTERLEAVE
             __builtin_amdgcn_sched_barrier(0);
-#endif
             if (t < 4) split_q(t, vlo, vhi);
             if (t > 0) {
                 // cprev[r] = d2[j] Z[k = 16 (t-1) + 4q + r][j = 16 wave + s]; W2[j][k] = wa[t-1][r], d1[k] = d1n[r]
@@ -746,16 +745,7 @@ k_trace3s(NetDesc nd, GradLayout gl, AdjMfmaLayout m, TraceLayout tl, const floa
                 for (int r = 0; r < 4; ++r) sum[r] = fmaf(cprev[r], wd[r], sum[r]);
             }
             d1n = *reinterpret_cast<const f32x4*>(db + m.o_off[0] + 16 * t + 4 * q);
-#ifdef TR3S_INTERLEAVE
-            // -DTR3S_INTERLEAVE=<n> (A/B, round 5): the tile's vector work BETWEEN its six dependent MFMAs, n VALU instructions per gap,
-            // instead of behind them.  Measured on the TestMode solve of the headline network (B = 8192, 74 evaluations): n = 3:
-            // 3.76-3.81 ms, n = 5: 3.60-3.70 ms, as shipped: 3.59-3.63 ms -- no gain: not the default.
-#pragma unroll
-            for (int g_ = 0; g_ < 6; ++g_) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, TR3S_INTERLEAVE, 0);
-            }
-#endif
+            // (the tile's vector work BETWEEN its six dependent MFMAs instead of behind them: measured in round 5, no gain -- DESIGN 4.3)
             __builtin_amdgcn_sched_barrier(0);
             cprev = c;
         }
@@ -1131,10 +1121,8 @@ hipError_t launch_jvp_mfma(const NetDesc& nd, const GradLayout& g, const AdjMfma
 
 // fused norms / the fused six-stage step exist in the split kernel of the 32-128-128-32 shape only
 bool trace_fused_supported(const NetDesc& nd, const AdjMfmaLayout& m, int B) {
-    static const bool generic_only = [] { const char* e = getenv("CNF_TRACE_GENERIC"); return e && e[0] == '1'; }();
-    static const bool trace_fp32 = [] { const char* e = getenv("CNF_TRACE_FP32"); return e && e[0] == '1'; }();
-    static const bool unfused = [] { const char* e = getenv("CNF_TRACE_UNFUSED"); return e && e[0] == '1'; }();
-    return trace3_shape(nd, m) && !generic_only && !trace_fp32 && !unfused && trace_fused_grid(B) <= 1024;
+    return trace3_shape(nd, m) && !cnf_switch<SW_TRACE_GENERIC>() && !cnf_switch<SW_TRACE_FP32>() && !cnf_switch<SW_TRACE_UNFUSED>() &&
+           trace_fused_grid(B) <= 1024;
 }
 // k_trace3s: 32 samples per workgroup once that still gives every CU of an MI355X a workgroup, 16 below (measured, config 3:
 // B = 8192: 59 against 67 us per evaluation; B = 4096: 52 against 35)
@@ -1146,8 +1134,7 @@ int trace_fused_grid(int B) { const int ns = trace3s_ns(B); return (B + ns - 1) 
 // must be resident at once: one workgroup per CU.
 bool trace_solve_supported(const NetDesc& nd, const AdjMfmaLayout& m, int B, int device) {
     if (!trace_fused_supported(nd, m, B)) return false;
-    static const bool off = [] { const char* e = getenv("CNF_PERSISTENT"); const char* w = getenv("CNF_TRACE_SOLVE"); return (e && e[0] == '0') || (w && w[0] == '0'); }();
-    if (off) return false;
+    if (!cnf_switch<SW_PERSISTENT>() || !cnf_switch<SW_TRACE_SOLVE>()) return false;
     int n_cu = 0;
     if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) { (void)hipGetLastError(); return false; }
     return trace_fused_grid(B) <= n_cu && trace_fused_grid(B) <= AM_THREADS;
@@ -1179,8 +1166,7 @@ hipError_t launch_trace_mfma(const NetDesc& nd, const GradLayout& g, const AdjMf
     bool all_tanh = true;
     for (int l = 0; l < nd.n_layers; ++l) all_tanh = all_tanh && nd.acts[l] == 1;
     const dim3 grid((a.B + AM_NS - 1) / AM_NS), block(AM_THREADS);
-    static const bool generic_only = [] { const char* e = getenv("CNF_TRACE_GENERIC"); return e && e[0] == '1'; }();
-    static const bool trace_fp32 = [] { const char* e = getenv("CNF_TRACE_FP32"); return e && e[0] == '1'; }();
+    const bool generic_only = cnf_switch<SW_TRACE_GENERIC>(), trace_fp32 = cnf_switch<SW_TRACE_FP32>();
     if (trace3_shape(nd, m) && !generic_only && !trace_fp32) {      // split-bf16 products (A/B switch: CNF_TRACE_FP32=1 -> k_trace3)
         const int PSf = pad8m16(m.maxd);
         const int ns = trace3s_ns(a.B);                  // samples per workgroup

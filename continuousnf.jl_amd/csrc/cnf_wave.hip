@@ -42,6 +42,7 @@
 #include <mutex>
 
 #include "cnf_wave.h"
+#include "cnf_switch.h"
 #include "cnf_mfma_dev.h"
 #include "cnf_wave_dev.h"
 
@@ -1680,8 +1681,7 @@ wave_fn wave_kernel(WaveForm form, const NetDesc& nd, bool train, WaveCot cw = W
 }
 // CNF_PERSISTENT=0 / CNF_WAVE=0: no one-launch solve / none of this file's
 bool wave_off() {
-    static const bool off = [] { const char* e = getenv("CNF_PERSISTENT"); const char* w = getenv("CNF_WAVE"); return (e && e[0] == '0') || (w && w[0] == '0'); }();
-    return off;
+    return !cnf_switch<SW_PERSISTENT>() || !cnf_switch<SW_WAVE>();
 }
 // workgroups of `threads` threads of an instantiation that the current device holds at once (asked once per device, kernel and
 // block size)
@@ -1721,15 +1721,13 @@ bool wave_solve_supported(const NetDesc& nd, bool train, int B) {
 int wave_grad_waves(int B) { return (B + 15) / 16; }
 // floats per accepted step of the rich store (0: this network / mode has no RICH form)
 size_t wave_grad_rich_floats(const NetDesc& nd, int B, bool train) {
-    static const bool off = [] { const char* e = getenv("CNF_WAVE_RICH"); return e && e[0] == '0'; }();
     const int ni = (nd.n_in + 15) / 16, nh = (nd.dims[1] + 15) / 16;
-    if (off || !train || nd.jvp || ni != 1 || nh > 4 || (nd.acts[1] != 1 && nh != 1)) return 0;
+    if (!cnf_switch<SW_WAVE_RICH>() || !train || nd.jvp || ni != 1 || nh > 4 || (nd.acts[1] != 1 && nh != 1)) return 0;
     return (size_t)6 * wave_grad_waves(B) * 64 * (3 * nh + 3 * ni) * 4;
 }
 size_t wave_grad_traj_floats(const NetDesc& nd, int B) { return (size_t)6 * wave_grad_waves(B) * 64 * ((nd.n_in + 15) / 16) * 4; }
 bool wave_grad_supported(const NetDesc& nd, int B, bool train) {
-    static const bool off = [] { const char* e = getenv("CNF_WAVE_GRAD"); return e && e[0] == '0'; }();
-    if (off || !wave_solve_supported(nd, train, B)) return false;
+    if (!cnf_switch<SW_WAVE_GRAD>() || !wave_solve_supported(nd, train, B)) return false;
     if (nd.acts[0] != 1 || !(nd.acts[1] == 1 || is_id2(nd))) return false;
     if (nd.n_cond > 0 && nd.n_in + nd.n_cond > 16 * ((nd.n_in + 15) / 16)) return false;       // [z; ys] within the input tiles
     return wave_kernel(WF_GRAD, nd, train) != nullptr && wave_grad_waves(B) <= 512;
@@ -1792,10 +1790,10 @@ cnf_status wave_solve_launch(const NetDesc& nd, bool train, const float* d_param
     else {
         // at most four tiles: the waves of ONE workgroup (they meet through LDS), where that form is instantiated; more than 512
         // tiles: workgroups of four tiles (LDS inside, the tagged words between them: wave_solve_supported has checked that they fit)
-        static const bool wg_off = [] { const char* e = getenv("CNF_WAVE_WG"); return e && e[0] == '0'; }();
+        const bool wg_off = !cnf_switch<SW_WAVE_WG>();
         // (CNF_WAVE_XWG_MIN=<tiles>: take the four-tile workgroups from that many tiles on -- measurements; the default is what 512
         // meeting words force)
-        static const int xwg_min = [] { const char* e = getenv("CNF_WAVE_XWG_MIN"); const int v = e ? atoi(e) : 0; return v > 4 ? v : 513; }();
+        const int xwg_min = cnf_switch<SW_WAVE_XWG_MIN>();
         const bool wg = wave_kernel(WF_WG4, nd, train) != nullptr;
         xwg = tiles > 512 || (tiles >= xwg_min && !cond && wg);
         if (xwg && (!wg || cond)) return CNF_ERR_UNSUPPORTED;

@@ -865,14 +865,8 @@ def test_loss_grad_headline_shape_variants():
 
 
 def test_ab_switches_take_the_other_kernels_and_stay_parity_green():
-    """CNF_PERSISTENT=0 (the streamed step launches instead of the one-launch solve), CNF_SOLVE_POLL_LIMIT=1 (every wait of the one-launch solve runs out: the streamed
-    fallback), CNF_STEP_FP32 (the fp32-MFMA step
-    kernels k_step3 / k_step3j instead of the split-bf16 ones), CNF_STEP_V1 /
-    CNF_TRACE_GENERIC / CNF_ADJ_GENERIC (the first-generation kernels), CNF_WGRAD_LDS (the contraction with LDS images,
-    k_wgrad_mfma_b, instead of the wave-local k_wgrad_wave), CNF_WAVE_GRAD=0 (the streamed gradient path for the small networks
-    k_solve_wave<GRAD> otherwise takes), CNF_WAVE_WG=0 (one workgroup per wave at small batches), CNF_WAVE_RICH=0 (the gradient
-    recomputes the forward half of its stages): read once per process; each
-    route runs its parity tests in a child process."""
+    """Each leg sets one switch of csrc/cnf_switch.h (the table says which kernel or route it selects) and runs that route's
+    parity tests in a child process: a switch is read once per process."""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for var, sel in (("CNF_PERSISTENT=0", "test_adaptive_solve_vs_oracles and 3-mfma or test_full_size_cfg3 or "
@@ -990,8 +984,7 @@ def test_bare_solve_reads_and_writes_the_callers_columns():
     cfg, _, _ = O.baseline_cfg(3)
     rng = np.random.default_rng(5)
     flat = O.glorot_params(cfg.net, rng, np.float32, 0.1)
-    persistent = os.environ.get("CNF_PERSISTENT") != "0" and os.environ.get("CNF_STEP_FP32") != "1" \
-        and os.environ.get("CNF_STEP_V1") != "1"
+    persistent = _one_launch_expected()
     for jvp in (False, True):
         for B in (1000, 8224):
             D = cfg.n_in + 3
@@ -1035,8 +1028,7 @@ def test_one_launch_solve_takes_the_headline_shape_and_agrees_with_the_streamed_
     cfg, _, _ = O.baseline_cfg(3)
     rng = np.random.default_rng(77)
     flat = O.glorot_params(cfg.net, rng, np.float32, 0.1)
-    persistent = os.environ.get("CNF_PERSISTENT") != "0" and os.environ.get("CNF_STEP_FP32") != "1" \
-        and os.environ.get("CNF_STEP_V1") != "1"
+    persistent = _one_launch_expected()
     res = {}
     for B in (8192, 1000, 8224):
         xs, eps = _dev(rng.standard_normal((cfg.nvars, B))), _dev(rng.standard_normal((cfg.n_in, B)))
